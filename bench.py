@@ -7,7 +7,7 @@ on a synthetic 512^3 sphere SDF (`Sdfs.Sphere(1)`, bounds -1.5..1.5, no clip, is
 writes the volume to HBM, the marching-cubes pipeline reads it and leaves the indexed mesh
 (vertices, colours, normals, triangles) in HBM; inputs and outputs stay device-resident.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
 
 N > 1: the SAME 512^3 grid is sharded by Z slab over the ranks (strong scaling); the exchange of the slab
@@ -40,9 +40,6 @@ import time
 # RCCL / device-memory sharing between the ranks of a node needs dmabuf IPC on this driver stack; the
 # launcher's environment normally carries this already
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-# one hardware queue per stream in play (the library's lanes, torch's stream, RCCL's): with the runtime's default of 4 a
-# stream that waits for an event holds up other streams in the same queue (sdfk_init says more); read at HIP initialisation
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -341,6 +338,46 @@ def mesh_digest(V, Cc, Nn, T):
             for name, a in (("Vertices", V), ("Colors", Cc), ("Normals", Nn), ("Triangles", T))}
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files together
+
+
+def mesh_outputs(m):
+    """What a caller of the timed path receives (a Mesh: .Vertices / .Colors / .Normals [n, 3] float32, .Triangles int32[], .Min / .Max),
+    as name -> array for dump_outputs; the triangles as [t, 3] rows."""
+    import numpy as np
+    return {"vertices": m.Vertices, "colors": m.Colors, "normals": m.Normals, "triangles": np.asarray(m.Triangles).reshape(-1, 3),
+            "bounds": np.stack([np.asarray(m.Min, np.float32), np.asarray(m.Max, np.float32)])}
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Writes every array of `arrays` as dirname/<name>.npy: floating point as it is (float32 / float64), integers as float64 (exact
+    below 2^53).  When the whole would exceed `limit` bytes, the arrays that have more than 1024 rows keep the same fraction of their
+    rows, drawn by a generator seeded with `seed` from the row count alone and kept in order -- two builds that computed the same
+    arrays write the same files.  Returns what was written (name -> shape, rows of the full array, dtype) for the result line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = a.astype(np.float64) if not np.issubdtype(a.dtype, np.floating) else a.astype(a.dtype.newbyteorder("="), copy=False)
+    total = sum(a.nbytes for a in conv.values())
+    big = {k for k, a in conv.items() if a.ndim and a.shape[0] > 1024}
+    fixed = sum(a.nbytes for k, a in conv.items() if k not in big)
+    limit -= 256 * len(conv)   # (room for the .npy headers)
+    frac = 1.0 if total <= limit else max(0.0, (limit - fixed) / max(1, total - fixed))
+    info = {}
+    for name, a in conv.items():
+        rows = a.shape[0] if a.ndim else 1
+        if name in big and frac < 1.0:
+            keep = int(rows * frac)
+            pick = np.sort(np.random.default_rng([seed, rows]).choice(rows, size=keep, replace=False))
+            a = a[pick]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = {"shape": list(a.shape), "rows_of": rows, "dtype": str(a.dtype)}
+    return {"dir": dirname, "bytes": sum(int(np.prod(v["shape"])) * np.dtype(v["dtype"]).itemsize for v in info.values()),
+            "sampled": frac < 1.0, "arrays": info}
+
+
 def compare_sharded_with_single(single, whole, slab_digests, counts, flip_one_index=False):
     """The comparison of the sharded content check, pure: `single` / `whole` = meshes (.Vertices / .Colors / .Normals / .Triangles numpy arrays) of
     the same grid from one GPU / gathered from the ranks; slab_digests[q] = (mesh_digest of rank q's own slab, (vertices, indices)) or None;
@@ -383,14 +420,19 @@ def main():
                     "latency, host-copy or host-Values legs, whose launches would mix into the per-kernel means)")
     ap.add_argument("--elide", action="store_true", help="PROFILING ONLY (with --minimal): the timed loop runs the product default -- the volume is not "
                     "stored (SDFK_OPT_ELIDE_VOLUME = 2) -- so that a rocprofv3 pass sees the volume-less step's kernels; such a line is not the contract's step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the mesh the last timed step of the headline produced (what a caller of the path receives: "
+                         "vertices, colors, normals, triangles, bounds) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing above has imported torch or
         # called HIP; the ranks are CHILD processes (a process that has touched the GPU must never exec).
         argv = ["--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--grid", str(args.n),
                 "--scene", args.scene, "--cpu-n", str(args.cpu_n), "--cpu-passes", str(args.cpu_passes)] + (["--no-cpu"] if args.no_cpu else []) + \
-               (["--minimal"] if args.minimal else [])
+               (["--minimal"] if args.minimal else []) + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])
         sys.exit(launch_ranks(argv, args.gpus))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and os.environ.get("SDFK_BENCH_WORKER") != "1":
         # a rank as the launcher (the driver's torch.distributed.run, or launch_ranks above) started it: supervise a worker
@@ -426,7 +468,7 @@ def main():
     # Control plane: a gloo group (barrier, max-over-ranks of the timings, handing the RCCL id round).  Data plane: the
     # library's own RCCL communicator and exchange stream (sdfk_dist_init) -- or, with every rank on ONE GPU (testing), the
     # library's host transport over the same gloo group.  No torch NCCL group: it would be a second communicator and two
-    # more streams competing for the hardware queues (see GPU_MAX_HW_QUEUES above).
+    # more streams competing for the hardware queues (sdfk_init in csrc/lib_context.hip says why that costs).
     if sharded:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
@@ -560,9 +602,12 @@ def main():
         ref_a, ref_b = C.byref(cnt_a), C.byref(cnt_b)
         f_march, f_counts, f_free, check = L.sdfk_sample_march, L.sdfk_mesh_counts, L.sdfk_mesh_free, N.check
 
-        def retire(m):
+        def retire(m, keep=None):
             check(f_counts(m, ref_a, ref_b))
-            f_free(m)
+            if keep is None:
+                f_free(m)
+            else:
+                keep.append(m)
             a, b = cnt_a.value, cnt_b.value
             if last[0] and (a != last[0] or b != last[1]):
                 raise SystemExit(f"mesh changed between steps: {last} -> {(a, b)}")
@@ -576,9 +621,11 @@ def main():
                 retire(inflight.pop(0))
             return last
 
-        def drain():
+        def drain(keep=None):
+            # keep: a list that receives the handle of the last step instead of freeing it (--dump-outputs; the caller frees it)
             while inflight:
-                retire(inflight.pop(0))
+                m = inflight.pop(0)
+                retire(m, keep if not inflight else None)
             return tuple(last)
         return step, drain, depth
 
@@ -649,16 +696,22 @@ def main():
     # block is 3 ms at 512^3: a single sample says little (box to box 0.147-0.154 ms in round 4).  SDFK_BENCH_BLOCKS=1: one block.
     n_blocks = max(1, int(os.environ.get("SDFK_BENCH_BLOCKS", "11")))
     block_dts = []
-    for _ in range(n_blocks):
+    kept = []   # --dump-outputs, one GPU: the mesh handle of the last timed step, freed once its arrays are copied out below
+    for b in range(n_blocks):
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             nv, ni = step()
-        nv, ni = drain()   # every queued step has completed and been checked before the clock stops
+        # every queued step has completed and been checked before the clock stops
+        nv, ni = drain(kept) if (args.dump_outputs and not sharded and b == n_blocks - 1) else drain()
         barrier()
         block_dts.append(max_over_ranks(time.perf_counter() - t0))
     dt = sorted(block_dts)[len(block_dts) // 2]
     gc.enable()
+    dumped = None
+    if kept:
+        from sdfkit_amd.api import Mesh as HostMesh
+        dumped = dump_outputs(args.dump_outputs, mesh_outputs(HostMesh._from_handle(kept.pop())))   # (frees the handle)
     # The same K steps with COLD clocks: the GPU idles long enough to drop its clocks, then W warm-up steps and K timed ones
     # -- what the driver's command measures without the clock warm-up above (the headline `value` has it, and says so).
     time.sleep(0.25)
@@ -684,7 +737,7 @@ def main():
     # gathered slabs concatenated; collective with exchange mode 3, where it runs the payload exchange of that step on demand), and
     # every rank's OWN slab (sdfk_dist_slab_mesh, global indices) with its slice of the single-GPU mesh.  First contact with a node
     # of several GPUs then yields correctness evidence, not just a time: `mesh_equals_single_gpu: false` makes the run exit non-zero.
-    def content_check(ses, sdf_x, mn_x, mx_x, clip_x, nn, mode_x):
+    def content_check(ses, sdf_x, mn_x, mx_x, clip_x, nn, mode_x, keep=None):
         # (mode_x: the SDFK_OPT_DIST_EXCHANGE the session was created with -- its stats report -1 for the host transport, whatever the mode)
         # A failure of the CHECK on one rank (an allocation, a copy) must cost neither the line nor the other ranks: rank-local parts are
         # guarded, the collectives (the on-demand payload exchange of mode 3, the gathering of the digests, the barrier) are always entered.
@@ -706,6 +759,8 @@ def main():
         whole = None
         if mode_x == 3 or rank == 0:     # (mode 3: collective -- the payload exchange of this step happens here; mode 2: only rank 0 holds it)
             whole = guarded("sdfk_dist_mesh", ses.mesh)
+        if keep is not None and whole is not None and rank == 0:
+            keep.append(whole)
         slabs = [None] * world
         if world > 1:
             dist.all_gather_object(slabs, (own_dn, list(problems)))
@@ -741,7 +796,10 @@ def main():
     dist_extra = {}
     headline_content = None
     if sharded:
-        headline_content = content_check(worker, sdf, mn, mx, clip, n, headline_mode)   # (before enqueue_only reuses slot 0's send buffer)
+        whole_kept = [] if args.dump_outputs else None
+        headline_content = content_check(worker, sdf, mn, mx, clip, n, headline_mode, whole_kept)   # (before enqueue_only reuses slot 0's send buffer)
+        if whole_kept:
+            dumped = dump_outputs(args.dump_outputs, mesh_outputs(whole_kept.pop()))
         st = worker.stats()
         for _ in range(3):
             worker.enqueue_only()
@@ -1447,6 +1505,7 @@ def main():
                        "ms_per_step_all": [round(b / args.steps * 1e3, 4) for b in block_dts],
                        "what": f"{len(block_dts)} timed blocks of K = {args.steps} steps, each bracketed by barrier + synchronize on both sides (max over "
                                "ranks); `value` / `ms_per_step` = the median block"},
+            **({"dump_outputs": dumped} if args.dump_outputs else {}),
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,

@@ -55,9 +55,6 @@ inline void EnsureInit()
 {
     static bool done = false;
     if (!done) {
-        // The library's streams want 8 hardware queues (sdfk_init in sdfkit_hip.hip says why); the HIP runtime reads the
-        // variable when it initialises, and the library never edits the environment itself: a host binding's job.
-        setenv("GPU_MAX_HW_QUEUES", "8", 0);
         Check(sdfk_init(0));
         done = true;
     }

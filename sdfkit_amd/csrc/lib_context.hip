@@ -125,7 +125,7 @@ void sync_all_lanes()
 // ---------------------------------------------------------------------------
 // Which streams are busy TOGETHER decides everything about overlap on this part (tools/ubench/ub_lanes2.hip: chains of 9 small
 // dependent kernels, one captured graph launch each, dealt round-robin over a subset of 8 streams created in order, with
-// GPU_MAX_HW_QUEUES = 8): streams 0,1,2,3 -> 16 us per chain (one stream: 61), but streams 0 and 4 ALONE -> 191 us, three
+// eight hardware queues): streams 0,1,2,3 -> 16 us per chain (one stream: 61), but streams 0 and 4 ALONE -> 191 us, three
 // times slower than one stream: the runtime gives the i-th stream the i-th hardware queue, the queues are dealt over FOUR
 // pipes, and a pipe that has two queues with work switches between them at ~15 us a switch.  (And with the runtime's default
 // of 4 queues streams 0 and 4 share a QUEUE: in order, the one behind an event wait holds up the other.)  Which queue a stream
@@ -571,9 +571,8 @@ int context_init(int device)
     // all streams of a process onto GPU_MAX_HW_QUEUES (default 4) in-order queues, and a stream that waits for an event (a
     // lane section's end, a collective) then holds up every OTHER stream behind it in the same queue.  Nor may two of them
     // that are busy together sit on queues of the same PIPE ("stream placement" above measures both).
-    // The runtime reads the variable when IT initialises, which may be long before this call (torch, the C# host), and a
-    // library must not edit its process's environment under the feet of other threads: the HOST BINDINGS export
-    // GPU_MAX_HW_QUEUES=8 before their first HIP call (sdfkit_amd/_native.py, shim/SdfKit.Hip/Native.cs, include/SdfKit.hpp);
+    // The runtime reads the queue count when IT initialises, which may be long before this call (torch, the C# host); neither
+    // the library nor its host bindings change it: the launcher's environment decides, and
     // sdfk_get_option(SDFK_OPT_HW_QUEUES) says what the process had when the library came up.
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);

@@ -218,3 +218,36 @@ def test_sharded_content_comparison_is_right_without_a_gpu():
     # a gathered mesh with a vertex too many is not the single-GPU mesh
     more = mesh(np.vstack([m.vertices, m.vertices[:1]]), np.vstack([m.colors, m.colors[:1]]), np.vstack([m.normals, m.normals[:1]]), m.triangles)
     assert bench.compare_sharded_with_single(single, more, slabs_of(single), counts)["mesh_equals_single_gpu"] is False
+
+
+def test_dump_outputs_types_limit_and_fixed_sample(tmp_path):
+    """--dump-outputs: float arrays as they are, integer arrays as float64, and past the size limit the same seeded rows every time."""
+    import numpy as np
+
+    class M:
+        pass
+    rng = np.random.default_rng(7)
+    m = M()
+    m.Vertices = rng.random((5000, 3), dtype=np.float32)
+    m.Colors = np.zeros((5000, 3), np.float32)
+    m.Normals = rng.random((5000, 3), dtype=np.float32)
+    m.Triangles = rng.integers(0, 5000, 3 * 9000).astype(np.int32)
+    m.Min, m.Max = [-1.5] * 3, [1.5] * 3
+    arrays = bench.mesh_outputs(m)
+    full = bench.dump_outputs(str(tmp_path / "full"), arrays)
+    assert not full["sampled"] and full["arrays"]["triangles"]["shape"] == [9000, 3]
+    t = np.load(tmp_path / "full" / "triangles.npy")
+    assert t.dtype == np.float64 and np.array_equal(t, m.Triangles.reshape(-1, 3))
+    assert np.load(tmp_path / "full" / "vertices.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "full" / "bounds.npy"), [[-1.5] * 3, [1.5] * 3])
+    limit = 200_000
+    a = bench.dump_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    b = bench.dump_outputs(str(tmp_path / "b"), arrays, limit=limit)
+    assert a["sampled"] and 0 < a["arrays"]["vertices"]["shape"][0] < 5000
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= limit
+    for name in arrays:
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert np.array_equal(x, y)
+    v = np.load(tmp_path / "a" / "vertices.npy")     # rows of the full array, in order
+    rows = [int(np.flatnonzero((m.Vertices == r).all(axis=1))[0]) for r in v]
+    assert rows == sorted(rows)

@@ -140,7 +140,7 @@ def test_two_gpus_real_rccl_parity(gpu, exchange, index16):
         pytest.skip("needs two GPUs")
     env = dict(os.environ)
     env.update({"SDFK_TEST_REAL_RCCL": "1", "SDFK_DIST_EXCHANGE": str(exchange), "SDFK_DIST_INDEX16": str(index16),
-                "HSA_ENABLE_IPC_MODE_LEGACY": "0", "GPU_MAX_HW_QUEUES": "8", "NCCL_SOCKET_IFNAME": "lo", "GLOO_SOCKET_IFNAME": "lo"})
+                "HSA_ENABLE_IPC_MODE_LEGACY": "0", "NCCL_SOCKET_IFNAME": "lo", "GLOO_SOCKET_IFNAME": "lo"})
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
                           "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "multirank_worker.py"), "readme_repeat_xy", "72", "64", "80"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)

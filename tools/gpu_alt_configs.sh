@@ -15,7 +15,6 @@ run() { if want "$1"; then run_impl "$@"; fi; }
 run placement_off SDFK_STREAM_PLACEMENT=0
 run lanes4 SDFK_LANES=4
 run lanes0 SDFK_LANES=0
-run hwq4 GPU_MAX_HW_QUEUES=4
 run graphs_off SDFK_GRAPHS=0
 run dist_conservative SDFK_DIST_LANES=0 SDFK_DIST_EXCHANGE=0
 run dist_index16 SDFK_DIST_INDEX16=1 SDFK_DIST_EXCHANGE=2

@@ -6,7 +6,6 @@ run() { echo "== $*"; env "$@" PROBE_STEPS=400 timeout 120 python3 tools/slab_st
 run PROBE_N=128
 run PROBE_N=128 PROBE_TORCH=1
 run PROBE_N=128 PROBE_TORCH=1 PROBE_BIND=1
-run PROBE_N=128 PROBE_TORCH=1 PROBE_BIND=1 GPU_MAX_HW_QUEUES=4
 run PROBE_N=128 PROBE_DEPTH=5
 run PROBE_N=512
 run PROBE_N=512 PROBE_TORCH=1 PROBE_BIND=1
