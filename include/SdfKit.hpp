@@ -589,6 +589,127 @@ struct Matrix4x4 {
         R[2][3] = -(a * fl_hj - b * el_hi + d * ej_fi) * inv; R[3][3] = +(a * fk_gj - b * ek_gi + c * ej_fi) * inv;
         return true;
     }
+    // (the members IterativeClosestPoint and its tests use; MathF.Sin / Cos are the C runtime's sinf / cosf)
+    static Matrix4x4 Identity() { return Matrix4x4(); }
+    static Matrix4x4 CreateTranslation(float x, float y, float z)
+    {
+        Matrix4x4 r;
+        r.M[3][0] = x; r.M[3][1] = y; r.M[3][2] = z;
+        return r;
+    }
+    static Matrix4x4 CreateRotationX(float radians)
+    {
+        const float c = std::cos(radians), s = std::sin(radians);
+        Matrix4x4 r;
+        r.M[1][1] = c; r.M[1][2] = s; r.M[2][1] = -s; r.M[2][2] = c;
+        return r;
+    }
+    static Matrix4x4 CreateRotationY(float radians)
+    {
+        const float c = std::cos(radians), s = std::sin(radians);
+        Matrix4x4 r;
+        r.M[0][0] = c; r.M[0][2] = -s; r.M[2][0] = s; r.M[2][2] = c;
+        return r;
+    }
+    Vector3 Translation() const { return {M[3][0], M[3][1], M[3][2]}; }
+    static Vector3 Transform(Vector3 v, const Matrix4x4& m)   // Vector3.Transform(position, matrix)
+    {
+        return {((v.X * m.M[0][0] + v.Y * m.M[1][0]) + v.Z * m.M[2][0]) + m.M[3][0], ((v.X * m.M[0][1] + v.Y * m.M[1][1]) + v.Z * m.M[2][1]) + m.M[3][1],
+                ((v.X * m.M[0][2] + v.Y * m.M[1][2]) + v.Z * m.M[2][2]) + m.M[3][2]};
+    }
+};
+
+// ---------------------------------------------------------------------------------------
+// KdTree (KdTree.cs) and IterativeClosestPoint (IterativeClosestPoint.cs) over sdfk_points_* / sdfk_icp_*
+// ---------------------------------------------------------------------------------------
+// The search is exact: the static point of least d2, ties to the lowest insertion index (sdfkit_hip.h).  The tree's
+// internals (Left, Right, SplitValue, IsLeaf) have no counterpart: the structure is a grid of cell lists on the GPU.
+static_assert(sizeof(Vector3) == 3 * sizeof(float), "Vector3 spans are passed as float triples");
+class KdTree {
+public:
+    Vector3 Point;
+    const uint8_t SplitAxis;
+    explicit KdTree(const std::vector<Vector3>& points, uint8_t axis = 0) : SplitAxis(axis)
+    {
+        if (points.empty()) throw std::invalid_argument("At least on point must be given (points)");
+        EnsureInit();
+        Point = points[0];
+        Check(sdfk_points_create(reinterpret_cast<const float*>(points.data()), (int64_t)points.size(), &h_));
+    }
+    KdTree(const KdTree&) = delete;
+    KdTree& operator=(const KdTree&) = delete;
+    ~KdTree() { sdfk_points_free(h_); }
+    int TotalPoints() const
+    {
+        int64_t n = 0;
+        Check(sdfk_points_count(h_, &n));
+        return (int)n;
+    }
+    void AddPoints(const std::vector<Vector3>& points)
+    {
+        Check(sdfk_points_add(h_, reinterpret_cast<const float*>(points.data()), (int64_t)points.size()));
+    }
+    Vector3 Search(Vector3 q, float& nearestDistance) const
+    {
+        Vector3 nearest;
+        Check(sdfk_points_search(h_, &q.X, 1, nullptr, &nearestDistance, &nearest.X));
+        return nearest;   // (no point counts: the first static point and float.MaxValue, as the reference)
+    }
+    sdfk_points* Handle() const { return h_; }
+
+private:
+    sdfk_points* h_ = nullptr;
+};
+
+class IterativeClosestPoint {
+public:
+    int MaxIterations = 100;
+    float GoodCorrespondenceDistance = 0.01f;
+    float ConvergedMaximumTranslation = 1.0e-4f;
+    float ConvergedMaximumRotation = 1.0e-5f;
+    int Iterations = 0;   // (extension: iterations of the last RegisterPoints)
+
+    explicit IterativeClosestPoint(const std::vector<Vector3>& staticPoints) : tree_(new KdTree(staticPoints)) {}
+    explicit IterativeClosestPoint(const std::vector<std::vector<Vector3>>& staticPoints)
+    {
+        if (staticPoints.empty()) throw std::invalid_argument("At least one set of points must be given (staticPoints)");
+        tree_.reset(new KdTree(staticPoints[0]));
+        for (size_t i = 1; i < staticPoints.size(); i++) tree_->AddPoints(staticPoints[i]);
+    }
+    void AddStaticPoints(const std::vector<Vector3>& staticPoints) { tree_->AddPoints(staticPoints); }
+    // Rigidly moves `points` (in place) onto the static points; returns the transform that did it.
+    Matrix4x4 RegisterPoints(std::vector<Vector3>& points)
+    {
+        const sdfk_icp_params prm{MaxIterations, GoodCorrespondenceDistance, ConvergedMaximumTranslation, ConvergedMaximumRotation};
+        Matrix4x4 total;
+        int32_t iters = 0;
+        Check(sdfk_icp_register(tree_->Handle(), &prm, reinterpret_cast<float*>(points.data()), (int64_t)points.size(), &total.M[0][0], &iters));
+        Iterations = iters;
+        return total;
+    }
+    std::vector<Matrix4x4> GlobalRegisterPoints(const std::vector<std::vector<Vector3>>& staticPoints, std::vector<std::vector<Vector3>>& dynamicPoints)
+    {
+        if (dynamicPoints.empty()) return {};
+        IterativeClosestPoint icp(staticPoints);
+        std::vector<Matrix4x4> transforms;
+        for (auto& d : dynamicPoints) {
+            transforms.push_back(icp.RegisterPoints(d));
+            icp.AddStaticPoints(d);
+        }
+        return transforms;
+    }
+    std::vector<Matrix4x4> GlobalRegisterPoints(std::vector<std::vector<Vector3>>& points)
+    {
+        if (points.empty()) return {};
+        if (points.size() == 1) return {Matrix4x4::Identity()};
+        std::vector<std::vector<Vector3>> s(points.begin(), points.begin() + 1), d(points.begin() + 1, points.end());
+        auto r = GlobalRegisterPoints(s, d);
+        for (size_t i = 0; i < d.size(); i++) points[i + 1] = d[i];
+        return r;
+    }
+
+private:
+    std::unique_ptr<KdTree> tree_;
 };
 
 inline void WriteTgaHeader(std::ostream& w, int imageType, int width, int height, int bpp)

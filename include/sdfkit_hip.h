@@ -31,7 +31,8 @@ extern "C" {
                                    mode 3 (the mesh stays sharded); sdfk_eval_points (SdfEx.Sample);
                                 6: SDFK_OPT_COLOR_PASSES; sdfk_dist_gathered refuses a step that brought this rank headers only and sdfk_dist_tune
                                    a session whose exchange mode is 2 or 3 (SDFK_ERR_UNSUPPORTED); gather-to-root has the same who-receives-what on
-                                   the host transport as over RCCL; sdfk_host_alloc works in a process whose only contexts are a node's */
+                                   the host transport as over RCCL; sdfk_host_alloc works in a process whose only contexts are a node's;
+                                   entry points added since, existing ones unchanged: sdfk_points_* (KdTree) and sdfk_icp_* (IterativeClosestPoint) */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -463,6 +464,53 @@ int sdfk_raymarch(const sdfk_program* p, int32_t width, int32_t height, const fl
 int sdfk_raymarch_device(const sdfk_program* p, int32_t width, int32_t height, const float camera_position[3],
                          const float view_projection_inverse[16], float near_plane, float far_plane,
                          int32_t depth_iterations, void* depth_dev, void* rgb_dev);
+
+/* ---- KdTree (KdTree.cs) / IterativeClosestPoint (IterativeClosestPoint.cs) -----------------------------------------
+ * sdfk_points: a static point set on the device (x, y, z triples), searched for the exact nearest point.  Static points are
+ * numbered in insertion order: the points of sdfk_points_create, then each sdfk_points_add batch appended (KdTree(points),
+ * KdTree.AddPoints).  The search structure is a uniform grid of sorted cell lists rebuilt on the device by every create / add;
+ * its shape is not part of the contract (the reference's Left / Right / SplitValue / IsLeaf have no counterpart).
+ *   - Nearest point of query q (KdTree.Search, KdTree.cs:160-197): the static point p of least
+ *     d2 = (dx*dx + dy*dy) + dz*dz (dx = q.x - p.x ..., binary32, no FMA), ties to the LOWEST index (the reference returns
+ *     whichever its traversal met first); distance = sqrtf(d2).  A point counts only if sqrtf(d2) < FLT_MAX; if none does
+ *     (a NaN / infinite query, overflow) index = -1, distance = FLT_MAX and nearest3 = the first static point (nearest = Point).
+ *   - Refused with SDFK_ERR_INVALID: an empty initial set (ArgumentException, KdTree.cs:41-45), static points with a NaN or
+ *     infinite coordinate, 2^31 static points or more in total.  Duplicate static points are allowed.
+ * sdfk_points_search: host arrays, synchronous; any output may be NULL.  sdfk_points_search_device: caller-owned device
+ * buffers, asynchronous on the library stream.  A set belongs to the device context it was made in.  Calls run in the calling
+ * thread's current context and stream, like sdfk_eval_points_device.
+ * sdfk_points_stats (diagnostics): stats[0..2] = grid cells along x, y, z; stats[3] = candidates (static points whose
+ * distance was computed) of the last search made while sdfk_profile_enable(1) was on, stats[4] = its query count. */
+typedef struct sdfk_points sdfk_points;
+int sdfk_points_create(const float* points3, int64_t n, sdfk_points** out);
+int sdfk_points_create_device(const void* points3_dev, int64_t n, sdfk_points** out);
+int sdfk_points_add(sdfk_points* s, const float* points3, int64_t n);              /* AddPoints / AddStaticPoints */
+int sdfk_points_add_device(sdfk_points* s, const void* points3_dev, int64_t n);
+int sdfk_points_count(const sdfk_points* s, int64_t* n);                           /* TotalPoints */
+int sdfk_points_search(const sdfk_points* s, const float* queries3, int64_t n, int32_t* index, float* distance, float* nearest3);
+int sdfk_points_search_device(const sdfk_points* s, const void* queries3_dev, int64_t n, void* index_dev, void* distance_dev,
+                              void* nearest3_dev);
+int sdfk_points_stats(const sdfk_points* s, int64_t stats[5]);
+void sdfk_points_free(sdfk_points* s);
+/* IterativeClosestPoint.RegisterPoints (IterativeClosestPoint.cs:53-196): rigidly moves the caller's points (in place) onto the
+ * static set and returns the total transform (row-major M11..M44, System.Numerics row-vector convention) and the number of
+ * iterations run.  Each iteration is the reference's: nearest static point of every point, the piecewise distMax from the
+ * distance mean and standard deviation, the points with dist <= distMax, C = sum of centred p q^T,
+ * R = V diag(1, 1, sign det(V U^T)) U^T, translation = Transform(pmean, Invert(R)) - qmean, step = Invert(R * CreateTranslation(t)),
+ * points = Transform(points, step), total = total * step, until the step moves less than both convergence limits or
+ * max_iterations steps were made.  Deviations: the reductions and the 3x3 SVD are in f64 (fixed reduction order, bitwise
+ * reproducible); R, pmean and qmean are rounded to f32 and every later step is the reference's f32 Matrix4x4 arithmetic.
+ * An empty dynamic set is refused (SDFK_ERR_INVALID).  sdfk_icp_register: host points, synchronous.  sdfk_icp_register_device:
+ * device points; returns when the registration has finished (the host reads the iteration count). */
+typedef struct sdfk_icp_params {
+    int32_t max_iterations;             /* MaxIterations = 100 */
+    float good_correspondence_distance; /* GoodCorrespondenceDistance = 0.01 */
+    float converged_max_translation;    /* ConvergedMaximumTranslation = 1e-4 */
+    float converged_max_rotation;       /* ConvergedMaximumRotation = 1e-5 */
+} sdfk_icp_params;
+int sdfk_icp_register(sdfk_points* s, const sdfk_icp_params* prm, float* points3, int64_t n, float total[16], int32_t* iterations);
+int sdfk_icp_register_device(sdfk_points* s, const sdfk_icp_params* prm, void* points3_dev, int64_t n, float total[16],
+                             int32_t* iterations);
 
 /* ---- pinned host arena -------------------------------------------------------
  * Host memory the GPU can write directly (hipHostMalloc), recycled through size-class free lists:

@@ -113,9 +113,26 @@ SIGNATURES = {
     "sdfk_node_mesh_begin": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32), _i32, _fp, _fp, _i32, _i32, _i32, _i32, _f, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32)]),
     "sdfk_node_mesh_copy": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _fp, _fp]),
     "sdfk_node_close": (None, [_vp]),
+    "sdfk_points_create": (C.c_int, [_vp, _i64, _vpp]),
+    "sdfk_points_create_device": (C.c_int, [_vp, _i64, _vpp]),
+    "sdfk_points_add": (C.c_int, [_vp, _vp, _i64]),
+    "sdfk_points_add_device": (C.c_int, [_vp, _vp, _i64]),
+    "sdfk_points_count": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "sdfk_points_search": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sdfk_points_search_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sdfk_points_stats": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "sdfk_points_free": (None, [_vp]),
+    "sdfk_icp_register": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),
+    "sdfk_icp_register_device": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),
     "sdfk_profile_count": (C.c_int, []),
     "sdfk_profile_get": (C.c_int, [_i32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_i64)]),
 }
+
+
+class IcpParams(C.Structure):
+    """struct sdfk_icp_params"""
+    _fields_ = [("max_iterations", C.c_int32), ("good_correspondence_distance", C.c_float),
+                ("converged_max_translation", C.c_float), ("converged_max_rotation", C.c_float)]
 
 
 # sdfk_allgather_fn: int (*)(void* ctx, const void* send, void* recv, int64_t bytes_per_rank)

@@ -7,7 +7,8 @@
 //   lib_mesh.hip     the accessors of a device-resident Mesh
 //   lib_dist.hip     the Z-slab sharded step (dist_rccl.h) and several GPUs from one process (node_local.h)
 //   mc_kernels.hip   the marching-cubes kernels (declared in mc_kernels.h)
-// Build: sdfkit_amd/build.py (the seven units in parallel, then one link with csrc/exports.map).  gfx950 only; there is no CPU path.
+//   lib_points.hip   KdTree / IterativeClosestPoint: the grid search structure, exact nearest-point search, ICP
+// Build: sdfkit_amd/build.py (the eight units in parallel, then one link with csrc/exports.map).  gfx950 only; there is no CPU path.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>

@@ -1,0 +1,952 @@
+// lib_points.hip -- KdTree (KdTree.cs) and IterativeClosestPoint (IterativeClosestPoint.cs): exact nearest-point search against a
+// static point set, and rigid ICP registration built on it.  Contract: include/sdfkit_hip.h, "KdTree / IterativeClosestPoint".
+//
+// Search structure: a uniform grid of sorted cell lists, built on the device by a counting sort --
+//   bounds (+ the non-finite check) -> cell key per point and per-cell counts (integer atomics) -> exclusive scan -> scatter into
+//   float4 (x, y, z, bits(index)) in cell order, so that one 16-byte load gives a candidate.
+// In-cell order comes from the atomics and varies from build to build; the (d2, index) rule makes every result independent of it.
+// Query: one lane per query; cells in growing Chebyshev shells around the query's cell (clamped to the grid), stopping when a
+// conservative f32 lower bound on the distance of every unvisited cell exceeds the best d2.  Queries run in the caller's order:
+// processing them in the order of a coarse counting sort of their cells was measured slower for mesh vertices, whose order is
+// already spatially coherent, and 5 % faster only for random queries (profiles/points_ab_query_order.txt).  Grid sizing and cell
+// assignment: points_grid.h.
+// ICP: per iteration search -> sum of d, then of (d - mean)^2 -> filtered sums (count, p, q) -> centred C -> a one-lane solve (f64 SVD, the
+// reference's f32 Matrix4x4 steps, convergence, running total) -> the step applied to the points.  Every reduction is f64 in a
+// fixed order (per-block partials of a fixed grid, then one block), with no float atomics: results are bitwise reproducible.
+#include "lib_internal.h"
+#include "points_grid.h"
+
+#include <cfloat>
+
+namespace {
+
+using namespace sdfk_points_grid;   // Grid, cell_of, key_of, grid_for_box; kMaxCells, kMaxAxisCells
+
+constexpr int kBlock = 256;
+constexpr int kRedBlocks = 256;   // partials of every ICP reduction: a fixed grid, so the summation order depends on n only
+
+// ---- build ------------------------------------------------------------------------------------------------------------------
+// per-block min / max of each coordinate and the number of non-finite points -> part[block][8]
+__global__ __launch_bounds__(kBlock) void k_pts_bounds(const float* __restrict__ p, int64_t n, float* __restrict__ part)
+{
+    __shared__ float s[7][kBlock];
+    float r[7] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY, 0.0f};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const float x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
+        if (!(isfinite(x) && isfinite(y) && isfinite(z))) { r[6] += 1.0f; continue; }
+        r[0] = fminf(r[0], x); r[1] = fminf(r[1], y); r[2] = fminf(r[2], z);
+        r[3] = fmaxf(r[3], x); r[4] = fmaxf(r[4], y); r[5] = fmaxf(r[5], z);
+    }
+    for (int j = 0; j < 7; j++) s[j][threadIdx.x] = r[j];
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            for (int j = 0; j < 3; j++) s[j][threadIdx.x] = fminf(s[j][threadIdx.x], s[j][threadIdx.x + o]);
+            for (int j = 3; j < 6; j++) s[j][threadIdx.x] = fmaxf(s[j][threadIdx.x], s[j][threadIdx.x + o]);
+            s[6][threadIdx.x] = fmaxf(s[6][threadIdx.x], s[6][threadIdx.x + o]);   // (any non-finite point: > 0)
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 7) part[blockIdx.x * 8 + threadIdx.x] = s[threadIdx.x][0];
+}
+
+__global__ __launch_bounds__(kBlock) void k_pts_bounds_final(const float* __restrict__ part, int blocks, float* __restrict__ out)
+{
+    __shared__ float s[7][kBlock];
+    float r[7] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY, 0.0f};
+    for (int b = threadIdx.x; b < blocks; b += kBlock) {
+        for (int j = 0; j < 3; j++) r[j] = fminf(r[j], part[b * 8 + j]);
+        for (int j = 3; j < 6; j++) r[j] = fmaxf(r[j], part[b * 8 + j]);
+        r[6] = fmaxf(r[6], part[b * 8 + 6]);
+    }
+    for (int j = 0; j < 7; j++) s[j][threadIdx.x] = r[j];
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            for (int j = 0; j < 3; j++) s[j][threadIdx.x] = fminf(s[j][threadIdx.x], s[j][threadIdx.x + o]);
+            for (int j = 3; j < 7; j++) s[j][threadIdx.x] = fmaxf(s[j][threadIdx.x], s[j][threadIdx.x + o]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 7) out[threadIdx.x] = s[threadIdx.x][0];
+}
+
+__global__ __launch_bounds__(kBlock) void k_pts_count(const float* __restrict__ p, int64_t n, Grid G, uint32_t* __restrict__ keys,
+                                                      uint32_t* __restrict__ counts)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    int cx, cy, cz;
+    const uint32_t k = key_of(G, p[3 * i], p[3 * i + 1], p[3 * i + 2], &cx, &cy, &cz);
+    keys[i] = k;
+    atomicAdd(&counts[k], 1u);
+}
+
+// exclusive scan of counts[0..m) into starts[0..m] (starts[m] = total), in place allowed: blocks of kScanItems, block totals
+// scanned by one block, then the block offsets added.
+constexpr int kScanItems = kBlock * 8;
+
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* s_tmp, uint32_t* total)
+{
+    // Hillis-Steele over the block's 256 values
+    s_tmp[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 1; o < kBlock; o <<= 1) {
+        const uint32_t a = (int)threadIdx.x >= o ? s_tmp[threadIdx.x - o] : 0u;
+        __syncthreads();
+        s_tmp[threadIdx.x] += a;
+        __syncthreads();
+    }
+    const uint32_t incl = s_tmp[threadIdx.x];
+    *total = s_tmp[kBlock - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(kBlock) void k_scan_blocks(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int64_t m,
+                                                        uint32_t* __restrict__ block_sums)
+{
+    __shared__ uint32_t s_tmp[kBlock];
+    const int64_t base = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * 8;
+    uint32_t v[8], sum = 0;
+    for (int j = 0; j < 8; j++) {
+        v[j] = base + j < m ? in[base + j] : 0u;
+        sum += v[j];
+    }
+    uint32_t total;
+    uint32_t run = block_exclusive_scan(sum, s_tmp, &total);
+    for (int j = 0; j < 8; j++) {
+        if (base + j < m) out[base + j] = run;
+        run += v[j];
+    }
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kBlock) void k_scan_sums(uint32_t* __restrict__ block_sums, int nb, uint32_t* __restrict__ grand)
+{
+    __shared__ uint32_t s_tmp[kBlock];
+    uint32_t carry = 0;
+    for (int b0 = 0; b0 < nb; b0 += kBlock) {
+        const int b = b0 + (int)threadIdx.x;
+        const uint32_t v = b < nb ? block_sums[b] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_exclusive_scan(v, s_tmp, &total);
+        if (b < nb) block_sums[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) *grand = carry;
+}
+
+__global__ __launch_bounds__(kBlock) void k_scan_add(uint32_t* __restrict__ out, int64_t m, const uint32_t* __restrict__ block_sums,
+                                                     const uint32_t* __restrict__ grand)
+{
+    const int64_t base = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * 8;
+    const uint32_t add = block_sums[blockIdx.x];
+    for (int j = 0; j < 8; j++)
+        if (base + j < m) out[base + j] += add;
+    if (blockIdx.x == 0 && threadIdx.x == 0) out[m] = *grand;
+}
+
+__global__ __launch_bounds__(kBlock) void k_pts_scatter(const float* __restrict__ p, int64_t n, const uint32_t* __restrict__ keys,
+                                                        uint32_t* __restrict__ cursor, float4* __restrict__ sorted)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t slot = atomicAdd(&cursor[keys[i]], 1u);
+    sorted[slot] = make_float4(p[3 * i], p[3 * i + 1], p[3 * i + 2], __int_as_float((int)i));
+}
+
+// ---- query ------------------------------------------------------------------------------------------------------------------
+struct SearchOut {
+    int32_t* index;     // any may be null
+    float* distance;
+    float* nearest3;
+    float4* cor;        // ICP: (x, y, z, distance) of the nearest point, caller order
+    unsigned long long* candidates;   // non-null: count candidates (measurement)
+};
+
+struct IcpState;
+__device__ __forceinline__ bool icp_stopped(const IcpState* S, int iter);
+
+__device__ __forceinline__ float lb_sq(const float gap[3][2], const float base2[3])
+{
+    float best = INFINITY;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float rest = base2[(a + 1) % 3] + base2[(a + 2) % 3];
+        const float gm = fminf(gap[a][0], gap[a][1]);
+        best = fminf(best, gm * gm + rest);
+    }
+    return best;
+}
+
+// One lane per query.  `icp` / `iter`: ICP iterations exit once the registration stopped.
+__global__ __launch_bounds__(kBlock) void k_pts_search(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
+                                                       float fx, float fy, float fz, const float* __restrict__ queries, int64_t nq,
+                                                       SearchOut O, const IcpState* icp, int iter)
+{
+    if (icp && icp_stopped(icp, iter)) return;
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool active = t < nq;   // (every lane stays for the candidate count's shuffle)
+    const int64_t qi = active ? t : 0;
+    const float qx = active ? queries[3 * qi] : NAN, qy = active ? queries[3 * qi + 1] : NAN, qz = active ? queries[3 * qi + 2] : NAN;
+    float best = INFINITY;
+    int bi = -1;
+    float bx = fx, by = fy, bz = fz;
+    unsigned long long ncand = 0;
+    if (isfinite(qx) && isfinite(qy) && isfinite(qz)) {
+        const float q[3] = {qx, qy, qz};
+        int c[3];
+        (void)key_of(G, qx, qy, qz, &c[0], &c[1], &c[2]);
+        const float slack = G.slack + fmaxf(fabsf(qx), fmaxf(fabsf(qy), fabsf(qz))) * 0x1p-20f;
+        float base2[3];
+        int rmax = 0;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const float out = fmaxf(fmaxf(G.lo[a] - q[a], q[a] - G.hi[a]) - slack, 0.0f);
+            base2[a] = out * out;
+            rmax = max(rmax, max(c[a], G.dim[a] - 1 - c[a]));
+        }
+        const int gx = G.dim[0], gy = G.dim[1];
+        for (int r = 0; r <= rmax; r++) {
+            const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, G.dim[2] - 1);
+            const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, gy - 1);
+            const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, gx - 1);
+            for (int z = z0; z <= z1; z++) {
+                const bool zf = z == c[2] - r || z == c[2] + r;
+                for (int y = y0; y <= y1; y++) {
+                    const bool full = zf || y == c[1] - r || y == c[1] + r;
+                    const uint32_t row = ((uint32_t)z * (uint32_t)gy + (uint32_t)y) * (uint32_t)gx;
+                    // a full row of the shell is one contiguous range of the sorted points; otherwise its two end cells
+                    for (int part = 0; part < (full ? 1 : 2); part++) {
+                        int xa, xb;
+                        if (full) { xa = x0; xb = x1; }
+                        else {
+                            xa = xb = part == 0 ? c[0] - r : c[0] + r;
+                            if (xa < 0 || xa >= gx) continue;
+                        }
+                        const uint32_t j0 = starts[row + (uint32_t)xa], j1 = starts[row + (uint32_t)xb + 1];
+                        ncand += j1 - j0;
+                        for (uint32_t j = j0; j < j1; j++) {
+                            const float4 s = sorted[j];
+                            const float dx = qx - s.x, dy = qy - s.y, dz = qz - s.z;
+                            const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                            const int id = __float_as_int(s.w);
+                            if (d2 < best || (d2 == best && id < bi)) { best = d2; bi = id; bx = s.x; by = s.y; bz = s.z; }
+                        }
+                    }
+                }
+            }
+            // every unvisited cell lies beyond shell r along some axis: the least distance it can have, made conservative
+            float gap[3][2];
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                gap[a][0] = c[a] - r - 1 >= 0 ? fmaxf(q[a] - (G.lo[a] + (float)(c[a] - r) * G.h) - slack, 0.0f) : INFINITY;
+                gap[a][1] = c[a] + r + 1 < G.dim[a] ? fmaxf((G.lo[a] + (float)(c[a] + r + 1) * G.h) - q[a] - slack, 0.0f) : INFINITY;
+            }
+            if (lb_sq(gap, base2) * (1.0f - 0x1p-18f) > best) break;
+        }
+    }
+    const float dist = bi < 0 ? FLT_MAX : (float)__builtin_sqrt((double)best);   // (correctly rounded sqrtf)
+    if (O.candidates) {
+        for (int o = 32; o > 0; o >>= 1) ncand += __shfl_down(ncand, o);
+        if ((threadIdx.x & 63) == 0) atomicAdd(O.candidates, ncand);
+    }
+    if (!active) return;
+    if (O.index) O.index[qi] = bi;
+    if (O.distance) O.distance[qi] = dist;
+    if (O.nearest3) { O.nearest3[3 * qi] = bx; O.nearest3[3 * qi + 1] = by; O.nearest3[3 * qi + 2] = bz; }
+    if (O.cor) O.cor[qi] = make_float4(bx, by, bz, dist);
+}
+
+// ---- ICP --------------------------------------------------------------------------------------------------------------------
+struct IcpState {
+    double part[kRedBlocks][9];   // per-block partial sums of the current reduction
+    double dist_mean;             // this iteration's distance mean (f64)
+    float dist_max;               // this iteration's filter
+    double pmean[3], qmean[3];    // filtered means (f64)
+    float step[16], total[16];    // row-major M11..M44
+    int iters;                    // iterations completed
+    int stop;                     // converged or max_iterations reached
+    int converged;
+};
+
+__device__ __forceinline__ bool icp_stopped(const IcpState* S, int iter) { return S->stop && S->iters <= iter; }
+
+// fixed-order block sum of K doubles per thread; thread 0 gets the block's totals
+template <int K>
+__device__ __forceinline__ void block_sum(double (&v)[K], double (*s)[kBlock])
+{
+#pragma unroll
+    for (int j = 0; j < K; j++) s[j][threadIdx.x] = v[j];
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o)
+#pragma unroll
+            for (int j = 0; j < K; j++) s[j][threadIdx.x] += s[j][threadIdx.x + o];
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < K; j++) v[j] = s[j][0];
+}
+
+struct IcpArgs {
+    float* points;        // n x 3, moved in place
+    const float4* cor;    // nearest static point + distance per point
+    int64_t n;
+    float good, conv_t, conv_r;
+    int max_iters;
+    IcpState* S;
+};
+
+// one block: the partials of the last pass (columns OFF .. OFF + K - 1) -> `out` (fixed order: thread t sums partials t,
+// t + 256, ..., then a tree): the same result in every block that calls it
+template <int K, int OFF = 0>
+__device__ __forceinline__ void reduce_parts(const IcpState* S, double (&out)[K], double (*s)[kBlock])
+{
+#pragma unroll
+    for (int j = 0; j < K; j++) out[j] = 0.0;
+    for (int b = threadIdx.x; b < kRedBlocks; b += kBlock)
+#pragma unroll
+        for (int j = 0; j < K; j++) out[j] += S->part[b][OFF + j];
+    block_sum<K>(out, s);
+}
+
+// pass 1: sum d -> part[b][0]
+__global__ __launch_bounds__(kBlock) void k_icp_dsum(IcpArgs A, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;
+    __shared__ double s[1][kBlock];
+    double v[1] = {0.0};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) v[0] += A.cor[i].w;
+    block_sum<1>(v, s);
+    if (threadIdx.x == 0) A.S->part[blockIdx.x][0] = v[0];
+}
+
+// pass 2: the mean (every block reduces pass 1's partials alike), then sum (d - mean)^2 -> part[b][1], the reference's
+// two-pass form (IterativeClosestPoint.cs:95-100)
+__global__ __launch_bounds__(kBlock) void k_icp_dvar(IcpArgs A, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;
+    __shared__ double s[1][kBlock];
+    double m[1];
+    reduce_parts<1, 0>(A.S, m, s);
+    const double mean = m[0] / (double)A.n;
+    __syncthreads();   // (s is reused)
+    double v[1] = {0.0};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
+        const double d = (double)A.cor[i].w - mean;
+        v[0] += d * d;
+    }
+    block_sum<1>(v, s);
+    if (threadIdx.x == 0) {
+        A.S->part[blockIdx.x][1] = v[0];
+        if (blockIdx.x == 0) A.S->dist_mean = mean;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_icp_dstats(IcpArgs A, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;
+    __shared__ double s[1][kBlock];
+    double r[1];
+    reduce_parts<1, 1>(A.S, r, s);
+    if (threadIdx.x != 0) return;
+    // mean and standard deviation in f64, rounded to f32; distMax in the reference's f32 (IterativeClosestPoint.cs:101-114)
+    const double mean = A.S->dist_mean;
+    const float m = (float)mean, sd = (float)__builtin_sqrt(r[0] / (double)A.n);
+    float dmax;
+    if (m < A.good) dmax = m + 3.0f * sd;
+    else if (m < 3.0f * A.good) dmax = m + 2.0f * sd;
+    else if (m < 6.0f * A.good) dmax = m + sd;
+    else dmax = (m + 0.5f) + sd;
+    A.S->dist_max = dmax;
+}
+
+// pass 2: count, sum p, sum q of the points with dist <= distMax
+__global__ __launch_bounds__(kBlock) void k_icp_fsum(IcpArgs A, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;
+    __shared__ double s[7][kBlock];
+    const float dmax = A.S->dist_max;
+    double v[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
+        const float4 c = A.cor[i];
+        if (c.w <= dmax) {
+            v[0] += 1.0;
+            v[1] += A.points[3 * i]; v[2] += A.points[3 * i + 1]; v[3] += A.points[3 * i + 2];
+            v[4] += c.x; v[5] += c.y; v[6] += c.z;
+        }
+    }
+    block_sum<7>(v, s);
+    if (threadIdx.x == 0)
+        for (int j = 0; j < 7; j++) A.S->part[blockIdx.x][j] = v[j];
+}
+
+__global__ __launch_bounds__(kBlock) void k_icp_means(IcpArgs A, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;
+    __shared__ double s[7][kBlock];
+    double r[7];
+    reduce_parts<7>(A.S, r, s);
+    if (threadIdx.x != 0) return;
+    for (int j = 0; j < 3; j++) { A.S->pmean[j] = r[1 + j] / r[0]; A.S->qmean[j] = r[4 + j] / r[0]; }
+}
+
+// pass 3: C = sum (p - pmean)(q - qmean)^T over the filtered points
+__global__ __launch_bounds__(kBlock) void k_icp_csum(IcpArgs A, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;
+    __shared__ double s[9][kBlock];
+    const float dmax = A.S->dist_max;
+    const double pm0 = A.S->pmean[0], pm1 = A.S->pmean[1], pm2 = A.S->pmean[2];
+    const double qm0 = A.S->qmean[0], qm1 = A.S->qmean[1], qm2 = A.S->qmean[2];
+    double v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
+        const float4 c = A.cor[i];
+        if (c.w <= dmax) {
+            const double p[3] = {A.points[3 * i] - pm0, A.points[3 * i + 1] - pm1, A.points[3 * i + 2] - pm2};
+            const double q[3] = {c.x - qm0, c.y - qm1, c.z - qm2};
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+#pragma unroll
+                for (int b = 0; b < 3; b++) v[3 * a + b] += p[a] * q[b];
+        }
+    }
+    block_sum<9>(v, s);
+    if (threadIdx.x == 0)
+        for (int j = 0; j < 9; j++) A.S->part[blockIdx.x][j] = v[j];
+}
+
+// ---- the f32 Matrix4x4 arithmetic of System.Numerics (software forms, as sdfkit_amd/raymarch.py restates them) ----
+__device__ void m4_mul(const float* a, const float* b, float* r)
+{
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++)
+            r[4 * i + j] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a[4 * i], b[j]), __fmul_rn(a[4 * i + 1], b[4 + j])),
+                                               __fmul_rn(a[4 * i + 2], b[8 + j])), __fmul_rn(a[4 * i + 3], b[12 + j]));
+}
+
+__device__ bool m4_invert(const float* s, float* R)
+{
+    const float a = s[0], b = s[1], c = s[2], d = s[3], e = s[4], f = s[5], gq = s[6], h = s[7];
+    const float i = s[8], j = s[9], k = s[10], l = s[11], m = s[12], n = s[13], o = s[14], p = s[15];
+    const float kp_lo = k * p - l * o, jp_ln = j * p - l * n, jo_kn = j * o - k * n, ip_lm = i * p - l * m, io_km = i * o - k * m, in_jm = i * n - j * m;
+    const float a11 = +(f * kp_lo - gq * jp_ln + h * jo_kn), a12 = -(e * kp_lo - gq * ip_lm + h * io_km);
+    const float a13 = +(e * jp_ln - f * ip_lm + h * in_jm), a14 = -(e * jo_kn - f * io_km + gq * in_jm);
+    const float det = a * a11 + b * a12 + c * a13 + d * a14;
+    if (fabsf(det) < 1.1920929e-07f) {
+        for (int q = 0; q < 16; q++) R[q] = __int_as_float(0x7fc00000);
+        return false;
+    }
+    const float inv = 1.0f / det;
+    R[0] = a11 * inv; R[4] = a12 * inv; R[8] = a13 * inv; R[12] = a14 * inv;
+    R[1] = -(b * kp_lo - c * jp_ln + d * jo_kn) * inv; R[5] = +(a * kp_lo - c * ip_lm + d * io_km) * inv;
+    R[9] = -(a * jp_ln - b * ip_lm + d * in_jm) * inv; R[13] = +(a * jo_kn - b * io_km + c * in_jm) * inv;
+    const float gp_ho = gq * p - h * o, fp_hn = f * p - h * n, fo_gn = f * o - gq * n, ep_hm = e * p - h * m, eo_gm = e * o - gq * m, en_fm = e * n - f * m;
+    R[2] = +(b * gp_ho - c * fp_hn + d * fo_gn) * inv; R[6] = -(a * gp_ho - c * ep_hm + d * eo_gm) * inv;
+    R[10] = +(a * fp_hn - b * ep_hm + d * en_fm) * inv; R[14] = -(a * fo_gn - b * eo_gm + c * en_fm) * inv;
+    const float gl_hk = gq * l - h * k, fl_hj = f * l - h * j, fk_gj = f * k - gq * j, el_hi = e * l - h * i, ek_gi = e * k - gq * i, ej_fi = e * j - f * i;
+    R[3] = -(b * gl_hk - c * fl_hj + d * fk_gj) * inv; R[7] = +(a * gl_hk - c * el_hi + d * ek_gi) * inv;
+    R[11] = -(a * fl_hj - b * el_hi + d * ej_fi) * inv; R[15] = +(a * fk_gj - b * ek_gi + c * ej_fi) * inv;
+    return true;
+}
+
+// C = U S V^T (f64, one-sided Jacobi on the columns of C); returns R = V diag(1, 1, sign det(V U^T)) U^T.  U and V are
+// orthogonal whatever the rank: u3 = u1 x u2 (R does not depend on the sign of u3: det(V U^T) flips with it), and u2 is
+// completed with a cross product when sigma2 vanishes.
+__device__ void kabsch_r(const double C[9], double R[9])
+{
+    double W[3][3], V[3][3];   // W = C V, columns orthogonalised
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) { W[a][b] = C[3 * a + b]; V[a][b] = a == b ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < 60; sweep++) {
+        bool rotated = false;
+        for (int i = 0; i < 2; i++)
+            for (int j = i + 1; j < 3; j++) {
+                double al = 0, be = 0, ga = 0;
+                for (int k = 0; k < 3; k++) { al += W[k][i] * W[k][i]; be += W[k][j] * W[k][j]; ga += W[k][i] * W[k][j]; }
+                if (ga == 0.0 || fabs(ga) <= 1e-15 * __builtin_sqrt(al * be)) continue;
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + __builtin_sqrt(1.0 + zeta * zeta));
+                const double cs = 1.0 / __builtin_sqrt(1.0 + t * t), sn = cs * t;
+                for (int k = 0; k < 3; k++) {
+                    const double wi = W[k][i], wj = W[k][j];
+                    W[k][i] = cs * wi - sn * wj; W[k][j] = sn * wi + cs * wj;
+                    const double vi = V[k][i], vj = V[k][j];
+                    V[k][i] = cs * vi - sn * vj; V[k][j] = sn * vi + cs * vj;
+                }
+            }
+        if (!rotated) break;
+    }
+    double sg[3];
+    int ord[3] = {0, 1, 2};
+    for (int i = 0; i < 3; i++) sg[i] = __builtin_sqrt(W[0][i] * W[0][i] + W[1][i] * W[1][i] + W[2][i] * W[2][i]);
+    for (int i = 0; i < 2; i++)   // descending singular values
+        for (int j = 0; j < 2 - i; j++)
+            if (sg[ord[j]] < sg[ord[j + 1]]) { const int t = ord[j]; ord[j] = ord[j + 1]; ord[j + 1] = t; }
+    double U[3][3], Vs[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int k = 0; k < 3; k++) Vs[k][i] = V[k][ord[i]];
+    const double s0 = sg[ord[0]], s1 = sg[ord[1]];
+    if (s0 == 0.0) {   // C = 0: U = V = I
+        for (int a = 0; a < 3; a++)
+            for (int b = 0; b < 3; b++) { U[a][b] = a == b; Vs[a][b] = a == b; }
+    } else {
+        for (int k = 0; k < 3; k++) U[k][0] = W[k][ord[0]] / s0;
+        if (s1 > 1e-12 * s0) {
+            for (int k = 0; k < 3; k++) U[k][1] = W[k][ord[1]] / s1;
+        } else {   // any unit vector orthogonal to u1
+            const double ax = fabs(U[0][0]), ay = fabs(U[1][0]), az = fabs(U[2][0]);
+            double e[3] = {0, 0, 0};
+            e[ax <= ay && ax <= az ? 0 : (ay <= az ? 1 : 2)] = 1.0;
+            double w[3] = {U[1][0] * e[2] - U[2][0] * e[1], U[2][0] * e[0] - U[0][0] * e[2], U[0][0] * e[1] - U[1][0] * e[0]};
+            const double l = __builtin_sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+            for (int k = 0; k < 3; k++) U[k][1] = w[k] / l;
+        }
+        U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
+        U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
+        U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
+    }
+    // sign det(V U^T) = sign det V * det U, det U = +1 by construction
+    const double detv = Vs[0][0] * (Vs[1][1] * Vs[2][2] - Vs[1][2] * Vs[2][1]) - Vs[0][1] * (Vs[1][0] * Vs[2][2] - Vs[1][2] * Vs[2][0]) +
+                        Vs[0][2] * (Vs[1][0] * Vs[2][1] - Vs[1][1] * Vs[2][0]);
+    const double d3 = detv > 0 ? 1.0 : (detv < 0 ? -1.0 : 0.0);
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) R[3 * a + b] = Vs[a][0] * U[b][0] + Vs[a][1] * U[b][1] + d3 * Vs[a][2] * U[b][2];
+}
+
+__global__ __launch_bounds__(kBlock) void k_icp_solve(IcpArgs A, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;
+    __shared__ double s[9][kBlock];
+    double Cs[9];
+    reduce_parts<9>(A.S, Cs, s);
+    if (threadIdx.x != 0) return;
+    IcpState* S = A.S;
+    double Rd[9];
+    kabsch_r(Cs, Rd);
+    float rm[16] = {(float)Rd[0], (float)Rd[1], (float)Rd[2], 0, (float)Rd[3], (float)Rd[4], (float)Rd[5], 0,
+                    (float)Rd[6], (float)Rd[7], (float)Rd[8], 0, 0, 0, 0, 1};
+    const float pm[3] = {(float)S->pmean[0], (float)S->pmean[1], (float)S->pmean[2]};
+    const float qm[3] = {(float)S->qmean[0], (float)S->qmean[1], (float)S->qmean[2]};
+    float inv_r[16], tm[16], xf[16], step[16], tot[16];
+    m4_invert(rm, inv_r);
+    float tr[3];
+    for (int j = 0; j < 3; j++)   // Vector3.Transform(pmean, invR) - qmean
+        tr[j] = __fsub_rn(__fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(pm[0], inv_r[j]), __fmul_rn(pm[1], inv_r[4 + j])), __fmul_rn(pm[2], inv_r[8 + j])),
+                                    inv_r[12 + j]), qm[j]);
+    for (int q = 0; q < 16; q++) tm[q] = (q % 5 == 0) ? 1.0f : 0.0f;
+    tm[12] = tr[0]; tm[13] = tr[1]; tm[14] = tr[2];
+    m4_mul(rm, tm, xf);
+    m4_invert(xf, step);
+    // convergence on the step (IterativeClosestPoint.cs:66-69) and total = total * step (:72)
+    const float drot = __fadd_rn(__fadd_rn(fabsf(__fsub_rn(1.0f, step[0])), fabsf(__fsub_rn(1.0f, step[5]))), fabsf(__fsub_rn(1.0f, step[10])));
+    const float dtrans = (float)__builtin_sqrt((double)__fadd_rn(__fadd_rn(__fmul_rn(step[12], step[12]), __fmul_rn(step[13], step[13])), __fmul_rn(step[14], step[14])));   // Vector3.Length
+    const bool conv = dtrans <= A.conv_t && drot <= A.conv_r;
+    m4_mul(S->total, step, tot);
+    for (int q = 0; q < 16; q++) { S->step[q] = step[q]; S->total[q] = tot[q]; }
+    S->iters = iter + 1;
+    S->converged = conv;
+    S->stop = conv || iter + 1 >= A.max_iters;
+}
+
+__global__ __launch_bounds__(kBlock) void k_icp_apply(IcpArgs A, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;   // (the iteration that stopped the registration still moves the points)
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= A.n) return;
+    const float* m = A.S->step;
+    const float x = A.points[3 * i], y = A.points[3 * i + 1], z = A.points[3 * i + 2];
+    float o[3];
+    for (int j = 0; j < 3; j++)
+        o[j] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(x, m[j]), __fmul_rn(y, m[4 + j])), __fmul_rn(z, m[8 + j])), m[12 + j]);
+    A.points[3 * i] = o[0]; A.points[3 * i + 1] = o[1]; A.points[3 * i + 2] = o[2];
+}
+
+__global__ void k_icp_init(IcpState* S)
+{
+    if (threadIdx.x != 0) return;
+    for (int q = 0; q < 16; q++) { S->total[q] = (q % 5 == 0) ? 1.0f : 0.0f; S->step[q] = S->total[q]; }
+    S->iters = 0;
+    S->stop = 0;
+    S->converged = 0;
+}
+
+unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock); }
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// the handle
+// ---------------------------------------------------------------------------------------------------------------------------
+struct sdfk_points {
+    DeviceState* owner = &cur_state();
+    int64_t n = 0;
+    float* xyz = nullptr;          // n x 3, insertion order (the source of every rebuild)
+    float4* sorted = nullptr;      // n, cell order: (x, y, z, bits(index))
+    uint32_t* starts = nullptr;    // cells + 1
+    int64_t cells = 0;
+    Grid G{};
+    float first[3] = {0, 0, 0};
+    int64_t last_candidates = 0, last_queries = 0;
+};
+
+namespace {
+
+void points_release(sdfk_points* s)
+{
+    dev_free(s->xyz);
+    dev_free(s->sorted);
+    dev_free(s->starts);
+    s->xyz = nullptr;
+    s->sorted = nullptr;
+    s->starts = nullptr;
+}
+
+int scan_launch(uint32_t* buf, int64_t m, uint32_t* aux /* >= nb + 1 */)
+{
+    const int64_t nb = (m + kScanItems - 1) / kScanItems;
+    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)std::max<int64_t>(nb, 1)), dim3(kBlock), 0, g.stream, buf, buf, m, aux);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, g.stream, aux, (int)std::max<int64_t>(nb, 1), aux + std::max<int64_t>(nb, 1));
+    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)std::max<int64_t>(nb, 1)), dim3(kBlock), 0, g.stream, buf, m, aux, aux + std::max<int64_t>(nb, 1));
+    HIPCHK(hipGetLastError());
+    return SDFK_OK;
+}
+
+// (Re)builds the search structure of s from s->xyz (synchronises: the host reads the bounding box to size the grid).  Refuses
+// non-finite points.
+int points_build(sdfk_points* s, const char* who)
+{
+    const int64_t n = s->n;
+    const unsigned bb = (unsigned)std::min<int64_t>(1024, (n + kBlock - 1) / kBlock);
+    float* part = nullptr;
+    float* box_dev = nullptr;
+    int r = dev_alloc((void**)&part, (size_t)bb * 8 * sizeof(float));
+    if (!r) r = dev_alloc((void**)&box_dev, 8 * sizeof(float));
+    if (r) { dev_free(part); return r; }
+    {
+        ProfScope ps("k_pts_bounds");
+        hipLaunchKernelGGL(k_pts_bounds, dim3(bb), dim3(kBlock), 0, g.stream, s->xyz, n, part);
+        hipLaunchKernelGGL(k_pts_bounds_final, dim3(1), dim3(kBlock), 0, g.stream, part, (int)bb, box_dev);
+    }
+    float box[8] = {};
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(box, box_dev, 7 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->first, s->xyz, 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    dev_free(part);
+    dev_free(box_dev);
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (box[6] > 0) return fail(SDFK_ERR_INVALID, "%s: a static point has a NaN or infinite coordinate", who);
+
+    s->G = grid_for_box(box, box + 3, n);
+    s->cells = (int64_t)s->G.dim[0] * s->G.dim[1] * s->G.dim[2];
+    const int64_t nb = (s->cells + 1 + kScanItems - 1) / kScanItems;
+    uint32_t* keys = nullptr;
+    uint32_t* aux = nullptr;
+    uint32_t* cursor = nullptr;
+    dev_free(s->sorted);
+    dev_free(s->starts);
+    s->sorted = nullptr;
+    s->starts = nullptr;
+    r = dev_alloc((void**)&s->sorted, (size_t)n * sizeof(float4));
+    if (!r) r = dev_alloc((void**)&s->starts, (size_t)(s->cells + 1) * sizeof(uint32_t));
+    if (!r) r = dev_alloc((void**)&keys, (size_t)n * sizeof(uint32_t));
+    if (!r) r = dev_alloc((void**)&aux, (size_t)(nb + 2) * sizeof(uint32_t));
+    if (!r) r = dev_alloc((void**)&cursor, (size_t)(s->cells + 1) * sizeof(uint32_t));
+    if (!r) {
+        ProfScope ps("k_pts_build");
+        e = hipMemsetAsync(s->starts, 0, (size_t)(s->cells + 1) * sizeof(uint32_t), g.stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_pts_count, dim3(grid1(n)), dim3(kBlock), 0, g.stream, s->xyz, n, s->G, keys, s->starts);
+            r = scan_launch(s->starts, s->cells, aux);
+        }
+        if (!r && e == hipSuccess) e = hipMemcpyAsync(cursor, s->starts, (size_t)s->cells * sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream);
+        if (!r && e == hipSuccess)
+            hipLaunchKernelGGL(k_pts_scatter, dim3(grid1(n)), dim3(kBlock), 0, g.stream, s->xyz, n, keys, cursor, s->sorted);
+        if (e == hipSuccess) e = hipGetLastError();
+    }
+    dev_free(keys);
+    dev_free(aux);
+    dev_free(cursor);
+    if (r) return r;
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return SDFK_OK;
+}
+
+// Queues the search of nq device queries (caller order in and out).  `icp`/`iter`: the launch of an ICP iteration.
+int points_search_launch(const sdfk_points* s, const float* q, int64_t nq, SearchOut O, const IcpState* icp, int iter)
+{
+    unsigned long long* cand = nullptr;
+    int r = SDFK_OK;
+    if (g.prof_on && !icp) {
+        r = dev_alloc((void**)&cand, sizeof(unsigned long long));
+        if (!r && hipMemsetAsync(cand, 0, sizeof(unsigned long long), g.stream) != hipSuccess) r = fail(SDFK_ERR_HIP, "points search: memset");
+        if (r) { dev_free(cand); return r; }
+        O.candidates = cand;
+    }
+    {
+        ProfScope ps("k_pts_search");
+        hipLaunchKernelGGL(k_pts_search, dim3(grid1(nq)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, s->first[0], s->first[1],
+                           s->first[2], q, nq, O, icp, iter);
+    }
+    hipError_t e = hipGetLastError();
+    if (cand) {
+        unsigned long long c = 0;
+        if (e == hipSuccess) e = hipMemcpyAsync(&c, cand, sizeof c, hipMemcpyDeviceToHost, g.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+        const_cast<sdfk_points*>(s)->last_candidates = (int64_t)c;
+        const_cast<sdfk_points*>(s)->last_queries = nq;
+        dev_free(cand);
+    }
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "points search: %s", hipGetErrorString(e));
+    return SDFK_OK;
+}
+
+int points_make(const void* pts, int64_t n, bool device, sdfk_points** out)
+{
+    if (int r = require_init()) return r;
+    if (!out) return fail(SDFK_ERR_INVALID, "sdfk_points_create: null argument");
+    *out = nullptr;
+    if (n < 1) return fail(SDFK_ERR_INVALID, "sdfk_points_create: at least one point must be given");
+    if (!pts) return fail(SDFK_ERR_INVALID, "sdfk_points_create: null points");
+    if (n >= (int64_t(1) << 31)) return fail(SDFK_ERR_INVALID, "sdfk_points_create: 2^31 points or more");
+    sdfk_points* s = new sdfk_points();
+    s->n = n;
+    int r = dev_alloc((void**)&s->xyz, (size_t)n * 3 * sizeof(float));
+    if (!r) {
+        const hipError_t e = hipMemcpyAsync(s->xyz, pts, (size_t)n * 3 * sizeof(float), device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                            g.stream);
+        if (e != hipSuccess) r = fail(SDFK_ERR_HIP, "sdfk_points_create: %s", hipGetErrorString(e));
+    }
+    if (!r) r = points_build(s, "sdfk_points_create");   // (synchronises: the caller's host array is not retained)
+    if (r) {
+        points_release(s);
+        delete s;
+        return r;
+    }
+    *out = s;
+    return SDFK_OK;
+}
+
+int points_append(sdfk_points* s, const void* pts, int64_t n, bool device)
+{
+    if (int r = require_init()) return r;
+    if (!s || n < 0 || (n > 0 && !pts)) return fail(SDFK_ERR_INVALID, "sdfk_points_add: null / negative argument");
+    if (s->n + n >= (int64_t(1) << 31)) return fail(SDFK_ERR_INVALID, "sdfk_points_add: 2^31 static points or more");
+    if (n == 0) return SDFK_OK;
+    // the concatenation, rebuilt; on a refusal the set stays as it was
+    sdfk_points t = *s;
+    t.n = s->n + n;
+    t.xyz = nullptr;
+    t.sorted = nullptr;
+    t.starts = nullptr;
+    int r = dev_alloc((void**)&t.xyz, (size_t)t.n * 3 * sizeof(float));
+    if (!r) {
+        hipError_t e = hipMemcpyAsync(t.xyz, s->xyz, (size_t)s->n * 3 * sizeof(float), hipMemcpyDeviceToDevice, g.stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(t.xyz + s->n * 3, pts, (size_t)n * 3 * sizeof(float), device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, g.stream);
+        if (e != hipSuccess) r = fail(SDFK_ERR_HIP, "sdfk_points_add: %s", hipGetErrorString(e));
+    }
+    if (!r) r = points_build(&t, "sdfk_points_add");
+    if (r) {
+        points_release(&t);
+        return r;
+    }
+    points_release(s);
+    *s = t;
+    return SDFK_OK;
+}
+
+int icp_run(sdfk_points* s, const sdfk_icp_params* prm, float* pts_dev, int64_t n, float total[16], int32_t* iterations)
+{
+    IcpState* S = nullptr;
+    float4* cor = nullptr;
+    int r = dev_alloc((void**)&S, sizeof(IcpState));
+    if (!r) r = dev_alloc((void**)&cor, (size_t)n * sizeof(float4));
+    IcpArgs A{pts_dev, cor, n, prm->good_correspondence_distance, prm->converged_max_translation, prm->converged_max_rotation, prm->max_iterations, S};
+    hipError_t e = hipSuccess;
+    struct { float total[16]; int iters, stop, converged; } host{};
+    for (int q = 0; q < 16; q++) host.total[q] = (q % 5 == 0) ? 1.0f : 0.0f;
+    if (!r && prm->max_iterations > 0) {
+        hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, g.stream, S);
+        // Iterations are queued in chunks; the launches of an iteration after the one that stopped the registration exit at once
+        // (they read the device flag), and the host looks at the flag between chunks.
+        constexpr int kChunk = 4;
+        for (int it0 = 0; !r && e == hipSuccess && it0 < prm->max_iterations; it0 += kChunk) {
+            for (int it = it0; it < std::min(it0 + kChunk, prm->max_iterations) && !r; it++) {
+                SearchOut O{nullptr, nullptr, nullptr, cor, nullptr};
+                r = points_search_launch(s, pts_dev, n, O, S, it);
+                if (r) break;
+                ProfScope ps("k_icp_step");
+                hipLaunchKernelGGL(k_icp_dsum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
+                hipLaunchKernelGGL(k_icp_dvar, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
+                hipLaunchKernelGGL(k_icp_dstats, dim3(1), dim3(kBlock), 0, g.stream, A, it);
+                hipLaunchKernelGGL(k_icp_fsum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
+                hipLaunchKernelGGL(k_icp_means, dim3(1), dim3(kBlock), 0, g.stream, A, it);
+                hipLaunchKernelGGL(k_icp_csum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
+                hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(kBlock), 0, g.stream, A, it);
+                hipLaunchKernelGGL(k_icp_apply, dim3(grid1(n)), dim3(kBlock), 0, g.stream, A, it);
+                e = hipGetLastError();
+            }
+            if (r || e != hipSuccess) break;
+            e = hipMemcpyAsync(&host, &S->total, sizeof host, hipMemcpyDeviceToHost, g.stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+            if (e != hipSuccess || host.stop) break;
+        }
+    }
+    dev_free(cor);
+    dev_free(S);
+    if (r) return r;
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_icp_register: %s", hipGetErrorString(e));
+    for (int q = 0; q < 16; q++) total[q] = host.total[q];
+    *iterations = host.iters;
+    return SDFK_OK;
+}
+
+int icp_check(sdfk_points* s, const sdfk_icp_params* prm, const void* pts, int64_t n, float* total, int32_t* iterations)
+{
+    if (int r = require_init()) return r;
+    if (!s || !prm || !total || !iterations || n < 0 || (n > 0 && !pts)) return fail(SDFK_ERR_INVALID, "sdfk_icp_register: null / negative argument");
+    if (n == 0) return fail(SDFK_ERR_INVALID, "sdfk_icp_register: no dynamic points");
+    if (n >= (int64_t(1) << 31)) return fail(SDFK_ERR_INVALID, "sdfk_icp_register: 2^31 points or more");
+    if (prm->max_iterations < 0) return fail(SDFK_ERR_INVALID, "sdfk_icp_register: negative max_iterations");
+    return SDFK_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// entry points
+// ---------------------------------------------------------------------------------------------------------------------------
+extern "C" int sdfk_points_create(const float* points3, int64_t n, sdfk_points** out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    return points_make(points3, n, false, out);
+}
+
+extern "C" int sdfk_points_create_device(const void* points3_dev, int64_t n, sdfk_points** out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    return points_make(points3_dev, n, true, out);
+}
+
+extern "C" int sdfk_points_add(sdfk_points* s, const float* points3, int64_t n)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    return points_append(s, points3, n, false);
+}
+
+extern "C" int sdfk_points_add_device(sdfk_points* s, const void* points3_dev, int64_t n)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    return points_append(s, points3_dev, n, true);
+}
+
+extern "C" int sdfk_points_count(const sdfk_points* s, int64_t* n)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);   // (sdfk_points_add replaces the set under the lock)
+    if (!s || !n) return fail(SDFK_ERR_INVALID, "sdfk_points_count: null argument");
+    *n = s->n;
+    return SDFK_OK;
+}
+
+extern "C" int sdfk_points_stats(const sdfk_points* s, int64_t stats[5])
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!s || !stats) return fail(SDFK_ERR_INVALID, "sdfk_points_stats: null argument");
+    stats[0] = s->G.dim[0];
+    stats[1] = s->G.dim[1];
+    stats[2] = s->G.dim[2];
+    stats[3] = s->last_candidates;
+    stats[4] = s->last_queries;
+    return SDFK_OK;
+}
+
+extern "C" int sdfk_points_search_device(const sdfk_points* s, const void* queries3_dev, int64_t n, void* index_dev, void* distance_dev,
+                                         void* nearest3_dev)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = require_init()) return r;
+    if (!s || n < 0 || (n > 0 && !queries3_dev)) return fail(SDFK_ERR_INVALID, "sdfk_points_search: null / negative argument");
+    if (n >= (int64_t(1) << 32)) return fail(SDFK_ERR_INVALID, "sdfk_points_search: 2^32 queries or more");
+    if (n == 0) return SDFK_OK;
+    SearchOut O{(int32_t*)index_dev, (float*)distance_dev, (float*)nearest3_dev, nullptr, nullptr};
+    return points_search_launch(s, (const float*)queries3_dev, n, O, nullptr, 0);
+}
+
+extern "C" int sdfk_points_search(const sdfk_points* s, const float* queries3, int64_t n, int32_t* index, float* distance, float* nearest3)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = require_init()) return r;
+    if (!s || n < 0 || (n > 0 && !queries3)) return fail(SDFK_ERR_INVALID, "sdfk_points_search: null / negative argument");
+    if (n >= (int64_t(1) << 32)) return fail(SDFK_ERR_INVALID, "sdfk_points_search: 2^32 queries or more");
+    if (n == 0) return SDFK_OK;
+    float* qd = nullptr;
+    int32_t* id = nullptr;
+    float* dd = nullptr;
+    float* nd = nullptr;
+    int r = dev_alloc((void**)&qd, (size_t)n * 3 * sizeof(float));
+    if (!r && index) r = dev_alloc((void**)&id, (size_t)n * sizeof(int32_t));
+    if (!r && distance) r = dev_alloc((void**)&dd, (size_t)n * sizeof(float));
+    if (!r && nearest3) r = dev_alloc((void**)&nd, (size_t)n * 3 * sizeof(float));
+    hipError_t e = hipSuccess;
+    if (!r) e = hipMemcpyAsync(qd, queries3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
+    if (!r && e == hipSuccess) r = points_search_launch(s, qd, n, SearchOut{id, dd, nd, nullptr, nullptr}, nullptr, 0);
+    if (!r && e == hipSuccess && id) e = hipMemcpyAsync(index, id, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
+    if (!r && e == hipSuccess && dd) e = hipMemcpyAsync(distance, dd, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, g.stream);
+    if (!r && e == hipSuccess && nd) e = hipMemcpyAsync(nearest3, nd, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
+    const hipError_t es = hipStreamSynchronize(g.stream);
+    dev_free(qd);
+    dev_free(id);
+    dev_free(dd);
+    dev_free(nd);
+    if (r) return r;
+    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_search: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    return SDFK_OK;
+}
+
+extern "C" int sdfk_icp_register_device(sdfk_points* s, const sdfk_icp_params* prm, void* points3_dev, int64_t n, float total[16],
+                                        int32_t* iterations)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = icp_check(s, prm, points3_dev, n, total, iterations)) return r;
+    return icp_run(s, prm, (float*)points3_dev, n, total, iterations);
+}
+
+extern "C" int sdfk_icp_register(sdfk_points* s, const sdfk_icp_params* prm, float* points3, int64_t n, float total[16], int32_t* iterations)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = icp_check(s, prm, points3, n, total, iterations)) return r;
+    float* pd = nullptr;
+    int r = dev_alloc((void**)&pd, (size_t)n * 3 * sizeof(float));
+    hipError_t e = hipSuccess;
+    if (!r) e = hipMemcpyAsync(pd, points3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
+    if (!r && e == hipSuccess) r = icp_run(s, prm, pd, n, total, iterations);
+    if (!r && e == hipSuccess) e = hipMemcpyAsync(points3, pd, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
+    const hipError_t es = hipStreamSynchronize(g.stream);
+    dev_free(pd);
+    if (r) return r;
+    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_icp_register: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    return SDFK_OK;
+}
+
+extern "C" void sdfk_points_free(sdfk_points* s)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    bind_thread();
+    if (!s) return;
+    if (g.inited) points_release(s);
+    delete s;
+}

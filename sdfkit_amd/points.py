@@ -1,0 +1,167 @@
+"""Host-side mirror of SdfKit's KdTree (KdTree.cs) and IterativeClosestPoint (IterativeClosestPoint.cs) over the C ABI
+entry points sdfk_points_* / sdfk_icp_* (include/sdfkit_hip.h, csrc/lib_points.hip).
+
+Vector3 is a float32 numpy array of 3; a span of Vector3 is an (n, 3) float32 array.  The search is exact (the static
+point of least d2, ties to the lowest insertion index); the structure behind it is a grid of cell lists on the device,
+so the reference's tree internals -- Left, Right, SplitValue, IsLeaf -- are not provided.  SplitAxis is kept as given.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+from .raymarch import Matrix4x4
+
+f32 = np.float32
+FLT_MAX = np.finfo(np.float32).max
+
+
+def _points(points):
+    a = np.ascontiguousarray(np.asarray(points, dtype=f32).reshape(-1, 3))
+    return a
+
+
+def _ptr(a):
+    return C.c_void_p(a.ctypes.data) if a is not None and a.size else C.c_void_p()
+
+
+class KdTree:
+    """KdTree(points, axis=0): the static points, numbered in insertion order."""
+
+    def __init__(self, points, axis=0):
+        N.init()
+        pts = _points(points)
+        h = C.c_void_p()
+        N.check(N.lib().sdfk_points_create(_ptr(pts), len(pts), C.byref(h)))
+        self._h = h
+        self.SplitAxis = int(axis)
+        self.Point = pts[0].copy()
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and h.value and N._lib is not None and N._inited_device is not None:
+            N._lib.sdfk_points_free(h)
+        self._h = None
+
+    @property
+    def handle(self):
+        """The sdfk_points* (extension: for the C ABI's device entry points)."""
+        return self._h
+
+    @property
+    def TotalPoints(self):
+        n = C.c_int64()
+        N.check(N.lib().sdfk_points_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def AddPoints(self, points):
+        pts = _points(points)
+        N.check(N.lib().sdfk_points_add(self._h, _ptr(pts), len(pts)))
+
+    def SearchMany(self, queries):
+        """Extension: every query at once -> (indices int32 (-1: none), distances float32, nearest (n, 3) float32)."""
+        q = _points(queries)
+        n = len(q)
+        idx = np.empty(n, np.int32)
+        dist = np.empty(n, f32)
+        near = np.empty((n, 3), f32)
+        if n:
+            N.check(N.lib().sdfk_points_search(self._h, _ptr(q), n, _ptr(idx), _ptr(dist), _ptr(near)))
+        return idx, dist, near
+
+    def Search(self, q):
+        """KdTree.Search(q, out nearestDistance) -> (nearest, nearestDistance)."""
+        _, d, p = self.SearchMany(np.asarray(q, f32).reshape(1, 3))
+        return p[0], f32(d[0])
+
+    def stats(self):
+        """sdfk_points_stats: {'grid': (nx, ny, nz), 'candidates', 'queries'} (candidates: last search under profiling)."""
+        s = (C.c_int64 * 5)()
+        N.check(N.lib().sdfk_points_stats(self._h, s))
+        return {"grid": (s[0], s[1], s[2]), "candidates": int(s[3]), "queries": int(s[4])}
+
+
+def _is_one_cloud(x):
+    if isinstance(x, np.ndarray):
+        return x.ndim == 2 or (x.ndim == 1 and x.size == 3)
+    try:
+        a = np.asarray(x, dtype=f32)
+    except ValueError:   # ragged: several clouds
+        return False
+    return a.ndim == 2 and a.shape[-1] == 3 and not (len(x) and isinstance(x[0], np.ndarray) and x[0].ndim == 2)
+
+
+class IterativeClosestPoint:
+    """IterativeClosestPoint(staticPoints) -- one cloud, or a list of clouds (the ReadOnlyMemory<Vector3>[] overload)."""
+
+    def __init__(self, staticPoints):
+        self.MaxIterations = 100
+        self.GoodCorrespondenceDistance = f32(0.01)
+        self.ConvergedMaximumTranslation = f32(1.0e-4)
+        self.ConvergedMaximumRotation = f32(1.0e-5)
+        self.Iterations = 0   # extension: iterations of the last RegisterPoints
+        if _is_one_cloud(staticPoints):
+            self._tree = KdTree(staticPoints)
+        else:
+            clouds = list(staticPoints)
+            if not clouds:
+                raise ValueError("At least one set of points must be given (staticPoints)")
+            self._tree = KdTree(clouds[0])
+            for c in clouds[1:]:
+                self._tree.AddPoints(c)
+
+    @property
+    def StaticTree(self):
+        return self._tree
+
+    def AddStaticPoints(self, staticPoints):
+        self._tree.AddPoints(staticPoints)
+
+    def _params(self):
+        return N.IcpParams(int(self.MaxIterations), float(f32(self.GoodCorrespondenceDistance)),
+                           float(f32(self.ConvergedMaximumTranslation)), float(f32(self.ConvergedMaximumRotation)))
+
+    def RegisterPoints(self, points):
+        """Moves `points` -- an (n, 3) float32 C-contiguous array -- in place onto the static points and returns the 4x4 float32
+        transform that did it (row-vector convention)."""
+        if not (isinstance(points, np.ndarray) and points.dtype == f32 and points.ndim == 2 and points.shape[1] == 3
+                and points.flags.c_contiguous and points.flags.writeable):
+            raise TypeError("RegisterPoints moves the points in place: pass a writable C-contiguous (n, 3) float32 array")
+        prm = self._params()
+        total = (C.c_float * 16)()
+        iters = C.c_int32()
+        N.check(N.lib().sdfk_icp_register(self._tree.handle, C.byref(prm), _ptr(points), len(points), total, C.byref(iters)))
+        self.Iterations = int(iters.value)
+        return np.array(total[:], f32).reshape(4, 4)
+
+    def RegisterDevicePoints(self, points_dev, n):
+        """Extension: RegisterPoints on n points (x, y, z float32) already in device memory (a raw pointer), moved in place."""
+        prm = self._params()
+        total = (C.c_float * 16)()
+        iters = C.c_int32()
+        N.check(N.lib().sdfk_icp_register_device(self._tree.handle, C.byref(prm), C.c_void_p(points_dev), int(n), total,
+                                                  C.byref(iters)))
+        self.Iterations = int(iters.value)
+        return np.array(total[:], f32).reshape(4, 4)
+
+    def GlobalRegisterPoints(self, *args):
+        """GlobalRegisterPoints(staticPoints, dynamicPoints) / GlobalRegisterPoints(points) (IterativeClosestPoint.cs:207-240).
+        The two-argument form registers against a NEW instance made from staticPoints, as the reference does; each registered
+        cloud then joins its static set."""
+        if len(args) == 1:
+            pts = list(args[0])
+            if not pts:
+                return []
+            if len(pts) == 1:
+                return [Matrix4x4.Identity.copy()]
+            return self.GlobalRegisterPoints(pts[:1], pts[1:])
+        staticPoints, dynamicPoints = args
+        dyn = list(dynamicPoints)
+        if not dyn:
+            return []
+        icp = IterativeClosestPoint(list(staticPoints))
+        out = []
+        for d in dyn:
+            out.append(icp.RegisterPoints(d))
+            icp.AddStaticPoints(d)
+        return out

@@ -28,6 +28,17 @@ def _tanf(x):
     return f32(_libm.tanf(C.c_float(float(x))))
 
 
+def _sincosf(x):
+    """MathF.Sin / MathF.Cos: the C runtime's sinf / cosf."""
+    global _libm
+    if _libm is None:
+        _tanf(0.0)
+    for name in ("sinf", "cosf"):
+        getattr(_libm, name).restype = C.c_float
+        getattr(_libm, name).argtypes = [C.c_float]
+    return f32(_libm.sinf(C.c_float(float(x)))), f32(_libm.cosf(C.c_float(float(x))))
+
+
 def _v3(v):
     return [f32(v[0]), f32(v[1]), f32(v[2])]
 
@@ -75,6 +86,38 @@ class Matrix4x4:
         m = np.zeros((4, 4), f32)
         m[0, 0], m[1, 1], m[2, 2], m[2, 3], m[3, 2] = xscale, yscale, nfr, f32(-1), near * nfr
         return m
+
+    Identity = np.eye(4, dtype=f32)
+
+    @staticmethod
+    def CreateTranslation(x, y=None, z=None):
+        """CreateTranslation(Vector3) or CreateTranslation(x, y, z)."""
+        if y is None:
+            x, y, z = x
+        m = np.eye(4, dtype=f32)
+        m[3, :3] = [f32(x), f32(y), f32(z)]
+        return m
+
+    @staticmethod
+    def CreateRotationX(radians):
+        s, c = _sincosf(f32(radians))
+        m = np.eye(4, dtype=f32)
+        m[1, 1], m[1, 2], m[2, 1], m[2, 2] = c, s, -s, c
+        return m
+
+    @staticmethod
+    def CreateRotationY(radians):
+        s, c = _sincosf(f32(radians))
+        m = np.eye(4, dtype=f32)
+        m[0, 0], m[0, 2], m[2, 0], m[2, 2] = c, -s, s, c
+        return m
+
+    @staticmethod
+    def Transform(v, m):
+        """Vector3.Transform(position, matrix): ((x M11 + y M21) + z M31) + M41, ... (float32, no FMA)."""
+        m = np.asarray(m, f32)
+        x, y, z = f32(v[0]), f32(v[1]), f32(v[2])
+        return np.array([((x * m[0, j] + y * m[1, j]) + z * m[2, j]) + m[3, j] for j in range(3)], f32)
 
     @staticmethod
     def Multiply(a, b):

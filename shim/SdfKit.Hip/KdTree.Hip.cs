@@ -1,0 +1,81 @@
+// KdTree.Hip.cs -- SdfKit.KdTree over sdfk_points_* (include/sdfkit_hip.h).  Replaces SdfKit/KdTree.cs: the public members
+// keep their names and meaning (KdTree.cs:8-198), the search is exact (ties to the lowest insertion index, a documented
+// deviation: the reference returns whichever point its traversal met first).  The tree internals -- Left, Right,
+// SplitValue, IsLeaf -- have no counterpart: the structure is a grid of cell lists on the GPU.
+// UNCOMPILED HERE (no .NET in the build image); sdfkit_amd/points.py's KdTree is the same layer, tested.
+using System;
+using System.Numerics;
+using SdfKit.Hip;
+
+namespace SdfKit
+{
+    public class KdTree : IDisposable
+    {
+        IntPtr handle;   // sdfk_points*
+
+        public Vector3 Point;
+        /// <summary>0 = x, 1 = y, 2 = z (kept as given; the GPU structure does not split)</summary>
+        public readonly byte SplitAxis;
+
+        public KdTree (ReadOnlySpan<Vector3> points, byte axis = 0)
+        {
+            if (points.Length == 0)
+                throw new ArgumentException ("At least on point must be given", nameof (points));
+            Native.EnsureInit ();
+            Point = points[0];
+            SplitAxis = axis;
+            unsafe {
+                fixed (Vector3* p = points)
+                    Native.Check (Native.sdfk_points_create ((float*)p, points.Length, out handle));
+            }
+        }
+
+        internal IntPtr Handle => handle;
+
+        public int TotalPoints {
+            get {
+                Native.Check (Native.sdfk_points_count (handle, out var n));
+                return (int)n;
+            }
+        }
+
+        public void AddPoints (ReadOnlySpan<Vector3> points)
+        {
+            if (points.Length == 0)
+                return;
+            unsafe {
+                fixed (Vector3* p = points)
+                    Native.Check (Native.sdfk_points_add (handle, (float*)p, points.Length));
+            }
+        }
+
+        public unsafe Vector3 Search (Vector3 q, out float nearestDistance)
+        {
+            Vector3 nearest;
+            float d;
+            Native.Check (Native.sdfk_points_search (handle, (float*)&q, 1, null, &d, (float*)&nearest));
+            nearestDistance = d;
+            return nearest;   // (no point counts: Point and float.MaxValue, as the reference)
+        }
+
+        /// <summary>Extension: every query at once; index -1 where no point counts.</summary>
+        public unsafe void Search (ReadOnlySpan<Vector3> queries, Span<int> indices, Span<float> distances, Span<Vector3> nearest)
+        {
+            if (indices.Length < queries.Length || distances.Length < queries.Length || nearest.Length < queries.Length)
+                throw new ArgumentException ("Output spans are shorter than the queries");
+            fixed (Vector3* q = queries) fixed (int* i = indices) fixed (float* d = distances) fixed (Vector3* n = nearest)
+                Native.Check (Native.sdfk_points_search (handle, (float*)q, queries.Length, i, d, (float*)n));
+        }
+
+        public void Dispose ()
+        {
+            if (handle != IntPtr.Zero) {
+                Native.sdfk_points_free (handle);
+                handle = IntPtr.Zero;
+            }
+            GC.SuppressFinalize (this);
+        }
+
+        ~KdTree () => Dispose ();
+    }
+}

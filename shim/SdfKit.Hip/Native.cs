@@ -16,6 +16,14 @@ namespace SdfKit.Hip
         public float Imm;
     }
 
+    /// <summary>struct sdfk_icp_params (include/sdfkit_hip.h)</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SdfkIcpParams
+    {
+        public int MaxIterations;
+        public float GoodCorrespondenceDistance, ConvergedMaximumTranslation, ConvergedMaximumRotation;
+    }
+
     /// <summary>enum sdfk_opcode</summary>
     public enum Op
     {
@@ -77,6 +85,20 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_dist_slab_mesh(IntPtr session, out IntPtr mesh);
         [DllImport(Lib)] public static extern void sdfk_dist_session_free(IntPtr session);
         [DllImport(Lib)] public static extern int sdfk_eval_points(IntPtr program, float* points3, long n, float* rgbw4);   // SdfEx.Sample, Sdf.cs:22-47
+        // KdTree.cs / IterativeClosestPoint.cs (KdTree.Hip.cs, IterativeClosestPoint.Hip.cs)
+        [DllImport(Lib)] public static extern int sdfk_points_create(float* points3, long n, out IntPtr points);
+        [DllImport(Lib)] public static extern int sdfk_points_create_device(IntPtr points3Dev, long n, out IntPtr points);
+        [DllImport(Lib)] public static extern int sdfk_points_add(IntPtr points, float* points3, long n);
+        [DllImport(Lib)] public static extern int sdfk_points_add_device(IntPtr points, IntPtr points3Dev, long n);
+        [DllImport(Lib)] public static extern int sdfk_points_count(IntPtr points, out long n);
+        [DllImport(Lib)] public static extern int sdfk_points_search(IntPtr points, float* queries3, long n, int* index, float* distance, float* nearest3);
+        [DllImport(Lib)] public static extern int sdfk_points_search_device(IntPtr points, IntPtr queries3Dev, long n, IntPtr indexDev, IntPtr distanceDev,
+                                                                            IntPtr nearest3Dev);
+        [DllImport(Lib)] public static extern int sdfk_points_stats(IntPtr points, long* stats5);
+        [DllImport(Lib)] public static extern void sdfk_points_free(IntPtr points);
+        [DllImport(Lib)] public static extern int sdfk_icp_register(IntPtr points, ref SdfkIcpParams prm, float* points3, long n, float* total16, out int iterations);
+        [DllImport(Lib)] public static extern int sdfk_icp_register_device(IntPtr points, ref SdfkIcpParams prm, IntPtr points3Dev, long n, float* total16,
+                                                                           out int iterations);
         // several GPUs from ONE process (the managed host is one process): include/sdfkit_hip.h, "one process, several GPUs"
         [DllImport(Lib)] public static extern int sdfk_node_open(int* devices, int nDevices, out IntPtr node);
         [DllImport(Lib)] public static extern int sdfk_node_info(IntPtr node, out int world, out int backend);
