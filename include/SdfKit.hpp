@@ -171,6 +171,7 @@ using SdfIndexedOutputModifierFunc = std::function<Vec3(Vec3 /*index*/, Vec3 /*p
 
 class Mesh;
 class Voxels;
+class MeshSdf;
 
 // The reference's `Sdf` delegate (Sdf.cs:8), restricted to SDFs that have a GPU program.
 class Sdf {
@@ -452,6 +453,7 @@ public:
     }
 
 private:
+    friend class MeshSdf;   // (writes distances straight into the device volume)
     void Ensure(bool colors)
     {
         EnsureInit();
@@ -718,6 +720,59 @@ inline void WriteTgaHeader(std::ostream& w, int imageType, int width, int height
                                  (unsigned char)(height & 255), (unsigned char)(height >> 8), (unsigned char)bpp, 0x20};
     w.write(reinterpret_cast<const char*>(h), 18);
 }
+// ---------------------------------------------------------------------------------------
+// Triangle meshes as signed distance fields (not in the reference: Mesh -> Voxels), sdfk_trimesh_* (include/sdfkit_hip.h)
+// ---------------------------------------------------------------------------------------
+class MeshSdf {
+public:
+    // The triangles of `vertices` / `triangles` (three indices each); `colors` (one per vertex) may be empty.
+    MeshSdf(const std::vector<Vector3>& vertices, const std::vector<int32_t>& triangles, const std::vector<Vector3>& colors = {})
+    {
+        EnsureInit();
+        hasColors_ = !colors.empty();
+        if (hasColors_ && colors.size() != vertices.size()) throw std::invalid_argument("one colour per vertex (colors)");
+        Check(sdfk_trimesh_create(reinterpret_cast<const float*>(vertices.data()), (int64_t)vertices.size(), triangles.data(),
+                                  (int64_t)triangles.size(), hasColors_ ? reinterpret_cast<const float*>(colors.data()) : nullptr, &h_));
+    }
+    explicit MeshSdf(const Mesh& m) : MeshSdf(m.Vertices, m.Triangles, AnyNonZero(m.Colors) ? m.Colors : std::vector<Vector3>{}) {}
+    MeshSdf(const MeshSdf&) = delete;
+    MeshSdf& operator=(const MeshSdf&) = delete;
+    ~MeshSdf() { sdfk_trimesh_free(h_); }
+    // Every query at once: the nearest triangle (-1 for a NaN / infinite query), its f32 distance and closest point.
+    void Search(const std::vector<Vector3>& queries, std::vector<int32_t>& triangle, std::vector<float>& distance, std::vector<Vector3>& closest) const
+    {
+        triangle.resize(queries.size()); distance.resize(queries.size()); closest.resize(queries.size());
+        if (queries.empty()) return;
+        Check(sdfk_trimesh_closest(h_, &queries.data()->X, (int64_t)queries.size(), triangle.data(), distance.data(), &closest.data()->X));
+    }
+    // The signed distance at the cell centres of Voxels(min, max, nx, ny, nz); distances above maxDistance become
+    // +-maxDistance.  Without a band, large volumes far from a fine mesh are slow.
+    Voxels ToVoxels(Vector3 min, Vector3 max, int nx, int ny, int nz, float maxDistance = INFINITY, bool clipToBounds = false) const
+    {
+        Voxels v(min, max, nx, ny, nz);
+        SampleInto(v, maxDistance);
+        if (clipToBounds) v.ClipToBounds();
+        return v;
+    }
+    void SampleInto(Voxels& v, float maxDistance = INFINITY) const
+    {
+        v.Ensure(hasColors_ || v.hasColors_);
+        Check(sdfk_trimesh_to_volume(h_, v.h_, maxDistance));
+        v.values_.clear();
+        v.hostNewer_ = false;
+    }
+    sdfk_trimesh* Handle() const { return h_; }
+
+private:
+    static bool AnyNonZero(const std::vector<Vector3>& c)
+    {
+        for (const Vector3& x : c) if (x.X != 0 || x.Y != 0 || x.Z != 0) return true;
+        return false;
+    }
+    sdfk_trimesh* h_ = nullptr;
+    bool hasColors_ = false;
+};
+
 struct FloatData {   // VectorData.cs:137-280; indexer is (x, y)
     int Width = 0, Height = 0;
     std::vector<float> Values;

@@ -32,7 +32,8 @@ extern "C" {
                                 6: SDFK_OPT_COLOR_PASSES; sdfk_dist_gathered refuses a step that brought this rank headers only and sdfk_dist_tune
                                    a session whose exchange mode is 2 or 3 (SDFK_ERR_UNSUPPORTED); gather-to-root has the same who-receives-what on
                                    the host transport as over RCCL; sdfk_host_alloc works in a process whose only contexts are a node's;
-                                   entry points added since, existing ones unchanged: sdfk_points_* (KdTree) and sdfk_icp_* (IterativeClosestPoint) */
+                                   entry points added since, existing ones unchanged: sdfk_points_* (KdTree), sdfk_icp_* (IterativeClosestPoint) and
+                                   sdfk_trimesh_* (triangle-mesh distance) */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -511,6 +512,53 @@ typedef struct sdfk_icp_params {
 int sdfk_icp_register(sdfk_points* s, const sdfk_icp_params* prm, float* points3, int64_t n, float total[16], int32_t* iterations);
 int sdfk_icp_register_device(sdfk_points* s, const sdfk_icp_params* prm, void* points3_dev, int64_t n, float total[16],
                              int32_t* iterations);
+
+/* ---- Triangle-mesh distance (Mesh -> Voxels) ------------------------------------------------------------------------------
+ * A triangle mesh as a signed distance field.  `triangles` holds n_indices int32 vertex indices, three per triangle; colors3
+ * (one RGB per vertex) may be NULL.  The arrays are copied: the caller's are not retained.
+ * Refused with SDFK_ERR_INVALID: no triangles, n_indices % 3 != 0, 2^31 triangles or more, n_vertices outside [1, 2^31), an
+ * index outside [0, n_vertices), a NaN or infinite vertex coordinate (any vertex, referenced or not), and a mesh whose triangles
+ * overlap 2^32 or more cells of the search grid in all (the grid has about one cell per triangle; each triangle is binned into
+ * every cell its AABB overlaps, so long diagonal slivers count for many).  The device form reads
+ * device arrays (e.g. those of sdfk_mesh_device_ptrs: no host round trip), validates them on the device and reports a refusal
+ * from the create call, which synchronises.
+ * Unsigned distance: for a query p, the triangle of least d2 wins, ties going to the lowest triangle index.  d2 is the squared
+ * distance to the closest point on the triangle, computed in binary64 from the f32 inputs by the region-based routine of
+ * csrc/trimesh_sdf.h (closest_on_triangle, no contraction); a triangle whose binary64 area term |ab x ac|^2 is exactly zero, or
+ * whose face-region numerators are not all >= 0, is measured as its three edges.  distance = (float)sqrt(d2) (correctly
+ * rounded); closest3 = the binary64 closest point rounded to f32.
+ * sdfk_trimesh_closest: triangle (-1 for a query with a NaN or infinite coordinate), distance (+inf there), closest3 (NaN there)
+ * per query; any output may be NULL; host arrays, synchronous.  _device: caller-owned device buffers, asynchronous on the
+ * library stream.
+ * sdfk_trimesh_to_volume: every voxel of `v` (a whole volume or a slab, rows padded as sdfk_volume_row_pitch says) gets the
+ * signed distance at its cell centre, the same f32 centres sdfk_sample evaluates (Voxels.cs:32-34,81,104-106: first centre
+ * min + size / n / 2, then + k size / n; slabs use their global z).  The sign counts crossings along z: a triangle crosses column
+ * (x_i, y_j) when the column point, moved by (+eps, +eps^2), lies inside its xy projection -- every edge function's sign exact
+ * (binary64 TwoSum expansion of six exact products), zero broken by the perturbation; a triangle whose exact projected area is
+ * zero covers no column.  On a closed mesh every sheet of surface along a column is counted exactly once, also where the column
+ * passes through a projected edge or vertex.  Each crossing has a binary64 z (trimesh_sdf.h z_cross); voxel (i, j, k) is inside
+ * iff the number of crossings with z < (double)z_k is odd, and its value is -d inside, d outside.  Parity needs no consistent
+ * orientation and handles nested shells; it is meaningless (but deterministic) for open and self-intersecting meshes.
+ * max_distance (>= 0; +inf: exact everywhere): voxels whose f32 distance exceeds it get +-max_distance with the exact sign (and
+ * zero colours); every other voxel equals the +inf run bit for bit, colours included.  Without a band, large volumes far from a
+ * fine mesh are slow (every voxel searches until its nearest triangle): give a band when only a shell around the surface is needed.  Colours, when the volume has them: the f32 blend of the nearest
+ * triangle's vertex colours with its closest-point weights rounded to f32, (ca wa + cb wb) + cc wc; zero when the mesh has
+ * none.  Cached sign bits of the volume are dropped, as for a write through sdfk_volume_device_ptrs.  No float atomics: results
+ * are bitwise reproducible.
+ * sdfk_trimesh_stats (diagnostics): stats[0..2] = grid cells along x, y, z; stats[3] = triangles; stats[4] = triangle-cell pairs
+ * binned; stats[5] = candidates (binary64 closest-point evaluations) of the last query or volume made while
+ * sdfk_profile_enable(1) was on, stats[6] = its query count; stats[7] = crossing records of the last sdfk_trimesh_to_volume. */
+typedef struct sdfk_trimesh sdfk_trimesh;
+int sdfk_trimesh_create(const float* vertices3, int64_t n_vertices, const int32_t* triangles, int64_t n_indices, const float* colors3,
+                        sdfk_trimesh** out);
+int sdfk_trimesh_create_device(const void* vertices3_dev, int64_t n_vertices, const void* triangles_dev, int64_t n_indices,
+                               const void* colors3_dev, sdfk_trimesh** out);
+int sdfk_trimesh_closest(const sdfk_trimesh* t, const float* queries3, int64_t n, int32_t* triangle, float* distance, float* closest3);
+int sdfk_trimesh_closest_device(const sdfk_trimesh* t, const void* queries3_dev, int64_t n, void* triangle_dev, void* distance_dev,
+                                void* closest3_dev);
+int sdfk_trimesh_to_volume(const sdfk_trimesh* t, sdfk_volume* v, float max_distance);
+int sdfk_trimesh_stats(const sdfk_trimesh* t, int64_t stats[8]);
+void sdfk_trimesh_free(sdfk_trimesh* t);
 
 /* ---- pinned host arena -------------------------------------------------------
  * Host memory the GPU can write directly (hipHostMalloc), recycled through size-class free lists:

@@ -122,6 +122,13 @@ SIGNATURES = {
     "sdfk_points_search_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "sdfk_points_stats": (C.c_int, [_vp, C.POINTER(_i64)]),
     "sdfk_points_free": (None, [_vp]),
+    "sdfk_trimesh_create": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vpp]),
+    "sdfk_trimesh_create_device": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vpp]),
+    "sdfk_trimesh_closest": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sdfk_trimesh_closest_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sdfk_trimesh_to_volume": (C.c_int, [_vp, _vp, C.c_float]),
+    "sdfk_trimesh_stats": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "sdfk_trimesh_free": (None, [_vp]),
     "sdfk_icp_register": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),
     "sdfk_icp_register_device": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),
     "sdfk_profile_count": (C.c_int, []),

@@ -659,6 +659,14 @@ class Mesh:
         s = self.Size
         return np.float32(np.sqrt((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]) * np.float32(0.5))
 
+    def ToVoxels(self, min, max, nx, ny, nz, maxDistance=float("inf"), clipToBounds=False):
+        """The mesh as a signed distance volume (sdfkit_amd.meshsdf.MeshSdf.ToVoxels): exact distances at the cell centres
+        Voxels.SampleSdf evaluates, signed by crossing parity along z (closed meshes), colours blended from the vertex
+        colours.  Not in the reference, which converts SDF -> Voxels -> Mesh only.  Give maxDistance for large volumes: the
+        unbanded search is slow far from a fine mesh (MeshSdf.ToVoxels)."""
+        from .meshsdf import MeshSdf
+        return MeshSdf(self).ToVoxels(min, max, nx, ny, nz, maxDistance, clipToBounds)
+
     def WriteObj(self, path_or_file):
         """Mesh.WriteObj (Mesh.cs:66-97): `v`, then `vn`, then `f a//a b//b c//c`, 1-based."""
         own = isinstance(path_or_file, str)

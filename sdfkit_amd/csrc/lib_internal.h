@@ -8,7 +8,8 @@
 //   lib_dist.hip     the Z-slab sharded step (dist_rccl.h) and several GPUs from one process (node_local.h)
 //   mc_kernels.hip   the marching-cubes kernels (declared in mc_kernels.h)
 //   lib_points.hip   KdTree / IterativeClosestPoint: the grid search structure, exact nearest-point search, ICP
-// Build: sdfkit_amd/build.py (the eight units in parallel, then one link with csrc/exports.map).  gfx950 only; there is no CPU path.
+//   lib_trimesh.hip  triangle-mesh distance: exact closest-triangle search, crossing parity, Mesh -> Voxels
+// Build: sdfkit_amd/build.py (the nine units in parallel, then one link with csrc/exports.map).  gfx950 only; there is no CPU path.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>

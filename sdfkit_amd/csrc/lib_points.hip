@@ -14,6 +14,7 @@
 // reference's f32 Matrix4x4 steps, convergence, running total) -> the step applied to the points.  Every reduction is f64 in a
 // fixed order (per-block partials of a fixed grid, then one block), with no float atomics: results are bitwise reproducible.
 #include "lib_internal.h"
+#include "device_scan.h"
 #include "points_grid.h"
 
 #include <cfloat>
@@ -82,70 +83,7 @@ __global__ __launch_bounds__(kBlock) void k_pts_count(const float* __restrict__ 
     atomicAdd(&counts[k], 1u);
 }
 
-// exclusive scan of counts[0..m) into starts[0..m] (starts[m] = total), in place allowed: blocks of kScanItems, block totals
-// scanned by one block, then the block offsets added.
-constexpr int kScanItems = kBlock * 8;
-
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* s_tmp, uint32_t* total)
-{
-    // Hillis-Steele over the block's 256 values
-    s_tmp[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < kBlock; o <<= 1) {
-        const uint32_t a = (int)threadIdx.x >= o ? s_tmp[threadIdx.x - o] : 0u;
-        __syncthreads();
-        s_tmp[threadIdx.x] += a;
-        __syncthreads();
-    }
-    const uint32_t incl = s_tmp[threadIdx.x];
-    *total = s_tmp[kBlock - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-__global__ __launch_bounds__(kBlock) void k_scan_blocks(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int64_t m,
-                                                        uint32_t* __restrict__ block_sums)
-{
-    __shared__ uint32_t s_tmp[kBlock];
-    const int64_t base = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * 8;
-    uint32_t v[8], sum = 0;
-    for (int j = 0; j < 8; j++) {
-        v[j] = base + j < m ? in[base + j] : 0u;
-        sum += v[j];
-    }
-    uint32_t total;
-    uint32_t run = block_exclusive_scan(sum, s_tmp, &total);
-    for (int j = 0; j < 8; j++) {
-        if (base + j < m) out[base + j] = run;
-        run += v[j];
-    }
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kBlock) void k_scan_sums(uint32_t* __restrict__ block_sums, int nb, uint32_t* __restrict__ grand)
-{
-    __shared__ uint32_t s_tmp[kBlock];
-    uint32_t carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += kBlock) {
-        const int b = b0 + (int)threadIdx.x;
-        const uint32_t v = b < nb ? block_sums[b] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_exclusive_scan(v, s_tmp, &total);
-        if (b < nb) block_sums[b] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) *grand = carry;
-}
-
-__global__ __launch_bounds__(kBlock) void k_scan_add(uint32_t* __restrict__ out, int64_t m, const uint32_t* __restrict__ block_sums,
-                                                     const uint32_t* __restrict__ grand)
-{
-    const int64_t base = (int64_t)blockIdx.x * kScanItems + (int64_t)threadIdx.x * 8;
-    const uint32_t add = block_sums[blockIdx.x];
-    for (int j = 0; j < 8; j++)
-        if (base + j < m) out[base + j] += add;
-    if (blockIdx.x == 0 && threadIdx.x == 0) out[m] = *grand;
-}
+// the exclusive scan of the cell counts: device_scan.h
 
 __global__ __launch_bounds__(kBlock) void k_pts_scatter(const float* __restrict__ p, int64_t n, const uint32_t* __restrict__ keys,
                                                         uint32_t* __restrict__ cursor, float4* __restrict__ sorted)
@@ -607,10 +545,7 @@ void points_release(sdfk_points* s)
 
 int scan_launch(uint32_t* buf, int64_t m, uint32_t* aux /* >= nb + 1 */)
 {
-    const int64_t nb = (m + kScanItems - 1) / kScanItems;
-    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)std::max<int64_t>(nb, 1)), dim3(kBlock), 0, g.stream, buf, buf, m, aux);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kBlock), 0, g.stream, aux, (int)std::max<int64_t>(nb, 1), aux + std::max<int64_t>(nb, 1));
-    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)std::max<int64_t>(nb, 1)), dim3(kBlock), 0, g.stream, buf, m, aux, aux + std::max<int64_t>(nb, 1));
+    sdfk_scan::scan_launch<uint32_t>(buf, m, aux, g.stream);
     HIPCHK(hipGetLastError());
     return SDFK_OK;
 }
@@ -643,7 +578,7 @@ int points_build(sdfk_points* s, const char* who)
 
     s->G = grid_for_box(box, box + 3, n);
     s->cells = (int64_t)s->G.dim[0] * s->G.dim[1] * s->G.dim[2];
-    const int64_t nb = (s->cells + 1 + kScanItems - 1) / kScanItems;
+    const int64_t nb = sdfk_scan::scan_blocks(s->cells + 1);
     uint32_t* keys = nullptr;
     uint32_t* aux = nullptr;
     uint32_t* cursor = nullptr;

@@ -1,0 +1,90 @@
+"""Triangle meshes as signed distance fields over the C ABI entry points sdfk_trimesh_* (include/sdfkit_hip.h,
+csrc/lib_trimesh.hip): the exact closest triangle of arbitrary points, and signed distance volumes (Mesh -> Voxels).
+
+The distance is exact (binary64 closest point, ties to the lowest triangle index); the sign is the parity of the mesh's
+crossings along z, meaningful for closed meshes (nested shells included) and deterministic for any mesh.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+
+f32 = np.float32
+
+
+def _ptr(a):
+    return C.c_void_p(a.ctypes.data) if a is not None and a.size else C.c_void_p()
+
+
+class MeshSdf:
+    """MeshSdf(mesh) or MeshSdf((vertices, triangles[, colors])): the triangles of a Mesh (Vertices, Triangles, Colors) as a
+    distance field.  Colours are used only when the mesh has a non-zero colour array."""
+
+    def __init__(self, mesh_or_arrays):
+        N.init()
+        if isinstance(mesh_or_arrays, (tuple, list)):
+            v, t = mesh_or_arrays[0], mesh_or_arrays[1]
+            c = mesh_or_arrays[2] if len(mesh_or_arrays) > 2 else None
+        else:
+            v, t, c = mesh_or_arrays.Vertices, mesh_or_arrays.Triangles, getattr(mesh_or_arrays, "Colors", None)
+        self.Vertices = np.ascontiguousarray(np.asarray(v, f32).reshape(-1, 3))
+        self.Triangles = np.ascontiguousarray(np.asarray(t, np.int32).reshape(-1))
+        cols = None
+        if c is not None:
+            cols = np.ascontiguousarray(np.asarray(c, f32).reshape(-1, 3))
+            if cols.shape != self.Vertices.shape or not np.any(cols):
+                cols = None
+        self.Colors = cols
+        h = C.c_void_p()
+        N.check(N.lib().sdfk_trimesh_create(_ptr(self.Vertices), len(self.Vertices), _ptr(self.Triangles), len(self.Triangles),
+                                            _ptr(cols) if cols is not None else C.c_void_p(), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and h.value and N._lib is not None and N._inited_device is not None:
+            N._lib.sdfk_trimesh_free(h)
+        self._h = None
+
+    @property
+    def handle(self):
+        """The sdfk_trimesh* (for the C ABI's device entry points)."""
+        return self._h
+
+    def Search(self, points):
+        """Every point at once -> (triangle int32 (-1 for a non-finite point), distance float32, closest (n, 3) float32)."""
+        q = np.ascontiguousarray(np.asarray(points, f32).reshape(-1, 3))
+        n = len(q)
+        tri = np.empty(n, np.int32)
+        dist = np.empty(n, f32)
+        cp = np.empty((n, 3), f32)
+        if n:
+            N.check(N.lib().sdfk_trimesh_closest(self._h, _ptr(q), n, _ptr(tri), _ptr(dist), _ptr(cp)))
+        return tri, dist, cp
+
+    def ToVoxels(self, min, max, nx, ny, nz, maxDistance=float("inf"), clipToBounds=False):
+        """The signed distance at the cell centres of Voxels(min, max, nx, ny, nz) (the centres Voxels.SampleSdf evaluates);
+        distances beyond maxDistance become +-maxDistance.  clipToBounds: Voxels.ClipToBounds afterwards.
+        Slow without a band on large volumes far from a fine mesh (every voxel searches until its nearest triangle: the 1.6 M
+        triangle sphere into 256^3 takes tens of seconds unbanded, a fraction of a second with a band of a few voxels)."""
+        from .api import Voxels
+        vox = Voxels(min, max, nx, ny, nz)
+        self.SampleInto(vox, maxDistance)
+        if clipToBounds:
+            vox.ClipToBounds()
+        return vox
+
+    def SampleInto(self, voxels, maxDistance=float("inf")):
+        """Writes the signed distance (and, when the mesh has colours, the blended colours) into an existing Voxels."""
+        h = voxels._ensure_device(self.Colors is not None or voxels._has_colors)
+        N.check(N.lib().sdfk_trimesh_to_volume(self._h, h, C.c_float(maxDistance)))
+        voxels._host_values = voxels._host_colors = None   # the device copy is now the truth
+        return voxels
+
+    def stats(self):
+        """sdfk_trimesh_stats: grid, triangles, binned pairs, candidates / queries of the last profiled call, crossings."""
+        s = (C.c_int64 * 8)()
+        N.check(N.lib().sdfk_trimesh_stats(self._h, s))
+        return {"grid": (s[0], s[1], s[2]), "triangles": int(s[3]), "entries": int(s[4]), "candidates": int(s[5]),
+                "queries": int(s[6]), "crossings": int(s[7])}

@@ -99,6 +99,17 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_icp_register(IntPtr points, ref SdfkIcpParams prm, float* points3, long n, float* total16, out int iterations);
         [DllImport(Lib)] public static extern int sdfk_icp_register_device(IntPtr points, ref SdfkIcpParams prm, IntPtr points3Dev, long n, float* total16,
                                                                            out int iterations);
+        // triangle-mesh distance (MeshSdf.Hip.cs)
+        [DllImport(Lib)] public static extern int sdfk_trimesh_create(float* vertices3, long nVertices, int* triangles, long nIndices, float* colors3,
+                                                                      out IntPtr trimesh);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_create_device(IntPtr vertices3Dev, long nVertices, IntPtr trianglesDev, long nIndices,
+                                                                             IntPtr colors3Dev, out IntPtr trimesh);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_closest(IntPtr trimesh, float* queries3, long n, int* triangle, float* distance, float* closest3);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_closest_device(IntPtr trimesh, IntPtr queries3Dev, long n, IntPtr triangleDev,
+                                                                              IntPtr distanceDev, IntPtr closest3Dev);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_to_volume(IntPtr trimesh, IntPtr volume, float maxDistance);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_stats(IntPtr trimesh, long* stats8);
+        [DllImport(Lib)] public static extern void sdfk_trimesh_free(IntPtr trimesh);
         // several GPUs from ONE process (the managed host is one process): include/sdfkit_hip.h, "one process, several GPUs"
         [DllImport(Lib)] public static extern int sdfk_node_open(int* devices, int nDevices, out IntPtr node);
         [DllImport(Lib)] public static extern int sdfk_node_info(IntPtr node, out int world, out int backend);
