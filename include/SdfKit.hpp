@@ -71,8 +71,18 @@ inline int64_t GetOption(sdfk_option key)
 // ---------------------------------------------------------------------------------------
 // symbolic float32 values (one SSA instruction each)
 // ---------------------------------------------------------------------------------------
+class Voxels;
 struct Builder {
     std::vector<sdfk_op> ops;
+    std::vector<const Voxels*> volumes;   // volumes the program reads (sdfk_program_create_bound), slot = index, deduplicated by identity
+    int slot(const Voxels* v)
+    {
+        for (size_t i = 0; i < volumes.size(); i++)
+            if (volumes[i] == v) return (int)i;
+        if (volumes.size() >= SDFK_MAX_VOLUMES) throw std::logic_error("SdfKit: an SDF program reads at most 8 volumes");
+        volumes.push_back(v);
+        return (int)volumes.size() - 1;
+    }
     int emit(int opcode, int a = -1, int b = -1, int c = -1, int d = -1, float imm = 0.f)
     {
         ops.push_back(sdfk_op{opcode, a, b, c, d, imm});
@@ -179,7 +189,7 @@ public:
     Sdf(PointFn fn, bool writesColor) : st_(std::make_shared<State>()) { st_->fn = std::move(fn); st_->writesColor = writesColor; }
     bool WritesColor() const { return st_->writesColor; }
     // the SDF as the flat op list the library compiles (what sdfk_program_create and sdfk_node_* take)
-    void Lower(std::vector<sdfk_op>& ops, int32_t out[4]) const
+    void Lower(std::vector<sdfk_op>& ops, int32_t out[4], std::vector<const Voxels*>* volumes = nullptr) const
     {
         Builder b;
         Vec3 p(Val(&b, b.emit(SDFK_OP_X)), Val(&b, b.emit(SDFK_OP_Y)), Val(&b, b.emit(SDFK_OP_Z)));
@@ -188,18 +198,11 @@ public:
         out[3] = o.W.bind(&b);
         if (st_->writesColor) { out[0] = o.X.bind(&b); out[1] = o.Y.bind(&b); out[2] = o.Z.bind(&b); }
         ops = b.ops;
+        if (volumes) *volumes = b.volumes;
     }
-    sdfk_program* Program() const
-    {
-        if (!st_->prog) {
-            EnsureInit();
-            std::vector<sdfk_op> ops;
-            int32_t out[4];
-            Lower(ops, out);
-            Check(sdfk_program_create(ops.data(), (int32_t)ops.size(), out, st_->writesColor ? 1 : 0, &st_->prog));
-        }
-        return st_->prog;
-    }
+    // A program that reads volumes holds a snapshot of them: an edit of one since (Sample, ClipToBounds, a write through the indexer,
+    // MeshSdf::SampleInto) bumps its version, and the next use binds it again.  The Voxels must outlive the Sdf's uses.
+    inline sdfk_program* Program() const;
     // SdfEx.WithColor (Sdf.cs:101-115)
     Sdf WithColor(Vector3 color) const { PointFn f = st_->fn; return Sdf([f, color](Vec3 p) { return Vec4(Vec3(color), f(p).W); }, true); }
     Sdf WithColor(float r, float g, float b) const { return WithColor(Vector3(r, g, b)); }
@@ -221,6 +224,8 @@ private:
         PointFn fn;
         bool writesColor = true;
         sdfk_program* prog = nullptr;
+        std::vector<const Voxels*> volumes;
+        std::vector<uint64_t> versions;
         ~State() { if (prog) sdfk_program_destroy(prog); }
     };
     std::shared_ptr<State> st_;
@@ -404,7 +409,7 @@ public:
     Voxels(Voxels&& o) noexcept { *this = std::move(o); }
     Voxels& operator=(Voxels&& o) noexcept
     {
-        NX = o.NX; NY = o.NY; NZ = o.NZ; DX = o.DX; DY = o.DY; DZ = o.DZ; Min = o.Min; Max = o.Max;
+        NX = o.NX; NY = o.NY; NZ = o.NZ; DX = o.DX; DY = o.DY; DZ = o.DZ; Min = o.Min; Max = o.Max; version_ = o.version_ + 1;
         h_ = o.h_; o.h_ = nullptr; hasColors_ = o.hasColors_; values_ = std::move(o.values_); hostNewer_ = o.hostNewer_;
         return *this;
     }
@@ -423,16 +428,19 @@ public:
     }
     void Sample(const Sdf& sdf, bool clip)
     {
+        sdfk_program* prog = sdf.Program();
         Ensure(sdf.WritesColor());
-        Check(sdfk_sample(sdf.Program(), h_, clip ? 1 : 0));
+        Check(sdfk_sample(prog, h_, clip ? 1 : 0));
         values_.clear();
         hostNewer_ = false;
+        version_++;
     }
     void ClipToBounds()   // Voxels.cs:133-167
     {
         Sync();
         Check(sdfk_volume_clip_to_bounds(h_));
         values_.clear();
+        version_++;
     }
     // indexer v[ix,iy,iz] (Voxels.cs:42-46): host copy of Values, z fastest
     float& operator()(int ix, int iy, int iz)
@@ -442,8 +450,26 @@ public:
             if (h_) Check(sdfk_volume_download(h_, values_.data(), nullptr));
         }
         hostNewer_ = true;
+        version_++;
         return values_[((size_t)ix * NY + iy) * NZ + iz];
     }
+    // Inside an SDF (include/sdfkit_hip.h, SDFK_OP_VOXEL_*): the reference's position indexer Voxels[p] (Voxels.cs:48-56; outside the box
+    // the nearest boundary voxel instead of IndexOutOfRangeException), the trilinear distance and colour between the cell centres, and
+    // the volume as an Sdf (colours when the volume has them, white otherwise).
+    Val operator[](const Vec3& p) const { return Read(SDFK_OP_VOXEL_NEAREST, p, 3); }
+    Val SampleAt(const Vec3& p) const { return Read(SDFK_OP_VOXEL_LINEAR, p, 3); }
+    Vec3 SampleColor(const Vec3& p) const { return Vec3(Read(SDFK_OP_VOXEL_LINEAR, p, 0), Read(SDFK_OP_VOXEL_LINEAR, p, 1), Read(SDFK_OP_VOXEL_LINEAR, p, 2)); }
+    Sdf ToSdf(bool interpolate = true) const
+    {
+        const Voxels* self = this;
+        const int op = interpolate ? SDFK_OP_VOXEL_LINEAR : SDFK_OP_VOXEL_NEAREST;
+        const bool colored = hasColors_;
+        return Sdf([self, op, colored](Vec3 p) {
+            const Val w = self->Read(op, p, 3);
+            return colored ? Vec4(Vec3(self->Read(op, p, 0), self->Read(op, p, 1), self->Read(op, p, 2)), w) : Vec4(Vec3(Vector3(1.0f, 1.0f, 1.0f)), w);
+        }, true);
+    }
+    uint64_t Version() const { return version_; }
     inline Mesh ToMesh(float isoValue = 0.0f, int step = 1, const std::function<void(float)>& progress = nullptr);
     sdfk_volume* Sync()
     {
@@ -454,6 +480,14 @@ public:
 
 private:
     friend class MeshSdf;   // (writes distances straight into the device volume)
+    Val Read(int opcode, const Vec3& p, int channel) const
+    {
+        Builder* b = p.X.b ? p.X.b : (p.Y.b ? p.Y.b : p.Z.b);
+        if (!b) throw std::logic_error("SdfKit::Voxels: a volume read needs a symbolic point (inside an SDF)");
+        const int x = p.X.bind(b), y = p.Y.bind(b), z = p.Z.bind(b);
+        return Val(b, b->emit(opcode, x, y, z, (b->slot(this) << 2) | channel));
+    }
+    uint64_t version_ = 0;
     void Ensure(bool colors)
     {
         EnsureInit();
@@ -465,6 +499,32 @@ private:
     std::vector<float> values_;
     bool hostNewer_ = false;
 };
+
+inline sdfk_program* Sdf::Program() const
+{
+    if (st_->prog && !st_->volumes.empty()) {
+        for (size_t i = 0; i < st_->volumes.size(); i++)
+            if (st_->volumes[i]->Version() != st_->versions[i]) { sdfk_program_destroy(st_->prog); st_->prog = nullptr; break; }
+    }
+    if (!st_->prog) {
+        EnsureInit();
+        std::vector<sdfk_op> ops;
+        int32_t out[4];
+        Lower(ops, out, &st_->volumes);
+        if (st_->volumes.empty()) {
+            Check(sdfk_program_create(ops.data(), (int32_t)ops.size(), out, st_->writesColor ? 1 : 0, &st_->prog));
+        } else {
+            std::vector<const sdfk_volume*> hs;
+            st_->versions.clear();
+            for (const Voxels* v : st_->volumes) {
+                hs.push_back(const_cast<Voxels*>(v)->Sync());   // (host edits go up first)
+                st_->versions.push_back(v->Version());
+            }
+            Check(sdfk_program_create_bound(ops.data(), (int32_t)ops.size(), out, st_->writesColor ? 1 : 0, hs.data(), (int32_t)hs.size(), &st_->prog));
+        }
+    }
+    return st_->prog;
+}
 
 struct MarchingCubes {
     // MarchingCubes.CreateMesh(Voxels, isoValue = 0, step = 1, progress = null)  (MarchingCubes.cs:39)
@@ -760,6 +820,7 @@ public:
         Check(sdfk_trimesh_to_volume(h_, v.h_, maxDistance));
         v.values_.clear();
         v.hostNewer_ = false;
+        v.version_++;
     }
     sdfk_trimesh* Handle() const { return h_; }
 

@@ -33,7 +33,8 @@ extern "C" {
                                    a session whose exchange mode is 2 or 3 (SDFK_ERR_UNSUPPORTED); gather-to-root has the same who-receives-what on
                                    the host transport as over RCCL; sdfk_host_alloc works in a process whose only contexts are a node's;
                                    entry points added since, existing ones unchanged: sdfk_points_* (KdTree), sdfk_icp_* (IterativeClosestPoint) and
-                                   sdfk_trimesh_* (triangle-mesh distance) */
+                                   sdfk_trimesh_* (triangle-mesh distance),
+                                   sdfk_program_create_bound / sdfk_program_check_bound (programs that read voxel volumes) */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -75,8 +76,26 @@ typedef enum sdfk_opcode {
     SDFK_OP_MAX_SEL = 13, /* (a > b) ? a : b   -- Vector3.Max component */
     SDFK_OP_MIN_IEEE = 14,/* Math.Min / MathF.Min (IEEE 754:2019 minimum) */
     SDFK_OP_MAX_IEEE = 15,/* Math.Max / MathF.Max (IEEE 754:2019 maximum) */
-    SDFK_OP_SEL_LT = 16   /* (a < b) ? c : d   -- SdfExprs.Union (SdfExpr.cs:63-66) */
+    SDFK_OP_SEL_LT = 16,  /* (a < b) ? c : d   -- SdfExprs.Union (SdfExpr.cs:63-66) */
+    /* Reads of a BOUND volume (sdfk_program_create_bound below) at the point (a, b, c); d is a literal, not a value id:
+     * d = (slot << 2) | channel, slot 0..7 = the bound volume, channel 0..2 = colour R / G / B, 3 = the distance value.  With
+     * D = (Max - Min) / N per axis (float, as Voxels computes DX, Voxels.cs:32-34) and every step ONE f32 operation (no contraction):
+     *   SDFK_OP_VOXEL_NEAREST -- the reference's position indexer Voxels[p] (Voxels.cs:48-56): per axis q = (X - Min) / D,
+     *     i = (int)q (truncation), CLAMPED to [0, N - 1] -- q <= 0 gives 0, q >= (float)(N - 1) gives N - 1, compared in float
+     *     before the conversion.  DEVIATION: where the reference throws IndexOutOfRangeException (a point outside the box) the
+     *     GPU form returns the nearest boundary voxel -- an SDF must be total.  A NaN quotient on any axis gives NaN.
+     *   SDFK_OP_VOXEL_LINEAR -- trilinear interpolation between the cell centres m + i D, m = Min + 0.5f D (where SampleSdf
+     *     samples, Voxels.cs:81): per axis u = (X - m) / D, clamped to [0, N - 1] by compare-select, i0 = min(floor(u), N - 2),
+     *     i1 = i0 + 1, f = u - i0 (an axis with N = 1: i0 = i1 = 0, f = 0).  lerp(a, b, f) = a + f (b - a), along x, then y,
+     *     then z; the result r is then clamped to [lo, hi] = IEEE minimum / maximum of the 8 corners as
+     *     r >= lo ? (r <= hi ? r : hi) : lo -- a NaN corner gives NaN, an overflowing lerp the nearest corner bound.  A NaN
+     *     coordinate gives NaN.
+     * The interval form (block culling) maps the box of points to a box of indices (both index maps are monotone) and reads
+     * its min / max from a min/max pyramid built at bind time; a non-finite voxel makes it unknown. */
+    SDFK_OP_VOXEL_NEAREST = 17,
+    SDFK_OP_VOXEL_LINEAR = 18
 } sdfk_opcode;
+#define SDFK_MAX_VOLUMES 8
 
 typedef struct sdfk_op {
     int32_t opcode;
@@ -201,6 +220,20 @@ int sdfk_program_create(const sdfk_op* ops, int32_t n_ops, const int32_t out_rgb
 /* Generate + hiprtc-compile EVERY kernel of the program for gfx950 without loading (needs no
  * device, never uses the cache): a lowering check the shim can run at build time. */
 int sdfk_program_check(const sdfk_op* ops, int32_t n_ops, const int32_t out_rgbw[4], int32_t writes_color);
+/* A program that reads volumes (SDFK_OP_VOXEL_NEAREST / SDFK_OP_VOXEL_LINEAR; sdfk_program_create / _check refuse those opcodes with
+ * SDFK_ERR_INVALID): the reference's Sdfs.Solid(p => voxels[p]) -- a closure over a Voxels.  volumes[slot] = the volume of slot
+ * `slot` (at most SDFK_MAX_VOLUMES).  Refused with SDFK_ERR_INVALID: a slot >= n_volumes, more than 8 volumes, a null, slab
+ * (z0 != 0 or nz != nz_global) or elided volume, a volume of another device context, an extent Max - Min <= 0 on any axis, and a
+ * COLOUR channel of a volume that has no colour array.
+ * SNAPSHOT: the program takes a device copy of each bound volume's Values (and Colors when it reads a colour channel) when it is
+ * created, plus a min/max pyramid of every channel it reads (about 8/7 x 8 bytes per 8 voxels per channel): a volume of N voxels
+ * costs the program 4 N bytes (+ 12 N with colours) + ~1.15 N bytes per channel read, until the program is destroyed.  Later
+ * uploads, samples or a free of the source volume change nothing; a program may be sampled into the very volume it was built
+ * from.  WHICH volume is bound is an argument, not structure: another volume with the same slots and channels compiles nothing. */
+int sdfk_program_create_bound(const sdfk_op* ops, int32_t n_ops, const int32_t out_rgbw[4], int32_t writes_color,
+                              const sdfk_volume* const* volumes, int32_t n_volumes, sdfk_program** out);
+/* sdfk_program_check for a program that reads `n_volumes` bound volumes: the offline compile (no device, no volume). */
+int sdfk_program_check_bound(const sdfk_op* ops, int32_t n_ops, const int32_t out_rgbw[4], int32_t writes_color, int32_t n_volumes);
 /* the generated HIP source of the program's STRUCTURE (constants appear as K.k[i]) */
 const char* sdfk_program_source(const sdfk_program* p);
 /* JIT bookkeeping of this process.  Compiled code objects are kept on disk (see csrc/lib_jit.hip,

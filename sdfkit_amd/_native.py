@@ -39,6 +39,8 @@ SIGNATURES = {
     "sdfk_last_error": (C.c_char_p, []),
     "sdfk_program_create": (C.c_int, [C.POINTER(Op), _i32, C.POINTER(_i32), _i32, _vpp]),
     "sdfk_program_check": (C.c_int, [C.POINTER(Op), _i32, C.POINTER(_i32), _i32]),
+    "sdfk_program_create_bound": (C.c_int, [C.POINTER(Op), _i32, C.POINTER(_i32), _i32, C.POINTER(_vp), _i32, _vpp]),
+    "sdfk_program_check_bound": (C.c_int, [C.POINTER(Op), _i32, C.POINTER(_i32), _i32, _i32]),
     "sdfk_program_source": (C.c_char_p, [_vp]),
     "sdfk_program_destroy": (None, [_vp]),
     "sdfk_jit_stats": (C.c_int, [C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_double)]),

@@ -13,7 +13,7 @@ import math
 import numpy as np
 
 from . import _native as N
-from .expr import MathF, Mod, VMax, Vec3, Vec4, select_lt, trace
+from .expr import OP_VOXEL_LINEAR, OP_VOXEL_NEAREST, MathF, Mod, Val, VMax, Vec3, Vec4, select_lt, trace_bound
 
 DefaultBatchSize = 2 * 1024  # SdfConfig.DefaultBatchSize (Sdf.cs:13); no meaning on the GPU
 
@@ -36,11 +36,13 @@ class Sdf:
         self.writes_color = bool(writes_color)
         self._prog = None
         self._ir = None
+        self._volumes = []        # Voxels the program reads (Voxels[p], Voxels.Sample), slot order
+        self._bound_versions = None
 
     # -- lowering -----------------------------------------------------------
     def ir(self):
         if self._ir is None:
-            ops, out = trace(self.fn, self.writes_color)
+            ops, out, self._volumes = trace_bound(self.fn, self.writes_color)
             arr = (N.Op * len(ops))()
             for i, (op, a, b, c, d, imm) in enumerate(ops):
                 arr[i].opcode, arr[i].a, arr[i].b, arr[i].c, arr[i].d, arr[i].imm = op, a, b, c, d, imm
@@ -50,16 +52,34 @@ class Sdf:
     def check(self):
         """Generate + compile the sampling kernel for gfx950 (no device needed)."""
         arr, n, out = self.ir()
-        N.check(N.lib().sdfk_program_check(arr, n, out, int(self.writes_color)))
+        if self._volumes:
+            N.check(N.lib().sdfk_program_check_bound(arr, n, out, int(self.writes_color), len(self._volumes)))
+        else:
+            N.check(N.lib().sdfk_program_check(arr, n, out, int(self.writes_color)))
 
     def program(self):
+        arr, n, out = self.ir()
+        # A program that reads volumes holds a SNAPSHOT of them (sdfk_program_create_bound): an edit of one since (Values written,
+        # re-sampled, MeshSdf.SampleInto) bumps its version, and the next use binds the volume as it is now -- as a closure over
+        # the reference's Voxels would see it.
+        if self._prog is not None and self._volumes and [v._version for v in self._volumes] != self._bound_versions:
+            self._destroy()
         if self._prog is None:
             N.init()
-            arr, n, out = self.ir()
             h = C.c_void_p()
-            N.check(N.lib().sdfk_program_create(arr, n, out, int(self.writes_color), C.byref(h)))
+            if self._volumes:
+                hs = (C.c_void_p * len(self._volumes))(*[v._sync_to_device().value for v in self._volumes])
+                N.check(N.lib().sdfk_program_create_bound(arr, n, out, int(self.writes_color), hs, len(self._volumes), C.byref(h)))
+                self._bound_versions = [v._version for v in self._volumes]
+            else:
+                N.check(N.lib().sdfk_program_create(arr, n, out, int(self.writes_color), C.byref(h)))
             self._prog = h
         return self._prog
+
+    def _destroy(self):
+        if self._prog is not None and N._lib is not None and N._inited_device is not None:
+            N._lib.sdfk_program_destroy(self._prog)
+        self._prog = None
 
     def source(self):
         return N.lib().sdfk_program_source(self.program()).decode()
@@ -373,6 +393,7 @@ class Voxels:
         self._host_values = values
         self._host_colors = colors
         self._host_newer = values is not None
+        self._version = 0         # bumped by every possible edit (Sdf programs that read this volume re-bind it)
 
     # IBoundedVolume (IBoundedVolume.cs:6-13; Voxels.cs:17-21)
     @property
@@ -438,11 +459,13 @@ class Voxels:
     @property
     def Values(self):
         self._download()
+        self._version += 1   # (the caller may write through the array: an Sdf that reads this volume binds it again)
         return self._host_values
 
     @property
     def Colors(self):
         self._download()
+        self._version += 1
         return self._host_colors
 
     def _index_of(self, p):
@@ -450,7 +473,22 @@ class Voxels:
         return (int((p[0] - self.Min[0]) / self.DX), int((p[1] - self.Min[1]) / self.DY),
                 int((p[2] - self.Min[2]) / self.DZ))
 
+    @staticmethod
+    def _symbolic(key):
+        """the symbolic point of an indexer key (Vec3, or three values one of which is symbolic), else None"""
+        if isinstance(key, Vec3):
+            return key
+        if isinstance(key, tuple) and len(key) == 1 and isinstance(key[0], Vec3):
+            return key[0]
+        if isinstance(key, tuple) and len(key) == 3 and any(isinstance(k, Val) for k in key):
+            b = next(k for k in key if isinstance(k, Val)).b
+            return Vec3(*(b.lift(k) for k in key))
+        return None
+
     def __getitem__(self, key):
+        p = Voxels._symbolic(key)
+        if p is not None:   # inside an SDF: the reference's position indexer (Voxels.cs:48-56) as a GPU op
+            return p.x.b.voxel(OP_VOXEL_NEAREST, self, p, 3)
         if len(key) != 3 or not all(isinstance(k, (int, np.integer)) for k in key):
             key = self._index_of(key[0] if len(key) == 1 else key)
         return self.Values[key]
@@ -459,6 +497,37 @@ class Voxels:
         if len(key) != 3 or not all(isinstance(k, (int, np.integer)) for k in key):
             key = self._index_of(key[0] if len(key) == 1 else key)
         self.Values[key] = value
+
+    # -- the volume as an SDF (sdfk_program_create_bound) -------------------------
+    def _colors_present(self):
+        if self._host_colors is not None:
+            return bool(np.any(self._host_colors))
+        return self._h is not None and self._has_colors
+
+    def Sample(self, p):
+        """The distance trilinearly interpolated between the cell centres at the symbolic point p (inside an SDF); outside the
+        centres' box the nearest boundary value (include/sdfkit_hip.h, SDFK_OP_VOXEL_LINEAR)."""
+        b = p.x.b if isinstance(p, Vec3) else p[0].b
+        return b.voxel(OP_VOXEL_LINEAR, self, p if isinstance(p, Vec3) else Vec3(*p), 3)
+
+    def SampleColor(self, p):
+        """The colour, trilinearly interpolated like Sample: a Vec3.  The volume must have colours."""
+        b = p.x.b if isinstance(p, Vec3) else p[0].b
+        q = p if isinstance(p, Vec3) else Vec3(*p)
+        return Vec3(*(b.voxel(OP_VOXEL_LINEAR, self, q, c) for c in range(3)))
+
+    def ToSdf(self, interpolate=True):
+        """This volume as an Sdf: Sample (interpolate=True) or the reference's indexer Voxels[p] (False).  The colour is the volume's
+        own (interpolated the same way) when it has colours, white otherwise -- as Sdfs.Solid colours a distance function."""
+        op = OP_VOXEL_LINEAR if interpolate else OP_VOXEL_NEAREST
+        colored = self._colors_present()
+
+        def fn(p):
+            b = p.x.b
+            w = b.voxel(op, self, p, 3)
+            col = Vec3(*(b.voxel(op, self, p, c) for c in range(3))) if colored else (1.0, 1.0, 1.0)
+            return Vec4.of(col, w)
+        return Sdf(fn, True)
 
     # -- sampling ---------------------------------------------------------------
     def _sample(self, sdf, clip=False):
@@ -469,6 +538,7 @@ class Voxels:
         h = self._ensure_device(sdf.writes_color)
         N.check(N.lib().sdfk_sample(prog, h, 1 if clip else 0))
         self._host_values = self._host_colors = None  # device copy is now the truth
+        self._version += 1
 
     def _sample_instance(self, sdf, batchSize=DefaultBatchSize, maxDegreeOfParallelism=-1):
         """Voxels.SampleSdf(Sdf, batchSize, maxDegreeOfParallelism) (Voxels.cs:72-125).
@@ -492,6 +562,7 @@ class Voxels:
         h = self._sync_to_device()
         N.check(N.lib().sdfk_volume_clip_to_bounds(h))
         self._host_values = self._host_colors = None
+        self._version += 1
 
     def ToMesh(self, isoValue=0.0, step=1, progress=None):
         """Voxels.ToMesh (Voxels.cs:67-70)."""

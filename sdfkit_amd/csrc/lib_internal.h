@@ -420,10 +420,16 @@ struct sdfk_program {
     int refs = 1;   // the caller's handle + volumes it has sampled + queued jobs that launch from its module
     bool orphaned = false;   // the caller's handle is gone (sdfk_program_destroy): captured jobs keyed on it can never be asked for again
     bool no_elide = false;   // a volume of this program had case-13 sign words (the dead-cell test reads voxels): its volumes are stored from then on
-    void* kargs() const { return const_cast<float*>(params.data()); }   // the by-value SdfkK argument of every generated kernel
+    // A program that reads bound volumes (sdfk_program_create_bound): its snapshot of them -- descriptor table, values, colours,
+    // pyramids -- in ONE device allocation (freed with the program), and kbuf = the SdfkK argument { k[], table pointer }.
+    void* vol_mem = nullptr;
+    DeviceState* owner = nullptr;
+    std::vector<uint64_t> kbuf;
+    void* kargs() const { return kbuf.empty() ? (void*)const_cast<float*>(params.data()) : (void*)const_cast<uint64_t*>(kbuf.data()); }   // the by-value SdfkK argument of every generated kernel
 };
 
 struct sdfk_volume {
+    DeviceState* owner = &cur_state();   // the device context the volume was made in (sdfk_program_create_bound refuses others)
     int nx = 0, ny = 0, nz = 0;       // local dims (nz = planes held)
     int nz_global = 0, z0 = 0;
     float gmin[3], gmax[3];
@@ -580,7 +586,7 @@ void code_unload(ProgCode* c);
 ProgCode* code_acquire(std::string&& src);
 void code_release(ProgCode* c);
 int generate_source(const sdfk_op* ops, int32_t n_ops, const int32_t out_rgbw[4], int32_t writes_color, std::string& src,
-                           std::vector<float>* params = nullptr);
+                           std::vector<float>* params = nullptr, int n_volumes = 0);
 int program_fn(const sdfk_program* cp, int k, hipFunction_t* fn);
 int job_volume_create(const sdfk_program* p, int nx, int ny, int nz, const float mn[3], const float mx[3], float iso, sdfk_volume** out);
 int volume_materialize(sdfk_volume* v);

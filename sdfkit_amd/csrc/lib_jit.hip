@@ -214,10 +214,10 @@ void code_release(ProgCode* c)
 
 
 int generate_source(const sdfk_op* ops, int32_t n_ops, const int32_t out_rgbw[4], int32_t writes_color, std::string& src,
-                           std::vector<float>* params)
+                           std::vector<float>* params, int n_volumes)
 {
     std::string err;
-    if (!generate_sample_source(ops, n_ops, out_rgbw, writes_color, src, err, params))
+    if (!generate_sample_source(ops, n_ops, out_rgbw, writes_color, src, err, params, n_volumes))
         return fail(SDFK_ERR_INVALID, "SDF program: %s", err.c_str());
     if (!g_cfg.dump_source.empty()) {   // debugging aid (SDFK_DUMP_SOURCE at start-up): the generated HIP source of the last program
         if (FILE* f = fopen(g_cfg.dump_source.c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
@@ -234,6 +234,200 @@ extern "C" int sdfk_program_check(const sdfk_op* ops, int32_t n_ops, const int32
     config_from_env();   // (first: SDFK_DUMP_SOURCE is honoured by generate_source)
     if (int r = generate_source(ops, n_ops, out_rgbw, writes_color, src)) return r;
     return compile_source(src, (1u << PK_COUNT) - 1u, code, false);   // every kernel, a real compile: this IS the check
+}
+
+extern "C" int sdfk_program_check_bound(const sdfk_op* ops, int32_t n_ops, const int32_t out_rgbw[4], int32_t writes_color, int32_t n_volumes)
+{
+    if (!ops || !out_rgbw || n_ops <= 0) return fail(SDFK_ERR_INVALID, "sdfk_program_check_bound: null/empty argument");
+    if (n_volumes < 0 || n_volumes > SDFK_MAX_VOLUMES) return fail(SDFK_ERR_INVALID, "sdfk_program_check_bound: %d volumes (0..%d)", n_volumes, SDFK_MAX_VOLUMES);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string src;
+    std::vector<char> code;
+    config_from_env();
+    if (int r = generate_source(ops, n_ops, out_rgbw, writes_color, src, nullptr, n_volumes)) return r;
+    return compile_source(src, (1u << PK_COUNT) - 1u, code, false);
+}
+
+// ---- programs that read bound volumes: the snapshot (sdfk_program_create_bound) -------------------------------------------------
+// One device allocation per program: the SdfkVol table, then per volume its Values (+ Colors) copied as they are (pitched rows),
+// then the min/max pyramid of every channel the program reads.  Built once, synchronously: a program is made once and used often.
+namespace {
+__host__ __device__ inline bool finite_f(float v) { return v - v == 0.0f; }
+// level 1 of a channel's pyramid from the voxels: cell c covers voxels [2c, 2c + 1] per axis (clipped); NaN when one is not finite
+__global__ void k_vol_pyr_base(const float* __restrict__ src, int stride, int nx, int ny, int nz, int pitch, int cx, int cy, int cz,
+                               float* __restrict__ out)
+{
+    const long total = (long)cx * cy * cz;
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < total; c += (long)gridDim.x * 256) {
+        const int k = (int)(c % cz);
+        const long t = c / cz;
+        const int j = (int)(t % cy), i = (int)(t / cy);
+        float lo = __builtin_inff(), hi = -__builtin_inff();
+        bool bad = false;
+        for (int q = 0; q < 8; q++) {
+            const int x = 2 * i + (q & 1), y = 2 * j + ((q >> 1) & 1), z = 2 * k + (q >> 2);
+            if (x >= nx || y >= ny || z >= nz) continue;
+            const float v = src[(((long)x * ny + y) * pitch + z) * stride];
+            bad |= !finite_f(v);
+            lo = __builtin_elementwise_minimum(lo, v);
+            hi = __builtin_elementwise_maximum(hi, v);
+        }
+        out[2 * c] = bad ? __builtin_nanf("") : lo;
+        out[2 * c + 1] = bad ? __builtin_nanf("") : hi;
+    }
+}
+// level L + 1 from level L: minimum / maximum of up to 8 cells (IEEE 754:2019: a poisoned cell poisons its parent)
+__global__ void k_vol_pyr_up(const float* __restrict__ in, int nx, int ny, int nz, float* __restrict__ out, int cx, int cy, int cz)
+{
+    const long total = (long)cx * cy * cz;
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < total; c += (long)gridDim.x * 256) {
+        const int k = (int)(c % cz);
+        const long t = c / cz;
+        const int j = (int)(t % cy), i = (int)(t / cy);
+        float lo = __builtin_inff(), hi = -__builtin_inff();
+        for (int q = 0; q < 8; q++) {
+            const int x = 2 * i + (q & 1), y = 2 * j + ((q >> 1) & 1), z = 2 * k + (q >> 2);
+            if (x >= nx || y >= ny || z >= nz) continue;
+            const long e = ((long)x * ny + y) * nz + z;
+            lo = __builtin_elementwise_minimum(lo, in[2 * e]);
+            hi = __builtin_elementwise_maximum(hi, in[2 * e + 1]);
+        }
+        out[2 * c] = lo;
+        out[2 * c + 1] = hi;
+    }
+}
+inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
+inline int cells(int n, int L) { return (int)(((long)n + (1l << L) - 1) >> L); }
+}  // namespace
+
+static int bind_volumes(sdfk_program* p, const sdfk_op* ops, int32_t n_ops, const sdfk_volume* const* vols, int32_t n_vol)
+{
+    unsigned used[SDFK_MAX_VOLUMES] = {};   // channel mask per slot (generate_source has checked every slot)
+    for (int i = 0; i < n_ops; i++)
+        if (ops[i].opcode == SDFK_OP_VOXEL_NEAREST || ops[i].opcode == SDFK_OP_VOXEL_LINEAR) used[ops[i].d >> 2] |= 1u << (ops[i].d & 3);
+    // layout
+    std::vector<SdfkVol> table((size_t)n_vol);
+    memset(table.data(), 0, table.size() * sizeof(SdfkVol));
+    size_t off = align256(sizeof(SdfkVol) * (size_t)n_vol);
+    size_t val_off[SDFK_MAX_VOLUMES] = {}, col_off[SDFK_MAX_VOLUMES] = {}, pyr_off[SDFK_MAX_VOLUMES][4] = {};
+    for (int s = 0; s < n_vol; s++) {
+        const sdfk_volume* v = vols[s];
+        SdfkVol& T = table[(size_t)s];
+        const int n[3] = {v->nx, v->ny, v->nz};
+        int top = 0;
+        for (int a = 0; a < 3; a++) {
+            T.n[a] = n[a];
+            T.mn[a] = v->gmin[a];
+            T.d[a] = (v->gmax[a] - v->gmin[a]) / (float)n[a];
+            T.m[a] = v->gmin[a] + 0.5f * T.d[a];
+            while ((1l << top) < n[a]) top++;
+        }
+        T.pitch = v->pitch();
+        T.nlev = top;
+        long long cells_so_far = 0;
+        for (int L = 1; L <= top; L++) {
+            T.lev[L] = cells_so_far;
+            cells_so_far += (long long)cells(n[0], L) * cells(n[1], L) * cells(n[2], L);
+        }
+        if (!used[s]) continue;
+        val_off[s] = off;
+        off = align256(off + v->nalloc() * sizeof(float));
+        if (used[s] & 7u) { col_off[s] = off; off = align256(off + v->nalloc() * 3 * sizeof(float)); }
+        for (int ch = 0; ch < 4; ch++)
+            if (((used[s] >> ch) & 1u) && top > 0) { pyr_off[s][ch] = off; off = align256(off + (size_t)cells_so_far * 2 * sizeof(float)); }
+    }
+    char* mem = nullptr;
+    if (hipMalloc((void**)&mem, off) != hipSuccess) { (void)hipGetLastError(); return fail(SDFK_ERR_NOMEM, "sdfk_program_create_bound: %zu bytes of volume snapshot", off); }
+    p->vol_mem = mem;   // (freed with the program from here on)
+    sync_all_lanes();   // whatever wrote the volumes has finished; the copies below run on the caller's stream
+    for (int s = 0; s < n_vol; s++) {
+        if (!used[s]) continue;
+        const sdfk_volume* v = vols[s];
+        SdfkVol& T = table[(size_t)s];
+        float* val = reinterpret_cast<float*>(mem + val_off[s]);
+        float* col = (used[s] & 7u) ? reinterpret_cast<float*>(mem + col_off[s]) : nullptr;
+        HIPCHK(hipMemcpyAsync(val, v->values, v->nalloc() * sizeof(float), hipMemcpyDeviceToDevice, g.stream));
+        if (col) HIPCHK(hipMemcpyAsync(col, v->colors, v->nalloc() * 3 * sizeof(float), hipMemcpyDeviceToDevice, g.stream));
+        T.val = val;
+        T.col = col;
+        for (int ch = 0; ch < 4; ch++) {
+            if (!((used[s] >> ch) & 1u) || T.nlev == 0) continue;
+            float* P = reinterpret_cast<float*>(mem + pyr_off[s][ch]);
+            T.pyr[ch] = P;
+            const float* src = ch == 3 ? val : col + ch;
+            const int stride = ch == 3 ? 1 : 3;
+            for (int L = 1; L <= T.nlev; L++) {
+                const int cx = cells(T.n[0], L), cy = cells(T.n[1], L), cz = cells(T.n[2], L);
+                const size_t nc = (size_t)cx * cy * cz;
+                if (L == 1)
+                    hipLaunchKernelGGL(k_vol_pyr_base, dim3(grid_for(nc)), dim3(256), 0, g.stream, src, stride, T.n[0], T.n[1], T.n[2], T.pitch,
+                                       cx, cy, cz, P + 2 * T.lev[1]);
+                else
+                    hipLaunchKernelGGL(k_vol_pyr_up, dim3(grid_for(nc)), dim3(256), 0, g.stream, P + 2 * T.lev[L - 1], cells(T.n[0], L - 1),
+                                       cells(T.n[1], L - 1), cells(T.n[2], L - 1), P + 2 * T.lev[L], cx, cy, cz);
+                HIPCHK(hipGetLastError());
+            }
+        }
+    }
+    HIPCHK(hipMemcpyAsync(mem, table.data(), sizeof(SdfkVol) * (size_t)n_vol, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));   // (the host table is a local)
+    // the SdfkK argument: k[] (at least one slot), padded to 8 bytes, then the table pointer
+    const size_t kbytes = (p->params.size() * sizeof(float) + 7) & ~size_t(7);
+    p->kbuf.assign(kbytes / 8 + 1, 0);
+    memcpy(p->kbuf.data(), p->params.data(), p->params.size() * sizeof(float));
+    const uint64_t tp = (uint64_t)(uintptr_t)mem;
+    memcpy(reinterpret_cast<char*>(p->kbuf.data()) + kbytes, &tp, sizeof tp);
+    return SDFK_OK;
+}
+
+extern "C" int sdfk_program_create_bound(const sdfk_op* ops, int32_t n_ops, const int32_t out_rgbw[4], int32_t writes_color,
+                                         const sdfk_volume* const* volumes, int32_t n_volumes, sdfk_program** out)
+{
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (!out || !ops || !out_rgbw || n_ops <= 0) return fail(SDFK_ERR_INVALID, "sdfk_program_create_bound: null/empty argument");
+    *out = nullptr;
+    if (n_volumes < 0 || n_volumes > SDFK_MAX_VOLUMES)
+        return fail(SDFK_ERR_INVALID, "sdfk_program_create_bound: %d volumes (at most %d)", n_volumes, SDFK_MAX_VOLUMES);
+    if (n_volumes > 0 && !volumes) return fail(SDFK_ERR_INVALID, "sdfk_program_create_bound: null volume list");
+    if (int r = require_init()) return r;
+    for (int s = 0; s < n_volumes; s++) {
+        const sdfk_volume* v = volumes[s];
+        if (!v) return fail(SDFK_ERR_INVALID, "sdfk_program_create_bound: volume %d is null", s);
+        if (v->owner != &cur_state()) return fail(SDFK_ERR_INVALID, "sdfk_program_create_bound: volume %d belongs to another device context", s);
+        if (v->elided || !v->values) return fail(SDFK_ERR_INVALID, "sdfk_program_create_bound: volume %d has no stored values", s);
+        if (v->z0 != 0 || v->nz != v->nz_global) return fail(SDFK_ERR_INVALID, "sdfk_program_create_bound: volume %d is a slab", s);
+        const int n[3] = {v->nx, v->ny, v->nz};
+        for (int a = 0; a < 3; a++) {
+            const float d = (v->gmax[a] - v->gmin[a]) / (float)n[a];
+            if (!(v->gmax[a] - v->gmin[a] > 0.0f) || !(d > 0.0f) || !finite_f(d) || !finite_f(v->gmin[a]))
+                return fail(SDFK_ERR_INVALID, "sdfk_program_create_bound: volume %d has no positive finite extent on axis %d", s, a);
+        }
+    }
+    int vol_ops = 0;
+    for (int i = 0; i < n_ops; i++) {
+        const sdfk_op& o = ops[i];
+        if (o.opcode != SDFK_OP_VOXEL_NEAREST && o.opcode != SDFK_OP_VOXEL_LINEAR) continue;
+        vol_ops++;
+        const int slot = o.d >> 2;
+        if (o.d >= 0 && slot < n_volumes && (o.d & 3) != 3 && !volumes[slot]->colors)
+            return fail(SDFK_ERR_INVALID, "op %d: colour channel %d of volume %d, which has no colours", i, o.d & 3, slot);
+    }
+    sdfk_program* p = new sdfk_program();
+    std::string src;
+    if (int r = generate_source(ops, n_ops, out_rgbw, writes_color, src, &p->params, n_volumes)) { delete p; return r; }
+    p->writes_color = writes_color;
+    p->n_ops = n_ops + 7 * vol_ops;   // (a volume read is 8 gathers: SDFK_OPT_COLOR_PASSES weighs it as 8 operations)
+    p->owner = &cur_state();
+    if (vol_ops) {
+        if (int r = bind_volumes(p, ops, n_ops, volumes, n_volumes)) {
+            if (p->vol_mem) (void)hipFree(p->vol_mem);
+            delete p;
+            return r;
+        }
+    }
+    p->code = code_acquire(std::move(src));
+    *out = p;
+    return SDFK_OK;
 }
 
 extern "C" int sdfk_program_create(const sdfk_op* ops, int32_t n_ops, const int32_t out_rgbw[4],
@@ -314,6 +508,12 @@ void program_release(sdfk_program* p)
 {
     if (!p || --p->refs > 0) return;
     code_release(p->code);   // (the modules stay loaded for the next program of this structure)
+    if (p->vol_mem) {   // the volume snapshot: kernels of this program may still be queued
+        StateScope in_owner(p->owner);
+        sync_all_lanes();
+        (void)hipStreamSynchronize(g.stream);
+        (void)hipFree(p->vol_mem);
+    }
     delete p;
 }
 

@@ -436,12 +436,22 @@ extern "C" int sdfk_node_info(const sdfk_node* n, int32_t* world, int32_t* backe
     return SDFK_OK;
 }
 
+// A node takes raw op lists and has no way to bind a volume: programs that read one are refused before any rank sees them.
+static int node_refuse_volume_ops(const sdfk_op* ops, int32_t n_ops, const char* who)
+{
+    for (int32_t i = 0; i < n_ops; i++)
+        if (ops[i].opcode == SDFK_OP_VOXEL_NEAREST || ops[i].opcode == SDFK_OP_VOXEL_LINEAR)
+            return fail(SDFK_ERR_UNSUPPORTED, "%s: op %d reads a volume; a node cannot bind volumes (sdfk_program_create_bound)", who, i);
+    return SDFK_OK;
+}
+
 extern "C" int sdfk_node_to_mesh(sdfk_node* n, const sdfk_op* ops, int32_t n_ops, const int32_t out_rgbw[4], int32_t writes_color,
                                  const float min[3], const float max[3], int32_t nx, int32_t ny, int32_t nz,
                                  int32_t clip_to_bounds, float iso_value, sdfk_mesh** out)
 {
     if (!n || !ops || n_ops <= 0 || !out_rgbw || !min || !max || !out) return fail(SDFK_ERR_INVALID, "sdfk_node_to_mesh: null/empty argument");
     *out = nullptr;
+    if (int r = node_refuse_volume_ops(ops, n_ops, "sdfk_node_to_mesh")) return r;
     std::lock_guard<std::mutex> one(n->call_mu);
     node_set_scene(n, ops, n_ops, out_rgbw, writes_color, min, max, nx, ny, nz, clip_to_bounds, iso_value);
     n->mesh0 = nullptr;
@@ -466,6 +476,7 @@ extern "C" int sdfk_node_mesh_begin(sdfk_node* n, const sdfk_op* ops, int32_t n_
                                     float iso_value, int64_t* n_vertices, int64_t* n_indices, int32_t* has_colors)
 {
     if (!n || !ops || n_ops <= 0 || !out_rgbw || !min || !max) return fail(SDFK_ERR_INVALID, "sdfk_node_mesh_begin: null/empty argument");
+    if (int r = node_refuse_volume_ops(ops, n_ops, "sdfk_node_mesh_begin")) return r;
     std::lock_guard<std::mutex> one(n->call_mu);
     node_set_scene(n, ops, n_ops, out_rgbw, writes_color, min, max, nx, ny, nz, clip_to_bounds, iso_value);
     n->step_open = false;

@@ -20,6 +20,16 @@
     int clip; float outside; int pitch8 /* row pitch of values, colors (x3) and bits8 */; int pad0; unsigned char* bits8; int nx8; float iso;
 
 struct SampleArgs { SDFK_SAMPLE_ARGS_BODY };
+// Descriptor of one volume bound to a program (sdfk_program_create_bound): a device table of these, one per slot, is the ONE
+// pointer a bound program adds to its kernel arguments (SdfkK::V).  val / col: the program's snapshot of Values / Colors in the
+// device layout of sdfk_volume (rows of `pitch` voxels, colour c of voxel i at 3 i + c); mn / d / m: Min, the cell size
+// (Max - Min) / N and the first cell centre Min + 0.5 D, per axis; pyr[ch]: the min/max pyramid of channel ch (0..2 colour, 3
+// distance; null when the program does not read it), level L >= 1 at cell offset lev[L]: cells of 2^L voxels per axis,
+// ((n + 2^L - 1) >> L) per axis, (lo, hi) per cell, NaN where the cell holds a non-finite value; nlev: the top level (1 cell).
+#define SDFK_VOL_BODY                                                                              \
+    const float* val; const float* col; const float* pyr[4]; int n[3]; int pitch; float mn[3], d[3], m[3]; int nlev; \
+    long long lev[32];
+struct SdfkVol { SDFK_VOL_BODY };
 struct RayArgs { float* depth; float* rgb; float cam[3]; float m[16]; int width, height; float nearp, farp; int iters; };
 
 namespace sdfk {
@@ -140,6 +150,119 @@ __device__ __forceinline__ sdfk_iv iv_sel_lt(sdfk_iv a, sdfk_iv b, sdfk_iv c, sd
     r.lo = sdfk_min_ieee(c.lo, d.lo);
     r.hi = sdfk_max_ieee(c.hi, d.hi);
     return iv_whole(r);
+}
+)SRC";
+
+// Reading bound volumes (SDFK_OP_VOXEL_NEAREST / SDFK_OP_VOXEL_LINEAR, include/sdfkit_hip.h has the formulas).  Pasted into the
+// source of bound programs only: the source of every other program is what it always was.
+static const char* const kVolumePrelude =
+    "struct SdfkVol { " SDFK_STR(SDFK_VOL_BODY) " };\n"
+    R"SRC(
+__device__ __forceinline__ float sdfk_vox_at(const SdfkVol& V, int ch, int ix, int iy, int iz)
+{
+    const long i = ((long)ix * V.n[1] + iy) * V.pitch + iz;
+    return ch == 3 ? V.val[i] : V.col[3 * i + ch];
+}
+// Voxels[p] (Voxels.cs:48-56) along one axis: (int)((X - Min) / D), clamped to [0, n - 1] -- compared in float first, so that a huge
+// quotient never reaches the conversion.  q is not NaN here.
+__device__ __forceinline__ int sdfk_vox_near_idx(float q, int n)
+{
+    if (!(q > 0.0f)) return 0;
+    if (!(q < (float)(n - 1))) return n - 1;
+    const int i = (int)q;
+    return i < n - 1 ? i : n - 1;
+}
+__device__ __forceinline__ float sdfk_vox_nearest(const SdfkVol& V, int ch, float X, float Y, float Z)
+{
+    const float qx = (X - V.mn[0]) / V.d[0], qy = (Y - V.mn[1]) / V.d[1], qz = (Z - V.mn[2]) / V.d[2];
+    if (qx != qx || qy != qy || qz != qz) return __builtin_nanf("");
+    return sdfk_vox_at(V, ch, sdfk_vox_near_idx(qx, V.n[0]), sdfk_vox_near_idx(qy, V.n[1]), sdfk_vox_near_idx(qz, V.n[2]));
+}
+// trilinear along one axis: u = (X - m) / D clamped to [0, n - 1], i0 = min(floor(u), n - 2), f = u - i0 (n = 1: i0 = i1 = 0, f = 0)
+__device__ __forceinline__ float sdfk_vox_u(float X, float m, float d, int n)
+{
+    float u = (X - m) / d;
+    u = u > 0.0f ? u : 0.0f;
+    const float top = (float)(n - 1);
+    return u < top ? u : top;
+}
+__device__ __forceinline__ int sdfk_vox_i0(float u, int n)
+{
+    if (n == 1) return 0;
+    const int i = (int)__builtin_floorf(u);
+    return i < n - 2 ? i : n - 2;
+}
+__device__ __forceinline__ float sdfk_lerp(float a, float b, float f) { return a + f * (b - a); }
+__device__ __forceinline__ float sdfk_vox_linear(const SdfkVol& V, int ch, float X, float Y, float Z)
+{
+    if (X != X || Y != Y || Z != Z) return __builtin_nanf("");
+    const float ux = sdfk_vox_u(X, V.m[0], V.d[0], V.n[0]), uy = sdfk_vox_u(Y, V.m[1], V.d[1], V.n[1]), uz = sdfk_vox_u(Z, V.m[2], V.d[2], V.n[2]);
+    const int x0 = sdfk_vox_i0(ux, V.n[0]), y0 = sdfk_vox_i0(uy, V.n[1]), z0 = sdfk_vox_i0(uz, V.n[2]);
+    const int x1 = V.n[0] > 1 ? x0 + 1 : x0, y1 = V.n[1] > 1 ? y0 + 1 : y0, z1 = V.n[2] > 1 ? z0 + 1 : z0;
+    const float fx = V.n[0] > 1 ? ux - (float)x0 : 0.0f, fy = V.n[1] > 1 ? uy - (float)y0 : 0.0f, fz = V.n[2] > 1 ? uz - (float)z0 : 0.0f;
+    const float c000 = sdfk_vox_at(V, ch, x0, y0, z0), c100 = sdfk_vox_at(V, ch, x1, y0, z0);
+    const float c010 = sdfk_vox_at(V, ch, x0, y1, z0), c110 = sdfk_vox_at(V, ch, x1, y1, z0);
+    const float c001 = sdfk_vox_at(V, ch, x0, y0, z1), c101 = sdfk_vox_at(V, ch, x1, y0, z1);
+    const float c011 = sdfk_vox_at(V, ch, x0, y1, z1), c111 = sdfk_vox_at(V, ch, x1, y1, z1);
+    const float a00 = sdfk_lerp(c000, c100, fx), a10 = sdfk_lerp(c010, c110, fx);
+    const float a01 = sdfk_lerp(c001, c101, fx), a11 = sdfk_lerp(c011, c111, fx);
+    const float b0 = sdfk_lerp(a00, a10, fy), b1 = sdfk_lerp(a01, a11, fy);
+    const float r = sdfk_lerp(b0, b1, fz);
+    const float lo = sdfk_min_ieee(sdfk_min_ieee(sdfk_min_ieee(c000, c100), sdfk_min_ieee(c010, c110)),
+                                   sdfk_min_ieee(sdfk_min_ieee(c001, c101), sdfk_min_ieee(c011, c111)));
+    const float hi = sdfk_max_ieee(sdfk_max_ieee(sdfk_max_ieee(c000, c100), sdfk_max_ieee(c010, c110)),
+                                   sdfk_max_ieee(sdfk_max_ieee(c001, c101), sdfk_max_ieee(c011, c111)));
+    return r >= lo ? (r <= hi ? r : hi) : lo;   // (a NaN corner: lo is NaN; a NaN r from inf - inf: lo)
+}
+// Interval form: both index maps are monotone, so a box of points maps to a box of indices; its min / max comes from the pyramid
+// level whose cells the box spans at most two of per axis (at most 8 reads).  Non-finite voxels make the result unknown.
+__device__ __forceinline__ sdfk_iv iv_vox_box(const SdfkVol& V, int ch, int x0, int x1, int y0, int y1, int z0, int z1)
+{
+    int L = 0;
+    while (((x1 >> L) - (x0 >> L)) > 1 || ((y1 >> L) - (y0 >> L)) > 1 || ((z1 >> L) - (z0 >> L)) > 1) L++;
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+    if (L == 0) {
+        for (int k = 0; k < 8; k++) {
+            const float v = sdfk_vox_at(V, ch, (k & 1) ? x1 : x0, (k & 2) ? y1 : y0, (k & 4) ? z1 : z0);
+            if (!__builtin_isfinite(v)) return iv_nan();
+            lo = sdfk_min_ieee(lo, v); hi = sdfk_max_ieee(hi, v);
+        }
+    } else {
+        const long s = 1l << L;
+        const int ny = (int)((V.n[1] + s - 1) >> L), nz = (int)((V.n[2] + s - 1) >> L);
+        const float* P = V.pyr[ch] + 2 * V.lev[L];
+        for (int k = 0; k < 8; k++) {
+            const int cx = ((k & 1) ? x1 : x0) >> L, cy = ((k & 2) ? y1 : y0) >> L, cz = ((k & 4) ? z1 : z0) >> L;
+            const long c = ((long)cx * ny + cy) * nz + cz;
+            lo = sdfk_min_ieee(lo, P[2 * c]); hi = sdfk_max_ieee(hi, P[2 * c + 1]);
+        }
+    }
+    sdfk_iv r; r.lo = lo; r.hi = hi; return iv_whole(r);
+}
+__device__ __forceinline__ sdfk_iv iv_vox_nearest(const SdfkVol& V, int ch, sdfk_iv X, sdfk_iv Y, sdfk_iv Z)
+{
+    if (iv_unknown(X) || iv_unknown(Y) || iv_unknown(Z)) return iv_nan();
+    int i0[3], i1[3];
+    const sdfk_iv A[3] = {X, Y, Z};
+    for (int a = 0; a < 3; a++) {
+        const float q0 = (A[a].lo - V.mn[a]) / V.d[a], q1 = (A[a].hi - V.mn[a]) / V.d[a];
+        if (q0 != q0 || q1 != q1) return iv_nan();   // (inf - inf cannot happen: Min is finite)
+        i0[a] = sdfk_vox_near_idx(q0, V.n[a]); i1[a] = sdfk_vox_near_idx(q1, V.n[a]);
+    }
+    return iv_vox_box(V, ch, i0[0], i1[0], i0[1], i1[1], i0[2], i1[2]);
+}
+__device__ __forceinline__ sdfk_iv iv_vox_linear(const SdfkVol& V, int ch, sdfk_iv X, sdfk_iv Y, sdfk_iv Z)
+{
+    if (iv_unknown(X) || iv_unknown(Y) || iv_unknown(Z)) return iv_nan();
+    int i0[3], i1[3];
+    const sdfk_iv A[3] = {X, Y, Z};
+    for (int a = 0; a < 3; a++) {
+        const int n = V.n[a];
+        i0[a] = sdfk_vox_i0(sdfk_vox_u(A[a].lo, V.m[a], V.d[a], n), n);
+        const int t = sdfk_vox_i0(sdfk_vox_u(A[a].hi, V.m[a], V.d[a], n), n);
+        i1[a] = n > 1 ? t + 1 : t;
+    }
+    return iv_vox_box(V, ch, i0[0], i1[0], i0[1], i1[1], i0[2], i1[2]);
 }
 )SRC";
 
@@ -894,8 +1017,11 @@ inline bool sdfk_const_is_baked(const sdfk_op* ops, int n_ops, int i)
     return false;
 }
 
+// n_volumes: volumes bound to the program (sdfk_program_create_bound); 0 refuses the volume opcodes.  A program with volume
+// operations gets the volume prelude and one more argument, K.V (the device table of SdfkVol descriptors); every other program's
+// source is byte for byte what it was before volumes existed.
 inline bool generate_sample_source(const sdfk_op* ops, int n_ops, const int32_t out_rgbw[4], int writes_color,
-                                   std::string& src, std::string& err, std::vector<float>* params = nullptr)
+                                   std::string& src, std::string& err, std::vector<float>* params = nullptr, int n_volumes = 0)
 {
     char buf[256];
     if (n_ops > (1 << 20)) { err = "program too long"; return false; }
@@ -903,6 +1029,7 @@ inline bool generate_sample_source(const sdfk_op* ops, int n_ops, const int32_t 
     body.reserve((size_t)n_ops * 48);
     ibody.reserve((size_t)n_ops * 56);
     int n_params = 0;
+    bool reads_volumes = false;
     bool parameterise = true;
     {
         int n_const = 0;
@@ -955,6 +1082,28 @@ inline bool generate_sample_source(const sdfk_op* ops, int n_ops, const int32_t 
         case SDFK_OP_MIN_IEEE: arity = 2; fmt = "sdfk_min_ieee(v%d, v%d)"; break;
         case SDFK_OP_MAX_IEEE: arity = 2; fmt = "sdfk_max_ieee(v%d, v%d)"; break;
         case SDFK_OP_SEL_LT: arity = 4; fmt = "(v%d < v%d) ? v%d : v%d"; break;
+        case SDFK_OP_VOXEL_NEAREST:
+        case SDFK_OP_VOXEL_LINEAR: {
+            if (n_volumes <= 0) {
+                snprintf(buf, sizeof buf, "op %d: opcode %d reads a volume and none is bound (sdfk_program_create_bound)", i, o.opcode);
+                err = buf;
+                return false;
+            }
+            const int slot = o.d >> 2, ch = o.d & 3;
+            if (o.d < 0 || slot >= n_volumes || slot >= SDFK_MAX_VOLUMES) {
+                snprintf(buf, sizeof buf, "op %d: volume slot %d is not bound (%d volumes)", i, o.d < 0 ? o.d : slot, n_volumes);
+                err = buf;
+                return false;
+            }
+            if (!arg(o.a, "a") || !arg(o.b, "b") || !arg(o.c, "c")) return false;
+            const char* fn = o.opcode == SDFK_OP_VOXEL_NEAREST ? "nearest" : "linear";
+            snprintf(buf, sizeof buf, "    const float v%d = sdfk_vox_%s(K.V[%d], %d, v%d, v%d, v%d);\n", i, fn, slot, ch, o.a, o.b, o.c);
+            body += buf;
+            snprintf(buf, sizeof buf, "    const sdfk_iv i%d = iv_vox_%s(K.V[%d], %d, i%d, i%d, i%d);\n", i, fn, slot, ch, o.a, o.b, o.c);
+            ibody += buf;
+            reads_volumes = true;
+            continue;
+        }
         default:
             snprintf(buf, sizeof buf, "op %d: unknown opcode %d", i, o.opcode);
             err = buf;
@@ -986,7 +1135,11 @@ inline bool generate_sample_source(const sdfk_op* ops, int n_ops, const int32_t 
     }
     src.clear();
     src += kSamplePrelude;
-    snprintf(buf, sizeof buf, "struct SdfkK { float k[%d]; };\n", n_params > 0 ? n_params : 1);
+    if (reads_volumes) {
+        src += kVolumePrelude;
+        snprintf(buf, sizeof buf, "struct SdfkK { float k[%d]; const SdfkVol* V; };\n", n_params > 0 ? n_params : 1);
+    } else
+        snprintf(buf, sizeof buf, "struct SdfkK { float k[%d]; };\n", n_params > 0 ? n_params : 1);
     src += buf;
     if (params && params->empty()) params->push_back(0.0f);   // (the argument always exists: one unused slot)
     src += "__device__ __forceinline__ void sdf_eval(const SdfkK& K, float X, float Y, float Z, float& R, float& G, float& B, float& W)\n{\n";

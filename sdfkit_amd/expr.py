@@ -19,6 +19,8 @@ OP_CONST, OP_X, OP_Y, OP_Z = 0, 1, 2, 3
 OP_ADD, OP_SUB, OP_MUL, OP_DIV = 4, 5, 6, 7
 OP_NEG, OP_ABS, OP_SQRT, OP_FLOOR = 8, 9, 10, 11
 OP_MIN_SEL, OP_MAX_SEL, OP_MIN_IEEE, OP_MAX_IEEE, OP_SEL_LT = 12, 13, 14, 15, 16
+OP_VOXEL_NEAREST, OP_VOXEL_LINEAR = 17, 18   # reads of a bound volume: d = (slot << 2) | channel (3 = distance)
+MAX_VOLUMES = 8
 
 
 class Builder:
@@ -27,6 +29,22 @@ class Builder:
     def __init__(self):
         self.ops = []           # (opcode, a, b, c, d, imm)
         self._inputs = {}
+        self.volumes = []       # volumes the program reads, slot = index (deduplicated by identity)
+
+    def bind(self, vol):
+        """The slot of volume `vol` (a Voxels), bound on first use."""
+        for i, v in enumerate(self.volumes):
+            if v is vol:
+                return i
+        if len(self.volumes) >= MAX_VOLUMES:
+            raise ValueError(f"an SDF program reads at most {MAX_VOLUMES} volumes")
+        self.volumes.append(vol)
+        return len(self.volumes) - 1
+
+    def voxel(self, opcode, vol, p, channel):
+        """SDFK_OP_VOXEL_NEAREST / _LINEAR of `vol` at the symbolic point p (Vec3)."""
+        slot = self.bind(vol)
+        return self.emit(opcode, self.lift(p.x).id, self.lift(p.y).id, self.lift(p.z).id, (slot << 2) | channel)
 
     def emit(self, opcode, a=-1, b=-1, c=-1, d=-1, imm=0.0):
         self.ops.append((opcode, a, b, c, d, float(imm)))
@@ -201,6 +219,12 @@ def VMax(v):
 def trace(fn, writes_color=True):
     """Run the per-point function `fn(Vec3) -> Vec4` symbolically.
     Returns (ops, out_rgbw) ready for sdfk_program_create."""
+    ops, out, _ = trace_bound(fn, writes_color)
+    return ops, out
+
+
+def trace_bound(fn, writes_color=True):
+    """trace() that also returns the volumes the program reads (slot order): (ops, out_rgbw, volumes)."""
     b = Builder()
     p = Vec3(b.input(0), b.input(1), b.input(2))
     out = fn(p)
@@ -211,4 +235,4 @@ def trace(fn, writes_color=True):
         rgb = [b.lift(out.x).id, b.lift(out.y).id, b.lift(out.z).id]
     else:
         rgb = [-1, -1, -1]
-    return b.ops, rgb + [w.id]
+    return b.ops, rgb + [w.id], list(b.volumes)

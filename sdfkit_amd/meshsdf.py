@@ -80,6 +80,7 @@ class MeshSdf:
         h = voxels._ensure_device(self.Colors is not None or voxels._has_colors)
         N.check(N.lib().sdfk_trimesh_to_volume(self._h, h, C.c_float(maxDistance)))
         voxels._host_values = voxels._host_colors = None   # the device copy is now the truth
+        voxels._version += 1
         return voxels
 
     def stats(self):

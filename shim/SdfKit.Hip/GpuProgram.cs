@@ -40,6 +40,18 @@ namespace SdfKit.Hip
         /// change because two parameters of a scene happen to be equal in one frame of an animation.</summary>
         public int Const(float x) => Emit(Op.Const, imm: x);
 
+        /// <summary>Volumes the program reads (Voxels indexer), slot = index, deduplicated by identity.  The program binds a
+        /// snapshot of them when it is created (sdfk_program_create_bound).</summary>
+        public readonly List<Voxels> Volumes = new List<Voxels>();
+        public int Slot(Voxels v)
+        {
+            int i = Volumes.IndexOf(v);
+            if (i >= 0) return i;
+            if (Volumes.Count >= 8) throw new NotSupportedException("an SDF program reads at most 8 volumes");
+            Volumes.Add(v);
+            return Volumes.Count - 1;
+        }
+
         /// <summary>sdfk_program_create on first use (hiprtc, or the library's on-disk code-object cache).</summary>
         public unsafe IntPtr Handle
         {
@@ -47,9 +59,14 @@ namespace SdfKit.Hip
                 if (handle == IntPtr.Zero) {
                     Native.EnsureInit();
                     var arr = ops.ToArray();
+                    var vols = new IntPtr[Math.Max(Volumes.Count, 1)];
+                    for (int i = 0; i < Volumes.Count; i++) vols[i] = Volumes[i].SyncToDevice();
                     fixed (SdfkOp* p = arr)
                     fixed (int* o = OutRgbw)
-                        Native.Check(Native.sdfk_program_create(p, arr.Length, o, WritesColor ? 1 : 0, out handle));
+                    fixed (IntPtr* v = vols) {
+                        if (Volumes.Count == 0) Native.Check(Native.sdfk_program_create(p, arr.Length, o, WritesColor ? 1 : 0, out handle));
+                        else Native.Check(Native.sdfk_program_create_bound(p, arr.Length, o, WritesColor ? 1 : 0, v, Volumes.Count, out handle));
+                    }
                 }
                 return handle;
             }

@@ -236,6 +236,13 @@ namespace SdfKit.Hip
 
             Val Call(MethodCallExpression c, Dictionary<ParameterExpression, Val> env)
             {
+                if (c.Method.DeclaringType == typeof(Voxels) && c.Method.Name == "get_Item" && c.Arguments.Count == 1 && c.Arguments[0].Type == typeof(Vector3)) {
+                    // voxels[p] (Voxels.cs:48-56) over a closure's Voxels: SDFK_OP_VOXEL_NEAREST of the distance channel.  Out of the
+                    // box the GPU form returns the nearest boundary voxel where the reference throws (include/sdfkit_hip.h)
+                    var vox = (Voxels)(Evaluate(c.Object!) ?? throw new NotSupportedException("null Voxels"));
+                    var p = Visit(c.Arguments[0], env).Ids;
+                    return Val.Of(g.Emit(Op.VoxelNearest, p[0], p[1], p[2], (g.Slot(vox) << 2) | 3));
+                }
                 var a = new List<Val>();
                 if (c.Object != null) a.Add(Visit(c.Object, env));
                 foreach (var x in c.Arguments) a.Add(Visit(x, env));

@@ -29,6 +29,7 @@ namespace SdfKit.Hip
     {
         Const = 0, X = 1, Y = 2, Z = 3, Add = 4, Sub = 5, Mul = 6, Div = 7, Neg = 8, Abs = 9, Sqrt = 10, Floor = 11,
         MinSel = 12, MaxSel = 13, MinIeee = 14, MaxIeee = 15, SelLt = 16,
+        VoxelNearest = 17, VoxelLinear = 18,   // reads of a bound volume: D = (slot << 2) | channel (3 = distance)
     }
 
     static unsafe class Native
@@ -44,6 +45,8 @@ namespace SdfKit.Hip
         // programs (Sdf delegate / SdfExprCompiler.Compile, Sdf.cs:8, SdfExpr.cs:225-273)
         [DllImport(Lib)] public static extern int sdfk_program_create(SdfkOp* ops, int nOps, int* outRgbw, int writesColor, out IntPtr program);
         [DllImport(Lib)] public static extern int sdfk_program_check(SdfkOp* ops, int nOps, int* outRgbw, int writesColor);
+        [DllImport(Lib)] public static extern int sdfk_program_create_bound(SdfkOp* ops, int nOps, int* outRgbw, int writesColor, IntPtr* volumes, int nVolumes, out IntPtr program);
+        [DllImport(Lib)] public static extern int sdfk_program_check_bound(SdfkOp* ops, int nOps, int* outRgbw, int writesColor, int nVolumes);
         [DllImport(Lib)] public static extern void sdfk_program_destroy(IntPtr program);
         // Voxels (Voxels.cs)
         [DllImport(Lib)] public static extern int sdfk_volume_create(int nx, int ny, int nz, float* min, float* max, int withColors, out IntPtr volume);
