@@ -140,6 +140,14 @@ struct MathF {   // System.MathF members used by the catalogue
     static Val Floor(const Val& a) { return un(SDFK_OP_FLOOR, a); }
     static Val Max(const Val& a, const Val& c) { return bin(SDFK_OP_MAX_IEEE, a, c); }
     static Val Min(const Val& a, const Val& c) { return bin(SDFK_OP_MIN_IEEE, a, c); }
+    // The transcendentals of SDF programs (SDFK_OP_SIN .. SDFK_OP_ATAN2: faithful float32 functions, sdfkit_hip.h states them).  They
+    // take symbolic values only -- a literal operand alone throws, it would have to be evaluated here -- so that plain float code
+    // (IterativeClosestPoint's rotations below) keeps calling the C runtime's std::sin / std::cos and never meets them.
+    static Val Sin(const Val& a) { return un(SDFK_OP_SIN, a); }
+    static Val Cos(const Val& a) { return un(SDFK_OP_COS, a); }
+    static Val Exp(const Val& a) { return un(SDFK_OP_EXP, a); }
+    static Val Log(const Val& a) { return un(SDFK_OP_LOG, a); }
+    static Val Atan2(const Val& y, const Val& x) { return bin(SDFK_OP_ATAN2, y, x); }   // MathF.Atan2(y, x)
 };
 
 struct Vec3 {   // System.Numerics.Vector3 over symbolic components

@@ -34,7 +34,8 @@ extern "C" {
                                    the host transport as over RCCL; sdfk_host_alloc works in a process whose only contexts are a node's;
                                    entry points added since, existing ones unchanged: sdfk_points_* (KdTree), sdfk_icp_* (IterativeClosestPoint) and
                                    sdfk_trimesh_* (triangle-mesh distance),
-                                   sdfk_program_create_bound / sdfk_program_check_bound (programs that read voxel volumes) */
+                                   sdfk_program_create_bound / sdfk_program_check_bound (programs that read voxel volumes); opcodes
+                                   SDFK_OP_SIN .. SDFK_OP_ATAN2 (19-23), accepted by every entry point that takes an op list */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -93,7 +94,29 @@ typedef enum sdfk_opcode {
      * The interval form (block culling) maps the box of points to a box of indices (both index maps are monotone) and reads
      * its min / max from a min/max pyramid built at bind time; a non-finite voxel makes it unknown. */
     SDFK_OP_VOXEL_NEAREST = 17,
-    SDFK_OP_VOXEL_LINEAR = 18
+    SDFK_OP_VOXEL_LINEAR = 18,
+    /* MathF.Sin / Cos / Exp / Log (f(a)) and MathF.Atan2 (a = y, b = x).  Each is ONE function of float32 to float32, total, and
+     * stated exactly (sdfkit_amd/csrc/mathops.h holds the text, which is what the JIT compiles): the argument is widened to
+     * binary64, reduced in binary64 (or exactly, in 64-bit integers), a fixed polynomial is evaluated with binary64 + - * / in
+     * the stated order (no fma, no hardware approximation, no device library), the result is scaled with ldexp and rounded ONCE
+     * to float32.  So numpy reproduces every result bit for bit, and each is faithful (within 1 ulp; nearly always correctly
+     * rounded) for every float32.
+     *   SIN / COS: q = rint(x (2/pi)), r = ((x - q P1) - q P2) - q P3 (pi/2 in three parts, P1 P2 of 30 bits) for |x| < 2^22;
+     *     above, r and q mod 4 from an exact Payne-Hanek reduction against 96 bits of 2/pi (64-bit integer products).  Then
+     *     s(r) = r + r^3 (S1 + r^2 (S2 + ... + r^2 S7)), c(r) = 1 + r^2 (C1 + r^2 (C2 + ... + r^2 C8)) (Taylor), and
+     *     sin x = s, c, -s, -c for (q & 3) = 0, 1, 2, 3 (cos x: (q + 1) & 3).  sin(+-0) = +-0, cos(+-0) = 1, (+-inf) = NaN.
+     *   EXP: k = rint(x log2 e), r = (x - k L1) - k L2 (ln 2 in two parts, L1 of 44 bits), p = 1 + r (1 + r (1/2! + ... r / 13!)),
+     *     ldexp(p, k).  x >= 89 gives +inf (overflow), x <= -104 gives +0 (below 2^-150), between: correctly rounded subnormals.
+     *     exp(-inf) = +0, exp(+inf) = +inf.
+     *   LOG: frexp(x) = m 2^e, m in [sqrt(1/2), sqrt(2)); f = m - 1, s = f / (2 + f), e L1 + (e L2 + (2s + 2s s^2 (1/3 + ... +
+     *     s^18 / 21))).  log(+-0) = -inf, log(x < 0) = NaN, log(1) = +0, log(+inf) = +inf.
+     *   ATAN2: t = min(|y|, |x|) / max(|y|, |x|), j = rint(8 t), u = (8 t - j) / (8 + t j), a = atan(j/8) + (u + u^3 (A1 + ...
+     *     + u^12 A7)); pi/2 - a when |y| > |x|, pi - a when x < 0, negated when y < 0.  C99 Annex F: atan2(+-0, x >= +0) = +-0,
+     *     atan2(+-0, x <= -0) = +-(float)pi ((float)pi > pi), atan2(+-inf, +inf) = +-pi/4, atan2(+-inf, -inf) = +-3pi/4,
+     *     atan2(y, +-0) = +-pi/2, atan2(y finite, +inf) = +-0, (y finite, -inf) = +-pi.
+     * NaN in gives NaN out.  The interval forms (block culling) widen faithful results by one ulp: see csrc/sample_codegen.h. */
+    SDFK_OP_SIN = 19, SDFK_OP_COS = 20, SDFK_OP_EXP = 21, SDFK_OP_LOG = 22,
+    SDFK_OP_ATAN2 = 23
 } sdfk_opcode;
 #define SDFK_MAX_VOLUMES 8
 

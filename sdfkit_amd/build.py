@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "libsdfkit_hip.so")
 # mesh accessors; the sharded step; the marching-cubes kernels; KdTree / IterativeClosestPoint; triangle-mesh distance volumes
 SOURCES = ["lib_context.hip", "lib_jit.hip", "lib_volume.hip", "lib_march.hip", "lib_mesh.hip", "lib_dist.hip", "mc_kernels.hip", "lib_points.hip",
            "lib_trimesh.hip"]
-HEADERS = ["lib_internal.h", "points_grid.h", "trimesh_sdf.h", "device_scan.h", "mc_kernels.h", "mc_device.h", "mc_decide.h", "mc_params.h", "mc_luts.h", "sample_codegen.h", "dist_rccl.h", "node_local.h",
+HEADERS = ["lib_internal.h", "points_grid.h", "trimesh_sdf.h", "device_scan.h", "mc_kernels.h", "mc_device.h", "mc_decide.h", "mc_params.h", "mc_luts.h", "sample_codegen.h", "mathops.h", "dist_rccl.h", "node_local.h",
            "slab_protocol.h", os.path.join("..", "..", "include", "sdfkit_hip.h")]
 DEPS = ["exports.map"] + SOURCES + HEADERS
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fno-fast-math", "-fvisibility=hidden", "-Wall",

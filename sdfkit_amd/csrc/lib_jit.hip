@@ -225,6 +225,16 @@ int generate_source(const sdfk_op* ops, int32_t n_ops, const int32_t out_rgbw[4]
     return SDFK_OK;
 }
 
+// What SDFK_OPT_COLOR_PASSES adds to the operation count of a program for its SDFK_OP_SIN .. SDFK_OP_ATAN2: each weighs 32 operations
+// (about 30 binary64 operations, at half the float rate), so that a program with one of them is never "cheap enough to be evaluated
+// twice" (DESIGN.md 8d).
+static int32_t math_weight(const sdfk_op* ops, int32_t n_ops)
+{
+    int32_t w = 0;
+    for (int32_t i = 0; i < n_ops; i++) w += ops[i].opcode >= SDFK_OP_SIN && ops[i].opcode <= SDFK_OP_ATAN2 ? 31 : 0;
+    return w;
+}
+
 extern "C" int sdfk_program_check(const sdfk_op* ops, int32_t n_ops, const int32_t out_rgbw[4], int32_t writes_color)
 {
     if (!ops || !out_rgbw || n_ops <= 0) return fail(SDFK_ERR_INVALID, "sdfk_program_check: null/empty argument");
@@ -416,7 +426,7 @@ extern "C" int sdfk_program_create_bound(const sdfk_op* ops, int32_t n_ops, cons
     std::string src;
     if (int r = generate_source(ops, n_ops, out_rgbw, writes_color, src, &p->params, n_volumes)) { delete p; return r; }
     p->writes_color = writes_color;
-    p->n_ops = n_ops + 7 * vol_ops;   // (a volume read is 8 gathers: SDFK_OPT_COLOR_PASSES weighs it as 8 operations)
+    p->n_ops = n_ops + 7 * vol_ops + math_weight(ops, n_ops);   // (a volume read is 8 gathers: SDFK_OPT_COLOR_PASSES weighs it as 8 operations)
     p->owner = &cur_state();
     if (vol_ops) {
         if (int r = bind_volumes(p, ops, n_ops, volumes, n_volumes)) {
@@ -441,7 +451,7 @@ extern "C" int sdfk_program_create(const sdfk_op* ops, int32_t n_ops, const int3
     std::string src;
     if (int r = generate_source(ops, n_ops, out_rgbw, writes_color, src, &p->params)) { delete p; return r; }   // validates the op list
     p->writes_color = writes_color;
-    p->n_ops = n_ops;
+    p->n_ops = n_ops + math_weight(ops, n_ops);
     p->code = code_acquire(std::move(src));
     *out = p;
     return SDFK_OK;

@@ -266,6 +266,80 @@ __device__ __forceinline__ sdfk_iv iv_vox_linear(const SdfkVol& V, int ch, sdfk_
 }
 )SRC";
 
+// MathF.Sin / Cos / Exp / Log / Atan2 (SDFK_OP_SIN .. SDFK_OP_ATAN2, include/sdfkit_hip.h has the formulas): the arithmetic is the
+// text of mathops.h -- one text, compiled here for the device and by tests/cpp/mathops_host.cpp for the host -- and pasted, with
+// the interval forms below, into the source of programs that use one of the five opcodes only: every other program's source is
+// byte for byte what it was before they existed.
+#define SDFK_MATHOPS_EMIT(...) static const char* const kMathText = #__VA_ARGS__;
+#include "mathops.h"
+#undef SDFK_MATHOPS_EMIT
+static const char* const kMathQualifiers = "#define SDFK_M_FN __device__ __forceinline__\n#define SDFK_M_TABLE __constant__ const\n";
+static const char* const kMathIntervals = R"SRC(
+// ---- interval forms of the five (block culling) ------------------------------------------------------------------------------------
+// The prelude's "no outward rounding" holds for correctly rounded monotone operations; these are faithful (within 1 ulp) instead.
+// If f is monotone on [lo, hi] and f^ is faithful, f^(x) >= RD(f(x)) >= RD(f(lo)) >= pred(f^(lo)) for every x inside, likewise
+// above: [pred f^(lo), succ f^(hi)] contains every f^ in between.  Unknown (NaN) stays a property of the whole interval.
+__device__ __forceinline__ float sdfk_succ(float v)
+{
+    if (v != v || v == __builtin_inff()) return v;
+    if (v == 0.0f) return __builtin_bit_cast(float, 1u);
+    const int b = __builtin_bit_cast(int, v);
+    return __builtin_bit_cast(float, v > 0.0f ? b + 1 : b - 1);
+}
+__device__ __forceinline__ float sdfk_pred(float v) { return -sdfk_succ(-v); }
+__device__ __forceinline__ sdfk_iv iv_exp(sdfk_iv a) { sdfk_iv r; r.lo = sdfk_pred(sdfk_expf(a.lo)); r.hi = sdfk_succ(sdfk_expf(a.hi)); return iv_whole(r); }
+// (an interval reaching below zero holds points whose logarithm is NaN: unknown, as iv_sqrt; log(-0) = -inf is not NaN)
+__device__ __forceinline__ sdfk_iv iv_log(sdfk_iv a)
+{
+    if (!(a.lo >= 0.0f)) return iv_nan();
+    sdfk_iv r; r.lo = sdfk_pred(sdfk_logf(a.lo)); r.hi = sdfk_succ(sdfk_logf(a.hi)); return iv_whole(r);
+}
+// sin (phase 0) / cos (phase 1): the ends, widened by one ulp, and +1 / -1 wherever the box may hold a maximum / minimum.  The
+// extrema lie at the centres of quadrants (r = 0 of sdfk_m_reduce): +1 where (quadrant + phase) & 3 == 1, -1 where it is 3.  The
+// position of each end in quadrant units, relative to the centre of lo's quadrant, comes from the same reduction; a centre within
+// 2^-20 quadrants of the box (the reduction is good to ~2^-50) counts as inside.  A box wider than 4 (< 2 pi, so the quadrants of
+// its ends are at most 3 apart and (qh - ql) & 3 is their distance) gives [-1, 1]; an infinite end holds a NaN point: unknown.
+// f^ never leaves [-1, 1] (|sin r| < 1 on the reduced range, cos r <= 1), so the result is clamped to it.
+__device__ __forceinline__ sdfk_iv iv_sincos(sdfk_iv a, int phase)
+{
+    if (iv_unknown(a) || __builtin_isinf(a.lo) || __builtin_isinf(a.hi)) return iv_nan();
+    sdfk_iv r;
+    if ((double)a.hi - (double)a.lo > 4.0) { r.lo = -1.0f; r.hi = 1.0f; return r; }
+    const float fl = sdfk_m_sincos(a.lo, phase), fh = sdfk_m_sincos(a.hi, phase);
+    r.lo = sdfk_min_ieee(sdfk_pred(fl), sdfk_pred(fh));
+    r.hi = sdfk_max_ieee(sdfk_succ(fl), sdfk_succ(fh));
+    int ql, qh;
+    const double rl = sdfk_m_reduce(a.lo, &ql), rh = sdfk_m_reduce(a.hi, &qh);
+    const double tl = rl * 0x1.45f306dc9c883p-1, th = (double)((qh - ql) & 3) + rh * 0x1.45f306dc9c883p-1;
+    bool hmax = false, hmin = false;
+    for (int j = 0; j < 4; j++) {
+        const bool inside = tl - 0x1p-20 <= (double)j && (double)j <= th + 0x1p-20;
+        const int k = (ql + j + phase) & 3;
+        hmax |= inside && k == 1;
+        hmin |= inside && k == 3;
+    }
+    r.hi = hmax ? 1.0f : sdfk_min_ieee(r.hi, 1.0f);
+    r.lo = hmin ? -1.0f : sdfk_max_ieee(r.lo, -1.0f);
+    return r;
+}
+__device__ __forceinline__ sdfk_iv iv_sin(sdfk_iv a) { return iv_sincos(a, 0); }
+__device__ __forceinline__ sdfk_iv iv_cos(sdfk_iv a) { return iv_sincos(a, 1); }
+// atan2(y, x): the angle of a box that contains neither the origin nor a point of the cut (x <= 0, y = +-0, where the result jumps
+// between -pi and pi) ranges over an interval whose ends are taken at corners (infinite corners included: their values are the
+// limits along the box's edges); otherwise [-(float)pi, (float)pi], every value f^ can take.
+__device__ __forceinline__ sdfk_iv iv_atan2(sdfk_iv y, sdfk_iv x)
+{
+    if (iv_unknown(y) || iv_unknown(x)) return iv_nan();
+    const float pi = 3.14159274101257324f;
+    sdfk_iv r;
+    if (x.lo <= 0.0f && y.lo <= 0.0f && y.hi >= 0.0f) { r.lo = -pi; r.hi = pi; return r; }
+    const float c0 = sdfk_atan2f(y.lo, x.lo), c1 = sdfk_atan2f(y.lo, x.hi), c2 = sdfk_atan2f(y.hi, x.lo), c3 = sdfk_atan2f(y.hi, x.hi);
+    r.lo = sdfk_max_ieee(sdfk_min_ieee(sdfk_min_ieee(sdfk_pred(c0), sdfk_pred(c1)), sdfk_min_ieee(sdfk_pred(c2), sdfk_pred(c3))), -pi);
+    r.hi = sdfk_min_ieee(sdfk_max_ieee(sdfk_max_ieee(sdfk_succ(c0), sdfk_succ(c1)), sdfk_max_ieee(sdfk_succ(c2), sdfk_succ(c3))), pi);
+    return iv_whole(r);
+}
+)SRC";
+
 static const char* const kSampleKernels = R"SRC(
 // Voxels.SampleSdf (Voxels.cs:72-125): sample point of voxel (ix,iy,iz) is
 //   p = (min + 0.5*D) + (float)i * D   per axis (Voxels.cs:81,104-106),
@@ -1019,7 +1093,8 @@ inline bool sdfk_const_is_baked(const sdfk_op* ops, int n_ops, int i)
 
 // n_volumes: volumes bound to the program (sdfk_program_create_bound); 0 refuses the volume opcodes.  A program with volume
 // operations gets the volume prelude and one more argument, K.V (the device table of SdfkVol descriptors); every other program's
-// source is byte for byte what it was before volumes existed.
+// source is byte for byte what it was before volumes existed.  Likewise a program with SDFK_OP_SIN .. SDFK_OP_ATAN2 gets the math
+// prelude (kMathText + kMathIntervals) and no new argument.
 inline bool generate_sample_source(const sdfk_op* ops, int n_ops, const int32_t out_rgbw[4], int writes_color,
                                    std::string& src, std::string& err, std::vector<float>* params = nullptr, int n_volumes = 0)
 {
@@ -1030,6 +1105,7 @@ inline bool generate_sample_source(const sdfk_op* ops, int n_ops, const int32_t 
     ibody.reserve((size_t)n_ops * 56);
     int n_params = 0;
     bool reads_volumes = false;
+    bool uses_math = false;   // SDFK_OP_SIN .. SDFK_OP_ATAN2: the math prelude
     bool parameterise = true;
     {
         int n_const = 0;
@@ -1082,6 +1158,11 @@ inline bool generate_sample_source(const sdfk_op* ops, int n_ops, const int32_t 
         case SDFK_OP_MIN_IEEE: arity = 2; fmt = "sdfk_min_ieee(v%d, v%d)"; break;
         case SDFK_OP_MAX_IEEE: arity = 2; fmt = "sdfk_max_ieee(v%d, v%d)"; break;
         case SDFK_OP_SEL_LT: arity = 4; fmt = "(v%d < v%d) ? v%d : v%d"; break;
+        case SDFK_OP_SIN: arity = 1; fmt = "sdfk_sinf(v%d)"; uses_math = true; break;
+        case SDFK_OP_COS: arity = 1; fmt = "sdfk_cosf(v%d)"; uses_math = true; break;
+        case SDFK_OP_EXP: arity = 1; fmt = "sdfk_expf(v%d)"; uses_math = true; break;
+        case SDFK_OP_LOG: arity = 1; fmt = "sdfk_logf(v%d)"; uses_math = true; break;
+        case SDFK_OP_ATAN2: arity = 2; fmt = "sdfk_atan2f(v%d, v%d)"; uses_math = true; break;
         case SDFK_OP_VOXEL_NEAREST:
         case SDFK_OP_VOXEL_LINEAR: {
             if (n_volumes <= 0) {
@@ -1121,7 +1202,8 @@ inline bool generate_sample_source(const sdfk_op* ops, int n_ops, const int32_t 
         body += buf;
         {   // the same operation on intervals
             static const char* const ifn[] = {nullptr, nullptr, nullptr, nullptr, "iv_add", "iv_sub", "iv_mul", "iv_div", "iv_neg", "iv_abs", "iv_sqrt",
-                                              "iv_floor", "iv_min", "iv_max", "iv_min", "iv_max", "iv_sel_lt"};
+                                              "iv_floor", "iv_min", "iv_max", "iv_min", "iv_max", "iv_sel_lt", nullptr, nullptr,
+                                              "iv_sin", "iv_cos", "iv_exp", "iv_log", "iv_atan2"};
             if (o.opcode == SDFK_OP_MUL && o.a == o.b) snprintf(buf, sizeof buf, "    const sdfk_iv i%d = iv_sqr(i%d);\n", i, o.a);
             else if (arity == 1) snprintf(buf, sizeof buf, "    const sdfk_iv i%d = %s(i%d);\n", i, ifn[o.opcode], o.a);
             else if (arity <= 3) snprintf(buf, sizeof buf, "    const sdfk_iv i%d = %s(i%d, i%d);\n", i, ifn[o.opcode], o.a, o.b);
@@ -1135,6 +1217,12 @@ inline bool generate_sample_source(const sdfk_op* ops, int n_ops, const int32_t 
     }
     src.clear();
     src += kSamplePrelude;
+    if (uses_math) {
+        src += kMathQualifiers;
+        src += kMathText;
+        src += "\n";
+        src += kMathIntervals;
+    }
     if (reads_volumes) {
         src += kVolumePrelude;
         snprintf(buf, sizeof buf, "struct SdfkK { float k[%d]; const SdfkVol* V; };\n", n_params > 0 ? n_params : 1);

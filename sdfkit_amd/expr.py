@@ -9,8 +9,9 @@ library JIT-compiles the list for the GPU.  Nothing is evaluated on the host.
 Arithmetic conventions restated from the .NET BCL (System.Numerics, not in the
 reference tree): Vector3.Length = sqrt((x*x + y*y) + z*z); Vector3.Dot likewise;
 Vector3.Min/Max = compare-select; MathF.Max/Min and Math.Max/Min = IEEE-754:2019
-maximum/minimum; Vector3 / float = component-wise division; float * Vector3 =
-component-wise multiply.
+maximum/minimum; MathF.Sin/Cos/Exp/Log/Atan2 = the faithful float32 functions
+include/sdfkit_hip.h states (Math.* on doubles is another function: not offered);
+Vector3 / float = component-wise division; float * Vector3 = component-wise multiply.
 """
 import numpy as np
 
@@ -20,6 +21,7 @@ OP_ADD, OP_SUB, OP_MUL, OP_DIV = 4, 5, 6, 7
 OP_NEG, OP_ABS, OP_SQRT, OP_FLOOR = 8, 9, 10, 11
 OP_MIN_SEL, OP_MAX_SEL, OP_MIN_IEEE, OP_MAX_IEEE, OP_SEL_LT = 12, 13, 14, 15, 16
 OP_VOXEL_NEAREST, OP_VOXEL_LINEAR = 17, 18   # reads of a bound volume: d = (slot << 2) | channel (3 = distance)
+OP_SIN, OP_COS, OP_EXP, OP_LOG, OP_ATAN2 = 19, 20, 21, 22, 23   # MathF.Sin / Cos / Exp / Log / Atan2(y, x) (csrc/mathops.h)
 MAX_VOLUMES = 8
 
 
@@ -119,6 +121,19 @@ class MathF:
     def Min(a, b_):
         b = _builder_of(a, b_)
         return b.emit(OP_MIN_IEEE, b.lift(a).id, b.lift(b_).id)
+    # the transcendentals: faithful float32 functions stated exactly in include/sdfkit_hip.h (SDFK_OP_SIN .. SDFK_OP_ATAN2)
+    @staticmethod
+    def Sin(a): return _builder_of(a).emit(OP_SIN, a.id)
+    @staticmethod
+    def Cos(a): return _builder_of(a).emit(OP_COS, a.id)
+    @staticmethod
+    def Exp(a): return _builder_of(a).emit(OP_EXP, a.id)
+    @staticmethod
+    def Log(a): return _builder_of(a).emit(OP_LOG, a.id)
+    @staticmethod
+    def Atan2(y, x):
+        b = _builder_of(y, x)
+        return b.emit(OP_ATAN2, b.lift(y).id, b.lift(x).id)
 
 
 def select_lt(a, b_, c, d):

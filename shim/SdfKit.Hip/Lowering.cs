@@ -15,6 +15,8 @@
 //   MemberAccess .X .Y .Z .W, SdfIndexedInput.Position/.Index, Vector3.One/Zero/UnitX.., closure fields (constants)
 //   + - * / unary -  on float and Vector3 (BCL operators are component-wise; float*Vector3 and Vector3/float
 //   broadcast the scalar), Call: MathF.Sqrt/Abs/Floor/Max/Min, Math.Max/Min/Abs/Sqrt/Floor on floats,
+//   MathF.Sin/Cos/Exp/Log/Atan2 (the float functions include/sdfkit_hip.h states; Math.Sin & co. on doubles are another function
+//   -- a double result rounded to float -- and stay unsupported),
 //   Vector3.Abs/Max/Min/Dot, v.Length(), v.LengthSquared(), VectorOps.Mod (VectorData.cs:697-698),
 //   VectorOps.VMax (:860-861), Convert(int|double constant -> float).
 // Anything else throws NotSupportedException: the caller then keeps the reference's CPU path for that SDF.
@@ -256,6 +258,15 @@ namespace SdfKit.Hip
                     case "Floor": return Val.Of(g.Emit(Op.Floor, Scalar(a[0])));
                     case "Max": return Val.Of(g.Emit(Op.MaxIeee, Scalar(a[0]), Scalar(a[1])));   // IEEE 754:2019 maximum (NaN-propagating, -0 < +0)
                     case "Min": return Val.Of(g.Emit(Op.MinIeee, Scalar(a[0]), Scalar(a[1])));
+                    }
+                    if (t == typeof(MathF)) {
+                        switch (name) {
+                        case "Sin": return Val.Of(g.Emit(Op.Sin, Scalar(a[0])));
+                        case "Cos": return Val.Of(g.Emit(Op.Cos, Scalar(a[0])));
+                        case "Exp": return Val.Of(g.Emit(Op.Exp, Scalar(a[0])));
+                        case "Log": return Val.Of(g.Emit(Op.Log, Scalar(a[0])));
+                        case "Atan2": return Val.Of(g.Emit(Op.Atan2, Scalar(a[0]), Scalar(a[1])));   // MathF.Atan2(y, x): A = y, B = x
+                        }
                     }
                 } else if (t == typeof(Vector3)) {
                     switch (name) {

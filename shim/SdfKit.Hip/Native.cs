@@ -30,6 +30,7 @@ namespace SdfKit.Hip
         Const = 0, X = 1, Y = 2, Z = 3, Add = 4, Sub = 5, Mul = 6, Div = 7, Neg = 8, Abs = 9, Sqrt = 10, Floor = 11,
         MinSel = 12, MaxSel = 13, MinIeee = 14, MaxIeee = 15, SelLt = 16,
         VoxelNearest = 17, VoxelLinear = 18,   // reads of a bound volume: D = (slot << 2) | channel (3 = distance)
+        Sin = 19, Cos = 20, Exp = 21, Log = 22, Atan2 = 23,   // MathF.Sin / Cos / Exp / Log / Atan2(y = A, x = B): faithful float32 functions
     }
 
     static unsafe class Native
