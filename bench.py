@@ -7,7 +7,7 @@ on a synthetic 512^3 sphere SDF (`Sdfs.Sphere(1)`, bounds -1.5..1.5, no clip, is
 writes the volume to HBM, the marching-cubes pipeline reads it and leaves the indexed mesh
 (vertices, colours, normals, triangles) in HBM; inputs and outputs stay device-resident.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1)
 
 N > 1: the SAME 512^3 grid is sharded by Z slab over the ranks (strong scaling); the exchange of the slab
@@ -21,7 +21,9 @@ Every rank a launcher starts is a SUPERVISOR that never touches HIP: the measuri
 limit; the supervisors agree (gloo) whether all workers finished and otherwise ALL start the next, more conservative
 configuration (RANK_TRIES) -- a collective that hangs on first contact with a node costs one time limit, not the run.
 
-Beside the headline, on the same JSON line (never as `value`):
+A plain run does what the headline needs and nothing else: set-up, the warm-up, the timed steps, --dump-outputs, the result line.
+(--minimal, the form for rocprofv3 counter passes, is what it was: the timed steps, their cold-clock repeat and the per-kernel pass.)
+With --full, beside the headline, on the same JSON line (never as `value`):
   N = 1   BASELINE's other configs -- c2_sphere_256, c3_repeatxy, c4_union8_1024 (the whole 1024^3 grid on one GPU), c5_raymarch --, the
           product default (`elided`: the temporary volume of SdfEx.ToMesh is not stored) with a bound of its own, the controls for the
           colour sampler, the host hand-off figures, the CPU baseline (oracle/, the reference algorithm restated in C).
@@ -402,6 +404,10 @@ def compare_sharded_with_single(single, whole, slab_digests, counts, flip_one_in
             "sha256_sharded": d_g if d_g != d_s else "identical"}
 
 
+# the result line of a plain run (no --full): the headline, how it was timed, and what set-up measures on its way
+PLAIN_RUN_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "blocks", "dump_outputs", "higher_is_better", "scaling",
+                  "vs_baseline", "dtype", "data", "config", "untimed_steps_before_timing", "mtris_per_s", "first_call_ms", "first_call")
+
 XGMI_LINKS = 7
 XGMI_LINK_GBS_PER_DIRECTION = 76.8   # 153.6 GB/s per link, both directions together
 
@@ -415,7 +421,10 @@ def main():
     ap.add_argument("--scene", default="sphere", choices=["sphere", "repeatxy", "union8"])
     ap.add_argument("--cpu-n", type=int, default=0, help="grid edge of the CPU-baseline run (default: the same grid as the GPU run)")
     ap.add_argument("--cpu-passes", type=int, default=3, help="timed passes of the CPU baseline (after 1 warm-up)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full or --minimal: leave the CPU baseline out (a plain run has none)")
+    ap.add_argument("--full", action="store_true", help="everything the benchmark measures or checks beside the headline: the first-call, cold-clock, per-kernel and "
+                    "roofline passes, the other configurations, the host hand-off figures, the CPU baseline; with --gpus N the content checks against "
+                    "one GPU and the passes after the headline.  Off by default: a plain run sets up, warms up, times the steps and prints the line")
     ap.add_argument("--minimal", action="store_true", help="timed loop + per-kernel pass only (for rocprofv3 counter passes: no cold-call, "
                     "latency, host-copy or host-Values legs, whose launches would mix into the per-kernel means)")
     ap.add_argument("--elide", action="store_true", help="PROFILING ONLY (with --minimal): the timed loop runs the product default -- the volume is not "
@@ -426,13 +435,15 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    lean = not (args.full or args.minimal)     # a plain run: the headline and nothing beside it
+    legs = args.full and not args.minimal      # --full: every leg beside the headline (--minimal keeps the per-kernel pass only)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing above has imported torch or
         # called HIP; the ranks are CHILD processes (a process that has touched the GPU must never exec).
         argv = ["--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--grid", str(args.n),
                 "--scene", args.scene, "--cpu-n", str(args.cpu_n), "--cpu-passes", str(args.cpu_passes)] + (["--no-cpu"] if args.no_cpu else []) + \
-               (["--minimal"] if args.minimal else []) + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])
+               (["--minimal"] if args.minimal else []) + (["--full"] if args.full else []) + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])
         sys.exit(launch_ranks(argv, args.gpus))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and os.environ.get("SDFK_BENCH_WORKER") != "1":
         # a rank as the launcher (the driver's torch.distributed.run, or launch_ranks above) started it: supervise a worker
@@ -518,7 +529,7 @@ def main():
     # the first call when the machine has never seen the program: code-object cache off, and the structure's modules unloaded
     # with the program afterwards (SDFK_OPT_IDLE_PROGRAMS = 0) so that the legs below start where a fresh process starts
     cold_first_call_ms = None
-    if world == 1 and not args.minimal:
+    if world == 1 and legs:
         with N.option(N.OPT_CODE_CACHE, 0), N.option(N.OPT_IDLE_PROGRAMS, 0):
             cold_sdf = scene_for(args.scene)[0]
             t0 = time.perf_counter()
@@ -544,6 +555,7 @@ def main():
                          "allocated from the driver")
         if cold_first_call_ms is not None:
             first["cold_first_call_ms"] = cold_first_call_ms
+    if world == 1 and not lean:
         # The same scene with OTHER constants (a new radius: the next frame of an animation, a parameter sweep).  The constants of
         # a program are kernel arguments and the compiled kernels belong to the program's STRUCTURE, so this is program creation
         # (tracing in the Python mirror + sdfk_program_create) + one sample -> mesh + the counts: no hiprtc, no cache file.
@@ -712,20 +724,22 @@ def main():
     if kept:
         from sdfkit_amd.api import Mesh as HostMesh
         dumped = dump_outputs(args.dump_outputs, mesh_outputs(HostMesh._from_handle(kept.pop())))   # (frees the handle)
-    # The same K steps with COLD clocks: the GPU idles long enough to drop its clocks, then W warm-up steps and K timed ones
-    # -- what the driver's command measures without the clock warm-up above (the headline `value` has it, and says so).
-    time.sleep(0.25)
-    barrier()
-    for _ in range(max(args.warmup, 1)):
-        step()
-    drain()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    drain()
-    barrier()
-    dt_cold = max_over_ranks(time.perf_counter() - t0)
+    dt_cold = None
+    if not lean:
+        # The same K steps with COLD clocks: the GPU idles long enough to drop its clocks, then W warm-up steps and K timed ones
+        # -- what the driver's command measures without the clock warm-up above (the headline `value` has it, and says so).
+        time.sleep(0.25)
+        barrier()
+        for _ in range(max(args.warmup, 1)):
+            step()
+        drain()
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        drain()
+        barrier()
+        dt_cold = max_over_ranks(time.perf_counter() - t0)
     per_rank = None
     if sharded:   # per-rank counts -> totals of the whole mesh (from the gathered headers of the last step)
         per_rank = [list(c) for c in worker.counts()]
@@ -795,7 +809,17 @@ def main():
     # (what "kernel-only" means at N > 1); max over ranks
     dist_extra = {}
     headline_content = None
-    if sharded:
+    if sharded and lean:
+        # (a plain run: who took part, and the mesh for --dump-outputs -- sdfk_dist_mesh is collective when the mesh stays sharded, see content_check)
+        dist_extra = {"world": world, "backend": backend, "per_rank_vertices_indices": per_rank}
+        if os.environ.get("SDFK_BENCH_NOTE"):
+            dist_extra["note"] = os.environ["SDFK_BENCH_NOTE"]
+        if args.dump_outputs and (headline_mode == 3 or rank == 0):
+            whole = worker.mesh()
+            if rank == 0:
+                dumped = dump_outputs(args.dump_outputs, mesh_outputs(whole))
+            del whole
+    if sharded and not lean:
         whole_kept = [] if args.dump_outputs else None
         headline_content = content_check(worker, sdf, mn, mx, clip, n, headline_mode, whole_kept)   # (before enqueue_only reuses slot 0's send buffer)
         if whole_kept:
@@ -879,23 +903,25 @@ def main():
     # jobs stay queued ahead (no host bubbles) but on ONE in-order stream: a kernel's roofline is
     # about the kernel having the GPU to itself, not about how it shares the chip with the
     # previous step's kernels on the other internal stream.
-    lanes_before = N.get_option(N.OPT_LANES)
-    N.set_option(N.OPT_LANES, 0)      # every job on ONE in-order stream
-    N.check(L.sdfk_profile_reset())
-    N.check(L.sdfk_profile_enable(1))
-    for _ in range(args.steps):
-        step()
-    drain()
-    barrier()
-    N.check(L.sdfk_profile_enable(0))
-    prof = N.profile_snapshot()
-    kern = {k: {"avg_us": round(v[0] / max(v[1], 1) * 1e3, 2), "launches": v[1]} for k, v in prof.items() if v[1]}
+    kern = {}
+    if not lean:
+        lanes_before = N.get_option(N.OPT_LANES)
+        N.set_option(N.OPT_LANES, 0)      # every job on ONE in-order stream
+        N.check(L.sdfk_profile_reset())
+        N.check(L.sdfk_profile_enable(1))
+        for _ in range(args.steps):
+            step()
+        drain()
+        barrier()
+        N.check(L.sdfk_profile_enable(0))
+        prof = N.profile_snapshot()
+        kern = {k: {"avg_us": round(v[0] / max(v[1], 1) * 1e3, 2), "launches": v[1]} for k, v in prof.items() if v[1]}
 
     # ---- latency of ONE call, nothing else in flight, everything on one stream: sdfk_sample_march,
     # then the accessor that waits for it (what a caller that needs each mesh before it builds the
     # next one gets; the headline `value` is the pipelined steady state)
     latency_ms = latency_default_ms = None
-    if not sharded and not args.minimal:
+    if not sharded and legs:
         for _ in range(3):
             sample_march_once()
         torch.cuda.synchronize()
@@ -914,14 +940,15 @@ def main():
                 for _ in range(args.steps):
                     sample_march_once()
                 latency_default_ms = (time.perf_counter() - t0) / args.steps * 1e3
-    N.set_option(N.OPT_LANES, lanes_before)
+    if not lean:
+        N.set_option(N.OPT_LANES, lanes_before)
 
     # The roofline kernel on its own: K back-to-back launches of the fused sampling kernel into a
     # resident volume (sdfk_sample), HIP event pairs around each launch on the launch stream.  In
     # the pipeline pass above the event pair of a job's FIRST kernel also contains the time the
     # stream sat idle waiting for the (event-laden, hence slower) host to queue the job.
     roof_us = None
-    if not sharded and not args.minimal:
+    if not sharded and legs:
         from sdfkit_amd.api import Voxels
         # (four volumes in turn, as the pipeline does: re-writing the SAME 512 MiB back to back is
         # 30 % slower than writing a buffer that was last touched a few launches ago)
@@ -972,7 +999,7 @@ def main():
 
     elided_ms = elided1_ms = None
     elided_kern = None
-    if not sharded and not args.minimal and n ** 3 > (1 << 24) and os.environ.get("SDFK_BENCH_NO_ELIDED") != "1":
+    if not sharded and legs and n ** 3 > (1 << 24) and os.environ.get("SDFK_BENCH_NO_ELIDED") != "1":
         elided1_ms = timed_elided(step, drain, args.steps, 1) * 1e3     # every voxel evaluated, nothing stored
         elided_ms = timed_elided(step, drain, args.steps, 2) * 1e3      # + blocks decided by interval arithmetic
         # the volume-less step's kernels, one in-order stream, event pairs per launch (like `kernels_us` for the stored step)
@@ -1072,7 +1099,7 @@ def main():
         del sdf_s
         return out_s
 
-    side_ok = not sharded and not args.minimal and args.scene == "sphere" and n == 512
+    side_ok = not sharded and legs and args.scene == "sphere" and n == 512
     c3 = c2 = c4 = None
 
     def side_leg(*a, **k):
@@ -1188,7 +1215,7 @@ def main():
     # scene, camera (-2, 2, 4) -> origin (Perf/Program.cs:54-58), images device-resident; never `value`.  ALU-bound (no HBM traffic to
     # speak of): the roofline figure is the share of the vector-issue time, from the committed SQ counter pass (profiles/pmc_traffic.json)
     c5 = None
-    if not sharded and not args.minimal and args.scene == "sphere" and n == 512 and os.environ.get("SDFK_BENCH_NO_C5") != "1":
+    if not sharded and legs and args.scene == "sphere" and n == 512 and os.environ.get("SDFK_BENCH_NO_C5") != "1":
         from sdfkit_amd import Matrix4x4, RayMarcher
         w5, h5, it5, k5 = 1920, 1080, 256, 10
         sdf5 = scene_for("repeatxy")[0]
@@ -1232,7 +1259,7 @@ def main():
     # context figures, outside the timed region, rank 0 only: what this box
     # reaches with a plain device fill / copy, and one step including the mesh copy to the host
     extra = {}
-    if rank == 0 and not args.minimal:
+    if rank == 0 and legs:
         x = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
         y = torch.empty_like(x)
         e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
@@ -1495,8 +1522,8 @@ def main():
             "unit": "Mvoxels/s",
             # (first among the extras: what the driver's command measures WITHOUT the clock warm-up `value` has -- the GPU idles, then
             # W warm-up steps and K timed ones)
-            "value_cold_clocks": round(n ** 3 / (dt_cold / args.steps) / 1e6, 1),
-            "ms_per_step_cold_clocks": round(dt_cold / args.steps * 1e3, 4),
+            **({} if dt_cold is None else {"value_cold_clocks": round(n ** 3 / (dt_cold / args.steps) / 1e6, 1),
+                                           "ms_per_step_cold_clocks": round(dt_cold / args.steps * 1e3, 4)}),
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             **({"NOT_THE_CONTRACT_STEP": "--elide: the volume is not stored (a profiling run of the product default)"} if (args.elide and args.minimal) else {}),
             "ms_per_step": round(ms_step, 4),
@@ -1524,7 +1551,7 @@ def main():
                                             "why": "W + 4 steps fill the allocator's pools; then the same step runs for ~80 ms so that the GPU is at "
                                                    "its sustained clocks when the K timed steps start (after idling it needs 10-15 ms of load: "
                                                    "0.20 -> 0.169 ms per step at 512^3, tools/step_transient_probe.py); SDFK_BENCH_CLOCK_WARM_MS=0 switches it off; "
-                                                   "value_cold_clocks is the figure without it"},
+                                                   "value_cold_clocks (--full) is the figure without it"},
             "mtris_per_s": round(ni / 3 / step_s / 1e6, 2),
             "latency_ms_single_stream": None if latency_ms is None else round(latency_ms, 4),
             "latency_ms_single_stream_product_default": None if latency_default_ms is None else round(latency_default_ms, 4),
@@ -1567,10 +1594,12 @@ def main():
                                 "voxel by voxel; = 1 (no_culling): every voxel evaluated.  Not the contract's step (which evaluates and stores "
                                 "every voxel): reported next to `value`, never as it",
         }
+        if lean:   # a plain run says what it measured: the keys of the legs that did not run are left out
+            out = {k: v for k, v in out.items() if k in PLAIN_RUN_KEYS}
         out.update(extra)
         if dist_extra:
             out["sharded"] = dist_extra
-        if world == 1 and not args.no_cpu:
+        if world == 1 and not lean and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args.scene, args.cpu_n or n, max(args.cpu_passes, 1))
     # ---- after the headline (N > 1).  The headline above used the plainest exchange.  The line is now SAFE: rank 0 leaves it in the file
     # its supervisor named, every rank leaves a marker -- a worker that dies or hangs from here on still counts as a finished headline
@@ -1580,7 +1609,7 @@ def main():
     # tries the exchanges that have never run between two GPUs.  Every pass has a watchdog of its own.
     result_base = os.environ.get("SDFK_BENCH_RESULT_BASE")
     multi = sharded and world > 1
-    after_on = multi and os.environ.get("SDFK_BENCH_NO_TUNE") != "1"
+    after_on = multi and not lean and os.environ.get("SDFK_BENCH_NO_TUNE") != "1"
     tune_it = after_on and D.info()[2] == 1
 
     def save_line():
@@ -1590,7 +1619,7 @@ def main():
             os.replace(result_base + ".json.tmp", result_base + ".json")
 
     if multi:
-        if rank == 0:
+        if rank == 0 and not lean:
             out["sharded"]["tuned_pass"] = "did not finish (the headline pass above is unaffected)" if tune_it else "off (SDFK_BENCH_NO_TUNE / host transport)"
             out["sharded"]["mesh_stays_sharded_pass"] = "did not finish" if after_on else "off"
             out["sharded"]["c4_union8_1024"] = "did not finish" if after_on else "off"
@@ -1796,7 +1825,7 @@ def main():
         save_line()
     content_ok = True
     if rank == 0:
-        if sharded:
+        if sharded and not lean:
             # every content check of this run: the headline's, the C4 passes', the mesh-stays-sharded pass's, the tuned pass's
             checks = {"headline": out["sharded"].get("mesh_equals_single_gpu")}
             for key in ("mesh_stays_sharded_pass", "tuned_pass"):

@@ -251,3 +251,16 @@ def test_dump_outputs_types_limit_and_fixed_sample(tmp_path):
     v = np.load(tmp_path / "a" / "vertices.npy")     # rows of the full array, in order
     rows = [int(np.flatnonzero((m.Vertices == r).all(axis=1))[0]) for r in v]
     assert rows == sorted(rows)
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_launcher_hands_full_to_its_ranks(monkeypatch, full):
+    """`python bench.py --gpus N [--full]`: the ranks get --full exactly when the launcher got it (a plain run stays plain)."""
+    seen = []
+    monkeypatch.setattr(bench, "launch_ranks", lambda argv, n: seen.append((argv, n)) or 0)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "4", "--steps", "5"] + (["--full"] if full else []))
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 0 and len(seen) == 1 and seen[0][1] == 4
+    assert ("--full" in seen[0][0]) is full and seen[0][0][:4] == ["--gpus", "4", "--steps", "5"]

@@ -34,7 +34,7 @@ def _bench(extra, env=None):
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_bench_on_one_gpu(gpu, world):
-    args = ["--steps", "6", "--warmup", "2", "--no-cpu", "--scene", "repeatxy", "--grid", "160"]
+    args = ["--full", "--steps", "6", "--warmup", "2", "--no-cpu", "--scene", "repeatxy", "--grid", "160"]
     one = _bench([sys.executable, "bench.py"] + args)
     many = _bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
                    "--master-port", str(_free_port()), "bench.py", "--gpus", str(world)] + args,
@@ -81,7 +81,7 @@ def test_a_flipped_index_turns_the_content_check_false_and_fails_the_run(gpu):
     """Fault injection for the check itself: SDFK_BENCH_FAULT_FLIP_INDEX=1 flips ONE index of the gathered mesh on rank 0 before it is
     hashed.  The line must say `mesh_equals_single_gpu: false` and the run must exit non-zero (4) -- on a node of real GPUs that is what
     a wrong exchange or a wrong rebase would look like."""
-    args = ["--steps", "4", "--warmup", "1", "--no-cpu", "--grid", "96"]
+    args = ["--full", "--steps", "4", "--warmup", "1", "--no-cpu", "--grid", "96"]
     e = dict(os.environ)
     e.update({"SDFK_BENCH_ONE_GPU": "1", "SDFK_BENCH_FAULT_FLIP_INDEX": "1", "SDFK_BENCH_C4_GRID": "64", "SDFK_BENCH_C4_STEPS": "2"})
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
@@ -100,7 +100,7 @@ def test_a_flipped_index_turns_the_content_check_false_and_fails_the_run(gpu):
 def test_bench_gpus_n_started_as_plain_python(gpu, world):
     """The way the driver starts the multi-GPU leg: `python bench.py --gpus N`, no launcher, no WORLD_SIZE.
     bench.py must spawn torch.distributed.run itself (as a child, before touching the GPU) and relay rank 0's line."""
-    args = ["--steps", "6", "--warmup", "2", "--no-cpu", "--grid", "128"]
+    args = ["--full", "--steps", "6", "--warmup", "2", "--no-cpu", "--grid", "128"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SDFK_BENCH_ONE_GPU"] = "1"
     env.update({"SDFK_BENCH_C4_GRID": "64", "SDFK_BENCH_C4_STEPS": "2"})
@@ -353,9 +353,9 @@ def test_pipelined_session_full_parity_multi_rank(gpu, world, name, dims, idx16,
 
 
 def test_bench_contract_fields(gpu):
-    """One default-shaped bench run (smaller grid, tiny CPU-baseline sample): the JSON line carries
+    """One `--full` bench run (smaller grid, tiny CPU-baseline sample): the JSON line carries
     every field of the contract, the roofline and the cpu_baseline objects."""
-    d = _bench([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--grid", "256", "--cpu-n", "64"])
+    d = _bench([sys.executable, "bench.py", "--full", "--steps", "6", "--warmup", "2", "--grid", "256", "--cpu-n", "64"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -369,10 +369,10 @@ def test_bench_contract_fields(gpu):
 
 
 def test_default_line_carries_every_baseline_config(gpu):
-    """The driver's N = 1 run (default flags; here without the CPU baseline): beside the 512^3 headline the line carries BASELINE's C2
+    """The N = 1 run with `--full` (here without the CPU baseline): beside the 512^3 headline the line carries BASELINE's C2
     (256^3 sphere), C3 (512^3 RepeatXY with colours), C4 (1024^3 union of 8 primitives, whole on one GPU) and C5 (ray marcher), the
     product-default (volume-less) path with a bound of its own, and the controls for the colour sampler."""
-    d = _bench([sys.executable, "bench.py", "--no-cpu", "--steps", "10", "--warmup", "2"], {"SDFK_BENCH_BLOCKS": "3"})
+    d = _bench([sys.executable, "bench.py", "--full", "--no-cpu", "--steps", "10", "--warmup", "2"], {"SDFK_BENCH_BLOCKS": "3"})
     assert d["config"]["vertices"] == 549144 and d["roofline"]["kernel"] == "sdfk_sample_bits"
     c2, c3, c4 = d["c2_sphere_256"], d["c3_repeatxy"], d["c4_union8_1024"]
     # (the volume-less path needs re-evaluated corners and vertex colours: under SDFK_NO_CORNER_EVAL / SDFK_NO_VCOLOR_EVAL the "product default"
@@ -395,3 +395,54 @@ def test_default_line_carries_every_baseline_config(gpu):
     assert d["c5_raymarch"]["ms_per_frame"] > 0
     assert 0 < d["one_step_incl_mesh_d2h_product_default_pooled_ms"] <= d["one_step_incl_mesh_d2h_product_default_ms"] * 1.5
     assert d["pipelined_handoff_product_default_ms_per_mesh"] > 0
+
+
+def _dumped(dirname):
+    import numpy as np
+    return {name: np.load(os.path.join(dirname, name + ".npy")) for name in ("vertices", "colors", "normals", "triangles", "bounds")}
+
+
+def test_plain_run_is_the_headline_alone(gpu, tmp_path):
+    """Without --full the run sets up, warms up, times its steps, writes --dump-outputs and prints the line: the contract's fields and how
+    they were timed, none of the legs beside the headline -- and the mesh it dumps is the mesh a --full run dumps."""
+    args = ["--steps", "6", "--warmup", "2", "--grid", "256"]
+    d = _bench([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path / "plain")])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "blocks"):
+        assert k in d, k
+    assert d["metric"] == "Mvoxels/s, 256^3 sphere SDF sample->mesh" and d["unit"] == "Mvoxels/s" and d["higher_is_better"] is True
+    assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["dtype"] == "f32 (sampling) / f64 (cell math)"
+    assert d["config"]["vertices"] == 137232            # SURVEY C2
+    assert abs(d["value"] - 256 ** 3 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 1e-2
+    assert d["blocks"]["ms_per_step_min"] <= d["ms_per_step"] <= d["blocks"]["ms_per_step_max"]
+    for k in ("cpu_baseline", "roofline", "kernels_us", "value_cold_clocks", "latency_ms_single_stream", "c2_sphere_256", "c3_repeatxy", "c4_union8_1024",
+              "c5_raymarch", "elided", "colour_sampler_control", "hbm_measured", "one_step_incl_mesh_d2h", "host_values_march_ms"):
+        assert k not in d, k
+    assert "new_constants" not in d["first_call"] and "cold_first_call_ms" not in d["first_call"]
+    f = _bench([sys.executable, "bench.py", "--full", "--no-cpu"] + args + ["--dump-outputs", str(tmp_path / "full")])
+    assert f["config"] == d["config"] and f["metric"] == d["metric"] and "roofline" in f and "value_cold_clocks" in f
+    import numpy as np
+    a, b = _dumped(tmp_path / "plain"), _dumped(tmp_path / "full")
+    assert a["vertices"].shape == (137232, 3) and all(np.array_equal(a[k], b[k]) for k in a)
+
+
+def test_plain_sharded_run_on_one_gpu(gpu, tmp_path):
+    """`bench.py --gpus 2` without --full (both ranks on this GPU, host transport): the headline of the sharded step and who took part, no
+    content check and no pass after the headline; --dump-outputs writes the gathered mesh, which is the single-GPU mesh of the same grid."""
+    args = ["--steps", "6", "--warmup", "2", "--grid", "128"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["SDFK_BENCH_ONE_GPU"] = "1"
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2"] + args + ["--dump-outputs", str(tmp_path / "two")], cwd=ROOT, env=env,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    many = json.loads(lines[0])
+    one = _bench([sys.executable, "bench.py"] + args + ["--dump-outputs", str(tmp_path / "one")])
+    assert many["n_gpus"] == 2 and many["config"]["vertices"] == one["config"]["vertices"] > 10000
+    sh = many["sharded"]
+    assert sh["world"] == 2 and sum(p[0] for p in sh["per_rank_vertices_indices"]) == many["config"]["vertices"]
+    for k in ("content_check", "mesh_equals_single_gpu", "every_mesh_equals_single_gpu", "c4_union8_1024", "mesh_stays_sharded_pass", "tuned_pass", "slab_kernels_only_ms"):
+        assert k not in sh, k
+    import numpy as np
+    a, b = _dumped(tmp_path / "two"), _dumped(tmp_path / "one")
+    assert all(np.array_equal(a[k], b[k]) for k in a)

@@ -6,6 +6,6 @@ V=${VARIANTS:-"memset default memset default"}
 for v in $V; do
     lib=$R/sdfkit_amd/_ablate/$v.so; [ "$v" = default ] && lib=$R/sdfkit_amd/libsdfkit_hip.so
     echo -n "$v  "
-    SDFKIT_HIP_LIBRARY=$lib SDFK_BENCH_NO_C3=1 timeout 300 python3 bench.py --no-cpu 2>/dev/null | grep "^{" | \
+    SDFKIT_HIP_LIBRARY=$lib SDFK_BENCH_NO_C3=1 timeout 300 python3 bench.py --full --no-cpu 2>/dev/null | grep "^{" | \
         python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('stored', d['ms_per_step'], 'volume-less', d['elided_volume_ms_per_step'], 'one call', d['latency_ms_single_stream_product_default'], 'one call stored', d['latency_ms_single_stream'])"
 done

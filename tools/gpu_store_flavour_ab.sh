@@ -18,7 +18,7 @@ echo "== nt";      SDFK_JIT_FLAGS="$OLD" tools/variants.sh run default --scene u
 echo "== sc1 nt";  tools/variants.sh run default --scene union8 --grid 1024 --steps 5 --warmup 2
 for f in "$OLD" ""; do
     echo "== roofline leg, SDFK_JIT_FLAGS='$f'"
-    SDFK_JIT_FLAGS="$f" python3 bench.py --no-cpu 2>/dev/null | grep "^{" | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['ms_per_step'], r['avg_launch_us'], r['frac'], 'c3 sampler', d['c3_repeatxy']['sampler_us_back_to_back'], d['c3_repeatxy']['sampler_frac'])"
+    SDFK_JIT_FLAGS="$f" python3 bench.py --full --no-cpu 2>/dev/null | grep "^{" | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['ms_per_step'], r['avg_launch_us'], r['frac'], 'c3 sampler', d['c3_repeatxy']['sampler_us_back_to_back'], d['c3_repeatxy']['sampler_frac'])"
 done
 } > $O/ab.log 2>&1
 grep -v "^  File\|^    \|Traceback\|json.decoder" $O/ab.log

@@ -16,8 +16,8 @@ else
     shift; name=$1; shift
     lib=$R/$D/$name.so; [ "$name" = default ] && lib=$R/sdfkit_amd/libsdfkit_hip.so
     echo -n "$name  "
-    SDFKIT_HIP_LIBRARY=$lib SDFK_LANES=0 timeout 300 python3 bench.py --no-cpu "$@" 2>/dev/null | grep "^{" | \
+    SDFKIT_HIP_LIBRARY=$lib SDFK_LANES=0 timeout 300 python3 bench.py --full --no-cpu "$@" 2>/dev/null | grep "^{" | \
         python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('serial ms/step', d['ms_per_step'], {k: v['avg_us'] for k, v in d['kernels_us'].items()})"
-    SDFKIT_HIP_LIBRARY=$lib timeout 300 python3 bench.py --no-cpu "$@" 2>/dev/null | grep "^{" | \
+    SDFKIT_HIP_LIBRARY=$lib timeout 300 python3 bench.py --full --no-cpu "$@" 2>/dev/null | grep "^{" | \
         python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('   pipelined ms/step', d['ms_per_step'], 'latency', d['latency_ms_single_stream'])"
 fi
