@@ -479,6 +479,18 @@ public:
     }
     uint64_t Version() const { return version_; }
     inline Mesh ToMesh(float isoValue = 0.0f, int step = 1, const std::function<void(float)>& progress = nullptr);
+    // A new volume of the same box and shape: the signed distance to this volume's iso-surface with this volume's sign at every
+    // voxel, distances beyond maxDistance clamped to +-maxDistance (include/sdfkit_hip.h, "Redistancing").  Colours are copied.
+    // stats (optional): sweeps, tile-sweeps, front voxels, clamped voxels.
+    Voxels Redistance(float isoValue = 0.0f, float maxDistance = INFINITY, int64_t* stats = nullptr) const
+    {
+        sdfk_volume* src = const_cast<Voxels*>(this)->Sync();   // (uploads pending host edits: the values stay what they are)
+        Voxels out(Min, Max, NX, NY, NZ);
+        out.Ensure(hasColors_);
+        Check(sdfk_volume_redistance(src, out.h_, isoValue, maxDistance, stats));
+        out.version_++;
+        return out;
+    }
     sdfk_volume* Sync()
     {
         Ensure(hasColors_);

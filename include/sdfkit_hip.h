@@ -616,6 +616,40 @@ int sdfk_trimesh_to_volume(const sdfk_trimesh* t, sdfk_volume* v, float max_dist
 int sdfk_trimesh_stats(const sdfk_trimesh* t, int64_t stats[8]);
 void sdfk_trimesh_free(sdfk_trimesh* t);
 
+/* ---- Redistancing (Voxels.Redistance) ---------------------------------------------------------------------------------------
+ * dst gets a signed distance to the iso-surface of src, with src's sign at every voxel: a first-order Eikonal solve (Godunov
+ * upwind, Jacobi sweeps to the fixed point -- the fast iterative method family, Jeong & Whitaker 2008).  src is not modified
+ * (dst may be src: in place).  Colours: copied from src when both volumes have them, zeroed when only dst has.  Cached sign
+ * bits of dst are dropped, as for a write through sdfk_volume_device_ptrs.  The result is ONE function of the input, computed
+ * by csrc/redistance.h (binary64 from the f32 inputs, the operations in the order given here, no contraction, one rounding to
+ * f32 per value; sqrt and the divisions correctly rounded), restated in tests/redistance_model.py and compared bit for bit:
+ *   h = (DX, DY, DZ), the f32 cell sizes (max - min) / n widened to binary64; s(x) = (double)v(x) - (double)iso_value;
+ *   outside(x) = s(x) > 0.0 -- the strict test marching cubes makes, so src and dst mesh to the same sign pattern.
+ * 1. Refusal (SDFK_ERR_INVALID, dst untouched): a NaN or infinite value in src (checked on the device; the call synchronises),
+ *    a non-finite iso_value, a NaN or negative max_distance, dst of another shape or box than src, volumes without storage.
+ * 2. Front.  x is on the front if one of its six in-range neighbours n has outside(n) != outside(x).  For each axis a with
+ *    such a neighbour, t_a = the least (h_a * |s(x)|) / (|s(x)| + |s(n)|) over them (the linear crossing marching cubes places
+ *    on that edge).  T0 = 0 if some t_a == 0, else (float)(1 / sqrt(q)), q = the sum of 1 / (t_a * t_a) over the axes that
+ *    have a crossing, added in x, y, z order (the distance to the plane through the crossings).  Front voxels are frozen at
+ *    T0; every other voxel starts at +inf.
+ * 3. Sweep.  T is f32.  One sweep reads T_k only and writes T_k+1 (Jacobi).  For a voxel that is not frozen: per axis
+ *    a_i = min(T_k(x - e_i), T_k(x + e_i)) (out of range: +inf), the axes sorted by ascending a_i, ties keeping x, y, z order;
+ *    w_i = 1 / (h_i * h_i); u = a_1 + h_1; if u > a_2: A = w_1 + w_2, B = w_1 a_1 + w_2 a_2,
+ *    S = (w_1 a_1) a_1 + (w_2 a_2) a_2, D = B B - A (S - 1), u = (B + sqrt(D > 0 ? D : 0)) / A; if that u > a_3: A, B, S each
+ *    gain the third axis' term (added last) and u is solved again the same way.  uf = (float)u;
+ *    T_k+1(x) = (uf < T_k(x) and uf <= max_distance) ? uf : T_k(x).
+ * 4. Fixed point.  Sweeps repeat until one changes nothing (f32 values only ever decrease: it terminates).
+ * 5. Result.  m = min(T, max_distance); the value is m where outside, -m elsewhere (v == iso: -0.0, inside, as marching cubes
+ *    treats it).  A volume without a front gives +-max_distance everywhere (+-inf unbanded).
+ * An upwind value exceeds every a_i it used, so values above max_distance never influence values below it: they are not stored
+ * (step 3) and the solve stops expanding there; a banded run equals the clamp of the unbanded one.
+ * Schedule (csrc/lib_redistance.hip): tiles of 8^3 voxels; a tile is swept in sweep k + 1 only if it or one of its six face
+ * neighbours changed in sweep k -- exactly the full Jacobi sweep, since an update reads the 6-neighbourhood only.  Works on the
+ * planes the volume holds (a slab is solved on its own).  Device memory: 8 bytes per voxel of the volume padded to whole tiles.
+ * stats (may be NULL; reading them synchronises): [0] sweeps of the full Jacobi iteration, the last one (which changes nothing)
+ * included, 0 when there is no front; [1] tile-sweeps executed; [2] front voxels; [3] voxels whose T exceeds max_distance. */
+int sdfk_volume_redistance(const sdfk_volume* src, sdfk_volume* dst, float iso_value, float max_distance, int64_t stats[4]);
+
 /* ---- pinned host arena -------------------------------------------------------
  * Host memory the GPU can write directly (hipHostMalloc), recycled through size-class free lists:
  * destinations inside such a block make sdfk_mesh_copy / sdfk_volume_download / sdfk_raymarch plain

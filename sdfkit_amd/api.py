@@ -568,6 +568,22 @@ class Voxels:
         """Voxels.ToMesh (Voxels.cs:67-70)."""
         return MarchingCubes.CreateMesh(self, isoValue, step, progress)
 
+    def Redistance(self, isoValue=0.0, maxDistance=float("inf"), stats=None):
+        """A new Voxels of the same box and shape holding a signed distance to this volume's iso-surface, with this volume's
+        sign at every voxel (value > isoValue is outside, as marching cubes decides it): a first-order Eikonal solve on the GPU
+        (include/sdfkit_hip.h, "Redistancing").  Distances beyond maxDistance become +-maxDistance.  Colours are copied; this
+        volume is not modified.  It makes a field again of what min / max CSG, repeats, twists or a band of Mesh.ToVoxels left:
+        banded mesh volume -> Redistance -> full field.  stats: a dict that receives sweeps, tile_sweeps, front, clamped."""
+        src = self._sync_to_device()
+        out = Voxels(self.Min, self.Max, self.NX, self.NY, self.NZ)
+        dst = out._ensure_device(self._has_colors)
+        st = (C.c_int64 * 4)() if stats is not None else None
+        N.check(N.lib().sdfk_volume_redistance(src, dst, C.c_float(isoValue), C.c_float(maxDistance), st))
+        out._version += 1   # the device copy is the truth
+        if stats is not None:
+            stats.update(sweeps=int(st[0]), tile_sweeps=int(st[1]), front=int(st[2]), clamped=int(st[3]))
+        return out
+
 
 # ---------------------------------------------------------------------------
 # MarchingCubes / Mesh

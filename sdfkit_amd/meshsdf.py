@@ -67,7 +67,8 @@ class MeshSdf:
         """The signed distance at the cell centres of Voxels(min, max, nx, ny, nz) (the centres Voxels.SampleSdf evaluates);
         distances beyond maxDistance become +-maxDistance.  clipToBounds: Voxels.ClipToBounds afterwards.
         Slow without a band on large volumes far from a fine mesh (every voxel searches until its nearest triangle: the 1.6 M
-        triangle sphere into 256^3 takes tens of seconds unbanded, a fraction of a second with a band of a few voxels)."""
+        triangle sphere into 256^3 takes tens of seconds unbanded, a fraction of a second with a band of a few voxels).  For the far
+        field of a large volume, give a band and call Voxels.Redistance() on the result."""
         from .api import Voxels
         vox = Voxels(min, max, nx, ny, nz)
         self.SampleInto(vox, maxDistance)

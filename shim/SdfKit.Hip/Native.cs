@@ -114,6 +114,7 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_trimesh_to_volume(IntPtr trimesh, IntPtr volume, float maxDistance);
         [DllImport(Lib)] public static extern int sdfk_trimesh_stats(IntPtr trimesh, long* stats8);
         [DllImport(Lib)] public static extern void sdfk_trimesh_free(IntPtr trimesh);
+        [DllImport(Lib)] public static extern int sdfk_volume_redistance(IntPtr src, IntPtr dst, float isoValue, float maxDistance, long* stats4);
         // several GPUs from ONE process (the managed host is one process): include/sdfkit_hip.h, "one process, several GPUs"
         [DllImport(Lib)] public static extern int sdfk_node_open(int* devices, int nDevices, out IntPtr node);
         [DllImport(Lib)] public static extern int sdfk_node_info(IntPtr node, out int world, out int backend);

@@ -75,6 +75,18 @@ namespace SdfKit
         }
 
         /// <summary>Voxels.ClipToBounds (Voxels.cs:133-167): all six faces become Size.X / NX.</summary>
+        /// <summary>A new volume of the same box and shape: the signed distance to this volume's iso-surface with this volume's sign
+        /// at every voxel, distances beyond maxDistance clamped (include/sdfkit_hip.h, "Redistancing").  Colours are copied on the
+        /// device; this volume is not modified.</summary>
+        public unsafe Voxels Redistance (float isoValue = 0.0f, float maxDistance = float.PositiveInfinity)
+        {
+            var src = SyncToDevice();
+            var result = new Voxels (Min, Max, NX, NY, NZ);
+            Native.Check (Native.sdfk_volume_redistance (src, result.EnsureDevice (deviceHasColors), isoValue, maxDistance, null));
+            result.deviceIsNewer = true; result.hostMayBeNewer = false;
+            return result;
+        }
+
         public void ClipToBounds()
         {
             Native.Check(Native.sdfk_volume_clip_to_bounds(SyncToDevice()));
