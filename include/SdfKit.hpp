@@ -18,6 +18,7 @@
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <ostream>
 #include <stdexcept>
@@ -704,7 +705,8 @@ struct Matrix4x4 {
 // ---------------------------------------------------------------------------------------
 // KdTree (KdTree.cs) and IterativeClosestPoint (IterativeClosestPoint.cs) over sdfk_points_* / sdfk_icp_*
 // ---------------------------------------------------------------------------------------
-// The search is exact: the static point of least d2, ties to the lowest insertion index (sdfkit_hip.h).  The tree's
+// The search is exact: the static point of least d2, ties to the lowest insertion index (sdfkit_hip.h); SearchKNearest and
+// SearchRadius return the k nearest / all within a radius in the same (d2, index) order.  The tree's
 // internals (Left, Right, SplitValue, IsLeaf) have no counterpart: the structure is a grid of cell lists on the GPU.
 static_assert(sizeof(Vector3) == 3 * sizeof(float), "Vector3 spans are passed as float triples");
 class KdTree {
@@ -736,6 +738,44 @@ public:
         Vector3 nearest;
         Check(sdfk_points_search(h_, &q.X, 1, nullptr, &nearestDistance, &nearest.X));
         return nearest;   // (no point counts: the first static point and float.MaxValue, as the reference)
+    }
+    // Extensions (sdfkit_hip.h, "k nearest / within a radius"): neighbours in (d2, index) order, ascending.
+    struct KNearest {
+        int K = 0;
+        std::vector<int32_t> Indices;   // queries x K; -1 in unused slots
+        std::vector<float> Distances;   // queries x K; float.MaxValue in unused slots
+        std::vector<int32_t> Found;     // per query: the number of real entries
+    };
+    struct InRadius {
+        std::vector<int64_t> Offsets;   // queries + 1: query i's neighbours are [Offsets[i], Offsets[i + 1])
+        std::vector<int32_t> Indices;
+        std::vector<float> Distances;
+    };
+    // the k nearest static points of every query, no farther than maxDistance; 1 <= k <= 64
+    KNearest SearchKNearest(const std::vector<Vector3>& queries, int k, float maxDistance = std::numeric_limits<float>::infinity()) const
+    {
+        KNearest r;
+        r.K = k;
+        const size_t n = queries.size(), nk = k > 0 ? n * (size_t)k : 0;
+        r.Indices.resize(nk);
+        r.Distances.resize(nk);
+        r.Found.resize(n);
+        Check(sdfk_points_knn(h_, reinterpret_cast<const float*>(queries.data()), (int64_t)n, k, maxDistance, r.Indices.data(), r.Distances.data(),
+                              r.Found.data()));
+        return r;
+    }
+    // every static point within `radius` of every query (sqrtf(d2) <= radius)
+    InRadius SearchRadius(const std::vector<Vector3>& queries, float radius) const
+    {
+        InRadius r;
+        const int64_t n = (int64_t)queries.size();
+        const float* q = reinterpret_cast<const float*>(queries.data());
+        r.Offsets.assign((size_t)n + 1, 0);
+        Check(sdfk_points_radius_count(h_, q, n, radius, r.Offsets.data()));
+        r.Indices.resize((size_t)r.Offsets[(size_t)n]);
+        r.Distances.resize(r.Indices.size());
+        if (!r.Indices.empty()) Check(sdfk_points_radius_fill(h_, q, n, radius, r.Offsets.data(), r.Indices.data(), r.Distances.data()));
+        return r;
     }
     sdfk_points* Handle() const { return h_; }
 

@@ -35,7 +35,8 @@ extern "C" {
                                    entry points added since, existing ones unchanged: sdfk_points_* (KdTree), sdfk_icp_* (IterativeClosestPoint) and
                                    sdfk_trimesh_* (triangle-mesh distance),
                                    sdfk_program_create_bound / sdfk_program_check_bound (programs that read voxel volumes); opcodes
-                                   SDFK_OP_SIN .. SDFK_OP_ATAN2 (19-23), accepted by every entry point that takes an op list */
+                                   SDFK_OP_SIN .. SDFK_OP_ATAN2 (19-23), accepted by every entry point that takes an op list;
+                                   sdfk_points_knn* / sdfk_points_radius_* (KdTree: k nearest, within a radius) */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -523,7 +524,7 @@ int sdfk_raymarch_device(const sdfk_program* p, int32_t width, int32_t height, c
                          int32_t depth_iterations, void* depth_dev, void* rgb_dev);
 
 /* ---- KdTree (KdTree.cs) / IterativeClosestPoint (IterativeClosestPoint.cs) -----------------------------------------
- * sdfk_points: a static point set on the device (x, y, z triples), searched for the exact nearest point.  Static points are
+ * sdfk_points: a static point set on the device (x, y, z triples), searched for the exact nearest point, the k nearest, or all within a radius.  Static points are
  * numbered in insertion order: the points of sdfk_points_create, then each sdfk_points_add batch appended (KdTree(points),
  * KdTree.AddPoints).  The search structure is a uniform grid of sorted cell lists rebuilt on the device by every create / add;
  * its shape is not part of the contract (the reference's Left / Right / SplitValue / IsLeaf have no counterpart).
@@ -549,6 +550,39 @@ int sdfk_points_search_device(const sdfk_points* s, const void* queries3_dev, in
                               void* nearest3_dev);
 int sdfk_points_stats(const sdfk_points* s, int64_t stats[5]);
 void sdfk_points_free(sdfk_points* s);
+/* k nearest / within a radius (extensions: the reference's KdTree has neither).
+ * Order: static points are ordered by the pair (d2, index): d2 = (dx*dx + dy*dy) + dz*dz in binary32 without FMA (the formula of
+ * sdfk_points_search), index = the insertion index; the smaller d2 first, equal d2 to the LOWER index.  A point counts only under
+ * the rule above (sqrtf(d2) < FLT_MAX): for a NaN or infinite query, or on overflow, no point counts.  distance = sqrtf(d2),
+ * correctly rounded.
+ * Within a radius: a counting point is within r iff sqrtf(d2) <= r -- decided on the f32 distance, so a point at distance exactly r
+ * is within r and not within nextafterf(r, 0).  r = +inf: every counting point.  r < 0 or NaN: SDFK_ERR_INVALID.
+ *   - sdfk_points_knn: row i of index / distance (n rows of k) holds the first min(k, counting points within max_distance) points
+ *     of that order, ascending; the remaining slots hold index = -1 and distance = FLT_MAX; found[i] = the number of real entries.
+ *     Any output may be NULL.  1 <= k <= 64, anything else is SDFK_ERR_INVALID (larger neighbourhoods: the radius query);
+ *     max_distance follows the radius rules (+inf: no limit).  With k = 1 and max_distance = +inf, index and distance equal
+ *     sdfk_points_search's bit for bit.
+ *   - sdfk_points_radius_count, then sdfk_points_radius_fill (the caller owns the result arrays, so their size comes first):
+ *     count writes offsets[0..n], the exclusive prefix sums of the neighbours per query, offsets[n] = the total.  fill writes query
+ *     i's neighbours to index / distance [offsets[i], offsets[i+1]), ascending in the same order (distance may be NULL): a query's
+ *     segment cut to k is its sdfk_points_knn row with max_distance = radius.  fill with offsets that are not count's for the same
+ *     set, queries and radius is undefined: the host form refuses offsets that do not start at 0 or do not ascend
+ *     (SDFK_ERR_INVALID) and otherwise leaves unspecified contents; the _device form trusts them, and offsets that reach beyond the
+ *     caller's arrays make it write outside them.
+ * The plain forms take host arrays and are synchronous.  The _device forms take caller-owned device buffers and are asynchronous
+ * on the library stream (the caller reads offsets[n] itself, after a synchronise).  While sdfk_profile_enable(1) is on,
+ * sdfk_points_stats[3..4] report the candidates and queries of the last knn / radius_count / radius_fill call as well (such a
+ * call synchronises). */
+int sdfk_points_knn(const sdfk_points* s, const float* queries3, int64_t n, int32_t k, float max_distance,
+                    int32_t* index /* n*k */, float* distance /* n*k */, int32_t* found /* n */);
+int sdfk_points_knn_device(const sdfk_points* s, const void* queries3_dev, int64_t n, int32_t k, float max_distance,
+                           void* index_dev, void* distance_dev, void* found_dev);
+int sdfk_points_radius_count(const sdfk_points* s, const float* queries3, int64_t n, float radius, int64_t* offsets /* n+1 */);
+int sdfk_points_radius_count_device(const sdfk_points* s, const void* queries3_dev, int64_t n, float radius, void* offsets_dev);
+int sdfk_points_radius_fill(const sdfk_points* s, const float* queries3, int64_t n, float radius, const int64_t* offsets,
+                            int32_t* index /* total */, float* distance /* total; may be NULL */);
+int sdfk_points_radius_fill_device(const sdfk_points* s, const void* queries3_dev, int64_t n, float radius, const void* offsets_dev,
+                                   void* index_dev, void* distance_dev);
 /* IterativeClosestPoint.RegisterPoints (IterativeClosestPoint.cs:53-196): rigidly moves the caller's points (in place) onto the
  * static set and returns the total transform (row-major M11..M44, System.Numerics row-vector convention) and the number of
  * iterations run.  Each iteration is the reference's: nearest static point of every point, the piecewise distMax from the

@@ -123,6 +123,12 @@ SIGNATURES = {
     "sdfk_points_search": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "sdfk_points_search_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "sdfk_points_stats": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "sdfk_points_knn": (C.c_int, [_vp, _vp, _i64, _i32, _f, _vp, _vp, _vp]),
+    "sdfk_points_knn_device": (C.c_int, [_vp, _vp, _i64, _i32, _f, _vp, _vp, _vp]),
+    "sdfk_points_radius_count": (C.c_int, [_vp, _vp, _i64, _f, _vp]),
+    "sdfk_points_radius_count_device": (C.c_int, [_vp, _vp, _i64, _f, _vp]),
+    "sdfk_points_radius_fill": (C.c_int, [_vp, _vp, _i64, _f, _vp, _vp, _vp]),
+    "sdfk_points_radius_fill_device": (C.c_int, [_vp, _vp, _i64, _f, _vp, _vp, _vp]),
     "sdfk_points_free": (None, [_vp]),
     "sdfk_trimesh_create": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vpp]),
     "sdfk_trimesh_create_device": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vpp]),

@@ -16,6 +16,7 @@
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "points_grid.h"
+#include "points_set.h"
 
 #include <cfloat>
 
@@ -119,6 +120,8 @@ __device__ __forceinline__ float lb_sq(const float gap[3][2], const float base2[
 }
 
 // One lane per query.  `icp` / `iter`: ICP iterations exit once the registration stopped.
+// lib_points_knn.hip restates this walk (lb_sq, slack, the shells, the 2^-18 margin) for the k-nearest and radius queries: a change
+// to any of them here has to be made there too (tests: k = 1 of sdfk_points_knn equals this kernel bit for bit).
 __global__ __launch_bounds__(kBlock) void k_pts_search(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
                                                        float fx, float fy, float fz, const float* __restrict__ queries, int64_t nq,
                                                        SearchOut O, const IcpState* icp, int iter)
@@ -519,17 +522,7 @@ unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlock - 
 // ---------------------------------------------------------------------------------------------------------------------------
 // the handle
 // ---------------------------------------------------------------------------------------------------------------------------
-struct sdfk_points {
-    DeviceState* owner = &cur_state();
-    int64_t n = 0;
-    float* xyz = nullptr;          // n x 3, insertion order (the source of every rebuild)
-    float4* sorted = nullptr;      // n, cell order: (x, y, z, bits(index))
-    uint32_t* starts = nullptr;    // cells + 1
-    int64_t cells = 0;
-    Grid G{};
-    float first[3] = {0, 0, 0};
-    int64_t last_candidates = 0, last_queries = 0;
-};
+// struct sdfk_points: points_set.h (shared with lib_points_knn.hip)
 
 namespace {
 

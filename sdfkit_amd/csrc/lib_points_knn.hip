@@ -1,0 +1,545 @@
+// lib_points_knn.hip -- KdTree's k-nearest and radius queries (sdfk_points_knn*, sdfk_points_radius_*) over the grid of sorted
+// cell lists that lib_points.hip builds.  Contract: include/sdfkit_hip.h, "k nearest / within a radius"; the arithmetic (packed
+// (d2, index) keys, bounded lists, radius predicate, stopping rule): points_knn.h, checked on the host.
+//
+// One lane per query, the shell walk of k_pts_search with the same `starts` / `sorted` reads; what differs is what a candidate
+// meets and when the walk stops:
+//   k_pts_knn<CAP>       the k least keys within the radius bound; stops when the lower bound of every unvisited cell exceeds the
+//                        k-th key's d2 (+inf until k are held) or the radius bound.  CAP = 8: a sorted list in registers; CAP = 16 /
+//                        32 / 64: a max-heap in LDS, slot-major (slot * 64 + lane: conflict-free across the wave), ordered in place
+//                        at the end.  Blocks of one wave: LDS per block = CAP * 512 B, so 20 / 10 / 5 waves per CU (160 KiB).
+//   k_pts_radius_count   the number of points within the bound; an exclusive 64-bit scan (device_scan.h) makes the offsets.
+//   k_pts_radius_fill    the same walk writes (index, bits(d2)) into the query's segment of the caller's arrays, a per-lane
+//                        in-place heap sort on the packed keys orders it, then d2 becomes the distance.  Without a distance
+//                        array the sort recomputes d2 from the stored index (bit-identical: the same formula on the same floats).
+#include "lib_internal.h"
+#include "device_scan.h"
+#include "points_knn.h"
+#include "points_set.h"
+
+#include <cfloat>
+
+namespace {
+
+using namespace sdfk_points_grid;
+using namespace sdfk_knn;
+
+constexpr int kBlock = 256;     // the register tier and the radius kernels
+constexpr int kLdsBlock = 64;   // the LDS tiers: one wave per block
+
+// the conservative lower bound of lib_points.hip (lb_sq), restated
+__device__ __forceinline__ float lb_sq(const float gap[3][2], const float base2[3])
+{
+    float best = INFINITY;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float rest = base2[(a + 1) % 3] + base2[(a + 2) % 3];
+        const float gm = fminf(gap[a][0], gap[a][1]);
+        best = fminf(best, gm * gm + rest);
+    }
+    return best;
+}
+
+// The shell walk of k_pts_search for a finite query: V::take(d2, index) per candidate, V::done(lb2) after each shell.
+// Returns the number of candidates.
+template <class V>
+__device__ __forceinline__ unsigned long long shell_walk(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, const Grid& G,
+                                                         float qx, float qy, float qz, V& v)
+{
+    unsigned long long ncand = 0;
+    const float q[3] = {qx, qy, qz};
+    int c[3];
+    (void)key_of(G, qx, qy, qz, &c[0], &c[1], &c[2]);
+    const float slack = G.slack + fmaxf(fabsf(qx), fmaxf(fabsf(qy), fabsf(qz))) * 0x1p-20f;
+    float base2[3];
+    int rmax = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float out = fmaxf(fmaxf(G.lo[a] - q[a], q[a] - G.hi[a]) - slack, 0.0f);
+        base2[a] = out * out;
+        rmax = max(rmax, max(c[a], G.dim[a] - 1 - c[a]));
+    }
+    const int gx = G.dim[0], gy = G.dim[1];
+    for (int r = 0; r <= rmax; r++) {
+        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, G.dim[2] - 1);
+        const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, gy - 1);
+        const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, gx - 1);
+        for (int z = z0; z <= z1; z++) {
+            const bool zf = z == c[2] - r || z == c[2] + r;
+            for (int y = y0; y <= y1; y++) {
+                const bool full = zf || y == c[1] - r || y == c[1] + r;
+                const uint32_t row = ((uint32_t)z * (uint32_t)gy + (uint32_t)y) * (uint32_t)gx;
+                // a full row of the shell is one contiguous range of the sorted points; otherwise its two end cells
+                for (int part = 0; part < (full ? 1 : 2); part++) {
+                    int xa, xb;
+                    if (full) { xa = x0; xb = x1; }
+                    else {
+                        xa = xb = part == 0 ? c[0] - r : c[0] + r;
+                        if (xa < 0 || xa >= gx) continue;
+                    }
+                    const uint32_t j0 = starts[row + (uint32_t)xa], j1 = starts[row + (uint32_t)xb + 1];
+                    ncand += j1 - j0;
+                    for (uint32_t j = j0; j < j1; j++) {
+                        const float4 s = sorted[j];
+                        v.take(dist2(qx, qy, qz, s.x, s.y, s.z), __float_as_int(s.w));
+                    }
+                }
+            }
+        }
+        // every unvisited cell lies beyond shell r along some axis: the least distance it can have, made conservative
+        float gap[3][2];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            gap[a][0] = c[a] - r - 1 >= 0 ? fmaxf(q[a] - (G.lo[a] + (float)(c[a] - r) * G.h) - slack, 0.0f) : INFINITY;
+            gap[a][1] = c[a] + r + 1 < G.dim[a] ? fmaxf((G.lo[a] + (float)(c[a] + r + 1) * G.h) - q[a] - slack, 0.0f) : INFINITY;
+        }
+        if (v.done(lb_sq(gap, base2))) break;
+    }
+    return ncand;
+}
+
+// every lane of the block calls this (the shuffle)
+__device__ __forceinline__ void add_candidates(unsigned long long* total, unsigned long long ncand)
+{
+    if (!total) return;
+    for (int o = 32; o > 0; o >>= 1) ncand += __shfl_down(ncand, o);
+    if ((threadIdx.x & 63) == 0) atomicAdd(total, ncand);
+}
+
+struct Query {
+    float x, y, z;
+    bool finite;
+};
+__device__ __forceinline__ Query load_query(const float* __restrict__ queries, int64_t t, int64_t nq)
+{
+    Query q{NAN, NAN, NAN, false};
+    if (t < nq) { q.x = queries[3 * t]; q.y = queries[3 * t + 1]; q.z = queries[3 * t + 2]; }
+    q.finite = isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
+    return q;
+}
+
+// ---- k nearest ---------------------------------------------------------------------------------------------------------------
+struct LdsSlots {   // slot-major keys of one lane
+    uint64_t* base;   // &s_keys[lane]
+    __device__ __forceinline__ uint64_t get(int i) const { return base[i * kLdsBlock]; }
+    __device__ __forceinline__ void set(int i, uint64_t key) { base[i * kLdsBlock] = key; }
+};
+
+template <class L>
+struct KnnVisitor {
+    L list;
+    uint64_t bound_key;   // (radius bound, index all ones): the greatest key within the radius
+    float d2_bound;
+    __device__ __forceinline__ void take(float d2, int id)
+    {
+        const uint64_t key = pack_key(d2, id);
+        if (key <= bound_key && key < list.worst()) list.insert(key);
+    }
+    __device__ __forceinline__ bool done(float lb2) const { return walk_done(lb2, list.worst(), d2_bound); }
+};
+
+struct KnnOut {
+    int32_t* index;     // n x k; any may be null
+    float* distance;    // n x k
+    int32_t* found;     // n
+    unsigned long long* candidates;
+};
+
+template <int CAP>
+__global__ __launch_bounds__(CAP == 8 ? kBlock : kLdsBlock) void k_pts_knn(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts,
+                                                                            Grid G, const float* __restrict__ queries, int64_t nq, int k,
+                                                                            float d2_bound, KnnOut O)
+{
+    constexpr int B = CAP == 8 ? kBlock : kLdsBlock;
+    const int64_t t = (int64_t)blockIdx.x * B + threadIdx.x;
+    const Query q = load_query(queries, t, nq);
+    unsigned long long ncand = 0;
+    int n_found = 0;
+    if constexpr (CAP == 8) {
+        KnnVisitor<SortedList<8>> v;
+        v.list.init(k);
+        v.bound_key = pack_key(d2_bound, -1);
+        v.d2_bound = d2_bound;
+        if (q.finite) ncand = shell_walk(sorted, starts, G, q.x, q.y, q.z, v);
+        n_found = v.list.count();
+        if (t < nq) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                if (i < k) {
+                    const uint64_t key = v.list.at(i);
+                    const bool real = key < kKeyInf;
+                    if (O.index) O.index[t * k + i] = real ? key_index(key) : -1;
+                    if (O.distance) O.distance[t * k + i] = real ? sqrt_rn(key_d2(key)) : FLT_MAX;
+                }
+            }
+        }
+    } else {
+        __shared__ uint64_t s_keys[CAP * kLdsBlock];
+        KnnVisitor<HeapList<LdsSlots>> v;
+        v.list.s.base = &s_keys[threadIdx.x];
+        v.list.init(k);
+        v.bound_key = pack_key(d2_bound, -1);
+        v.d2_bound = d2_bound;
+        if (q.finite) ncand = shell_walk(sorted, starts, G, q.x, q.y, q.z, v);
+        v.list.finish();
+        n_found = v.list.count();
+        if (t < nq) {
+            for (int i = 0; i < k; i++) {
+                const uint64_t key = v.list.at(i);
+                const bool real = key < kKeyInf;
+                if (O.index) O.index[t * k + i] = real ? key_index(key) : -1;
+                if (O.distance) O.distance[t * k + i] = real ? sqrt_rn(key_d2(key)) : FLT_MAX;
+            }
+        }
+    }
+    if (t < nq && O.found) O.found[t] = n_found;
+    add_candidates(O.candidates, ncand);
+}
+
+// ---- within a radius ---------------------------------------------------------------------------------------------------------
+struct CountVisitor {
+    float d2_bound;
+    unsigned long long n;
+    __device__ __forceinline__ void take(float d2, int) { n += within(d2, d2_bound) ? 1u : 0u; }
+    __device__ __forceinline__ bool done(float lb2) const { return walk_done(lb2, kKeyInf, d2_bound); }
+};
+
+// counts[t] = neighbours of query t (the scan turns them into offsets in place)
+__global__ __launch_bounds__(kBlock) void k_pts_radius_count(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
+                                                             const float* __restrict__ queries, int64_t nq, float d2_bound,
+                                                             unsigned long long* __restrict__ counts, unsigned long long* candidates)
+{
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const Query q = load_query(queries, t, nq);
+    CountVisitor v{d2_bound, 0};
+    unsigned long long ncand = 0;
+    if (q.finite) ncand = shell_walk(sorted, starts, G, q.x, q.y, q.z, v);
+    if (t < nq) counts[t] = v.n;
+    add_candidates(candidates, ncand);
+}
+
+// a query's segment as heap storage.  WITH_D2: the d2 bits live in the distance array until the end.
+template <bool WITH_D2>
+struct Segment {
+    int32_t* index;
+    uint32_t* d2bits;      // WITH_D2
+    const float* xyz;      // !WITH_D2: the static points in insertion order
+    float qx, qy, qz;
+    __device__ __forceinline__ uint64_t get(int i) const
+    {
+        const int32_t id = index[i];
+        if constexpr (WITH_D2) return (uint64_t)d2bits[i] << 32 | (uint32_t)id;
+        else return pack_key(dist2(qx, qy, qz, xyz[3 * (int64_t)id], xyz[3 * (int64_t)id + 1], xyz[3 * (int64_t)id + 2]), id);
+    }
+    __device__ __forceinline__ void set(int i, uint64_t key)
+    {
+        index[i] = key_index(key);
+        if constexpr (WITH_D2) d2bits[i] = (uint32_t)(key >> 32);
+    }
+};
+
+template <bool WITH_D2>
+struct FillVisitor {
+    Segment<WITH_D2> seg;
+    float d2_bound;
+    int64_t n, cap;   // written so far, the segment's length (a segment is never overrun, whatever the offsets say)
+    __device__ __forceinline__ void take(float d2, int id)
+    {
+        if (within(d2, d2_bound) && n < cap) {
+            seg.index[n] = id;
+            if constexpr (WITH_D2) seg.d2bits[n] = f32_bits(d2);
+            n++;
+        }
+    }
+    __device__ __forceinline__ bool done(float lb2) const { return walk_done(lb2, kKeyInf, d2_bound); }
+};
+
+template <bool WITH_D2>
+__global__ __launch_bounds__(kBlock) void k_pts_radius_fill(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
+                                                            const float* __restrict__ xyz, const float* __restrict__ queries, int64_t nq,
+                                                            float d2_bound, const int64_t* __restrict__ offsets, int32_t* __restrict__ index,
+                                                            float* __restrict__ distance, unsigned long long* candidates)
+{
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const Query q = load_query(queries, t, nq);
+    unsigned long long ncand = 0;
+    if (q.finite) {
+        const int64_t o0 = offsets[t], o1 = offsets[t + 1];
+        FillVisitor<WITH_D2> v;
+        v.seg = Segment<WITH_D2>{index + o0, WITH_D2 ? (uint32_t*)distance + o0 : nullptr, xyz, q.x, q.y, q.z};
+        v.d2_bound = d2_bound;
+        v.n = 0;
+        v.cap = o1 > o0 ? o1 - o0 : 0;
+        ncand = shell_walk(sorted, starts, G, q.x, q.y, q.z, v);
+        const int m = (int)v.n;   // (< 2^31: the static points)
+        heap_make(v.seg, m);
+        heap_sort(v.seg, m);
+        if constexpr (WITH_D2)
+            for (int i = 0; i < m; i++) v.seg.d2bits[i] = f32_bits(sqrt_rn(bits_f32(v.seg.d2bits[i])));   // d2 -> distance, in place
+    }
+    add_candidates(candidates, ncand);
+}
+
+unsigned grid_of(int64_t n, int block) { return (unsigned)std::max<int64_t>(1, (n + block - 1) / block); }
+
+// ---- launches ----------------------------------------------------------------------------------------------------------------
+// the candidate counter of a profiled call (sdfk_points_stats[3..4]); null when profiling is off
+struct Candidates {
+    unsigned long long* dev = nullptr;
+    int begin()
+    {
+        if (!g.prof_on) return SDFK_OK;
+        if (int r = dev_alloc((void**)&dev, sizeof(unsigned long long))) return r;
+        if (hipMemsetAsync(dev, 0, sizeof(unsigned long long), g.stream) != hipSuccess) {
+            dev_free(dev);
+            dev = nullptr;
+            return fail(SDFK_ERR_HIP, "points query: memset");
+        }
+        return SDFK_OK;
+    }
+    hipError_t end(const sdfk_points* s, int64_t nq)   // (synchronises, as the profiled search does)
+    {
+        if (!dev) return hipSuccess;
+        unsigned long long c = 0;
+        hipError_t e = hipMemcpyAsync(&c, dev, sizeof c, hipMemcpyDeviceToHost, g.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+        const_cast<sdfk_points*>(s)->last_candidates = (int64_t)c;
+        const_cast<sdfk_points*>(s)->last_queries = nq;
+        dev_free(dev);
+        dev = nullptr;
+        return e;
+    }
+};
+
+int knn_launch(const sdfk_points* s, const float* q, int64_t nq, int k, float d2_bound, KnnOut O)
+{
+    Candidates cand;
+    if (int r = cand.begin()) return r;
+    O.candidates = cand.dev;
+    {
+        ProfScope ps("k_pts_knn");
+        switch (tier_of(k)) {
+        case 8:
+            hipLaunchKernelGGL(k_pts_knn<8>, dim3(grid_of(nq, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, q, nq, k, d2_bound, O);
+            break;
+        case 16:
+            hipLaunchKernelGGL(k_pts_knn<16>, dim3(grid_of(nq, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, q, nq, k, d2_bound, O);
+            break;
+        case 32:
+            hipLaunchKernelGGL(k_pts_knn<32>, dim3(grid_of(nq, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, q, nq, k, d2_bound, O);
+            break;
+        default:
+            hipLaunchKernelGGL(k_pts_knn<64>, dim3(grid_of(nq, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, q, nq, k, d2_bound, O);
+            break;
+        }
+    }
+    hipError_t e = hipGetLastError();
+    const hipError_t ec = cand.end(s, nq);
+    if (e == hipSuccess) e = ec;
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_knn: %s", hipGetErrorString(e));
+    return SDFK_OK;
+}
+
+// offsets_dev[0 .. nq]: the counts, scanned in place
+int count_launch(const sdfk_points* s, const float* q, int64_t nq, float d2_bound, int64_t* offsets_dev)
+{
+    unsigned long long* off = reinterpret_cast<unsigned long long*>(offsets_dev);
+    unsigned long long* aux = nullptr;
+    if (int r = dev_alloc((void**)&aux, (size_t)(sdfk_scan::scan_blocks(nq) + 1) * sizeof(unsigned long long))) return r;
+    Candidates cand;
+    if (int r = cand.begin()) { dev_free(aux); return r; }
+    {
+        ProfScope ps("k_pts_radius_count");
+        hipLaunchKernelGGL(k_pts_radius_count, dim3(grid_of(nq, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, q, nq, d2_bound, off,
+                           cand.dev);
+        sdfk_scan::scan_launch<unsigned long long>(off, nq, aux, g.stream);
+    }
+    dev_free(aux);   // (stream-ordered pool)
+    hipError_t e = hipGetLastError();
+    const hipError_t ec = cand.end(s, nq);
+    if (e == hipSuccess) e = ec;
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_radius_count: %s", hipGetErrorString(e));
+    return SDFK_OK;
+}
+
+int fill_launch(const sdfk_points* s, const float* q, int64_t nq, float d2_bound, const int64_t* offsets_dev, int32_t* index, float* distance)
+{
+    Candidates cand;
+    if (int r = cand.begin()) return r;
+    {
+        ProfScope ps("k_pts_radius_fill");
+        if (distance)
+            hipLaunchKernelGGL(k_pts_radius_fill<true>, dim3(grid_of(nq, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, q, nq,
+                               d2_bound, offsets_dev, index, distance, cand.dev);
+        else
+            hipLaunchKernelGGL(k_pts_radius_fill<false>, dim3(grid_of(nq, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, q, nq,
+                               d2_bound, offsets_dev, index, distance, cand.dev);
+    }
+    hipError_t e = hipGetLastError();
+    const hipError_t ec = cand.end(s, nq);
+    if (e == hipSuccess) e = ec;
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_radius_fill: %s", hipGetErrorString(e));
+    return SDFK_OK;
+}
+
+int check_queries(const sdfk_points* s, const void* queries, int64_t n, const char* who)
+{
+    if (int r = require_init()) return r;
+    if (!s || n < 0 || (n > 0 && !queries)) return fail(SDFK_ERR_INVALID, "%s: null / negative argument", who);
+    if (n >= (int64_t(1) << 32)) return fail(SDFK_ERR_INVALID, "%s: 2^32 queries or more", who);
+    return SDFK_OK;
+}
+
+int check_knn(const sdfk_points* s, const void* queries, int64_t n, int32_t k, float max_distance)
+{
+    if (int r = check_queries(s, queries, n, "sdfk_points_knn")) return r;
+    if (k < 1 || k > kMaxK) return fail(SDFK_ERR_INVALID, "sdfk_points_knn: k = %d is outside [1, %d] (larger neighbourhoods: sdfk_points_radius_*)", (int)k, kMaxK);
+    if (!radius_is_valid(max_distance)) return fail(SDFK_ERR_INVALID, "sdfk_points_knn: max_distance is negative or NaN");
+    return SDFK_OK;
+}
+
+int check_radius(const sdfk_points* s, const void* queries, int64_t n, float radius, const void* offsets, const char* who)
+{
+    if (int r = check_queries(s, queries, n, who)) return r;
+    if (!offsets) return fail(SDFK_ERR_INVALID, "%s: null offsets", who);
+    if (!radius_is_valid(radius)) return fail(SDFK_ERR_INVALID, "%s: the radius is negative or NaN", who);
+    return SDFK_OK;
+}
+
+hipError_t upload_queries(float* qd, const float* queries3, int64_t n)
+{
+    return hipMemcpyAsync(qd, queries3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// entry points
+// ---------------------------------------------------------------------------------------------------------------------------
+extern "C" int sdfk_points_knn_device(const sdfk_points* s, const void* queries3_dev, int64_t n, int32_t k, float max_distance, void* index_dev,
+                                      void* distance_dev, void* found_dev)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_knn(s, queries3_dev, n, k, max_distance)) return r;
+    if (n == 0) return SDFK_OK;
+    return knn_launch(s, (const float*)queries3_dev, n, k, radius_d2_bound(max_distance), KnnOut{(int32_t*)index_dev, (float*)distance_dev, (int32_t*)found_dev, nullptr});
+}
+
+extern "C" int sdfk_points_knn(const sdfk_points* s, const float* queries3, int64_t n, int32_t k, float max_distance, int32_t* index, float* distance,
+                               int32_t* found)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_knn(s, queries3, n, k, max_distance)) return r;
+    if (n == 0) return SDFK_OK;
+    float* qd = nullptr;
+    int32_t* id = nullptr;
+    float* dd = nullptr;
+    int32_t* fd = nullptr;
+    const size_t nk = (size_t)n * (size_t)k;
+    int r = dev_alloc((void**)&qd, (size_t)n * 3 * sizeof(float));
+    if (!r && index) r = dev_alloc((void**)&id, nk * sizeof(int32_t));
+    if (!r && distance) r = dev_alloc((void**)&dd, nk * sizeof(float));
+    if (!r && found) r = dev_alloc((void**)&fd, (size_t)n * sizeof(int32_t));
+    hipError_t e = hipSuccess;
+    if (!r) e = upload_queries(qd, queries3, n);
+    if (!r && e == hipSuccess) r = knn_launch(s, qd, n, k, radius_d2_bound(max_distance), KnnOut{id, dd, fd, nullptr});
+    if (!r && e == hipSuccess && id) e = hipMemcpyAsync(index, id, nk * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
+    if (!r && e == hipSuccess && dd) e = hipMemcpyAsync(distance, dd, nk * sizeof(float), hipMemcpyDeviceToHost, g.stream);
+    if (!r && e == hipSuccess && fd) e = hipMemcpyAsync(found, fd, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
+    const hipError_t es = hipStreamSynchronize(g.stream);
+    dev_free(qd);
+    dev_free(id);
+    dev_free(dd);
+    dev_free(fd);
+    if (r) return r;
+    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_knn: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    return SDFK_OK;
+}
+
+extern "C" int sdfk_points_radius_count_device(const sdfk_points* s, const void* queries3_dev, int64_t n, float radius, void* offsets_dev)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_radius(s, queries3_dev, n, radius, offsets_dev, "sdfk_points_radius_count")) return r;
+    if (n == 0) {
+        if (hipMemsetAsync(offsets_dev, 0, sizeof(int64_t), g.stream) != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_radius_count: memset");
+        return SDFK_OK;
+    }
+    return count_launch(s, (const float*)queries3_dev, n, radius_d2_bound(radius), (int64_t*)offsets_dev);
+}
+
+extern "C" int sdfk_points_radius_count(const sdfk_points* s, const float* queries3, int64_t n, float radius, int64_t* offsets)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_radius(s, queries3, n, radius, offsets, "sdfk_points_radius_count")) return r;
+    if (n == 0) {
+        offsets[0] = 0;
+        return SDFK_OK;
+    }
+    float* qd = nullptr;
+    int64_t* od = nullptr;
+    int r = dev_alloc((void**)&qd, (size_t)n * 3 * sizeof(float));
+    if (!r) r = dev_alloc((void**)&od, (size_t)(n + 1) * sizeof(int64_t));
+    hipError_t e = hipSuccess;
+    if (!r) e = upload_queries(qd, queries3, n);
+    if (!r && e == hipSuccess) r = count_launch(s, qd, n, radius_d2_bound(radius), od);
+    if (!r && e == hipSuccess) e = hipMemcpyAsync(offsets, od, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, g.stream);
+    const hipError_t es = hipStreamSynchronize(g.stream);
+    dev_free(qd);
+    dev_free(od);
+    if (r) return r;
+    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_radius_count: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    return SDFK_OK;
+}
+
+extern "C" int sdfk_points_radius_fill_device(const sdfk_points* s, const void* queries3_dev, int64_t n, float radius, const void* offsets_dev,
+                                              void* index_dev, void* distance_dev)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_radius(s, queries3_dev, n, radius, offsets_dev, "sdfk_points_radius_fill")) return r;
+    if (n == 0) return SDFK_OK;
+    if (!index_dev) return fail(SDFK_ERR_INVALID, "sdfk_points_radius_fill: null index");
+    return fill_launch(s, (const float*)queries3_dev, n, radius_d2_bound(radius), (const int64_t*)offsets_dev, (int32_t*)index_dev, (float*)distance_dev);
+}
+
+extern "C" int sdfk_points_radius_fill(const sdfk_points* s, const float* queries3, int64_t n, float radius, const int64_t* offsets, int32_t* index,
+                                       float* distance)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_radius(s, queries3, n, radius, offsets, "sdfk_points_radius_fill")) return r;
+    if (n == 0) return SDFK_OK;
+    // the host form sizes its device arrays by offsets[n]: offsets that do not start at 0 and ascend to it would leave them
+    const int64_t total = offsets[n];
+    if (offsets[0] != 0) return fail(SDFK_ERR_INVALID, "sdfk_points_radius_fill: offsets[0] is not 0");
+    for (int64_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) return fail(SDFK_ERR_INVALID, "sdfk_points_radius_fill: offsets do not ascend (at query %lld)", (long long)i);
+    if (total == 0) return SDFK_OK;
+    if (!index) return fail(SDFK_ERR_INVALID, "sdfk_points_radius_fill: null index");
+    float* qd = nullptr;
+    int64_t* od = nullptr;
+    int32_t* id = nullptr;
+    float* dd = nullptr;
+    int r = dev_alloc((void**)&qd, (size_t)n * 3 * sizeof(float));
+    if (!r) r = dev_alloc((void**)&od, (size_t)(n + 1) * sizeof(int64_t));
+    if (!r) r = dev_alloc((void**)&id, (size_t)total * sizeof(int32_t));
+    if (!r && distance) r = dev_alloc((void**)&dd, (size_t)total * sizeof(float));
+    hipError_t e = hipSuccess;
+    if (!r) e = upload_queries(qd, queries3, n);
+    if (!r && e == hipSuccess) e = hipMemcpyAsync(od, offsets, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, g.stream);
+    if (!r && e == hipSuccess) r = fill_launch(s, qd, n, radius_d2_bound(radius), od, id, dd);
+    if (!r && e == hipSuccess) e = hipMemcpyAsync(index, id, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
+    if (!r && e == hipSuccess && dd) e = hipMemcpyAsync(distance, dd, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, g.stream);
+    const hipError_t es = hipStreamSynchronize(g.stream);
+    dev_free(qd);
+    dev_free(od);
+    dev_free(id);
+    dev_free(dd);
+    if (r) return r;
+    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_radius_fill: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    return SDFK_OK;
+}

@@ -1,0 +1,17 @@
+// points_set.h -- the handle behind sdfk_points_* (KdTree): the static points and their search grid, built by lib_points.hip and
+// read by the queries of lib_points.hip (nearest point, ICP) and lib_points_knn.hip (k nearest, within a radius).
+#pragma once
+#include "lib_internal.h"
+#include "points_grid.h"
+
+struct sdfk_points {
+    DeviceState* owner = &cur_state();
+    int64_t n = 0;
+    float* xyz = nullptr;          // n x 3, insertion order (the source of every rebuild)
+    float4* sorted = nullptr;      // n, cell order: (x, y, z, bits(index))
+    uint32_t* starts = nullptr;    // cells + 1
+    int64_t cells = 0;
+    sdfk_points_grid::Grid G{};
+    float first[3] = {0, 0, 0};
+    int64_t last_candidates = 0, last_queries = 0;   // of the last profiled query call, whichever kind
+};

@@ -2,7 +2,8 @@
 entry points sdfk_points_* / sdfk_icp_* (include/sdfkit_hip.h, csrc/lib_points.hip).
 
 Vector3 is a float32 numpy array of 3; a span of Vector3 is an (n, 3) float32 array.  The search is exact (the static
-point of least d2, ties to the lowest insertion index); the structure behind it is a grid of cell lists on the device,
+point of least d2, ties to the lowest insertion index; SearchKNearest and
+SearchRadius extend it to the k nearest and to all within a radius, in the same (d2, index) order); the structure behind it is a grid of cell lists on the device,
 so the reference's tree internals -- Left, Right, SplitValue, IsLeaf -- are not provided.  SplitAxis is kept as given.
 """
 import ctypes as C
@@ -69,13 +70,43 @@ class KdTree:
             N.check(N.lib().sdfk_points_search(self._h, _ptr(q), n, _ptr(idx), _ptr(dist), _ptr(near)))
         return idx, dist, near
 
+    def SearchKNearest(self, queries, k, maxDistance=np.inf):
+        """Extension: the k nearest static points of every query, ascending by (d2, index), no farther than maxDistance
+        -> (indices (n, k) int32, distances (n, k) float32, found (n,) int32); unused slots hold -1 and FLT_MAX.  1 <= k <= 64."""
+        q = _points(queries)
+        n, k = len(q), int(k)
+        if k < 1:   # (no array has such a shape: the library's refusal, without the call)
+            raise N.SdfKitNativeError(N.ERR_INVALID, f"sdfk_points_knn: k = {k} is outside [1, 64]")
+        idx = np.empty((n, k), np.int32)
+        dist = np.empty((n, k), f32)
+        found = np.empty(n, np.int32)
+        # (n == 0 still goes to the library: it is what refuses a bad k or maxDistance)
+        N.check(N.lib().sdfk_points_knn(self._h, _ptr(q), n, k, float(f32(maxDistance)), _ptr(idx), _ptr(dist), _ptr(found)))
+        return idx, dist, found
+
+    def SearchRadius(self, queries, radius):
+        """Extension: every static point within `radius` of every query (sqrtf(d2) <= radius), as a CSR
+        -> (offsets (n + 1,) int64, indices int32, distances float32): query i's neighbours are [offsets[i], offsets[i + 1]),
+        ascending by (d2, index)."""
+        q = _points(queries)
+        n = len(q)
+        r = float(f32(radius))
+        off = np.zeros(n + 1, np.int64)
+        N.check(N.lib().sdfk_points_radius_count(self._h, _ptr(q), n, r, _ptr(off)))
+        total = int(off[n])
+        idx = np.empty(total, np.int32)
+        dist = np.empty(total, f32)
+        if total:
+            N.check(N.lib().sdfk_points_radius_fill(self._h, _ptr(q), n, r, _ptr(off), _ptr(idx), _ptr(dist)))
+        return off, idx, dist
+
     def Search(self, q):
         """KdTree.Search(q, out nearestDistance) -> (nearest, nearestDistance)."""
         _, d, p = self.SearchMany(np.asarray(q, f32).reshape(1, 3))
         return p[0], f32(d[0])
 
     def stats(self):
-        """sdfk_points_stats: {'grid': (nx, ny, nz), 'candidates', 'queries'} (candidates: last search under profiling)."""
+        """sdfk_points_stats: {'grid': (nx, ny, nz), 'candidates', 'queries'} (candidates: last query call under profiling)."""
         s = (C.c_int64 * 5)()
         N.check(N.lib().sdfk_points_stats(self._h, s))
         return {"grid": (s[0], s[1], s[2]), "candidates": int(s[3]), "queries": int(s[4])}

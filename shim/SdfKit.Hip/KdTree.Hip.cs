@@ -67,6 +67,36 @@ namespace SdfKit
                 Native.Check (Native.sdfk_points_search (handle, (float*)q, queries.Length, i, d, (float*)n));
         }
 
+        /// <summary>Extension: the k nearest static points of every query (1..64), ascending by (d2, index), no farther than
+        /// maxDistance.  indices / distances hold queries.Length rows of k (-1 and float.MaxValue in unused slots), found the
+        /// number of real entries per query.</summary>
+        public unsafe void SearchKNearest (ReadOnlySpan<Vector3> queries, int k, Span<int> indices, Span<float> distances, Span<int> found,
+                                           float maxDistance = float.PositiveInfinity)
+        {
+            if (k < 1 || k > 64)
+                throw new ArgumentOutOfRangeException (nameof (k), "k must be in 1..64 (larger neighbourhoods: SearchRadius)");
+            long nk = (long)queries.Length * k;
+            if (indices.Length < nk || distances.Length < nk || found.Length < queries.Length)
+                throw new ArgumentException ("Output spans are shorter than queries x k");
+            fixed (Vector3* q = queries) fixed (int* i = indices) fixed (float* d = distances) fixed (int* f = found)
+                Native.Check (Native.sdfk_points_knn (handle, (float*)q, queries.Length, k, maxDistance, i, d, f));
+        }
+
+        /// <summary>Extension: every static point within radius of every query (distance &lt;= radius), as a CSR: query i's
+        /// neighbours are [offsets[i], offsets[i + 1]), ascending by (d2, index).</summary>
+        public unsafe void SearchRadius (ReadOnlySpan<Vector3> queries, float radius, out long[] offsets, out int[] indices, out float[] distances)
+        {
+            offsets = new long[queries.Length + 1];
+            fixed (Vector3* q = queries) fixed (long* o = offsets) {
+                Native.Check (Native.sdfk_points_radius_count (handle, (float*)q, queries.Length, radius, o));
+                indices = new int[offsets[queries.Length]];
+                distances = new float[indices.Length];
+                if (indices.Length > 0)
+                    fixed (int* i = indices) fixed (float* d = distances)
+                        Native.Check (Native.sdfk_points_radius_fill (handle, (float*)q, queries.Length, radius, o, i, d));
+            }
+        }
+
         public void Dispose ()
         {
             if (handle != IntPtr.Zero) {

@@ -99,6 +99,14 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_points_search_device(IntPtr points, IntPtr queries3Dev, long n, IntPtr indexDev, IntPtr distanceDev,
                                                                             IntPtr nearest3Dev);
         [DllImport(Lib)] public static extern int sdfk_points_stats(IntPtr points, long* stats5);
+        [DllImport(Lib)] public static extern int sdfk_points_knn(IntPtr points, float* queries3, long n, int k, float maxDistance, int* index, float* distance, int* found);
+        [DllImport(Lib)] public static extern int sdfk_points_knn_device(IntPtr points, IntPtr queries3Dev, long n, int k, float maxDistance, IntPtr indexDev,
+                                                                         IntPtr distanceDev, IntPtr foundDev);
+        [DllImport(Lib)] public static extern int sdfk_points_radius_count(IntPtr points, float* queries3, long n, float radius, long* offsets);
+        [DllImport(Lib)] public static extern int sdfk_points_radius_count_device(IntPtr points, IntPtr queries3Dev, long n, float radius, IntPtr offsetsDev);
+        [DllImport(Lib)] public static extern int sdfk_points_radius_fill(IntPtr points, float* queries3, long n, float radius, long* offsets, int* index, float* distance);
+        [DllImport(Lib)] public static extern int sdfk_points_radius_fill_device(IntPtr points, IntPtr queries3Dev, long n, float radius, IntPtr offsetsDev,
+                                                                                 IntPtr indexDev, IntPtr distanceDev);
         [DllImport(Lib)] public static extern void sdfk_points_free(IntPtr points);
         [DllImport(Lib)] public static extern int sdfk_icp_register(IntPtr points, ref SdfkIcpParams prm, float* points3, long n, float* total16, out int iterations);
         [DllImport(Lib)] public static extern int sdfk_icp_register_device(IntPtr points, ref SdfkIcpParams prm, IntPtr points3Dev, long n, float* total16,
