@@ -501,6 +501,7 @@ public:
 
 private:
     friend class MeshSdf;   // (writes distances straight into the device volume)
+    friend class KdTree;    // (likewise: KdTree::SampleInto)
     Val Read(int opcode, const Vec3& p, int channel) const
     {
         Builder* b = p.X.b ? p.X.b : (p.Y.b ? p.Y.b : p.Z.b);
@@ -776,6 +777,50 @@ public:
         r.Distances.resize(r.Indices.size());
         if (!r.Indices.empty()) Check(sdfk_points_radius_fill(h_, q, n, radius, r.Offsets.data(), r.Indices.data(), r.Distances.data()));
         return r;
+    }
+    // Extensions (sdfkit_hip.h, "Point clouds: normals and volumes").
+    struct Normals {
+        std::vector<Vector3> Normal;     // per static point; (0, 0, 0) where the neighbourhood is degenerate
+        std::vector<float> Variation;    // lmin / (l0 + l1 + l2)
+    };
+    // A normal per static point from its k nearest (3 <= k <= 64), turned towards the viewpoints: none (the largest component is
+    // made positive -- not a consistent orientation of a closed surface, which is out of scope), one, or one per point.
+    Normals EstimateNormals(int k, const std::vector<Vector3>& viewpoints = {}, float maxDistance = std::numeric_limits<float>::infinity()) const
+    {
+        Normals r;
+        const size_t n = (size_t)TotalPoints();
+        r.Normal.resize(n);
+        r.Variation.resize(n);
+        Check(sdfk_points_normals(h_, k, maxDistance, viewpoints.empty() ? nullptr : &viewpoints[0].X, (int64_t)viewpoints.size(), &r.Normal[0].X,
+                                  r.Variation.data()));
+        return r;
+    }
+    Normals EstimateNormals(int k, Vector3 viewpoint, float maxDistance = std::numeric_limits<float>::infinity()) const
+    {
+        return EstimateNormals(k, std::vector<Vector3>{viewpoint}, maxDistance);
+    }
+    struct VolumeStats { int64_t Known = 0, Unknown = 0, Candidates = 0, Queries = 0; };
+    // The cloud with one outward normal per static point as a signed distance volume: the blend of the tangent-plane distances of the
+    // k nearest points within maxDistance; voxels beyond get +-maxDistance (give a band, then Voxels::Redistance, for a full field).
+    Voxels ToVoxels(const std::vector<Vector3>& normals, Vector3 min, Vector3 max, int nx, int ny, int nz, int k = 8,
+                    float maxDistance = std::numeric_limits<float>::infinity(), bool clipToBounds = false, VolumeStats* stats = nullptr) const
+    {
+        Voxels v(min, max, nx, ny, nz);
+        SampleInto(v, normals, k, maxDistance, stats);
+        if (clipToBounds) v.ClipToBounds();
+        return v;
+    }
+    void SampleInto(Voxels& v, const std::vector<Vector3>& normals, int k = 8, float maxDistance = std::numeric_limits<float>::infinity(),
+                    VolumeStats* stats = nullptr) const
+    {
+        if ((int64_t)normals.size() != (int64_t)TotalPoints()) throw std::invalid_argument("one normal per static point (normals)");
+        if (v.hostNewer_) v.Sync(); else v.Ensure(v.hasColors_);   // (host edits go up first; the colours stay what they are)
+        int64_t st[4] = {0, 0, 0, 0};
+        Check(sdfk_points_to_volume(h_, &normals[0].X, v.h_, k, maxDistance, stats ? st : nullptr));
+        if (stats) { stats->Known = st[0]; stats->Unknown = st[1]; stats->Candidates = st[2]; stats->Queries = st[3]; }
+        v.values_.clear();
+        v.hostNewer_ = false;
+        v.version_++;
     }
     sdfk_points* Handle() const { return h_; }
 

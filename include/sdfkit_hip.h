@@ -36,7 +36,8 @@ extern "C" {
                                    sdfk_trimesh_* (triangle-mesh distance),
                                    sdfk_program_create_bound / sdfk_program_check_bound (programs that read voxel volumes); opcodes
                                    SDFK_OP_SIN .. SDFK_OP_ATAN2 (19-23), accepted by every entry point that takes an op list;
-                                   sdfk_points_knn* / sdfk_points_radius_* (KdTree: k nearest, within a radius) */
+                                   sdfk_points_knn* / sdfk_points_radius_* (KdTree: k nearest, within a radius);
+                                   sdfk_points_normals* / sdfk_points_to_volume* (point clouds: normals, signed distance volumes) */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -583,6 +584,65 @@ int sdfk_points_radius_fill(const sdfk_points* s, const float* queries3, int64_t
                             int32_t* index /* total */, float* distance /* total; may be NULL */);
 int sdfk_points_radius_fill_device(const sdfk_points* s, const void* queries3_dev, int64_t n, float radius, const void* offsets_dev,
                                    void* index_dev, void* distance_dev);
+/* ---- Point clouds: normals and volumes (extensions: the reference stops at IterativeClosestPoint) ---------------------------------
+ * The static points of a set as a surface: a normal per point from its neighbourhood, and the set with normals as a signed
+ * distance volume -- scan -> sdfk_icp_register -> sdfk_points_normals -> sdfk_points_to_volume (with a band) -> sdfk_volume_redistance
+ * -> programs, meshes.  Both are ONE function of their inputs, computed by csrc/points_normals.h (binary64 from the f32 inputs,
+ * + - * / and sqrt only, each correctly rounded, in the order given, no contraction, one rounding to f32 per result), restated in
+ * tests/pointcloud_model.py and compared bit for bit.  Neighbours are sdfk_points_knn's: the same (d2, index) order, d2 formula
+ * and max_distance rule; m = the number found.
+ *
+ * sdfk_points_normals: for every static point i (insertion order), 3 <= k <= 64:
+ * 1. Neighbours: the sdfk_points_knn row of p_i (k, max_distance) -- the point itself and any duplicates included.
+ * 2. Covariance: q_j = p_j - p_i per component; mean = (the sum of the q_j in neighbour order) / m; with d = q_j - mean the six
+ *    sums c00 += d0 d0, c01 += d0 d1, c02 += d0 d2, c11 += d1 d1, c12 += d1 d2, c22 += d2 d2 in neighbour order (not divided by
+ *    m: nothing below depends on the scale).
+ * 3. Eigenvectors: cyclic Jacobi on the symmetric 3x3, V = I at first; exactly 8 sweeps, each over the pairs (p, q) = (0,1), (0,2),
+ *    (1,2), r the third index.  A pair whose a_pq is exactly 0 is skipped.  Otherwise theta = (a_qq - a_pp) / (2 a_pq);
+ *    t = 1 / (|theta| + sqrt(theta theta + 1)), negated when theta < 0; c = 1 / sqrt(t t + 1); s = t c; a_pp -= t a_pq;
+ *    a_qq += t a_pq; a_pq = 0; (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq); every row of V: (v_kp, v_kq) = (c v_kp - s v_kq,
+ *    s v_kp + c v_kq).  The eigenvalues l are the diagonal.  n = the column of V of the least l (ties: the lowest column), divided
+ *    by its length sqrt((n0 n0 + n1 n1) + n2 n2).
+ * 4. Orientation: with a viewpoint w (n_viewpoints = 1: one for all; = the number of static points: one each; = 0: none),
+ *    d = ((w0 - p0) n0 + (w1 - p1) n1) + (w2 - p2) n2; d < 0 flips n.  With no viewpoint, or d exactly 0, the component of n of
+ *    largest magnitude is made positive (ties: the lowest axis).  A CONSISTENT orientation without a viewpoint (propagation along
+ *    a spanning tree of the neighbourhood graph) is not provided.
+ * 5. normal = n rounded to f32; variation = (float)(l_min / ((l_0 + l_1) + l_2)) (surface variation: 0 on a plane, up to 1/3).
+ * 6. Degenerate: m < 3, or (c00 + c11) + c22 == 0: normal = (0, 0, 0), variation = 0.  A collinear neighbourhood gives a
+ *    deterministic but meaningless direction.
+ * 7. SDFK_ERR_INVALID: k outside [3, 64], a NaN or negative max_distance, n_viewpoints not 0, 1 or the number of static points, a
+ *    NaN or infinite viewpoint (host form; the _device form does not read them on the host: such a d is compared as it comes, a
+ *    NaN one falling to the rule without viewpoint).  normals3 / variation may be NULL.
+ *
+ * sdfk_points_to_volume: normals3 holds one normal per static point (sdfk_points_normals' or the caller's; finite, not checked);
+ * 1 <= k <= 64; max_distance > 0, +inf allowed (SDFK_ERR_INVALID otherwise, and for a volume without storage).  The value is
+ * (x - p) . n: normals point to the positive (outside) side.  Every voxel of `v` (a whole volume or a slab, rows padded as
+ * sdfk_volume_row_pitch says) is evaluated at its cell centre x, the f32 centres sdfk_sample and sdfk_trimesh_to_volume use:
+ * 1. Neighbours: the sdfk_points_knn row of x (k, max_distance).  Those whose normal is (0, 0, 0) are skipped; if none is left (or
+ *    none was found) the voxel is UNKNOWN.
+ * 2. Cut-off: h2 = the d2 of neighbour k - 1 when m == k, else the greatest d2 within max_distance (FLT_MAX for +inf).
+ * 3. Blend over the unskipped neighbours in order: e_j = ((x0 - p0) n0 + (x1 - p1) n1) + (x2 - p2) n2; when h2 > 0: t = d2_j / h2,
+ *    u = 1 - t, w = u u, S += w e_j, W += w.  value = S / W when W > 0, else e of the first unskipped neighbour (k = 1: Hoppe's
+ *    tangent-plane distance; h2 == 0; every d2 equal).  A neighbour that enters or leaves the set does so with weight 0, so
+ *    the field is continuous where the set changes.  The value is rounded to f32, then clamped to [-max_distance, max_distance].
+ * 4. Unknown voxels get +-max_distance, the sign carried from the known ones (a known value < 0 is negative, anything else
+ *    positive) by three passes: along every line in z an unknown voxel takes the last sign below it, the ones below the first sign
+ *    the first sign above; lines still without a sign repeat this along y with what the z pass left, then along x; a volume
+ *    without any known voxel becomes +max_distance.  This is right where the band of known voxels covers the surface, so that
+ *    every sign change happens inside it (a closed surface, a band of at least a voxel's diagonal, points no sparser than the band);
+ *    otherwise -- an open scan, a band thinner than the sampling -- it is deterministic, not meaningful.
+ * 5. stats (may be NULL; reading them synchronises): [0] known voxels, [1] unknown voxels, [2] candidates and [3] queries of the
+ *    call when sdfk_profile_enable(1) is on (else 0; sdfk_points_stats[3..4] report them too).
+ * 6. Colours are left as they are.  Cached sign bits of the volume are dropped, as for a write through sdfk_volume_device_ptrs.
+ * The plain forms take host arrays and are synchronous; the _device forms take device arrays and are asynchronous on the library
+ * stream (unless stats or profiling make them wait). */
+int sdfk_points_normals(const sdfk_points* s, int32_t k, float max_distance, const float* viewpoints3, int64_t n_viewpoints,
+                        float* normals3 /* n*3 */, float* variation /* n */);
+int sdfk_points_normals_device(const sdfk_points* s, int32_t k, float max_distance, const void* viewpoints3_dev, int64_t n_viewpoints,
+                               void* normals3_dev, void* variation_dev);
+int sdfk_points_to_volume(const sdfk_points* s, const float* normals3, sdfk_volume* v, int32_t k, float max_distance, int64_t stats[4]);
+int sdfk_points_to_volume_device(const sdfk_points* s, const void* normals3_dev, sdfk_volume* v, int32_t k, float max_distance,
+                                 int64_t stats[4]);
 /* IterativeClosestPoint.RegisterPoints (IterativeClosestPoint.cs:53-196): rigidly moves the caller's points (in place) onto the
  * static set and returns the total transform (row-major M11..M44, System.Numerics row-vector convention) and the number of
  * iterations run.  Each iteration is the reference's: nearest static point of every point, the piecewise distMax from the

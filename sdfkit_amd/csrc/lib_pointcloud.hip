@@ -1,0 +1,350 @@
+// lib_pointcloud.hip -- the KdTree's point cloud as geometry: normals (sdfk_points_normals*) and signed distance volumes
+// (sdfk_points_to_volume*).  Contract: include/sdfkit_hip.h, "Point clouds: normals and volumes"; the arithmetic (covariance,
+// Jacobi eigenvectors, orientation, the blend of tangent-plane distances, the fill of one line): points_normals.h, checked on the
+// host; the walk and the bounded lists: points_walk.h / points_knn.h, shared with lib_points_knn.hip.
+//
+//   k_pc_normals<CAP>   one lane per static point: its k nearest (itself included) exactly as k_pts_knn<CAP> finds them -- CAP = 8
+//                       in registers, 16 / 32 / 64 a heap in LDS, one wave per block --, then two passes over the list (mean,
+//                       covariance; the neighbours' coordinates gathered from the insertion-order array) and the binary64 eigen
+//                       step, all in the same lane.
+//   k_pc_volume<CAP>    one lane per voxel: the k nearest of the cell centre, the blend over them (coordinates and normals
+//                       gathered), the value and a sign byte (0: unknown).
+//   k_pc_fill<AXIS>     one lane per line of sign bytes along z, then y, then x: unknown voxels take the sign carried along the
+//                       line and the value +-max_distance.  Lines along z are walked by neighbouring lanes nz bytes apart
+//                       (uncoalesced; the array is one byte per voxel and each line stays in cache), the other two coalesce.
+#include "lib_internal.h"
+#include "points_knn.h"
+#include "points_normals.h"
+#include "points_set.h"
+#include "points_walk.h"
+
+#include <cfloat>
+
+namespace {
+
+using namespace sdfk_walk;
+using namespace sdfk_pc;
+
+template <int CAP>
+constexpr int block_of() { return CAP == 8 ? kBlock : kLdsBlock; }
+template <int CAP>
+constexpr int lds_keys() { return CAP == 8 ? 1 : CAP * kLdsBlock; }   // (the register tier keeps no keys in LDS)
+
+__device__ __forceinline__ void load3(const float* __restrict__ a, int64_t i, float out[3])
+{
+    out[0] = a[3 * i]; out[1] = a[3 * i + 1]; out[2] = a[3 * i + 2];
+}
+
+// ---- normals -------------------------------------------------------------------------------------------------------------------
+struct NormalsArgs {
+    const float* xyz;        // the static points, insertion order
+    int64_t n;
+    int k;
+    float d2_bound;
+    const float* view;       // n_view x 3
+    int64_t n_view;          // 0: none, 1: one for all, n: one per point
+    float* normals;          // n x 3, may be null
+    float* variation;        // n, may be null
+    unsigned long long* candidates;
+};
+
+template <int CAP>
+__global__ __launch_bounds__(block_of<CAP>()) void k_pc_normals(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
+                                                                 NormalsArgs A)
+{
+    __shared__ uint64_t s_keys[lds_keys<CAP>()];
+    const int64_t t = (int64_t)blockIdx.x * block_of<CAP>() + threadIdx.x;
+    const Query q = load_query(A.xyz, t, A.n);
+    Neighbours<CAP> nb;
+    const unsigned long long ncand = nb.collect(sorted, starts, G, q, A.k, A.d2_bound, s_keys);
+    if (t < A.n) {
+        const float pi[3] = {q.x, q.y, q.z};
+        Mean mean;
+        nb.each([&](uint64_t key) {
+            float p[3];
+            load3(A.xyz, key_index(key), p);
+            mean.add(p, pi);
+            return true;
+        });
+        if (nb.m > 0) mean.finish(nb.m);
+        Cov C;
+        nb.each([&](uint64_t key) {
+            float p[3];
+            load3(A.xyz, key_index(key), p);
+            C.add(p, pi, mean);
+            return true;
+        });
+        float w[3] = {0.0f, 0.0f, 0.0f};
+        if (A.n_view) load3(A.view, A.n_view == 1 ? 0 : t, w);
+        float nrm[3], var;
+        normal_of(C, nb.m, pi, A.n_view != 0, w, nrm, &var);
+        if (A.normals) { A.normals[3 * t] = nrm[0]; A.normals[3 * t + 1] = nrm[1]; A.normals[3 * t + 2] = nrm[2]; }
+        if (A.variation) A.variation[t] = var;
+    }
+    add_candidates(A.candidates, ncand);
+}
+
+// ---- the volume ----------------------------------------------------------------------------------------------------------------
+struct VolumeArgs {
+    const float* xyz;
+    const float* normals;    // one per static point
+    float* values;
+    signed char* sgn;        // nx * ny * nz (unpadded rows): 0 unknown, +-1
+    int nx, ny, nz, pitch, z0;
+    float mx, my, mz, dx, dy, dz;
+    int k;
+    float d2_bound, max_distance;
+    unsigned long long* known;        // null: not counted
+    unsigned long long* candidates;
+};
+
+template <int CAP>
+__global__ __launch_bounds__(block_of<CAP>()) void k_pc_volume(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
+                                                                VolumeArgs A)
+{
+    __shared__ uint64_t s_keys[lds_keys<CAP>()];
+    const int64_t n = (int64_t)A.nx * A.ny * A.nz;
+    const int64_t g0 = (int64_t)blockIdx.x * block_of<CAP>() + threadIdx.x;
+    const bool active = g0 < n;
+    const int64_t gidx = active ? g0 : 0;
+    const int kz = (int)(gidx % A.nz);
+    const int64_t row = gidx / A.nz;   // = i * ny + j
+    const int j = (int)(row % A.ny), i = (int)(row / A.ny);
+    // the cell centre, as sdfk_sample and sdfk_trimesh_to_volume place it
+    const float x[3] = {A.mx + (float)i * A.dx, A.my + (float)j * A.dy, A.mz + (float)(A.z0 + kz) * A.dz};
+    Query q{x[0], x[1], x[2], false};
+    q.finite = active && isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);
+    Neighbours<CAP> nb;
+    const unsigned long long ncand = nb.collect(sorted, starts, G, q, A.k, A.d2_bound, s_keys);
+    bool known = false;
+    if (active) {
+        Blend b;
+        if (nb.m > 0) {
+            const float h2 = cutoff_d2(nb.m, A.k, key_d2(nb.last()), A.d2_bound);
+            nb.each([&](uint64_t key) {
+                float p[3], nr[3];
+                load3(A.xyz, key_index(key), p);
+                load3(A.normals, key_index(key), nr);
+                b.add(x, p, nr, key_d2(key), h2);
+                return true;
+            });
+        }
+        known = b.known();
+        signed char s = 0;
+        if (known) {
+            const float v = b.value(A.max_distance);
+            A.values[(size_t)row * A.pitch + kz] = v;
+            s = (signed char)sign_of(v);
+        }
+        A.sgn[gidx] = s;
+    }
+    if (A.known) {
+        const unsigned long long c = (unsigned long long)__popcll(__ballot(known));
+        if ((threadIdx.x & 63) == 0 && c) atomicAdd(A.known, c);
+    }
+    add_candidates(A.candidates, ncand);
+}
+
+// One lane per line along AXIS (2: z, 1: y, 0: x).  LAST (the pass along x): a line without a sign means a volume without one,
+// which becomes +max_distance.
+template <int AXIS>
+__global__ __launch_bounds__(kBlock) void k_pc_fill(signed char* __restrict__ sgn, float* __restrict__ values, int nx, int ny, int nz, int pitch,
+                                                    float max_distance)
+{
+    const int64_t lines = AXIS == 2 ? (int64_t)nx * ny : AXIS == 1 ? (int64_t)nx * nz : (int64_t)ny * nz;
+    const int64_t L = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (L >= lines) return;
+    int64_t sbase, vbase;
+    long long sstride, vstride;
+    int len;
+    if (AXIS == 2) {
+        sbase = L * nz; vbase = L * pitch; sstride = 1; vstride = 1; len = nz;
+    } else if (AXIS == 1) {
+        const int64_t i = L / nz, k = L % nz;
+        sbase = i * ny * nz + k; vbase = i * ny * pitch + k; sstride = nz; vstride = pitch; len = ny;
+    } else {
+        const int64_t j = L / nz, k = L % nz;
+        sbase = j * nz + k; vbase = j * pitch + k; sstride = (long long)ny * nz; vstride = (long long)ny * pitch; len = nx;
+    }
+    float* val = values + vbase;
+    const bool had = fill_line(sgn + sbase, len, sstride, [&](int i, int s) { val[(long long)i * vstride] = s < 0 ? -max_distance : max_distance; });
+    if (AXIS == 0 && !had)
+        for (int i = 0; i < len; i++) {
+            sgn[sbase + (long long)i * sstride] = 1;
+            val[(long long)i * vstride] = max_distance;
+        }
+}
+
+// ---- launches ----------------------------------------------------------------------------------------------------------------
+int normals_launch(const sdfk_points* s, int k, float d2_bound, const float* view_dev, int64_t n_view, float* normals_dev, float* variation_dev)
+{
+    Candidates cand;
+    if (int r = cand.begin()) return r;
+    NormalsArgs A{s->xyz, s->n, k, d2_bound, view_dev, n_view, normals_dev, variation_dev, cand.dev};
+    {
+        ProfScope ps("k_pc_normals");
+        switch (tier_of(k)) {
+        case 8: hipLaunchKernelGGL(k_pc_normals<8>, dim3(grid_of(s->n, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
+        case 16: hipLaunchKernelGGL(k_pc_normals<16>, dim3(grid_of(s->n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
+        case 32: hipLaunchKernelGGL(k_pc_normals<32>, dim3(grid_of(s->n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
+        default: hipLaunchKernelGGL(k_pc_normals<64>, dim3(grid_of(s->n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
+        }
+    }
+    hipError_t e = hipGetLastError();
+    const hipError_t ec = cand.end(s, s->n);
+    if (e == hipSuccess) e = ec;
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_normals: %s", hipGetErrorString(e));
+    return SDFK_OK;
+}
+
+int check_normals(const sdfk_points* s, int32_t k, float max_distance, const void* view, int64_t n_view)
+{
+    static const char* who = "sdfk_points_normals";
+    if (int r = require_init()) return r;
+    if (!s) return fail(SDFK_ERR_INVALID, "%s: null point set", who);
+    if (k < kMinNormalK || k > kMaxK) return fail(SDFK_ERR_INVALID, "%s: k = %d is outside [%d, %d]", who, (int)k, kMinNormalK, kMaxK);
+    if (!radius_is_valid(max_distance)) return fail(SDFK_ERR_INVALID, "%s: max_distance is negative or NaN", who);
+    if (!(n_view == 0 || n_view == 1 || n_view == s->n) || (n_view > 0 && !view))
+        return fail(SDFK_ERR_INVALID, "%s: viewpoints must be none, one, or one per static point", who);
+    return SDFK_OK;
+}
+
+int to_volume(const sdfk_points* s, const float* normals_dev, sdfk_volume* v, int k, float max_distance, int64_t stats[4])
+{
+    static const char* who = "sdfk_points_to_volume";
+    resolve_dependents(v);   // (a queued mesh may still read the old values)
+    volume_values_changed(v);
+    float d[3], m[3], outside;
+    grid_constants(v, d, m, &outside);
+    const int64_t nvox = (int64_t)v->nx * v->ny * v->nz;
+    signed char* sgn = nullptr;
+    unsigned long long* known = nullptr;
+    int r = dev_alloc((void**)&sgn, (size_t)nvox);
+    hipError_t e = hipSuccess;
+    if (!r && stats) {
+        r = dev_alloc((void**)&known, sizeof(unsigned long long));
+        if (!r) e = hipMemsetAsync(known, 0, sizeof(unsigned long long), g.stream);
+    }
+    Candidates cand;
+    if (!r && e == hipSuccess) r = cand.begin();
+    if (!r && e == hipSuccess) {
+        VolumeArgs A{s->xyz, normals_dev, v->values, sgn, v->nx, v->ny, v->nz, v->pitch(), v->z0, m[0], m[1], m[2], d[0], d[1], d[2],
+                     k, radius_d2_bound(max_distance), max_distance, known, cand.dev};
+        {
+            ProfScope ps("k_pc_volume");
+            switch (tier_of(k)) {
+            case 8: hipLaunchKernelGGL(k_pc_volume<8>, dim3(grid_of(nvox, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
+            case 16: hipLaunchKernelGGL(k_pc_volume<16>, dim3(grid_of(nvox, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
+            case 32: hipLaunchKernelGGL(k_pc_volume<32>, dim3(grid_of(nvox, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
+            default: hipLaunchKernelGGL(k_pc_volume<64>, dim3(grid_of(nvox, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
+            }
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) {
+            ProfScope ps("k_pc_fill");
+            const int nx = v->nx, ny = v->ny, nz = v->nz, pitch = v->pitch();
+            hipLaunchKernelGGL(k_pc_fill<2>, dim3(grid_of((int64_t)nx * ny, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
+            hipLaunchKernelGGL(k_pc_fill<1>, dim3(grid_of((int64_t)nx * nz, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
+            hipLaunchKernelGGL(k_pc_fill<0>, dim3(grid_of((int64_t)ny * nz, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
+            e = hipGetLastError();
+        }
+        const hipError_t ec = cand.end(s, nvox);
+        if (e == hipSuccess) e = ec;
+    }
+    if (!r && e == hipSuccess && stats) {
+        unsigned long long c = 0;
+        e = hipMemcpyAsync(&c, known, sizeof c, hipMemcpyDeviceToHost, g.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+        stats[0] = (int64_t)c;
+        stats[1] = nvox - (int64_t)c;
+        stats[2] = g.prof_on ? s->last_candidates : 0;
+        stats[3] = g.prof_on ? s->last_queries : 0;
+    }
+    dev_free(sgn);   // (stream-ordered pool)
+    dev_free(known);
+    if (r) return r;
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return SDFK_OK;
+}
+
+int check_volume(const sdfk_points* s, const void* normals, const sdfk_volume* v, int32_t k, float max_distance)
+{
+    static const char* who = "sdfk_points_to_volume";
+    if (int r = require_init()) return r;
+    if (!s || !v || !normals) return fail(SDFK_ERR_INVALID, "%s: null argument", who);
+    if (k < 1 || k > kMaxK) return fail(SDFK_ERR_INVALID, "%s: k = %d is outside [1, %d]", who, (int)k, kMaxK);
+    if (!(max_distance > 0.0f)) return fail(SDFK_ERR_INVALID, "%s: max_distance must be > 0 (+inf: no band)", who);
+    if (v->elided || !v->values) return fail(SDFK_ERR_INVALID, "%s: the volume has no storage", who);
+    if (v->owner != s->owner) return fail(SDFK_ERR_INVALID, "%s: the volume belongs to another device context", who);
+    return SDFK_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// entry points
+// ---------------------------------------------------------------------------------------------------------------------------
+extern "C" int sdfk_points_normals_device(const sdfk_points* s, int32_t k, float max_distance, const void* viewpoints3_dev, int64_t n_viewpoints,
+                                          void* normals3_dev, void* variation_dev)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_normals(s, k, max_distance, viewpoints3_dev, n_viewpoints)) return r;
+    return normals_launch(s, k, radius_d2_bound(max_distance), (const float*)viewpoints3_dev, n_viewpoints, (float*)normals3_dev, (float*)variation_dev);
+}
+
+extern "C" int sdfk_points_normals(const sdfk_points* s, int32_t k, float max_distance, const float* viewpoints3, int64_t n_viewpoints, float* normals3,
+                                   float* variation)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_normals(s, k, max_distance, viewpoints3, n_viewpoints)) return r;
+    for (int64_t i = 0; i < 3 * n_viewpoints; i++)
+        if (!std::isfinite(viewpoints3[i])) return fail(SDFK_ERR_INVALID, "sdfk_points_normals: viewpoint %lld has a NaN or infinite coordinate", (long long)(i / 3));
+    const int64_t n = s->n;
+    float* vd = nullptr;
+    float* nd = nullptr;
+    float* wd = nullptr;
+    int r = SDFK_OK;
+    if (n_viewpoints) r = dev_alloc((void**)&vd, (size_t)n_viewpoints * 3 * sizeof(float));
+    if (!r && normals3) r = dev_alloc((void**)&nd, (size_t)n * 3 * sizeof(float));
+    if (!r && variation) r = dev_alloc((void**)&wd, (size_t)n * sizeof(float));
+    hipError_t e = hipSuccess;
+    if (!r && vd) e = hipMemcpyAsync(vd, viewpoints3, (size_t)n_viewpoints * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
+    if (!r && e == hipSuccess) r = normals_launch(s, k, radius_d2_bound(max_distance), vd, n_viewpoints, nd, wd);
+    if (!r && e == hipSuccess && nd) e = hipMemcpyAsync(normals3, nd, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
+    if (!r && e == hipSuccess && wd) e = hipMemcpyAsync(variation, wd, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, g.stream);
+    const hipError_t es = hipStreamSynchronize(g.stream);
+    dev_free(vd);
+    dev_free(nd);
+    dev_free(wd);
+    if (r) return r;
+    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_normals: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    return SDFK_OK;
+}
+
+extern "C" int sdfk_points_to_volume_device(const sdfk_points* s, const void* normals3_dev, sdfk_volume* v, int32_t k, float max_distance,
+                                            int64_t stats[4])
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_volume(s, normals3_dev, v, k, max_distance)) return r;
+    return to_volume(s, (const float*)normals3_dev, v, k, max_distance, stats);
+}
+
+extern "C" int sdfk_points_to_volume(const sdfk_points* s, const float* normals3, sdfk_volume* v, int32_t k, float max_distance, int64_t stats[4])
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_volume(s, normals3, v, k, max_distance)) return r;
+    float* nd = nullptr;
+    int r = dev_alloc((void**)&nd, (size_t)s->n * 3 * sizeof(float));
+    hipError_t e = hipSuccess;
+    if (!r) e = hipMemcpyAsync(nd, normals3, (size_t)s->n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
+    if (!r && e == hipSuccess) r = to_volume(s, nd, v, k, max_distance, stats);
+    const hipError_t es = hipStreamSynchronize(g.stream);   // (the caller's array is not retained)
+    dev_free(nd);
+    if (r) return r;
+    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_to_volume: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    return SDFK_OK;
+}

@@ -3,7 +3,8 @@ entry points sdfk_points_* / sdfk_icp_* (include/sdfkit_hip.h, csrc/lib_points.h
 
 Vector3 is a float32 numpy array of 3; a span of Vector3 is an (n, 3) float32 array.  The search is exact (the static
 point of least d2, ties to the lowest insertion index; SearchKNearest and
-SearchRadius extend it to the k nearest and to all within a radius, in the same (d2, index) order); the structure behind it is a grid of cell lists on the device,
+SearchRadius extend it to the k nearest and to all within a radius, in the same (d2, index) order; EstimateNormals and ToVoxels
+turn the points into normals and a signed distance volume); the structure behind it is a grid of cell lists on the device,
 so the reference's tree internals -- Left, Right, SplitValue, IsLeaf -- are not provided.  SplitAxis is kept as given.
 """
 import ctypes as C
@@ -99,6 +100,50 @@ class KdTree:
         if total:
             N.check(N.lib().sdfk_points_radius_fill(self._h, _ptr(q), n, r, _ptr(off), _ptr(idx), _ptr(dist)))
         return off, idx, dist
+
+    def EstimateNormals(self, k, viewpoint=None, maxDistance=np.inf):
+        """Extension: a normal per static point from its k nearest (itself included; 3 <= k <= 64, no farther than maxDistance)
+        -> (normals (n, 3) float32, variation (n,) float32): the eigenvector of the least eigenvalue of the neighbourhood's
+        covariance and the surface variation lmin / (l0 + l1 + l2) (include/sdfkit_hip.h, "Point clouds").  A point with fewer
+        than 3 neighbours, or all of them equal, gets (0, 0, 0) and 0.
+        viewpoint: one Vector3, or one per point -- each normal is turned towards it.  Without one the component of largest
+        magnitude is made positive, which is NOT a consistent orientation of a closed surface: propagating one along a spanning
+        tree of the neighbourhood graph is out of scope here; scans know their sensor position, meshes their normals."""
+        n = self.TotalPoints
+        view = None if viewpoint is None else _points(viewpoint)
+        nrm = np.empty((n, 3), f32)
+        var = np.empty(n, f32)
+        N.check(N.lib().sdfk_points_normals(self._h, int(k), float(f32(maxDistance)), _ptr(view), 0 if view is None else len(view),
+                                            _ptr(nrm), _ptr(var)))
+        return nrm, var
+
+    def ToVoxels(self, normals, min, max, nx, ny, nz, k=8, maxDistance=np.inf, clipToBounds=False, stats=None):
+        """Extension: the point cloud with `normals` (one per static point, pointing outside) as a signed distance volume at the
+        cell centres of Voxels(min, max, nx, ny, nz): a blend of the tangent-plane distances (x - p) . n of the k nearest points
+        within maxDistance.  Voxels with no point within maxDistance get +-maxDistance, the sign carried over from the known
+        ones -- right when the band of known voxels covers a closed surface.  Give a band of a few voxels and call
+        Voxels.Redistance() on the result for a full field.  stats: a dict that receives known, unknown, candidates, queries."""
+        from .api import Voxels
+        vox = Voxels(min, max, nx, ny, nz)
+        self.SampleInto(vox, normals, k, maxDistance, stats)
+        if clipToBounds:
+            vox.ClipToBounds()
+        return vox
+
+    def SampleInto(self, voxels, normals, k=8, maxDistance=np.inf, stats=None):
+        """ToVoxels into an existing Voxels (its colours are left alone)."""
+        nrm = _points(normals)
+        if len(nrm) != self.TotalPoints:
+            raise ValueError("one normal per static point (normals)")
+        # values the host may have edited go up first: the call writes the distances only, the colours stay what they were
+        h = voxels._sync_to_device() if voxels._host_values is not None else voxels._ensure_device(voxels._has_colors)
+        st = (C.c_int64 * 4)() if stats is not None else None
+        N.check(N.lib().sdfk_points_to_volume(self._h, _ptr(nrm), h, int(k), float(f32(maxDistance)), st))
+        voxels._host_values = voxels._host_colors = None   # the device copy is now the truth
+        voxels._version += 1
+        if stats is not None:
+            stats.update(known=int(st[0]), unknown=int(st[1]), candidates=int(st[2]), queries=int(st[3]))
+        return voxels
 
     def Search(self, q):
         """KdTree.Search(q, out nearestDistance) -> (nearest, nearestDistance)."""

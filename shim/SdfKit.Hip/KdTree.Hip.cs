@@ -97,6 +97,35 @@ namespace SdfKit
             }
         }
 
+        /// <summary>Extension: a normal per static point (insertion order) from its k nearest (3..64, itself included, no farther than
+        /// maxDistance): the eigenvector of the least eigenvalue of the neighbourhood's covariance, and the surface variation
+        /// lmin / (l0 + l1 + l2).  viewpoints: empty (the largest component is made positive -- not a consistent orientation of
+        /// a closed surface, which is out of scope), one for all points, or one per point; each normal is turned towards its
+        /// viewpoint.  Degenerate neighbourhoods give (0, 0, 0) and 0.</summary>
+        public unsafe void EstimateNormals (int k, Span<Vector3> normals, Span<float> variation, ReadOnlySpan<Vector3> viewpoints = default,
+                                            float maxDistance = float.PositiveInfinity)
+        {
+            if (k < 3 || k > 64)
+                throw new ArgumentOutOfRangeException (nameof (k), "k must be in 3..64");
+            int n = TotalPoints;
+            if (normals.Length < n || variation.Length < n)
+                throw new ArgumentException ("Output spans are shorter than the static points");
+            fixed (Vector3* v = viewpoints) fixed (Vector3* o = normals) fixed (float* w = variation)
+                Native.Check (Native.sdfk_points_normals (handle, k, maxDistance, (float*)v, viewpoints.Length, (float*)o, w));
+        }
+
+        /// <summary>Extension: the static points with one outward normal each as a signed distance volume: the blend of the
+        /// tangent-plane distances of the k nearest points (1..64) within maxDistance at every cell centre; voxels farther away
+        /// get +-maxDistance, the sign carried over from the known ones.  Give a band, then Voxels.Redistance, for a full field.</summary>
+        public Voxels ToVoxels (ReadOnlySpan<Vector3> normals, Vector3 min, Vector3 max, int nx, int ny, int nz, int k = 8,
+                                float maxDistance = float.PositiveInfinity, bool clipToBounds = false)
+        {
+            var v = new Voxels (min, max, nx, ny, nz);
+            v.SamplePoints (this, normals, k, maxDistance);
+            if (clipToBounds) v.ClipToBounds ();
+            return v;
+        }
+
         public void Dispose ()
         {
             if (handle != IntPtr.Zero) {
@@ -107,5 +136,19 @@ namespace SdfKit
         }
 
         ~KdTree () => Dispose ();
+    }
+
+    public partial class Voxels
+    {
+        /// <summary>Writes the point cloud's signed distance into this volume's device twin; the colours stay what they are.</summary>
+        public unsafe void SamplePoints (KdTree points, ReadOnlySpan<Vector3> normals, int k = 8, float maxDistance = float.PositiveInfinity)
+        {
+            if (normals.Length != points.TotalPoints)
+                throw new ArgumentException ("One normal per static point", nameof (normals));
+            IntPtr v = hostMayBeNewer ? SyncToDevice () : EnsureDevice (deviceHasColors);
+            fixed (Vector3* nrm = normals)
+                Native.Check (Native.sdfk_points_to_volume (points.Handle, (float*)nrm, v, k, maxDistance, null));
+            deviceIsNewer = true; hostMayBeNewer = false;
+        }
     }
 }

@@ -107,6 +107,14 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_points_radius_fill(IntPtr points, float* queries3, long n, float radius, long* offsets, int* index, float* distance);
         [DllImport(Lib)] public static extern int sdfk_points_radius_fill_device(IntPtr points, IntPtr queries3Dev, long n, float radius, IntPtr offsetsDev,
                                                                                  IntPtr indexDev, IntPtr distanceDev);
+        // point clouds: normals and signed distance volumes (KdTree.Hip.cs)
+        [DllImport(Lib)] public static extern int sdfk_points_normals(IntPtr points, int k, float maxDistance, float* viewpoints3, long nViewpoints, float* normals3,
+                                                                      float* variation);
+        [DllImport(Lib)] public static extern int sdfk_points_normals_device(IntPtr points, int k, float maxDistance, IntPtr viewpoints3Dev, long nViewpoints,
+                                                                             IntPtr normals3Dev, IntPtr variationDev);
+        [DllImport(Lib)] public static extern int sdfk_points_to_volume(IntPtr points, float* normals3, IntPtr volume, int k, float maxDistance, long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_points_to_volume_device(IntPtr points, IntPtr normals3Dev, IntPtr volume, int k, float maxDistance,
+                                                                               long* stats4);
         [DllImport(Lib)] public static extern void sdfk_points_free(IntPtr points);
         [DllImport(Lib)] public static extern int sdfk_icp_register(IntPtr points, ref SdfkIcpParams prm, float* points3, long n, float* total16, out int iterations);
         [DllImport(Lib)] public static extern int sdfk_icp_register_device(IntPtr points, ref SdfkIcpParams prm, IntPtr points3Dev, long n, float* total16,
