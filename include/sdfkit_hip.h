@@ -651,8 +651,36 @@ int sdfk_points_to_volume_device(const sdfk_points* s, const void* normals3_dev,
  * points = Transform(points, step), total = total * step, until the step moves less than both convergence limits or
  * max_iterations steps were made.  Deviations: the reductions and the 3x3 SVD are in f64 (fixed reduction order, bitwise
  * reproducible); R, pmean and qmean are rounded to f32 and every later step is the reference's f32 Matrix4x4 arithmetic.
- * An empty dynamic set is refused (SDFK_ERR_INVALID).  sdfk_icp_register: host points, synchronous.  sdfk_icp_register_device:
- * device points; returns when the registration has finished (the host reads the iteration count). */
+ * The result is ONE function of its inputs, computed by csrc/icp_solve.h after the reductions (one rounding per written operation,
+ * + - * / and sqrt only, no contraction), restated in tests/points_model.py (register_exact) and compared bit for bit:
+ * 1. Reductions (every sum of an iteration: d; (d - mean)^2 with mean = sum / n; count, p, q of the kept points; the nine products
+ *    (p_a - pmean_a)(q_b - qmean_b) of the kept points, the f32 coordinates widened first): binary64.  Element i is added to the
+ *    accumulator (0.0 at first) of thread i % 256 of block (i / 256) % 256, i.e. in strides of 65536 taken in order of i; a point
+ *    that is not kept adds nothing.  Within a block a halving tree: s[t] += s[t + o] for t < o, o = 128, 64, ..., 1.  Then the 256
+ *    block partials, each added to a 0.0, through the same tree.
+ * 2. The filter: m = (float)mean, sd = (float)sqrt(sqsum / n); distMax = m + 3 sd when m < good, else m + 2 sd when m < 3 good, else
+ *    m + sd when m < 6 good, else (m + 0.5) + sd, all binary32 (good = good_correspondence_distance, 3 good and 6 good the f32
+ *    products); a point is kept iff dist <= distMax.  pmean = sum p / count, qmean = sum q / count.
+ * 3. The solve: W = C scaled by the power of two that brings its largest magnitude into [1, 2) (exact; without it the products
+ *    below leave binary64 for |C| beyond 2^+-256; C = 0 or non-finite: as it is), V = I.  One-sided Jacobi on the columns of W: at
+ *    most 60 sweeps, each over the pairs (i, j) = (0,1), (0,2), (1,2); al = sum_k W_ki W_ki, be = sum_k W_kj W_kj,
+ *    ga = sum_k W_ki W_kj (k ascending, from 0.0).  The pair is skipped when ga == 0 or |ga| <= 1e-15 sqrt(al be); otherwise
+ *    zeta = (be - al) / (2 ga); t = (zeta >= 0 ? 1 : -1) / (|zeta| + sqrt(1 + zeta zeta)); c = 1 / sqrt(1 + t t); s = c t; every row of
+ *    W and of V: (x_i, x_j) = (c x_i - s x_j, s x_i + c x_j).  A sweep without a rotation ends the loop.  sigma_i = sqrt((W_0i W_0i +
+ *    W_1i W_1i) + W_2i W_2i); the columns are ordered by descending sigma with a bubble sort that swaps on `<` only (equal sigma
+ *    keep their order); V's columns follow.  sigma_0 == 0 (C = 0): U = V = I.  Otherwise u_0 = w_0 / sigma_0; u_1 = w_1 / sigma_1 when
+ *    sigma_1 > 1e-12 sigma_0, else (rank 1) u_1 = (u_0 x e) / |u_0 x e|, e the unit axis on which |u_0| is least (ties: the lowest);
+ *    u_2 = u_0 x u_1.  d3 = the sign of det V (cofactors along its first row; 0 stays 0), and
+ *    R_ab = (V_a0 U_b0 + V_a1 U_b1) + (d3 V_a2) U_b2.
+ * 4. R, pmean and qmean are rounded to f32; translation, step, convergence (dtrans = the f32 length of the step's translation <=
+ *    converged_max_translation and (|1 - M11| + |1 - M22|) + |1 - M33| <= converged_max_rotation) and total are the f32 Matrix4x4
+ *    arithmetic of System.Numerics' software forms (Invert refuses |det| < 1.1920929e-07 with the all-NaN matrix).
+ * Refused with SDFK_ERR_INVALID, points and outputs untouched: an empty dynamic set; by sdfk_icp_register also a dynamic point with a
+ * NaN or infinite coordinate.  sdfk_icp_register_device does not read the points on the host and leaves them UNCHECKED: such a
+ * point's correspondence is (the first static point, FLT_MAX) under the search rule above, and the arithmetic takes its course (a
+ * single such point makes the whole transform NaN; among many it is usually filtered out).
+ * sdfk_icp_register: host points, synchronous.  sdfk_icp_register_device: device points; returns when the registration has
+ * finished (the host reads the iteration count). */
 typedef struct sdfk_icp_params {
     int32_t max_iterations;             /* MaxIterations = 100 */
     float good_correspondence_distance; /* GoodCorrespondenceDistance = 0.01 */

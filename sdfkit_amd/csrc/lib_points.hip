@@ -13,10 +13,12 @@
 // ICP: per iteration search -> sum of d, then of (d - mean)^2 -> filtered sums (count, p, q) -> centred C -> a one-lane solve (f64 SVD, the
 // reference's f32 Matrix4x4 steps, convergence, running total) -> the step applied to the points.  Every reduction is f64 in a
 // fixed order (per-block partials of a fixed grid, then one block), with no float atomics: results are bitwise reproducible.
+// Everything after the reductions (the distMax rule, the filter, the solve, the Matrix4x4 steps) is icp_solve.h, shared with the host.
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "points_grid.h"
 #include "points_set.h"
+#include "icp_solve.h"
 
 #include <cfloat>
 
@@ -293,15 +295,7 @@ __global__ __launch_bounds__(kBlock) void k_icp_dstats(IcpArgs A, int iter)
     double r[1];
     reduce_parts<1, 1>(A.S, r, s);
     if (threadIdx.x != 0) return;
-    // mean and standard deviation in f64, rounded to f32; distMax in the reference's f32 (IterativeClosestPoint.cs:101-114)
-    const double mean = A.S->dist_mean;
-    const float m = (float)mean, sd = (float)__builtin_sqrt(r[0] / (double)A.n);
-    float dmax;
-    if (m < A.good) dmax = m + 3.0f * sd;
-    else if (m < 3.0f * A.good) dmax = m + 2.0f * sd;
-    else if (m < 6.0f * A.good) dmax = m + sd;
-    else dmax = (m + 0.5f) + sd;
-    A.S->dist_max = dmax;
+    A.S->dist_max = sdfk_icp::dist_max(A.S->dist_mean, r[0], (double)A.n, A.good);   // (icp_solve.h)
 }
 
 // pass 2: count, sum p, sum q of the points with dist <= distMax
@@ -313,7 +307,7 @@ __global__ __launch_bounds__(kBlock) void k_icp_fsum(IcpArgs A, int iter)
     double v[7] = {0, 0, 0, 0, 0, 0, 0};
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
         const float4 c = A.cor[i];
-        if (c.w <= dmax) {
+        if (sdfk_icp::kept(c.w, dmax)) {
             v[0] += 1.0;
             v[1] += A.points[3 * i]; v[2] += A.points[3 * i + 1]; v[3] += A.points[3 * i + 2];
             v[4] += c.x; v[5] += c.y; v[6] += c.z;
@@ -345,7 +339,7 @@ __global__ __launch_bounds__(kBlock) void k_icp_csum(IcpArgs A, int iter)
     double v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
         const float4 c = A.cor[i];
-        if (c.w <= dmax) {
+        if (sdfk_icp::kept(c.w, dmax)) {
             const double p[3] = {A.points[3 * i] - pm0, A.points[3 * i + 1] - pm1, A.points[3 * i + 2] - pm2};
             const double q[3] = {c.x - qm0, c.y - qm1, c.z - qm2};
 #pragma unroll
@@ -359,105 +353,7 @@ __global__ __launch_bounds__(kBlock) void k_icp_csum(IcpArgs A, int iter)
         for (int j = 0; j < 9; j++) A.S->part[blockIdx.x][j] = v[j];
 }
 
-// ---- the f32 Matrix4x4 arithmetic of System.Numerics (software forms, as sdfkit_amd/raymarch.py restates them) ----
-__device__ void m4_mul(const float* a, const float* b, float* r)
-{
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++)
-            r[4 * i + j] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a[4 * i], b[j]), __fmul_rn(a[4 * i + 1], b[4 + j])),
-                                               __fmul_rn(a[4 * i + 2], b[8 + j])), __fmul_rn(a[4 * i + 3], b[12 + j]));
-}
-
-__device__ bool m4_invert(const float* s, float* R)
-{
-    const float a = s[0], b = s[1], c = s[2], d = s[3], e = s[4], f = s[5], gq = s[6], h = s[7];
-    const float i = s[8], j = s[9], k = s[10], l = s[11], m = s[12], n = s[13], o = s[14], p = s[15];
-    const float kp_lo = k * p - l * o, jp_ln = j * p - l * n, jo_kn = j * o - k * n, ip_lm = i * p - l * m, io_km = i * o - k * m, in_jm = i * n - j * m;
-    const float a11 = +(f * kp_lo - gq * jp_ln + h * jo_kn), a12 = -(e * kp_lo - gq * ip_lm + h * io_km);
-    const float a13 = +(e * jp_ln - f * ip_lm + h * in_jm), a14 = -(e * jo_kn - f * io_km + gq * in_jm);
-    const float det = a * a11 + b * a12 + c * a13 + d * a14;
-    if (fabsf(det) < 1.1920929e-07f) {
-        for (int q = 0; q < 16; q++) R[q] = __int_as_float(0x7fc00000);
-        return false;
-    }
-    const float inv = 1.0f / det;
-    R[0] = a11 * inv; R[4] = a12 * inv; R[8] = a13 * inv; R[12] = a14 * inv;
-    R[1] = -(b * kp_lo - c * jp_ln + d * jo_kn) * inv; R[5] = +(a * kp_lo - c * ip_lm + d * io_km) * inv;
-    R[9] = -(a * jp_ln - b * ip_lm + d * in_jm) * inv; R[13] = +(a * jo_kn - b * io_km + c * in_jm) * inv;
-    const float gp_ho = gq * p - h * o, fp_hn = f * p - h * n, fo_gn = f * o - gq * n, ep_hm = e * p - h * m, eo_gm = e * o - gq * m, en_fm = e * n - f * m;
-    R[2] = +(b * gp_ho - c * fp_hn + d * fo_gn) * inv; R[6] = -(a * gp_ho - c * ep_hm + d * eo_gm) * inv;
-    R[10] = +(a * fp_hn - b * ep_hm + d * en_fm) * inv; R[14] = -(a * fo_gn - b * eo_gm + c * en_fm) * inv;
-    const float gl_hk = gq * l - h * k, fl_hj = f * l - h * j, fk_gj = f * k - gq * j, el_hi = e * l - h * i, ek_gi = e * k - gq * i, ej_fi = e * j - f * i;
-    R[3] = -(b * gl_hk - c * fl_hj + d * fk_gj) * inv; R[7] = +(a * gl_hk - c * el_hi + d * ek_gi) * inv;
-    R[11] = -(a * fl_hj - b * el_hi + d * ej_fi) * inv; R[15] = +(a * fk_gj - b * ek_gi + c * ej_fi) * inv;
-    return true;
-}
-
-// C = U S V^T (f64, one-sided Jacobi on the columns of C); returns R = V diag(1, 1, sign det(V U^T)) U^T.  U and V are
-// orthogonal whatever the rank: u3 = u1 x u2 (R does not depend on the sign of u3: det(V U^T) flips with it), and u2 is
-// completed with a cross product when sigma2 vanishes.
-__device__ void kabsch_r(const double C[9], double R[9])
-{
-    double W[3][3], V[3][3];   // W = C V, columns orthogonalised
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) { W[a][b] = C[3 * a + b]; V[a][b] = a == b ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < 60; sweep++) {
-        bool rotated = false;
-        for (int i = 0; i < 2; i++)
-            for (int j = i + 1; j < 3; j++) {
-                double al = 0, be = 0, ga = 0;
-                for (int k = 0; k < 3; k++) { al += W[k][i] * W[k][i]; be += W[k][j] * W[k][j]; ga += W[k][i] * W[k][j]; }
-                if (ga == 0.0 || fabs(ga) <= 1e-15 * __builtin_sqrt(al * be)) continue;
-                rotated = true;
-                const double zeta = (be - al) / (2.0 * ga);
-                const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + __builtin_sqrt(1.0 + zeta * zeta));
-                const double cs = 1.0 / __builtin_sqrt(1.0 + t * t), sn = cs * t;
-                for (int k = 0; k < 3; k++) {
-                    const double wi = W[k][i], wj = W[k][j];
-                    W[k][i] = cs * wi - sn * wj; W[k][j] = sn * wi + cs * wj;
-                    const double vi = V[k][i], vj = V[k][j];
-                    V[k][i] = cs * vi - sn * vj; V[k][j] = sn * vi + cs * vj;
-                }
-            }
-        if (!rotated) break;
-    }
-    double sg[3];
-    int ord[3] = {0, 1, 2};
-    for (int i = 0; i < 3; i++) sg[i] = __builtin_sqrt(W[0][i] * W[0][i] + W[1][i] * W[1][i] + W[2][i] * W[2][i]);
-    for (int i = 0; i < 2; i++)   // descending singular values
-        for (int j = 0; j < 2 - i; j++)
-            if (sg[ord[j]] < sg[ord[j + 1]]) { const int t = ord[j]; ord[j] = ord[j + 1]; ord[j + 1] = t; }
-    double U[3][3], Vs[3][3];
-    for (int i = 0; i < 3; i++)
-        for (int k = 0; k < 3; k++) Vs[k][i] = V[k][ord[i]];
-    const double s0 = sg[ord[0]], s1 = sg[ord[1]];
-    if (s0 == 0.0) {   // C = 0: U = V = I
-        for (int a = 0; a < 3; a++)
-            for (int b = 0; b < 3; b++) { U[a][b] = a == b; Vs[a][b] = a == b; }
-    } else {
-        for (int k = 0; k < 3; k++) U[k][0] = W[k][ord[0]] / s0;
-        if (s1 > 1e-12 * s0) {
-            for (int k = 0; k < 3; k++) U[k][1] = W[k][ord[1]] / s1;
-        } else {   // any unit vector orthogonal to u1
-            const double ax = fabs(U[0][0]), ay = fabs(U[1][0]), az = fabs(U[2][0]);
-            double e[3] = {0, 0, 0};
-            e[ax <= ay && ax <= az ? 0 : (ay <= az ? 1 : 2)] = 1.0;
-            double w[3] = {U[1][0] * e[2] - U[2][0] * e[1], U[2][0] * e[0] - U[0][0] * e[2], U[0][0] * e[1] - U[1][0] * e[0]};
-            const double l = __builtin_sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-            for (int k = 0; k < 3; k++) U[k][1] = w[k] / l;
-        }
-        U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-        U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-        U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-    }
-    // sign det(V U^T) = sign det V * det U, det U = +1 by construction
-    const double detv = Vs[0][0] * (Vs[1][1] * Vs[2][2] - Vs[1][2] * Vs[2][1]) - Vs[0][1] * (Vs[1][0] * Vs[2][2] - Vs[1][2] * Vs[2][0]) +
-                        Vs[0][2] * (Vs[1][0] * Vs[2][1] - Vs[1][1] * Vs[2][0]);
-    const double d3 = detv > 0 ? 1.0 : (detv < 0 ? -1.0 : 0.0);
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) R[3 * a + b] = Vs[a][0] * U[b][0] + Vs[a][1] * U[b][1] + d3 * Vs[a][2] * U[b][2];
-}
-
+// the solve (icp_solve.h) on one lane: the f64 SVD, the reference's f32 Matrix4x4 steps, convergence, the running total
 __global__ __launch_bounds__(kBlock) void k_icp_solve(IcpArgs A, int iter)
 {
     if (icp_stopped(A.S, iter)) return;
@@ -466,27 +362,9 @@ __global__ __launch_bounds__(kBlock) void k_icp_solve(IcpArgs A, int iter)
     reduce_parts<9>(A.S, Cs, s);
     if (threadIdx.x != 0) return;
     IcpState* S = A.S;
-    double Rd[9];
-    kabsch_r(Cs, Rd);
-    float rm[16] = {(float)Rd[0], (float)Rd[1], (float)Rd[2], 0, (float)Rd[3], (float)Rd[4], (float)Rd[5], 0,
-                    (float)Rd[6], (float)Rd[7], (float)Rd[8], 0, 0, 0, 0, 1};
-    const float pm[3] = {(float)S->pmean[0], (float)S->pmean[1], (float)S->pmean[2]};
-    const float qm[3] = {(float)S->qmean[0], (float)S->qmean[1], (float)S->qmean[2]};
-    float inv_r[16], tm[16], xf[16], step[16], tot[16];
-    m4_invert(rm, inv_r);
-    float tr[3];
-    for (int j = 0; j < 3; j++)   // Vector3.Transform(pmean, invR) - qmean
-        tr[j] = __fsub_rn(__fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(pm[0], inv_r[j]), __fmul_rn(pm[1], inv_r[4 + j])), __fmul_rn(pm[2], inv_r[8 + j])),
-                                    inv_r[12 + j]), qm[j]);
-    for (int q = 0; q < 16; q++) tm[q] = (q % 5 == 0) ? 1.0f : 0.0f;
-    tm[12] = tr[0]; tm[13] = tr[1]; tm[14] = tr[2];
-    m4_mul(rm, tm, xf);
-    m4_invert(xf, step);
-    // convergence on the step (IterativeClosestPoint.cs:66-69) and total = total * step (:72)
-    const float drot = __fadd_rn(__fadd_rn(fabsf(__fsub_rn(1.0f, step[0])), fabsf(__fsub_rn(1.0f, step[5]))), fabsf(__fsub_rn(1.0f, step[10])));
-    const float dtrans = (float)__builtin_sqrt((double)__fadd_rn(__fadd_rn(__fmul_rn(step[12], step[12]), __fmul_rn(step[13], step[13])), __fmul_rn(step[14], step[14])));   // Vector3.Length
-    const bool conv = dtrans <= A.conv_t && drot <= A.conv_r;
-    m4_mul(S->total, step, tot);
+    float step[16], tot[16];
+    bool conv;
+    sdfk_icp::solve_step(Cs, S->pmean, S->qmean, S->total, A.conv_t, A.conv_r, step, tot, &conv);
     for (int q = 0; q < 16; q++) { S->step[q] = step[q]; S->total[q] = tot[q]; }
     S->iters = iter + 1;
     S->converged = conv;
@@ -856,6 +734,8 @@ extern "C" int sdfk_icp_register(sdfk_points* s, const sdfk_icp_params* prm, flo
     StateScope in_owner_context(s ? s->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (int r = icp_check(s, prm, points3, n, total, iterations)) return r;
+    for (int64_t i = 0; i < 3 * n; i++)   // (as static sets are: nothing is touched)
+        if (!std::isfinite(points3[i])) return fail(SDFK_ERR_INVALID, "sdfk_icp_register: dynamic point %lld has a NaN or infinite coordinate", (long long)(i / 3));
     float* pd = nullptr;
     int r = dev_alloc((void**)&pd, (size_t)n * 3 * sizeof(float));
     hipError_t e = hipSuccess;

@@ -1,7 +1,8 @@
 // IterativeClosestPoint.Hip.cs -- SdfKit.IterativeClosestPoint over sdfk_icp_register (include/sdfkit_hip.h).  Replaces
 // SdfKit/IterativeClosestPoint.cs with the same public members (IterativeClosestPoint.cs:10-240).  Each iteration is the
 // reference's; the reductions and the 3x3 SVD are f64 on the GPU instead of MathNet's float SVD (a stated deviation), every
-// later step is the reference's float Matrix4x4 arithmetic.  An empty dynamic set is refused (the reference returns NaN).
+// later step is the reference's float Matrix4x4 arithmetic.  An empty dynamic set is refused (the reference returns NaN),
+// and so is a dynamic point with a NaN or infinite coordinate (the native call checks host points; device points are unchecked).
 // UNCOMPILED HERE (no .NET in the build image); sdfkit_amd/points.py's IterativeClosestPoint is the same layer, tested.
 using System;
 using System.Linq;
