@@ -325,23 +325,6 @@ struct Columns {
     float mx, my, dx, dy;   // column (i, j) is at (mx + i dx, my + j dy)
 };
 
-__device__ __forceinline__ float col_coord(float m, int i, float d) { return m + (float)i * d; }
-
-// The columns i whose coordinate lies in [lo, hi]: [*i0, *i1] (empty when *i0 > *i1).  An estimate, then exact steps along the
-// monotone coordinate sequence.
-__device__ __forceinline__ void col_range(float lo, float hi, float m, float d, int n, int* i0, int* i1)
-{
-    if (!(d > 0.0f) || !isfinite(d)) { *i0 = 0; *i1 = n - 1; return; }
-    double e0 = floor(((double)lo - (double)m) / (double)d), e1 = ceil(((double)hi - (double)m) / (double)d);
-    int a = (int)fmin(fmax(e0, 0.0), (double)n), b = (int)fmin(fmax(e1, -1.0), (double)(n - 1));
-    while (a > 0 && col_coord(m, a - 1, d) >= lo) a--;
-    while (a < n && col_coord(m, a, d) < lo) a++;
-    while (b < n - 1 && col_coord(m, b + 1, d) <= hi) b++;
-    while (b >= 0 && col_coord(m, b, d) > hi) b--;
-    *i0 = a;
-    *i1 = b;
-}
-
 // per triangle: its column box and item count (0 for a zero projected area)
 __global__ __launch_bounds__(kBlock) void k_tm_items(const TriPack* __restrict__ tri, int64_t nt, Columns Q, int4* __restrict__ box,
                                                      unsigned long long* __restrict__ items)

@@ -1,8 +1,10 @@
 // trimesh_sdf.h -- the arithmetic of lib_trimesh.hip (signed distance volumes from triangle meshes): the binary64 closest point
 // on a triangle, the exact orientation sign of three f32 points in the xy plane with its symbolic perturbation, the column
-// inside test and the z of a crossing.  Plain C++ outside hipcc, so that tests/cpp/trimesh_sdf_host.cpp runs exactly the code
-// the kernels run.  Compiled with -ffp-contract=off everywhere: no expression below may be fused.
+// inside test, the z of a crossing and the columns of a volume that an interval covers.  Plain C++ outside hipcc, so that
+// tests/cpp/trimesh_sdf_host.cpp runs exactly the code the kernels run.  Compiled with -ffp-contract=off everywhere: no
+// expression below may be fused.
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -196,6 +198,25 @@ SDFK_TRI_HD inline double z_cross(const float a[3], const float b[3], const floa
     const double s = (wa + wb) + wc;
     if (!(s > 0.0)) return (double)a[2];
     return (((wa * (double)a[2]) + (wb * (double)b[2])) + (wc * (double)c[2])) / s;
+}
+
+// ---- the columns of a volume ----------------------------------------------------------------------------------------------
+// column / plane i of an axis that starts at m with spacing d (f32, as the volume's cell centres are computed)
+SDFK_TRI_HD inline float col_coord(float m, int i, float d) { return m + (float)i * d; }
+
+// The columns i whose coordinate lies in [lo, hi]: [*i0, *i1] (empty when *i0 > *i1).  An estimate, then exact steps along the
+// monotone coordinate sequence.  A spacing that is not positive and finite gives the whole range [0, n - 1].
+SDFK_TRI_HD inline void col_range(float lo, float hi, float m, float d, int n, int* i0, int* i1)
+{
+    if (!(d > 0.0f) || !std::isfinite(d)) { *i0 = 0; *i1 = n - 1; return; }
+    double e0 = std::floor(((double)lo - (double)m) / (double)d), e1 = std::ceil(((double)hi - (double)m) / (double)d);
+    int a = (int)std::fmin(std::fmax(e0, 0.0), (double)n), b = (int)std::fmin(std::fmax(e1, -1.0), (double)(n - 1));
+    while (a > 0 && col_coord(m, a - 1, d) >= lo) a--;
+    while (a < n && col_coord(m, a, d) < lo) a++;
+    while (b < n - 1 && col_coord(m, b + 1, d) <= hi) b++;
+    while (b >= 0 && col_coord(m, b, d) > hi) b--;
+    *i0 = a;
+    *i1 = b;
 }
 
 // The f32 colour blend: weights rounded to f32, (ca wa + cb wb) + cc wc per channel.

@@ -4,6 +4,7 @@
 //   trimesh_sdf_host closest IN OUT   IN: n x 12 float32 (p, a, b, c)     OUT: n x 7 float64 (d2, cp[3], w[3])
 //   trimesh_sdf_host orient IN OUT    IN: n x 6 float32 (a, b, p in xy)   OUT: n x 2 int32 (exact sign, perturbed sign)
 //   trimesh_sdf_host column IN OUT    IN: n x 11 float32 (a, b, c, px, py) OUT: n x 2 float64 (area * 2 + inside, z_cross)
+//   trimesh_sdf_host colrange IN OUT  IN: n x 5 float32 (lo, hi, m, d, count) OUT: n x 2 int32 (i0, i1 of col_range)
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -26,7 +27,7 @@ static std::vector<T> read_all(const char* path)
 
 int main(int argc, char** argv)
 {
-    if (argc != 4) { fprintf(stderr, "usage: %s closest|orient|column IN OUT\n", argv[0]); return 2; }
+    if (argc != 4) { fprintf(stderr, "usage: %s closest|orient|column|colrange IN OUT\n", argv[0]); return 2; }
     const std::vector<float> in = read_all<float>(argv[2]);
     FILE* out = fopen(argv[3], "wb");
     if (!out) return 2;
@@ -50,6 +51,12 @@ int main(int argc, char** argv)
             const int area = projected_area_sign(a, b, c);
             const bool inside = area != 0 && column_inside(a, b, c, area, in[i + 9], in[i + 10]);
             const double o[2] = {(double)(area * 2 + (inside ? 1 : 0)), area != 0 ? z_cross(a, b, c, area, in[i + 9], in[i + 10]) : 0.0};
+            fwrite(o, sizeof o, 1, out);
+        }
+    } else if (!strcmp(argv[1], "colrange")) {
+        for (size_t i = 0; i + 5 <= in.size(); i += 5) {
+            int32_t o[2];
+            col_range(in[i], in[i + 1], in[i + 2], in[i + 3], (int)in[i + 4], &o[0], &o[1]);
             fwrite(o, sizeof o, 1, out);
         }
     } else {

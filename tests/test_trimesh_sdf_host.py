@@ -1,7 +1,8 @@
 """CPU check of the triangle-mesh distance arithmetic (sdfkit_amd/csrc/trimesh_sdf.h, the functions the kernels call, built with
 g++ -ffp-contract=off by tests/cpp/trimesh_sdf_host.cpp) against the numpy model (tests/meshsdf_model.py), bit for bit: the
 binary64 closest point on random, needle, collinear, coincident-vertex and zero-area triangles with queries at vertices, on edges
-and on faces; exact orient2d signs on near-degenerate inputs; the perturbed column test and z_cross."""
+and on faces; exact orient2d signs on near-degenerate inputs; the perturbed column test and z_cross; col_range against every
+coordinate of the axis."""
 import os
 import subprocess
 
@@ -156,3 +157,60 @@ def test_header_counts_each_lattice_column_once_per_sheet(host_exe, tmp_path):
         covered = (got[:, 0].astype(int) & 1).reshape(len(tris), len(cols)).sum(0)
         inside = (cols[:, 0] >= 0) & (cols[:, 0] < 2) & (cols[:, 1] >= 0) & (cols[:, 1] < 2)
         assert np.array_equal(covered, inside.astype(int)), name
+
+
+def _colrange_cases(rng):
+    """Rows (lo, hi, m, d, n).  The coordinates of an axis are m + f32(i) * d, i in [0, n)."""
+    rows = []
+
+    def axis(m, d, n):
+        return f32(m) + np.arange(n, dtype=f32) * f32(d)
+
+    for m, d, n in ((-1.0, 0.0625, 32), (-0.97, 0.031, 96), (0.3, 0.7, 5), (1e6, 0.37, 400), (-3e6, 1.5, 64),
+                    (1e6, 1e-3, 2000), (4096.0, 2.0 ** -13, 3000), (65536.0, 1e-4, 257)):   # (the last three: neighbours repeat)
+        xs = axis(m, d, n)
+        span = float(xs[-1]) - float(xs[0])
+        lo = rng.uniform(xs[0] - 0.2 * span, xs[-1] + 0.2 * span, 40)
+        hi = lo + rng.uniform(0, 0.5 * span, 40) * rng.integers(0, 2, 40)        # (half of them lo == hi)
+        rows += [(a, b, m, d, n) for a, b in zip(lo, hi)]
+        pick = xs[rng.integers(0, n, 30)]                                          # exactly on a coordinate
+        rows += [(a, a, m, d, n) for a in pick[:10]]
+        rows += [(a, xs[-1], m, d, n) for a in pick[10:20]] + [(xs[0], a, m, d, n) for a in pick[20:]]
+        rows += [(np.nextafter(a, f32(np.inf)), np.nextafter(b, f32(-np.inf)), m, d, n) for a, b in zip(pick[:10], pick[10:20])]
+        rows += [(xs[0] - 3 * span - 1, xs[0] - span - 1, m, d, n), (xs[-1] + span + 1, xs[-1] + 3 * span + 1, m, d, n),   # left, right
+                 (np.nextafter(xs[0], f32(-np.inf)), np.nextafter(xs[0], f32(-np.inf)), m, d, n), (xs[0] - 1, xs[-1] + 1, m, d, n)]
+        k = n // 2                                                                 # strictly between two columns
+        if xs[k + 1] > np.nextafter(xs[k], f32(np.inf)):
+            rows.append((np.nextafter(xs[k], f32(np.inf)), np.nextafter(xs[k + 1], f32(-np.inf)), m, d, n))
+    for m, d in ((0.25, 0.5), (-7.0, 0.0), (1e6, 3.0), (2.0, -0.5), (2.0, np.inf), (1e6, 0.0), (0.0, -np.inf), (1.0, np.nan)):
+        rows += [(m - 1, m + 1, m, d, 1), (m, m, m, d, 1), (m + 1, m + 2, m, d, 1), (m - 2, m - 1, m, d, 1), (m - 1, m + 1, m, d, 7)]
+    return np.array(rows, np.float64).astype(f32)
+
+
+def test_col_range_matches_every_coordinate(host_exe, tmp_path):
+    """col_range (the columns a triangle's xy box is tested against) against the plain statement: compute all n coordinates
+    m + f32(i) * d in f32; [i0, i1] is the first and the last index whose coordinate lies in [lo, hi].  An empty interval comes
+    back as i0 > i1, at the position the monotone sequence gives: i0 = #(coordinates < lo), i1 = #(coordinates <= hi) - 1.
+    A spacing that is zero, negative, infinite or NaN gives the whole range, as the header states."""
+    rows = _colrange_cases(np.random.default_rng(23))
+    got = _run(host_exe, "colrange", rows, tmp_path, np.int32, 2)
+    assert len(got) == len(rows)
+    kinds = {"empty": 0, "whole": 0, "repeats": 0, "on_coordinate": 0}
+    for (lo, hi, m, d, nf), (i0, i1) in zip(rows, got):
+        n = int(nf)
+        if not (d > 0) or not np.isfinite(d):
+            assert (i0, i1) == (0, n - 1), (lo, hi, m, d, n, i0, i1)
+            kinds["whole"] += 1
+            continue
+        xs = f32(m) + np.arange(n, dtype=f32) * f32(d)
+        assert np.all(np.diff(xs) >= 0)
+        inside = np.nonzero((xs >= lo) & (xs <= hi))[0]
+        if len(inside):
+            assert (i0, i1) == (inside[0], inside[-1]), (lo, hi, m, d, n, i0, i1, inside[0], inside[-1])
+            kinds["on_coordinate"] += int(xs[i0] == lo or xs[i1] == hi)
+            kinds["repeats"] += int(np.any(np.diff(xs[i0:i1 + 1]) == 0))
+        else:
+            assert i0 > i1, (lo, hi, m, d, n, i0, i1)
+            kinds["empty"] += 1
+        assert (i0, i1) == (np.count_nonzero(xs < lo), np.count_nonzero(xs <= hi) - 1), (lo, hi, m, d, n, i0, i1)
+    assert min(kinds.values()) >= 20, kinds
