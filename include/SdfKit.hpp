@@ -843,14 +843,62 @@ public:
         tree_.reset(new KdTree(staticPoints[0]));
         for (size_t i = 1; i < staticPoints.size(); i++) tree_->AddPoints(staticPoints[i]);
     }
-    void AddStaticPoints(const std::vector<Vector3>& staticPoints) { tree_->AddPoints(staticPoints); }
+    // Extension (sdfkit_hip.h, "point to plane"): one normal per static point, e.g. StaticTree().EstimateNormals(k).Normal.  With normals
+    // set, RegisterPoints minimises the distances to the tangent planes at the nearest static points; their orientation does not
+    // matter, and a point whose normal is (0, 0, 0) takes no part.
+    enum class Metric { Auto, Point, Plane };   // Auto: Plane iff normals are set
+    struct PlaneStats {
+        bool Valid = false;        // false after a point-to-point registration
+        int64_t Kept = 0;          // kept correspondences of the last iteration
+        double SumR2 = 0.0;        // sum of their squared plane distances before the step
+        bool Converged = false;
+        int Retained = 0;          // eigenvalues of the normal equations the solve retained (6: every direction observed)
+    };
+    PlaneStats LastStats;
+    bool HasStaticNormals() const { return hasNormals_; }
+    const std::vector<Vector3>& StaticNormals() const { return normals_; }
+    void SetStaticNormals(const std::vector<Vector3>& normals)
+    {
+        if ((int64_t)normals.size() != (int64_t)tree_->TotalPoints()) throw std::invalid_argument("one normal per static point (StaticNormals)");
+        normals_ = normals;
+        hasNormals_ = true;
+    }
+    void ClearStaticNormals() { normals_.clear(); hasNormals_ = false; }
+    KdTree& StaticTree() { return *tree_; }
+
+    void AddStaticPoints(const std::vector<Vector3>& staticPoints)
+    {
+        if (hasNormals_) throw std::invalid_argument("AddStaticPoints would leave StaticNormals out of step: pass the new points' normals");
+        tree_->AddPoints(staticPoints);
+    }
+    void AddStaticPoints(const std::vector<Vector3>& staticPoints, const std::vector<Vector3>& normals)
+    {
+        if (!hasNormals_) throw std::invalid_argument("AddStaticPoints with normals: set StaticNormals first");
+        if (normals.size() != staticPoints.size()) throw std::invalid_argument("one normal per added point (normals)");
+        tree_->AddPoints(staticPoints);
+        normals_.insert(normals_.end(), normals.begin(), normals.end());
+    }
     // Rigidly moves `points` (in place) onto the static points; returns the transform that did it.
-    Matrix4x4 RegisterPoints(std::vector<Vector3>& points)
+    Matrix4x4 RegisterPoints(std::vector<Vector3>& points, Metric metric = Metric::Auto)
     {
         const sdfk_icp_params prm{MaxIterations, GoodCorrespondenceDistance, ConvergedMaximumTranslation, ConvergedMaximumRotation};
         Matrix4x4 total;
         int32_t iters = 0;
-        Check(sdfk_icp_register(tree_->Handle(), &prm, reinterpret_cast<float*>(points.data()), (int64_t)points.size(), &total.M[0][0], &iters));
+        if (metric == Metric::Plane && !hasNormals_) throw std::invalid_argument("Metric::Plane needs StaticNormals");
+        LastStats = PlaneStats();
+        if (metric == Metric::Plane || (metric == Metric::Auto && hasNormals_)) {
+            if ((int64_t)normals_.size() != (int64_t)tree_->TotalPoints()) throw std::invalid_argument("StaticNormals is out of step with the static points");
+            int64_t st[4] = {0, 0, 0, 0};
+            Check(sdfk_icp_register_plane(tree_->Handle(), &prm, reinterpret_cast<const float*>(normals_.data()), reinterpret_cast<float*>(points.data()),
+                                          (int64_t)points.size(), &total.M[0][0], &iters, st));
+            LastStats.Valid = true;
+            LastStats.Kept = st[0];
+            std::memcpy(&LastStats.SumR2, &st[1], sizeof(double));
+            LastStats.Converged = st[2] != 0;
+            LastStats.Retained = (int)st[3];
+        } else {
+            Check(sdfk_icp_register(tree_->Handle(), &prm, reinterpret_cast<float*>(points.data()), (int64_t)points.size(), &total.M[0][0], &iters));
+        }
         Iterations = iters;
         return total;
     }
@@ -877,6 +925,8 @@ public:
 
 private:
     std::unique_ptr<KdTree> tree_;
+    std::vector<Vector3> normals_;
+    bool hasNormals_ = false;
 };
 
 inline void WriteTgaHeader(std::ostream& w, int imageType, int width, int height, int bpp)

@@ -690,6 +690,50 @@ typedef struct sdfk_icp_params {
 int sdfk_icp_register(sdfk_points* s, const sdfk_icp_params* prm, float* points3, int64_t n, float total[16], int32_t* iterations);
 int sdfk_icp_register_device(sdfk_points* s, const sdfk_icp_params* prm, void* points3_dev, int64_t n, float total[16],
                              int32_t* iterations);
+/* IterativeClosestPoint.RegisterPoints, point to plane (an extension: the reference has the point-to-point step only).  The same
+ * registration with a second metric: each iteration minimises the squared distances of the kept points to the TANGENT PLANES at
+ * their nearest static points, which needs one normal per static point (normals3, in insertion order, from sdfk_points_normals or
+ * from the caller; their orientation does not matter: the residual is squared, so a flipped normal changes nothing).  Where the
+ * static cloud samples a surface and the dynamic points lie between its samples this converges in a few iterations where the
+ * point-to-point step stalls.  prm and its defaults, the search, the filter, the stop rule, `total` and the moved points are those of
+ * sdfk_icp_register; so is the result: ONE function of its inputs, computed by csrc/icp_solve.h after the reductions, restated in
+ * tests/icp_plane_model.py (register_plane_exact) and compared bit for bit.  One iteration:
+ * 1. Search and filter as above (steps 1 and 2 of sdfk_icp_register; the distance statistics run over all n points).  A point is
+ *    kept iff dist <= distMax, it has a correspondence (index >= 0: the unchecked device form's non-finite points have none) and
+ *    the static normal there is not exactly (0, 0, 0) (either sign of zero) -- sdfk_points_normals' degenerate result.
+ * 2. count and pmean over the kept points: f64 sums by reduction rule 1, pmean = sum / count.  (No kept point: 0 / 0, and the NaN
+ *    takes its course through T into total and the points.)
+ * 3. The normal equations, binary64 from the f32 inputs widened first, one rounding per written operation, no contraction.  Per kept
+ *    point, q its static point and n the normal there: d = p - pmean; c = (d1 n2 - d2 n1, d2 n0 - d0 n2, d0 n1 - d1 n0);
+ *    J = (c0, c1, c2, n0, n1, n2); r = ((p0 - q0) n0 + (p1 - q1) n1) + (p2 - q2) n2.  The 21 products J_a J_b (a <= b), the 6
+ *    products J_a r and r r are each reduced on their own by reduction rule 1: A (symmetric 6x6), b, and the sum of r^2.
+ * 4. A x = -b.  Cyclic Jacobi on A, V = I at first: kSweeps6 = 8 sweeps, each over the pairs (p, q), p < q, in the order (0,1),
+ *    (0,2), ..., (0,5), (1,2), ..., (4,5).  A pair whose a_pq is exactly 0 is skipped; otherwise theta = (a_qq - a_pp) / (2 a_pq);
+ *    t = 1 / (|theta| + sqrt(theta theta + 1)), negated when theta < 0; c = 1 / sqrt(t t + 1); s = t c; a_pp' = a_pp - t a_pq;
+ *    a_qq' = a_qq + t a_pq; a_pq' = 0; for every other index r, ascending: a_rp' = c a_rp - s a_rq, a_rq' = s a_rp + c a_rq; for
+ *    every row k of V: v_kp' = c v_kp - s v_kq, v_kq' = s v_kp + c v_kq.  lambda = the diagonal, lambda_max its largest entry.  When
+ *    lambda_max is not a positive finite number, x = 0 and nothing is retained.  Otherwise, for k = 0 .. 5 in order, the eigenpairs
+ *    with lambda_k > kPlaneTau lambda_max (kPlaneTau = 1e-12, the product rounded once) are retained: dot = 0.0, dot += v_ak (-b_a)
+ *    for a = 0 .. 5; coef = dot / lambda_k; x_a += v_ak coef (x = 0.0 at first).  Directions the kept correspondences do not observe
+ *    (a plane leaves two translations and a rotation free, a sphere three rotations) get no step.
+ * 5. The step.  w_a = x_a / 2 (a < 3); ww = (w0 w0 + w1 w1) + w2 w2; Cayley's rotation R = ((1 - ww) I + 2 w w^T + 2 [w]x) / (1 + ww),
+ *    entry by entry R_aa = ((1 - ww) + 2 (w_a w_a)) / (1 + ww), R_01 = (2 (w0 w1) - 2 w2) / (1 + ww), R_10 = (2 (w0 w1) + 2 w2) / (1 + ww),
+ *    R_02 = (2 (w0 w2) + 2 w1) / .., R_20 = (2 (w0 w2) - 2 w1) / .., R_12 = (2 (w1 w2) - 2 w0) / .., R_21 = (2 (w1 w2) + 2 w0) / ..;
+ *    T_a = (pmean_a + x_{3+a}) - ((R_a0 pmean_0 + R_a1 pmean_1) + R_a2 pmean_2).  R and T are rounded to f32; step is the row-vector
+ *    Matrix4x4 with R^T in its upper 3x3 and T in its fourth row (Transform(p, step) = R p + T).  Convergence on the step,
+ *    total = total * step and the move of the points are the f32 arithmetic of sdfk_icp_register, step 4.  Cayley's rotation turns by
+ *    2 atan(|x| / 2) where the linearisation says |x|: they differ at third order in the angle, which the next iteration removes.
+ * stats (int64[4], may be NULL), of the last iteration run (no iteration: zeros): [0] the kept count; [1] the bits of the f64 sum of
+ * r^2 over the kept points before the step; [2] 1 if converged; [3] the number of retained eigenvalues.
+ * Refused with SDFK_ERR_INVALID, points and outputs untouched: NULL normals, n == 0, a negative max_iterations; by
+ * sdfk_icp_register_plane also a dynamic point or a normal with a NaN or infinite component.  sdfk_icp_register_plane_device reads
+ * neither on the host and leaves them UNCHECKED.  normals3 holds one normal per static point of s AT THE TIME OF THE CALL.
+ * sdfk_icp_register_plane: host arrays, synchronous.  sdfk_icp_register_plane_device: device arrays; returns when the registration
+ * has finished. */
+int sdfk_icp_register_plane(sdfk_points* s, const sdfk_icp_params* prm, const float* normals3, float* points3, int64_t n, float total[16],
+                            int32_t* iterations, int64_t stats[4]);
+int sdfk_icp_register_plane_device(sdfk_points* s, const sdfk_icp_params* prm, const void* normals3_dev, void* points3_dev, int64_t n,
+                                   float total[16], int32_t* iterations, int64_t stats[4]);
 
 /* ---- Triangle-mesh distance (Mesh -> Voxels) ------------------------------------------------------------------------------
  * A triangle mesh as a signed distance field.  `triangles` holds n_indices int32 vertex indices, three per triangle; colors3

@@ -144,6 +144,8 @@ SIGNATURES = {
     "sdfk_volume_redistance": (C.c_int, [_vp, _vp, C.c_float, C.c_float, C.POINTER(_i64)]),
     "sdfk_icp_register": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),
     "sdfk_icp_register_device": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),
+    "sdfk_icp_register_plane": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _fp, C.POINTER(_i32), C.POINTER(_i64)]),
+    "sdfk_icp_register_plane_device": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _fp, C.POINTER(_i32), C.POINTER(_i64)]),
     "sdfk_profile_count": (C.c_int, []),
     "sdfk_profile_get": (C.c_int, [_i32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_i64)]),
 }

@@ -195,3 +195,172 @@ SDFK_ICP_HD void solve_step(const double C[9], const double pmean[3], const doub
 }
 
 }  // namespace sdfk_icp
+
+// ---- point to plane ------------------------------------------------------------------------------------------------------------
+// The second metric (contract: include/sdfkit_hip.h, "IterativeClosestPoint.RegisterPoints, point to plane"): the distance to the
+// tangent plane at the nearest static point is minimised.  With R = I + [omega]x about the kept points' mean and a translation t,
+// the residual of a kept point is r + J . (omega, t), J = (d x n, n), d = p - pmean, r = (p - q) . n; the kernels reduce
+// A = sum J J^T and b = sum J r, and everything after that is here.  tests/cpp/icp_plane_host.cpp checks it on the host and
+// tests/icp_plane_model.py restates it in numpy.  Binary64 throughout, one rounding per written operation.
+namespace sdfk_icp {
+
+constexpr int kSweeps6 = 8;            // cyclic Jacobi sweeps on the 6x6, fixed (x stops changing after 6, rarely 7)
+constexpr double kPlaneTau = 1e-12;    // eigenvalues at or below kPlaneTau * lambda_max are unobserved directions: no step along them
+
+// a correspondence takes part iff it exists, passes the distance filter and its static normal is not (0, 0, 0)
+SDFK_ICP_HD bool kept_plane(int index, float dist, float dmax, const float n[3])
+{
+    return index >= 0 && kept(dist, dmax) && !(n[0] == 0.0f && n[1] == 0.0f && n[2] == 0.0f);
+}
+
+// one kept point: the row J and the residual r
+SDFK_ICP_HD void plane_row(const float p[3], const float q[3], const float n[3], const double pmean[3], double J[6], double* r)
+{
+    const double p0 = (double)p[0], p1 = (double)p[1], p2 = (double)p[2];
+    const double n0 = (double)n[0], n1 = (double)n[1], n2 = (double)n[2];
+    const double d0 = p0 - pmean[0], d1 = p1 - pmean[1], d2 = p2 - pmean[2];
+    J[0] = d1 * n2 - d2 * n1; J[1] = d2 * n0 - d0 * n2; J[2] = d0 * n1 - d1 * n0;
+    J[3] = n0; J[4] = n1; J[5] = n2;
+    *r = ((p0 - (double)q[0]) * n0 + (p1 - (double)q[1]) * n1) + (p2 - (double)q[2]) * n2;
+}
+
+// Cyclic Jacobi on the symmetric 6x6 A, the conventions of points_normals.h's Eigen3 widened: V = I at the start; kSweeps6 sweeps,
+// each over the pairs (p, q), p < q, in row order (0,1), (0,2), ..., (0,5), (1,2), ..., (4,5).  A pair whose a_pq is exactly 0 is
+// skipped.  Otherwise theta = (a_qq - a_pp) / (2 a_pq);  t = 1 / (|theta| + sqrt(theta theta + 1)), negated when theta < 0;
+// c = 1 / sqrt(t t + 1);  s = t c;  a_pp' = a_pp - t a_pq;  a_qq' = a_qq + t a_pq;  a_pq' = 0;  for every other index r in
+// ascending order a_rp' = c a_rp - s a_rq, a_rq' = s a_rp + c a_rq;  for each row k of V: v_kp' = c v_kp - s v_kq,
+// v_kq' = s v_kp + c v_kq.  Afterwards the eigenvalues are the diagonal, the eigenvectors the columns of V.
+// (Every index is a compile-time constant after unrolling, so that the device keeps both matrices in registers.)
+struct Eigen6 {
+    double a[6][6];
+    double v[6][6];
+    template <int p, int q>
+    SDFK_ICP_HD void rotate()
+    {
+        const double apq = a[p][q];
+        if (apq == 0.0) return;
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+        const double at = theta < 0.0 ? -theta : theta;
+        double t = 1.0 / (at + __builtin_sqrt(theta * theta + 1.0));
+        if (theta < 0.0) t = -t;
+        const double c = 1.0 / __builtin_sqrt(t * t + 1.0);
+        const double s = t * c;
+        a[p][p] = a[p][p] - t * apq;
+        a[q][q] = a[q][q] + t * apq;
+        a[p][q] = a[q][p] = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+            if (r == p || r == q) continue;
+            const double arp = a[r][p], arq = a[r][q];
+            a[r][p] = a[p][r] = c * arp - s * arq;
+            a[r][q] = a[q][r] = s * arp + c * arq;
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            const double vkp = v[k][p], vkq = v[k][q];
+            v[k][p] = c * vkp - s * vkq;
+            v[k][q] = s * vkp + c * vkq;
+        }
+    }
+    SDFK_ICP_HD void sweep()
+    {
+        rotate<0, 1>(); rotate<0, 2>(); rotate<0, 3>(); rotate<0, 4>(); rotate<0, 5>();
+        rotate<1, 2>(); rotate<1, 3>(); rotate<1, 4>(); rotate<1, 5>();
+        rotate<2, 3>(); rotate<2, 4>(); rotate<2, 5>();
+        rotate<3, 4>(); rotate<3, 5>();
+        rotate<4, 5>();
+    }
+};
+
+// A21: the upper triangle of A in row order, (0,0), (0,1), ..., (0,5), (1,1), ..., (5,5)
+SDFK_ICP_HD void jacobi6(const double A21[21], Eigen6& E)
+{
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = i; j < 6; j++) { E.a[i][j] = E.a[j][i] = A21[k]; k++; }
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j < 6; j++) E.v[i][j] = i == j ? 1.0 : 0.0;
+#pragma unroll 1
+    for (int sweep = 0; sweep < kSweeps6; sweep++) E.sweep();
+}
+
+// x = sum_k v_k (v_k . (-b)) / lambda_k over the eigenpairs with lambda_k > kPlaneTau lambda_max, k ascending: the least-squares
+// solution of A x = -b of least norm, with the directions the correspondences do not observe left at zero.  lambda_max = the
+// largest diagonal entry after the sweeps; when it is not a positive finite number (A = 0, or NaN / infinity got in), x = 0 and
+// nothing is retained.  Per retained k: dot = 0.0, then dot += v_ak (-b_a) for a = 0 .. 5;  coef = dot / lambda_k;
+// x_a += v_ak coef (x = 0.0 at first).  Returns the number of retained eigenvalues; lam receives the six eigenvalues.
+SDFK_ICP_HD int pinv_solve6(const double A21[21], const double b[6], double x[6], double lam[6])
+{
+    Eigen6 E;
+    jacobi6(A21, E);
+    double nb[6];
+#pragma unroll
+    for (int a = 0; a < 6; a++) { x[a] = 0.0; nb[a] = -b[a]; lam[a] = E.a[a][a]; }
+    double lmax = lam[0];
+#pragma unroll
+    for (int k = 1; k < 6; k++)
+        if (lam[k] > lmax) lmax = lam[k];
+    if (!(lmax > 0.0) || !(lmax < (double)INFINITY)) return 0;
+    const double cut = kPlaneTau * lmax;
+    int retained = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        if (!(lam[k] > cut)) continue;
+        retained++;
+        double dot = 0.0;
+#pragma unroll
+        for (int a = 0; a < 6; a++) dot += E.v[a][k] * nb[a];
+        const double coef = dot / lam[k];
+#pragma unroll
+        for (int a = 0; a < 6; a++) x[a] += E.v[a][k] * coef;
+    }
+    return retained;
+}
+
+// Cayley's rotation of w = x[0..2] / 2 -- exactly orthogonal in exact arithmetic, + - * / only, the rotation by 2 atan |w| about w,
+// which agrees with the linearised omega = x[0..2] to second order:  R = ((1 - w.w) I + 2 w w^T + 2 [w]x) / (1 + w.w), with
+// ww = (w0 w0 + w1 w1) + w2 w2;  R_aa = ((1 - ww) + 2 (w_a w_a)) / (1 + ww);  R_ab = (2 (w_a w_b) -+ 2 w_c) / (1 + ww), minus for
+// (a, b) = (0,1), (1,2), (2,0).  T_a = (pmean_a + x_{3+a}) - ((R_a0 pmean_0 + R_a1 pmean_1) + R_a2 pmean_2): the rotation is about pmean.
+SDFK_ICP_HD void cayley_step(const double x[6], const double pmean[3], double R[9], double T[3])
+{
+    const double w0 = x[0] / 2.0, w1 = x[1] / 2.0, w2 = x[2] / 2.0;
+    const double ww = (w0 * w0 + w1 * w1) + w2 * w2;
+    const double om = 1.0 - ww, den = 1.0 + ww;
+    R[0] = (om + 2.0 * (w0 * w0)) / den;
+    R[4] = (om + 2.0 * (w1 * w1)) / den;
+    R[8] = (om + 2.0 * (w2 * w2)) / den;
+    R[1] = (2.0 * (w0 * w1) - 2.0 * w2) / den;
+    R[3] = (2.0 * (w0 * w1) + 2.0 * w2) / den;
+    R[2] = (2.0 * (w0 * w2) + 2.0 * w1) / den;
+    R[6] = (2.0 * (w0 * w2) - 2.0 * w1) / den;
+    R[5] = (2.0 * (w1 * w2) - 2.0 * w0) / den;
+    R[7] = (2.0 * (w1 * w2) + 2.0 * w0) / den;
+    for (int a = 0; a < 3; a++) T[a] = (pmean[a] + x[3 + a]) - ((R[3 * a] * pmean[0] + R[3 * a + 1] * pmean[1]) + R[3 * a + 2] * pmean[2]);
+}
+
+// From the reduced A and b, the kept points' mean and the running total: x (pinv_solve6), R and T (cayley_step) rounded to f32 into the
+// row-vector step (R^T in its upper 3x3, T in its fourth row: Transform(p, step) = R p + T), then convergence on the step and
+// total = total * step exactly as solve_step.  `total_prev` and `total` may not overlap.
+SDFK_ICP_HD void solve_step_plane(const double A21[21], const double b[6], const double pmean[3], const float total_prev[16], float conv_t, float conv_r,
+                                  float step[16], float total[16], bool* converged, int* retained)
+{
+    double x[6], lam[6], R[9], T[3];
+    *retained = pinv_solve6(A21, b, x, lam);
+    cayley_step(x, pmean, R, T);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) step[4 * i + j] = (float)R[3 * j + i];
+        step[4 * i + 3] = 0.0f;
+        step[12 + i] = (float)T[i];
+    }
+    step[15] = 1.0f;
+    const float drot = (fabsf(1.0f - step[0]) + fabsf(1.0f - step[5])) + fabsf(1.0f - step[10]);
+    const float dtrans = (float)__builtin_sqrt((double)((step[12] * step[12] + step[13] * step[13]) + step[14] * step[14]));   // Vector3.Length
+    *converged = dtrans <= conv_t && drot <= conv_r;
+    m4_mul(total_prev, step, total);
+}
+
+}  // namespace sdfk_icp

@@ -14,6 +14,8 @@
 // reference's f32 Matrix4x4 steps, convergence, running total) -> the step applied to the points.  Every reduction is f64 in a
 // fixed order (per-block partials of a fixed grid, then one block), with no float atomics: results are bitwise reproducible.
 // Everything after the reductions (the distMax rule, the filter, the solve, the Matrix4x4 steps) is icp_solve.h, shared with the host.
+// With a normal per static point the same loop runs the point-to-plane metric: kept count and mean -> the 28 sums of the 6x6 normal
+// equations -> a one-lane eigen-solve and Cayley step ("ICP, point to plane" below).
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "points_grid.h"
@@ -393,6 +395,144 @@ __global__ void k_icp_init(IcpState* S)
     S->converged = 0;
 }
 
+// ---- ICP, point to plane ----------------------------------------------------------------------------------------------------
+// The second metric: after the same search (which also delivers the static index) and distance statistics, the kept points' count
+// and mean, then the 28 sums of the normal equations -- the 21 products J_a J_b (a <= b), the 6 products J_a r, and r r -- and a
+// one-lane solve (icp_solve.h: plane_row, solve_step_plane).  A block reduces its 28 columns seven at a time through one [7][256]
+// buffer (14 KB, the size k_icp_fsum uses): block_sum<28> would take 56 KB of the 160 KB LDS of a CU and leave room for two blocks
+// where the accumulation loop, which is what takes the time, wants the CU full; the four passes cost 4 x 8 barriers per block.
+constexpr int kPlaneCols = 28;
+constexpr int kPlaneGroup = 7;
+
+struct IcpPlane {
+    double part[kRedBlocks][kPlaneCols];   // per-block partial sums of the current reduction
+    double count;                          // kept points of this iteration
+    double rsq;                            // sum of r^2 over them, before the step
+    int retained;                          // eigenvalues the solve retained
+};
+
+struct IcpPlaneArgs {
+    const int32_t* index;    // the nearest static point per point (-1: none)
+    const float* normals;    // one per static point
+    IcpPlane* P;
+};
+
+// the correspondence of point i: whether it is kept, its static point and normal
+__device__ __forceinline__ bool plane_cor(const IcpArgs& A, const IcpPlaneArgs& B, int64_t i, float dmax, float q[3], float nrm[3])
+{
+    const float4 c = A.cor[i];
+    const int id = B.index[i];
+    q[0] = c.x; q[1] = c.y; q[2] = c.z;
+    nrm[0] = nrm[1] = nrm[2] = 0.0f;
+    if (id >= 0) { nrm[0] = B.normals[3 * (int64_t)id]; nrm[1] = B.normals[3 * (int64_t)id + 1]; nrm[2] = B.normals[3 * (int64_t)id + 2]; }
+    return sdfk_icp::kept_plane(id, c.w, dmax, nrm);
+}
+
+template <int K>
+__device__ __forceinline__ void reduce_plane_parts(const IcpPlane* P, int off, double (&out)[K], double (*s)[kBlock])
+{
+#pragma unroll
+    for (int j = 0; j < K; j++) out[j] = 0.0;
+    for (int b = threadIdx.x; b < kRedBlocks; b += kBlock)
+#pragma unroll
+        for (int j = 0; j < K; j++) out[j] += P->part[b][off + j];
+    block_sum<K>(out, s);
+}
+
+// count and sum p of the kept points
+__global__ __launch_bounds__(kBlock) void k_icpp_centre(IcpArgs A, IcpPlaneArgs B, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;
+    __shared__ double s[4][kBlock];
+    const float dmax = A.S->dist_max;
+    double v[4] = {0, 0, 0, 0};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
+        float q[3], nrm[3];
+        if (plane_cor(A, B, i, dmax, q, nrm)) {
+            v[0] += 1.0;
+            v[1] += A.points[3 * i]; v[2] += A.points[3 * i + 1]; v[3] += A.points[3 * i + 2];
+        }
+    }
+    block_sum<4>(v, s);
+    if (threadIdx.x == 0)
+        for (int j = 0; j < 4; j++) B.P->part[blockIdx.x][j] = v[j];
+}
+
+__global__ __launch_bounds__(kBlock) void k_icpp_mean(IcpArgs A, IcpPlaneArgs B, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;
+    __shared__ double s[4][kBlock];
+    double r[4];
+    reduce_plane_parts<4>(B.P, 0, r, s);
+    if (threadIdx.x != 0) return;
+    for (int j = 0; j < 3; j++) A.S->pmean[j] = r[1 + j] / r[0];
+    B.P->count = r[0];
+}
+
+// the normal equations: columns 0 .. 20 J_a J_b, 21 .. 26 J_a r, 27 r r
+__global__ __launch_bounds__(kBlock) void k_icpp_nsum(IcpArgs A, IcpPlaneArgs B, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;
+    __shared__ double s[kPlaneGroup][kBlock];
+    const float dmax = A.S->dist_max;
+    const double pm[3] = {A.S->pmean[0], A.S->pmean[1], A.S->pmean[2]};
+    double v[kPlaneCols / kPlaneGroup][kPlaneGroup];
+#pragma unroll
+    for (int c = 0; c < kPlaneCols; c++) v[c / kPlaneGroup][c % kPlaneGroup] = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
+        float q[3], nrm[3];
+        if (!plane_cor(A, B, i, dmax, q, nrm)) continue;
+        const float p[3] = {A.points[3 * i], A.points[3 * i + 1], A.points[3 * i + 2]};
+        double J[6], r;
+        sdfk_icp::plane_row(p, q, nrm, pm, J, &r);
+        int c = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int b = a; b < 6; b++) { v[c / kPlaneGroup][c % kPlaneGroup] += J[a] * J[b]; c++; }
+#pragma unroll
+        for (int a = 0; a < 6; a++) { v[c / kPlaneGroup][c % kPlaneGroup] += J[a] * r; c++; }
+        v[c / kPlaneGroup][c % kPlaneGroup] += r * r;
+    }
+#pragma unroll
+    for (int gq = 0; gq < kPlaneCols / kPlaneGroup; gq++) {
+        block_sum<kPlaneGroup>(v[gq], s);
+        if (threadIdx.x == 0)
+            for (int j = 0; j < kPlaneGroup; j++) B.P->part[blockIdx.x][gq * kPlaneGroup + j] = v[gq][j];
+        __syncthreads();   // (s is reused)
+    }
+}
+
+// the solve (icp_solve.h) on one lane: the 6x6 Jacobi, the truncated solve, Cayley's rotation, convergence, the running total
+__global__ __launch_bounds__(kBlock) void k_icpp_solve(IcpArgs A, IcpPlaneArgs B, int iter)
+{
+    if (icp_stopped(A.S, iter)) return;
+    __shared__ double s[kPlaneGroup][kBlock];
+    double red[kPlaneCols / kPlaneGroup][kPlaneGroup];
+#pragma unroll
+    for (int gq = 0; gq < kPlaneCols / kPlaneGroup; gq++) {
+        reduce_plane_parts<kPlaneGroup>(B.P, gq * kPlaneGroup, red[gq], s);
+        __syncthreads();   // (s is reused)
+    }
+    if (threadIdx.x != 0) return;
+    double A21[21], b[6];
+#pragma unroll
+    for (int c = 0; c < 21; c++) A21[c] = red[c / kPlaneGroup][c % kPlaneGroup];
+#pragma unroll
+    for (int c = 0; c < 6; c++) b[c] = red[(21 + c) / kPlaneGroup][(21 + c) % kPlaneGroup];
+    IcpState* S = A.S;
+    float step[16], tot[16];
+    bool conv;
+    int retained;
+    sdfk_icp::solve_step_plane(A21, b, S->pmean, S->total, A.conv_t, A.conv_r, step, tot, &conv, &retained);
+    for (int q = 0; q < 16; q++) { S->step[q] = step[q]; S->total[q] = tot[q]; }
+    B.P->rsq = red[27 / kPlaneGroup][27 % kPlaneGroup];
+    B.P->retained = retained;
+    S->iters = iter + 1;
+    S->converged = conv;
+    S->stop = conv || iter + 1 >= A.max_iters;
+}
+
 unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock); }
 
 }  // namespace
@@ -566,12 +706,21 @@ int points_append(sdfk_points* s, const void* pts, int64_t n, bool device)
     return SDFK_OK;
 }
 
-int icp_run(sdfk_points* s, const sdfk_icp_params* prm, float* pts_dev, int64_t n, float total[16], int32_t* iterations)
+// `normals_dev` null: point to point.  Otherwise point to plane with one normal per static point; `stats` (may be null) receives its int64[4].
+int icp_run(sdfk_points* s, const sdfk_icp_params* prm, const float* normals_dev, float* pts_dev, int64_t n, float total[16], int32_t* iterations,
+            int64_t* stats = nullptr)
 {
     IcpState* S = nullptr;
     float4* cor = nullptr;
+    IcpPlane* P = nullptr;
+    int32_t* index = nullptr;
+    const bool plane = normals_dev != nullptr;
     int r = dev_alloc((void**)&S, sizeof(IcpState));
     if (!r) r = dev_alloc((void**)&cor, (size_t)n * sizeof(float4));
+    if (!r && plane) r = dev_alloc((void**)&P, sizeof(IcpPlane));
+    if (!r && plane) r = dev_alloc((void**)&index, (size_t)n * sizeof(int32_t));
+    IcpPlaneArgs B{index, normals_dev, P};
+    struct { double count, rsq; int retained; } host_plane{};
     IcpArgs A{pts_dev, cor, n, prm->good_correspondence_distance, prm->converged_max_translation, prm->converged_max_rotation, prm->max_iterations, S};
     hipError_t e = hipSuccess;
     struct { float total[16]; int iters, stop, converged; } host{};
@@ -583,32 +732,48 @@ int icp_run(sdfk_points* s, const sdfk_icp_params* prm, float* pts_dev, int64_t 
         constexpr int kChunk = 4;
         for (int it0 = 0; !r && e == hipSuccess && it0 < prm->max_iterations; it0 += kChunk) {
             for (int it = it0; it < std::min(it0 + kChunk, prm->max_iterations) && !r; it++) {
-                SearchOut O{nullptr, nullptr, nullptr, cor, nullptr};
+                SearchOut O{index, nullptr, nullptr, cor, nullptr};
                 r = points_search_launch(s, pts_dev, n, O, S, it);
                 if (r) break;
-                ProfScope ps("k_icp_step");
+                ProfScope ps(plane ? "k_icpp_step" : "k_icp_step");
                 hipLaunchKernelGGL(k_icp_dsum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
                 hipLaunchKernelGGL(k_icp_dvar, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
                 hipLaunchKernelGGL(k_icp_dstats, dim3(1), dim3(kBlock), 0, g.stream, A, it);
-                hipLaunchKernelGGL(k_icp_fsum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
-                hipLaunchKernelGGL(k_icp_means, dim3(1), dim3(kBlock), 0, g.stream, A, it);
-                hipLaunchKernelGGL(k_icp_csum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
-                hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(kBlock), 0, g.stream, A, it);
+                if (plane) {
+                    hipLaunchKernelGGL(k_icpp_centre, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, B, it);
+                    hipLaunchKernelGGL(k_icpp_mean, dim3(1), dim3(kBlock), 0, g.stream, A, B, it);
+                    hipLaunchKernelGGL(k_icpp_nsum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, B, it);
+                    hipLaunchKernelGGL(k_icpp_solve, dim3(1), dim3(kBlock), 0, g.stream, A, B, it);
+                } else {
+                    hipLaunchKernelGGL(k_icp_fsum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
+                    hipLaunchKernelGGL(k_icp_means, dim3(1), dim3(kBlock), 0, g.stream, A, it);
+                    hipLaunchKernelGGL(k_icp_csum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
+                    hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(kBlock), 0, g.stream, A, it);
+                }
                 hipLaunchKernelGGL(k_icp_apply, dim3(grid1(n)), dim3(kBlock), 0, g.stream, A, it);
                 e = hipGetLastError();
             }
             if (r || e != hipSuccess) break;
             e = hipMemcpyAsync(&host, &S->total, sizeof host, hipMemcpyDeviceToHost, g.stream);
+            if (e == hipSuccess && plane) e = hipMemcpyAsync(&host_plane, &P->count, sizeof host_plane, hipMemcpyDeviceToHost, g.stream);
             if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
             if (e != hipSuccess || host.stop) break;
         }
     }
     dev_free(cor);
     dev_free(S);
+    dev_free(P);
+    dev_free(index);
     if (r) return r;
     if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_icp_register: %s", hipGetErrorString(e));
     for (int q = 0; q < 16; q++) total[q] = host.total[q];
     *iterations = host.iters;
+    if (stats) {   // (of the last iteration run; no iteration: zeros)
+        stats[0] = (int64_t)host_plane.count;
+        stats[1] = (int64_t)sdfk_icp::f64_bits(host_plane.rsq);
+        stats[2] = host.converged;
+        stats[3] = host_plane.retained;
+    }
     return SDFK_OK;
 }
 
@@ -726,7 +891,7 @@ extern "C" int sdfk_icp_register_device(sdfk_points* s, const sdfk_icp_params* p
     StateScope in_owner_context(s ? s->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (int r = icp_check(s, prm, points3_dev, n, total, iterations)) return r;
-    return icp_run(s, prm, (float*)points3_dev, n, total, iterations);
+    return icp_run(s, prm, nullptr, (float*)points3_dev, n, total, iterations);
 }
 
 extern "C" int sdfk_icp_register(sdfk_points* s, const sdfk_icp_params* prm, float* points3, int64_t n, float total[16], int32_t* iterations)
@@ -740,12 +905,57 @@ extern "C" int sdfk_icp_register(sdfk_points* s, const sdfk_icp_params* prm, flo
     int r = dev_alloc((void**)&pd, (size_t)n * 3 * sizeof(float));
     hipError_t e = hipSuccess;
     if (!r) e = hipMemcpyAsync(pd, points3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) r = icp_run(s, prm, pd, n, total, iterations);
+    if (!r && e == hipSuccess) r = icp_run(s, prm, nullptr, pd, n, total, iterations);
     if (!r && e == hipSuccess) e = hipMemcpyAsync(points3, pd, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
     const hipError_t es = hipStreamSynchronize(g.stream);
     dev_free(pd);
     if (r) return r;
     if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_icp_register: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    return SDFK_OK;
+}
+
+extern "C" int sdfk_icp_register_plane_device(sdfk_points* s, const sdfk_icp_params* prm, const void* normals3_dev, void* points3_dev, int64_t n,
+                                              float total[16], int32_t* iterations, int64_t stats[4])
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = icp_check(s, prm, points3_dev, n, total, iterations)) return r;
+    if (!normals3_dev) return fail(SDFK_ERR_INVALID, "sdfk_icp_register_plane: null normals");
+    return icp_run(s, prm, (const float*)normals3_dev, (float*)points3_dev, n, total, iterations, stats);
+}
+
+extern "C" int sdfk_icp_register_plane(sdfk_points* s, const sdfk_icp_params* prm, const float* normals3, float* points3, int64_t n, float total[16],
+                                       int32_t* iterations, int64_t stats[4])
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = icp_check(s, prm, points3, n, total, iterations)) return r;
+    if (!normals3) return fail(SDFK_ERR_INVALID, "sdfk_icp_register_plane: null normals");
+    for (int64_t i = 0; i < 3 * n; i++)   // (nothing is touched)
+        if (!std::isfinite(points3[i])) return fail(SDFK_ERR_INVALID, "sdfk_icp_register_plane: dynamic point %lld has a NaN or infinite coordinate", (long long)(i / 3));
+    for (int64_t i = 0; i < 3 * s->n; i++)
+        if (!std::isfinite(normals3[i])) return fail(SDFK_ERR_INVALID, "sdfk_icp_register_plane: normal %lld has a NaN or infinite component", (long long)(i / 3));
+    float* pd = nullptr;
+    float* nd = nullptr;
+    int r = dev_alloc((void**)&pd, (size_t)n * 3 * sizeof(float));
+    if (!r) r = dev_alloc((void**)&nd, (size_t)s->n * 3 * sizeof(float));
+    hipError_t e = hipSuccess;
+    if (!r) e = hipMemcpyAsync(pd, points3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
+    if (!r && e == hipSuccess) e = hipMemcpyAsync(nd, normals3, (size_t)s->n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
+    float tot[16];
+    int32_t iters = 0;
+    int64_t st[4] = {0, 0, 0, 0};
+    if (!r && e == hipSuccess) r = icp_run(s, prm, nd, pd, n, tot, &iters, st);
+    if (!r && e == hipSuccess) e = hipMemcpyAsync(points3, pd, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
+    const hipError_t es = hipStreamSynchronize(g.stream);
+    dev_free(pd);
+    dev_free(nd);
+    if (r) return r;
+    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_icp_register_plane: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    for (int q = 0; q < 16; q++) total[q] = tot[q];
+    *iterations = iters;
+    if (stats)
+        for (int q = 0; q < 4; q++) stats[q] = st[q];
     return SDFK_OK;
 }
 

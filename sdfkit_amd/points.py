@@ -176,6 +176,8 @@ class IterativeClosestPoint:
         self.ConvergedMaximumTranslation = f32(1.0e-4)
         self.ConvergedMaximumRotation = f32(1.0e-5)
         self.Iterations = 0   # extension: iterations of the last RegisterPoints
+        self.LastStats = None  # extension: the point-to-plane stats of the last RegisterPoints (None after a point-to-point one)
+        self._normals = None
         if _is_one_cloud(staticPoints):
             self._tree = KdTree(staticPoints)
         else:
@@ -190,33 +192,105 @@ class IterativeClosestPoint:
     def StaticTree(self):
         return self._tree
 
-    def AddStaticPoints(self, staticPoints):
-        self._tree.AddPoints(staticPoints)
+    @property
+    def StaticNormals(self):
+        """Extension: one normal per static point ((TotalPoints, 3) float32, e.g. StaticTree.EstimateNormals(k)[0]), or None.  With
+        normals set, RegisterPoints minimises the distances to the tangent planes at the nearest static points (point to plane);
+        their orientation does not matter, and a point whose normal is (0, 0, 0) takes no part."""
+        return self._normals
+
+    @StaticNormals.setter
+    def StaticNormals(self, normals):
+        if normals is None:
+            self._normals = None
+            return
+        a = np.ascontiguousarray(np.asarray(normals, dtype=f32))
+        if a.shape != (self._tree.TotalPoints, 3):
+            raise ValueError(f"one normal per static point: shape {(self._tree.TotalPoints, 3)} expected, got {a.shape} (StaticNormals)")
+        self._normals = a.copy()
+
+    def AddStaticPoints(self, staticPoints, normals=None):
+        """normals (extension): the new points' normals -- required when StaticNormals is set, refused when it is not."""
+        pts = _points(staticPoints)
+        if (normals is None) != (self._normals is None):
+            raise ValueError("AddStaticPoints would leave StaticNormals out of step with the static points: "
+                             + ("pass normals= for the new points" if normals is None else "set StaticNormals first"))
+        if normals is not None:
+            nrm = np.ascontiguousarray(np.asarray(normals, dtype=f32))
+            if nrm.shape != pts.shape:
+                raise ValueError(f"one normal per added point: shape {pts.shape} expected, got {nrm.shape} (normals)")
+        self._tree.AddPoints(pts)
+        if normals is not None:
+            self._normals = np.concatenate([self._normals, nrm])
+
+    def _metric(self, metric):
+        if metric is None:
+            return "plane" if self._normals is not None else "point"
+        if metric not in ("point", "plane"):
+            raise ValueError(f"metric must be None, 'point' or 'plane', not {metric!r}")
+        if metric == "plane" and self._normals is None:
+            raise ValueError("metric='plane' needs StaticNormals")
+        return metric
+
+    def _stats(self, st):
+        self.LastStats = {"kept": int(st[0]), "sum_r2": float(np.array([st[1]], np.int64).view(np.float64)[0]), "converged": bool(st[2]),
+                          "retained": int(st[3]), "raw": [int(v) for v in st]}
 
     def _params(self):
         return N.IcpParams(int(self.MaxIterations), float(f32(self.GoodCorrespondenceDistance)),
                            float(f32(self.ConvergedMaximumTranslation)), float(f32(self.ConvergedMaximumRotation)))
 
-    def RegisterPoints(self, points):
+    def RegisterPoints(self, points, metric=None):
         """Moves `points` -- an (n, 3) float32 C-contiguous array -- in place onto the static points and returns the 4x4 float32
-        transform that did it (row-vector convention)."""
+        transform that did it (row-vector convention).  metric (extension): "point" (the reference's step), "plane" (needs
+        StaticNormals), or None: "plane" iff StaticNormals is set.  A plane registration leaves its stats in LastStats."""
+        metric = self._metric(metric)
         if not (isinstance(points, np.ndarray) and points.dtype == f32 and points.ndim == 2 and points.shape[1] == 3
                 and points.flags.c_contiguous and points.flags.writeable):
             raise TypeError("RegisterPoints moves the points in place: pass a writable C-contiguous (n, 3) float32 array")
         prm = self._params()
         total = (C.c_float * 16)()
         iters = C.c_int32()
-        N.check(N.lib().sdfk_icp_register(self._tree.handle, C.byref(prm), _ptr(points), len(points), total, C.byref(iters)))
+        if metric == "plane":
+            self._check_normals()
+            st = (C.c_int64 * 4)()
+            N.check(N.lib().sdfk_icp_register_plane(self._tree.handle, C.byref(prm), _ptr(self._normals), _ptr(points), len(points), total,
+                                                     C.byref(iters), st))
+            self._stats(st)
+        else:
+            N.check(N.lib().sdfk_icp_register(self._tree.handle, C.byref(prm), _ptr(points), len(points), total, C.byref(iters)))
+            self.LastStats = None
         self.Iterations = int(iters.value)
         return np.array(total[:], f32).reshape(4, 4)
 
-    def RegisterDevicePoints(self, points_dev, n):
-        """Extension: RegisterPoints on n points (x, y, z float32) already in device memory (a raw pointer), moved in place."""
+    def _check_normals(self):
+        if len(self._normals) != self._tree.TotalPoints:   # (points added through StaticTree behind our back)
+            raise ValueError("StaticNormals is out of step with the static points")
+
+    def RegisterDevicePoints(self, points_dev, n, metric=None, normals_dev=None):
+        """Extension: RegisterPoints on n points (x, y, z float32) already in device memory (a raw pointer), moved in place.
+        normals_dev: StaticNormals already in device memory (a raw pointer); without it a plane registration uploads them."""
+        metric = self._metric(metric)
         prm = self._params()
         total = (C.c_float * 16)()
         iters = C.c_int32()
-        N.check(N.lib().sdfk_icp_register_device(self._tree.handle, C.byref(prm), C.c_void_p(points_dev), int(n), total,
-                                                  C.byref(iters)))
+        if metric == "plane":
+            self._check_normals()
+            keep = None
+            if normals_dev is None:
+                import torch
+                keep = torch.from_numpy(self._normals).to(torch.device("cuda", N._inited_device or 0))
+                torch.cuda.synchronize()
+                normals_dev = keep.data_ptr()
+            st = (C.c_int64 * 4)()
+            N.check(N.lib().sdfk_icp_register_plane_device(self._tree.handle, C.byref(prm), C.c_void_p(normals_dev), C.c_void_p(points_dev), int(n),
+                                                            total, C.byref(iters), st))
+            self._stats(st)
+            del keep
+        else:
+            N.check(N.lib().sdfk_icp_register_device(self._tree.handle, C.byref(prm), C.c_void_p(points_dev), int(n), total,
+                                                      C.byref(iters)))
+            self.LastStats = None
         self.Iterations = int(iters.value)
         return np.array(total[:], f32).reshape(4, 4)
 
@@ -238,6 +312,6 @@ class IterativeClosestPoint:
         icp = IterativeClosestPoint(list(staticPoints))
         out = []
         for d in dyn:
-            out.append(icp.RegisterPoints(d))
+            out.append(icp.RegisterPoints(d))   # (point to point, as the reference: the new instance has no normals)
             icp.AddStaticPoints(d)
         return out

@@ -3,6 +3,8 @@
 // reference's; the reductions and the 3x3 SVD are f64 on the GPU instead of MathNet's float SVD (a stated deviation), every
 // later step is the reference's float Matrix4x4 arithmetic.  An empty dynamic set is refused (the reference returns NaN),
 // and so is a dynamic point with a NaN or infinite coordinate (the native call checks host points; device points are unchecked).
+// Extension: RegisterPoints (points, IcpMetric) and StaticNormals add the point-to-plane metric over sdfk_icp_register_plane; the
+// reference's RegisterPoints (points) stays point to point, and so does GlobalRegisterPoints.
 // UNCOMPILED HERE (no .NET in the build image); sdfkit_amd/points.py's IterativeClosestPoint is the same layer, tested.
 using System;
 using System.Linq;
@@ -40,7 +42,76 @@ namespace SdfKit
 
         public void AddStaticPoints (ReadOnlySpan<Vector3> staticPoints)
         {
+            if (staticNormals != null)
+                throw new ArgumentException ("AddStaticPoints would leave StaticNormals out of step: pass the new points' normals", nameof (staticPoints));
             staticTree.AddPoints (staticPoints);
+        }
+
+        // ---- extension: point to plane (include/sdfkit_hip.h, "IterativeClosestPoint.RegisterPoints, point to plane") ----
+        public enum IcpMetric { Auto, Point, Plane }   // Auto: Plane iff StaticNormals is set
+
+        public struct PlaneStats
+        {
+            public long Kept;        // kept correspondences of the last iteration
+            public double SumR2;     // sum of their squared plane distances before the step
+            public bool Converged;
+            public int Retained;     // eigenvalues of the normal equations the solve retained
+        }
+
+        Vector3[]? staticNormals;
+
+        /// <summary>One normal per static point (e.g. from KdTree.EstimateNormals), or null.  With normals set, RegisterPoints
+        /// minimises the distances to the tangent planes at the nearest static points.  Their orientation does not matter; a
+        /// point whose normal is (0, 0, 0) takes no part.</summary>
+        public Vector3[]? StaticNormals {
+            get => staticNormals;
+            set {
+                if (value != null && value.Length != staticTree.TotalPoints)
+                    throw new ArgumentException ("One normal per static point must be given", nameof (value));
+                staticNormals = value == null ? null : (Vector3[])value.Clone ();
+            }
+        }
+
+        /// <summary>The stats of the last point-to-plane registration (null after a point-to-point one).</summary>
+        public PlaneStats? LastStats { get; private set; }
+
+        public void AddStaticPoints (ReadOnlySpan<Vector3> staticPoints, ReadOnlySpan<Vector3> normals)
+        {
+            if (staticNormals == null)
+                throw new ArgumentException ("Set StaticNormals first", nameof (normals));
+            if (normals.Length != staticPoints.Length)
+                throw new ArgumentException ("One normal per added point must be given", nameof (normals));
+            staticTree.AddPoints (staticPoints);
+            var all = new Vector3[staticNormals.Length + normals.Length];
+            staticNormals.CopyTo (all, 0);
+            normals.CopyTo (all.AsSpan (staticNormals.Length));
+            staticNormals = all;
+        }
+
+        public unsafe Matrix4x4 RegisterPoints (Span<Vector3> points, IcpMetric metric)
+        {
+            if (metric == IcpMetric.Point || (metric == IcpMetric.Auto && staticNormals == null)) {
+                var t = RegisterPoints (points);
+                LastStats = null;
+                return t;
+            }
+            if (staticNormals == null)
+                throw new ArgumentException ("IcpMetric.Plane needs StaticNormals", nameof (metric));
+            if (staticNormals.Length != staticTree.TotalPoints)
+                throw new InvalidOperationException ("StaticNormals is out of step with the static points");
+            var prm = new SdfkIcpParams {
+                MaxIterations = MaxIterations,
+                GoodCorrespondenceDistance = GoodCorrespondenceDistance,
+                ConvergedMaximumTranslation = ConvergedMaximumTranslation,
+                ConvergedMaximumRotation = ConvergedMaximumRotation,
+            };
+            Matrix4x4 total;
+            long* st = stackalloc long[4];
+            fixed (Vector3* p = points)
+            fixed (Vector3* nrm = staticNormals)
+                Native.Check (Native.sdfk_icp_register_plane (staticTree.Handle, ref prm, (float*)nrm, (float*)p, points.Length, (float*)&total, out _, st));
+            LastStats = new PlaneStats { Kept = st[0], SumR2 = BitConverter.Int64BitsToDouble (st[1]), Converged = st[2] != 0, Retained = (int)st[3] };
+            return total;
         }
 
         /// <summary>

@@ -119,6 +119,10 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_icp_register(IntPtr points, ref SdfkIcpParams prm, float* points3, long n, float* total16, out int iterations);
         [DllImport(Lib)] public static extern int sdfk_icp_register_device(IntPtr points, ref SdfkIcpParams prm, IntPtr points3Dev, long n, float* total16,
                                                                            out int iterations);
+        [DllImport(Lib)] public static extern int sdfk_icp_register_plane(IntPtr points, ref SdfkIcpParams prm, float* normals3, float* points3, long n,
+                                                                          float* total16, out int iterations, long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_icp_register_plane_device(IntPtr points, ref SdfkIcpParams prm, IntPtr normals3Dev, IntPtr points3Dev,
+                                                                                 long n, float* total16, out int iterations, long* stats4);
         // triangle-mesh distance (MeshSdf.Hip.cs)
         [DllImport(Lib)] public static extern int sdfk_trimesh_create(float* vertices3, long nVertices, int* triangles, long nIndices, float* colors3,
                                                                       out IntPtr trimesh);
