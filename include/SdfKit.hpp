@@ -784,7 +784,7 @@ public:
         std::vector<float> Variation;    // lmin / (l0 + l1 + l2)
     };
     // A normal per static point from its k nearest (3 <= k <= 64), turned towards the viewpoints: none (the largest component is
-    // made positive -- not a consistent orientation of a closed surface, which is out of scope), one, or one per point.
+    // made positive -- not a consistent orientation of a closed surface: OrientNormals makes one afterwards), one, or one per point.
     Normals EstimateNormals(int k, const std::vector<Vector3>& viewpoints = {}, float maxDistance = std::numeric_limits<float>::infinity()) const
     {
         Normals r;
@@ -798,6 +798,23 @@ public:
     Normals EstimateNormals(int k, Vector3 viewpoint, float maxDistance = std::numeric_limits<float>::infinity()) const
     {
         return EstimateNormals(k, std::vector<Vector3>{viewpoint}, maxDistance);
+    }
+    struct OrientStats { int64_t Rounds = 0, Seeds = 0, Flipped = 0, Unreached = 0, Invalid = 0, Levels[4] = {0, 0, 0, 0}; };
+    // `normals` (one per static point) with the sign of some flipped, so that neighbouring normals agree and the top of every connected
+    // piece points up: a deterministic region growing over the k-nearest graph (2 <= k <= 64), confident edges first, from at most
+    // maxSeeds seeds (sdfkit_hip.h, "Point clouds: a consistent orientation").  Bit-identical to the input up to sign; normals that are
+    // not finite or all zero, and those no seed reached, are left alone.
+    std::vector<Vector3> OrientNormals(std::vector<Vector3> normals, int k = 8, float maxDistance = std::numeric_limits<float>::infinity(),
+                                       int maxSeeds = 64, OrientStats* stats = nullptr) const
+    {
+        if ((int64_t)normals.size() != (int64_t)TotalPoints()) throw std::invalid_argument("one normal per static point (normals)");
+        int64_t st[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        Check(sdfk_points_orient_normals(h_, k, maxDistance, maxSeeds, &normals[0].X, st));
+        if (stats) {
+            stats->Rounds = st[0]; stats->Seeds = st[1]; stats->Flipped = st[2]; stats->Unreached = st[3]; stats->Invalid = st[4];
+            for (int l = 0; l < 4; l++) stats->Levels[l] = st[5 + l];
+        }
+        return normals;
     }
     struct VolumeStats { int64_t Known = 0, Unknown = 0, Candidates = 0, Queries = 0; };
     // The cloud with one outward normal per static point as a signed distance volume: the blend of the tangent-plane distances of the

@@ -37,7 +37,8 @@ extern "C" {
                                    sdfk_program_create_bound / sdfk_program_check_bound (programs that read voxel volumes); opcodes
                                    SDFK_OP_SIN .. SDFK_OP_ATAN2 (19-23), accepted by every entry point that takes an op list;
                                    sdfk_points_knn* / sdfk_points_radius_* (KdTree: k nearest, within a radius);
-                                   sdfk_points_normals* / sdfk_points_to_volume* (point clouds: normals, signed distance volumes) */
+                                   sdfk_points_normals* / sdfk_points_to_volume* (point clouds: normals, signed distance volumes);
+                                   sdfk_points_orient_normals* (point clouds: a consistent orientation of the normals) */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -605,8 +606,8 @@ int sdfk_points_radius_fill_device(const sdfk_points* s, const void* queries3_de
  *    by its length sqrt((n0 n0 + n1 n1) + n2 n2).
  * 4. Orientation: with a viewpoint w (n_viewpoints = 1: one for all; = the number of static points: one each; = 0: none),
  *    d = ((w0 - p0) n0 + (w1 - p1) n1) + (w2 - p2) n2; d < 0 flips n.  With no viewpoint, or d exactly 0, the component of n of
- *    largest magnitude is made positive (ties: the lowest axis).  A CONSISTENT orientation without a viewpoint (propagation along
- *    a spanning tree of the neighbourhood graph) is not provided.
+ *    largest magnitude is made positive (ties: the lowest axis).  That is NOT a consistent orientation of a closed surface; one
+ *    without a viewpoint is sdfk_points_orient_normals' (below), applied to these normals afterwards.
  * 5. normal = n rounded to f32; variation = (float)(l_min / ((l_0 + l_1) + l_2)) (surface variation: 0 on a plane, up to 1/3).
  * 6. Degenerate: m < 3, or (c00 + c11) + c22 == 0: normal = (0, 0, 0), variation = 0.  A collinear neighbourhood gives a
  *    deterministic but meaningless direction.
@@ -643,6 +644,49 @@ int sdfk_points_normals_device(const sdfk_points* s, int32_t k, float max_distan
 int sdfk_points_to_volume(const sdfk_points* s, const float* normals3, sdfk_volume* v, int32_t k, float max_distance, int64_t stats[4]);
 int sdfk_points_to_volume_device(const sdfk_points* s, const void* normals3_dev, sdfk_volume* v, int32_t k, float max_distance,
                                  int64_t stats[4]);
+/* ---- Point clouds: a consistent orientation (extension) ------------------------------------------------------------------------
+ * sdfk_points_to_volume wants normals that point outside.  A viewpoint gives that for what one sensor position sees; a merged scan,
+ * the vertices of a mesh whose normals were lost, or a cloud of unknown origin has none.  sdfk_points_orient_normals flips the sign
+ * of some of the given normals so that neighbouring normals agree and the top of every connected piece points up (Hoppe's seed
+ * rule), and changes nothing else: a parallel, deterministic region growing over the k-nearest graph that accepts confident edges
+ * first.  It is ONE function of its inputs, computed by csrc/points_orient.h (binary64 from the f32 inputs, no contraction),
+ * restated in tests/orient_model.py and compared bit for bit.  Inputs: the static points p_i (insertion order), normals3 (one
+ * normal per static point), k, max_distance, max_seeds.
+ * 1. Graph: row i is the sdfk_points_knn row of p_i for (k, max_distance): the same order, d2 formula and max_distance rule; the
+ *    point itself and any duplicates are included.  2 <= k <= 64.
+ * 2. Validity: a normal is VALID iff its three components are finite and not all zero (either sign of zero).  An invalid normal is
+ *    never oriented and never a source; it is returned untouched and counted.
+ * 3. Dot: dot(i, j) = (n_i0 n_j0 + n_i1 n_j1) + n_i2 n_j2 in binary64 from the f32 inputs as given (the products are exact).  The
+ *    weight of the edge is |dot|.
+ * 4. State: every point is UNORIENTED, or ORIENTED IN ROUND r with a sign s = +-1.  Rounds are numbered from 1; every seed and
+ *    every propagation round takes one number.
+ * 5. Seed round: among the unoriented valid points the one of greatest p_z (f32 compare; -0 equals +0, a NaN p_z counts as -inf),
+ *    ties to the lowest index.  Its sign makes n_z positive; when n_z == 0 the component of largest magnitude is made positive,
+ *    ties to the lowest axis (sdfk_points_normals' step 4).  The level is set to 0.
+ * 6. Propagation round r at level L, thresholds T = {0.9375, 0.75, 0.5, 0.0}: every unoriented valid point i looks at the entries
+ *    j of its row that are valid and were oriented in a round < r, and among them takes the one of greatest |dot(i, j)|, ties to
+ *    the first in row order.  If that weight is >= T[L], i becomes oriented in round r with s_i = -1 if dot(i, j) * s_j < 0, else
+ *    +1.  Every point decides from the state at the end of round r - 1 (Jacobi), so the result does not depend on scheduling.  If
+ *    the round oriented nothing, L becomes L + 1, otherwise L stays; past the last level the growth of this seed is over.  The
+ *    level never goes back up within a seed; every new seed starts at level 0.
+ * 7. Steps 5 and 6 repeat while unoriented valid points remain and fewer than max_seeds seeds were used (max_seeds >= 1).  What
+ *    then remains is UNREACHED and returned untouched.
+ * 8. Output: n_i with the sign bit of each component flipped where s_i = -1: bit-identical to the input up to sign.  stats (may be
+ *    NULL): [0] rounds, seed rounds and the propagation rounds that oriented nothing included; [1] seeds; [2] normals flipped;
+ *    [3] unreached; [4] invalid; [5..8] points oriented at each level (the seeds are in none).
+ * 9. SDFK_ERR_INVALID: k outside [2, 64], a NaN or negative max_distance, max_seeds < 1, a NULL normals3.  (A set always holds a
+ *    point: sdfk_points_create refuses an empty one.)
+ * Limits (Hoppe's method's): it trusts that the k nearest of a point lie on the same sheet of the surface -- two sheets closer
+ * than the sampling, or an edge sharper than the sampling resolves, can carry a wrong sign across; and a dot of exactly 0 carries
+ * no information: the normal is kept as it is.  The rounds are about the diameter of the graph, each one a kernel launch.
+ * Temporaries of a call, freed at its end: n * k int32 (the rows), n int32 (the round stamps), n bytes (the signs).
+ * sdfk_points_orient_normals takes a host array, in place, and is synchronous.  sdfk_points_orient_normals_device takes a device
+ * array, in place, on the library stream; it waits internally wherever it reads its control block (once per batch of 32 queued
+ * rounds and once per seed), so it has returned only after every round ran; the last flip may still be queued when stats is NULL. */
+int sdfk_points_orient_normals(const sdfk_points* s, int32_t k, float max_distance, int32_t max_seeds, float* normals3 /* n*3, in place */,
+                               int64_t stats[9]);
+int sdfk_points_orient_normals_device(const sdfk_points* s, int32_t k, float max_distance, int32_t max_seeds, void* normals3_dev,
+                                      int64_t stats[9]);
 /* IterativeClosestPoint.RegisterPoints (IterativeClosestPoint.cs:53-196): rigidly moves the caller's points (in place) onto the
  * static set and returns the total transform (row-major M11..M44, System.Numerics row-vector convention) and the number of
  * iterations run.  Each iteration is the reference's: nearest static point of every point, the piecewise distMax from the

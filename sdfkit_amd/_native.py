@@ -133,6 +133,8 @@ SIGNATURES = {
     "sdfk_points_normals_device": (C.c_int, [_vp, _i32, _f, _vp, _i64, _vp, _vp]),
     "sdfk_points_to_volume": (C.c_int, [_vp, _vp, _vp, _i32, _f, C.POINTER(_i64)]),
     "sdfk_points_to_volume_device": (C.c_int, [_vp, _vp, _vp, _i32, _f, C.POINTER(_i64)]),
+    "sdfk_points_orient_normals": (C.c_int, [_vp, _i32, _f, _i32, _vp, C.POINTER(_i64)]),
+    "sdfk_points_orient_normals_device": (C.c_int, [_vp, _i32, _f, _i32, _vp, C.POINTER(_i64)]),
     "sdfk_points_free": (None, [_vp]),
     "sdfk_trimesh_create": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vpp]),
     "sdfk_trimesh_create_device": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vpp]),

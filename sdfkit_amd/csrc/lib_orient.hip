@@ -1,0 +1,316 @@
+// lib_orient.hip -- a consistent orientation of point-cloud normals (sdfk_points_orient_normals*): a parallel, deterministic
+// region growing over the k-nearest graph, confident edges first.  Contract: include/sdfkit_hip.h, "Point clouds: a consistent
+// orientation"; the decisions (validity, dot, the seed's order and sign, one point's choice from its row, the level rule):
+// points_orient.h, checked on the host; the walk and the bounded lists: points_walk.h / points_knn.h, shared with
+// lib_points_knn.hip and lib_pointcloud.hip.
+//
+//   k_or_rows<CAP>   one lane per static point: its k nearest exactly as k_pts_knn<CAP> finds them (the same tiers), written once
+//                    for the call as SLOT-MAJOR rows (slot * n + point; -1 from the count on): in a round lane i reads slot s of
+//                    its own row, so neighbouring lanes read neighbouring words.  Also the point's state: stamp 0, sign byte 0
+//                    (invalid normal) or +1, and the count of valid normals.
+//   k_or_seed_find   the unoriented valid point of greatest (z, lowest index) as ONE integer key (points_orient.h seed_key):
+//                    a shuffle maximum per wave, then an integer atomicMax -- no float atomics, the result is order-free.
+//   k_or_seed_apply  one lane: the seed's sign and stamp, level 0.
+//   k_or_round       one lane per point; a lane whose point is oriented or invalid leaves at once.  The others scan their row
+//                    for sources (0 < stamp < this launch's number), take the one of greatest |dot| and, if its weight reaches
+//                    the level's threshold, write their sign byte and stamp.
+// State: one int32 stamp per point (0: unoriented, else the number of the launch that oriented it) and a sign byte -- the Jacobi
+// rule without a second buffer: a stamp written concurrently in launch q reads as 0 or q, and both mean "not yet".
+// Schedule: every launch (seed or round) takes the next number q.  The control block keeps, in rings of three indexed by q % 3,
+// the level launch q ran at and how many points it oriented: launch q reads slot q - 1 (written by the launch before it, so the
+// stream order is the only hand-off), writes slot q and clears slot q + 1.  The level of launch q follows on the device
+// (points_orient.h next_level); once it passes the last level the growth of the seed is over and every later round of the batch
+// leaves after those two loads.  The host queues rounds kBatch at a time and reads the control block once per batch; the same
+// read tells it whether the seed's growth ended and whether unoriented valid points remain for another seed.
+// Rounds that left early are not counted: stats[0] counts seeds and live rounds only, whatever the batch length.
+#include "lib_internal.h"
+#include "points_knn.h"
+#include "points_orient.h"
+#include "points_set.h"
+#include "points_walk.h"
+
+namespace {
+
+using namespace sdfk_walk;
+using namespace sdfk_orient;
+
+constexpr int kBatch = 32;   // rounds queued between two reads of the control block (tests/test_gpu_orient.py BATCH restates it: keep them equal)
+
+struct Ctl {
+    unsigned long long seed_key;             // k_or_seed_find's maximum; 0: no candidate (cleared by k_or_seed_apply)
+    unsigned long long rounds, seeds;        // live rounds (seed rounds included), seeds
+    unsigned long long valid;                // valid normals
+    unsigned long long flipped, unreached;   // k_or_finish
+    unsigned long long per_level[kLevels];   // points oriented at each level
+    int level[3];                            // ring by launch number: the level launch q ran at (kLevels: growth over)
+    unsigned count[3];                       // ring: the points launch q oriented
+};
+
+template <int CAP>
+constexpr int block_of() { return CAP == 8 ? kBlock : kLdsBlock; }
+template <int CAP>
+constexpr int lds_keys() { return CAP == 8 ? 1 : CAP * kLdsBlock; }   // (the register tier keeps no keys in LDS)
+
+__device__ __forceinline__ void load3(const float* a, int64_t i, float out[3])
+{
+    out[0] = a[3 * i]; out[1] = a[3 * i + 1]; out[2] = a[3 * i + 2];
+}
+
+__device__ __forceinline__ unsigned wave_count(bool flag) { return (unsigned)__popcll(__ballot(flag)); }
+
+template <int CAP>
+__global__ __launch_bounds__(block_of<CAP>()) void k_or_rows(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
+                                                              const float* __restrict__ xyz, int64_t n, int k, float d2_bound,
+                                                              const float* __restrict__ normals, int32_t* __restrict__ rows,
+                                                              int32_t* __restrict__ stamp, signed char* __restrict__ sgn, Ctl* ctl)
+{
+    __shared__ uint64_t s_keys[lds_keys<CAP>()];
+    const int64_t t = (int64_t)blockIdx.x * block_of<CAP>() + threadIdx.x;
+    const Query q = load_query(xyz, t, n);
+    Neighbours<CAP> nb;
+    (void)nb.collect(sorted, starts, G, q, k, d2_bound, s_keys);
+    bool ok = false;
+    if (t < n) {
+        int slot = 0;
+        nb.each([&](uint64_t key) {
+            rows[(int64_t)slot * n + t] = key_index(key);
+            slot++;
+            return true;
+        });
+        for (; slot < k; slot++) rows[(int64_t)slot * n + t] = -1;
+        float nrm[3];
+        load3(normals, t, nrm);
+        ok = valid(nrm);
+        stamp[t] = 0;
+        sgn[t] = ok ? 1 : 0;
+    }
+    const unsigned c = wave_count(ok);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&ctl->valid, (unsigned long long)c);
+}
+
+__global__ __launch_bounds__(kBlock) void k_or_seed_find(const float* __restrict__ xyz, int64_t n, const int32_t* __restrict__ stamp,
+                                                         const signed char* __restrict__ sgn, Ctl* ctl)
+{
+    unsigned long long best = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+        if (sgn[i] != 0 && stamp[i] == 0) {
+            const unsigned long long key = seed_key(xyz[3 * i + 2], (int32_t)i);
+            best = key > best ? key : best;
+        }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_down(best, o);
+        best = other > best ? other : best;
+    }
+    if ((threadIdx.x & 63) == 0 && best) atomicMax(&ctl->seed_key, best);
+}
+
+__global__ __launch_bounds__(64) void k_or_seed_apply(int q, const float* __restrict__ normals, int32_t* __restrict__ stamp,
+                                                      signed char* __restrict__ sgn, Ctl* ctl)
+{
+    if (threadIdx.x != 0) return;
+    const unsigned long long key = ctl->seed_key;
+    ctl->seed_key = 0;
+    ctl->count[(q + 1) % 3] = 0;
+    if (!key) {   // no unoriented valid point: nothing grows
+        ctl->level[q % 3] = kLevels;
+        ctl->count[q % 3] = 0;
+        return;
+    }
+    const int32_t i = seed_index(key);
+    float nrm[3];
+    load3(normals, i, nrm);
+    sgn[i] = (signed char)seed_sign(nrm);
+    stamp[i] = q;
+    ctl->level[q % 3] = 0;
+    ctl->count[q % 3] = 1;   // (the round after a seed stays at level 0)
+    ctl->rounds += 1;
+    ctl->seeds += 1;
+}
+
+__global__ __launch_bounds__(kBlock) void k_or_round(const int32_t* __restrict__ rows, int64_t n, int k, int q, const float* __restrict__ normals,
+                                                     int32_t* stamp, signed char* sgn, Ctl* ctl)
+{
+    const int prev = (q + 2) % 3, cur = q % 3;
+    const int level = next_level(__atomic_load_n(&ctl->level[prev], __ATOMIC_RELAXED), __atomic_load_n(&ctl->count[prev], __ATOMIC_RELAXED));
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        ctl->level[cur] = level;
+        ctl->count[(q + 1) % 3] = 0;
+        if (level < kLevels) ctl->rounds += 1;
+    }
+    if (level >= kLevels) return;   // the growth of this seed ended before this launch
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool did = false;
+    if (i < n && sgn[i] != 0 && stamp[i] == 0) {
+        float ni[3];
+        load3(normals, i, ni);
+        Choice c;
+        for (int s = 0; s < k; s++) {
+            const int32_t j = rows[(int64_t)s * n + i];
+            if (j < 0) break;
+            const int32_t st = __atomic_load_n(&stamp[j], __ATOMIC_RELAXED);
+            if (st > 0 && st < q) {   // (oriented before this launch: its sign byte is final; tested here to spare the loads of the others)
+                float nj[3];
+                load3(normals, j, nj);
+                if (is_source(st, q, nj)) c.offer(ni, nj, (int)sgn[j]);
+            }
+        }
+        if (c.accepted(level)) {
+            sgn[i] = (signed char)c.sign();
+            __atomic_store_n(&stamp[i], q, __ATOMIC_RELAXED);
+            did = true;
+        }
+    }
+    const unsigned cnt = wave_count(did);
+    if ((threadIdx.x & 63) == 0 && cnt) {
+        atomicAdd(&ctl->count[cur], cnt);
+        atomicAdd(&ctl->per_level[level], (unsigned long long)cnt);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_or_finish(int64_t n, float* __restrict__ normals, const int32_t* __restrict__ stamp,
+                                                      const signed char* __restrict__ sgn, Ctl* ctl)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool flip = false, unreached = false;
+    if (i < n) {
+        const signed char s = sgn[i];
+        flip = s < 0;
+        unreached = s != 0 && stamp[i] == 0;
+        if (flip)
+            for (int a = 0; a < 3; a++) normals[3 * i + a] = flipped(normals[3 * i + a]);
+    }
+    const unsigned cf = wave_count(flip), cu = wave_count(unreached);
+    if ((threadIdx.x & 63) == 0) {
+        if (cf) atomicAdd(&ctl->flipped, (unsigned long long)cf);
+        if (cu) atomicAdd(&ctl->unreached, (unsigned long long)cu);
+    }
+}
+
+hipError_t read_ctl(Ctl* host, const Ctl* dev)
+{
+    hipError_t e = hipMemcpyAsync(host, dev, sizeof(Ctl), hipMemcpyDeviceToHost, g.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    return e;
+}
+
+int orient(const sdfk_points* s, int k, float max_distance, int64_t max_seeds, float* normals, int64_t stats[9])
+{
+    static const char* who = "sdfk_points_orient_normals";
+    const int64_t n = s->n;
+    int32_t* rows = nullptr;
+    int32_t* stamp = nullptr;
+    signed char* sgn = nullptr;
+    Ctl* ctl = nullptr;
+    Ctl host{};
+    int r = dev_alloc((void**)&rows, (size_t)n * (size_t)k * sizeof(int32_t));
+    if (!r) r = dev_alloc((void**)&stamp, (size_t)n * sizeof(int32_t));
+    if (!r) r = dev_alloc((void**)&sgn, (size_t)n);
+    if (!r) r = dev_alloc((void**)&ctl, sizeof(Ctl));
+    hipError_t e = hipSuccess;
+    if (!r) e = hipMemsetAsync(ctl, 0, sizeof(Ctl), g.stream);
+    if (!r && e == hipSuccess) {
+        ProfScope ps("k_or_rows");
+        const float d2b = radius_d2_bound(max_distance);
+        switch (tier_of(k)) {
+        case 8: hipLaunchKernelGGL(k_or_rows<8>, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, normals, rows, stamp, sgn, ctl); break;
+        case 16: hipLaunchKernelGGL(k_or_rows<16>, dim3(grid_of(n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, normals, rows, stamp, sgn, ctl); break;
+        case 32: hipLaunchKernelGGL(k_or_rows<32>, dim3(grid_of(n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, normals, rows, stamp, sgn, ctl); break;
+        default: hipLaunchKernelGGL(k_or_rows<64>, dim3(grid_of(n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, normals, rows, stamp, sgn, ctl); break;
+        }
+        e = hipGetLastError();
+    }
+    const unsigned blocks = grid_of(n, kBlock);
+    int64_t q = 0;   // launches numbered so far
+    while (!r && e == hipSuccess) {
+        {
+            ProfScope ps("k_or_seed");
+            q++;
+            hipLaunchKernelGGL(k_or_seed_find, dim3((unsigned)grid_for((size_t)n, kBlock, 2048)), dim3(kBlock), 0, g.stream, s->xyz, n, stamp, sgn, ctl);
+            hipLaunchKernelGGL(k_or_seed_apply, dim3(1), dim3(64), 0, g.stream, (int)q, normals, stamp, sgn, ctl);
+            e = hipGetLastError();
+        }
+        while (e == hipSuccess) {   // this seed's growth, a batch at a time
+            {
+                ProfScope ps("k_or_round");
+                for (int b = 0; b < kBatch; b++) {
+                    q++;
+                    hipLaunchKernelGGL(k_or_round, dim3(blocks), dim3(kBlock), 0, g.stream, rows, n, k, (int)q, normals, stamp, sgn, ctl);
+                }
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = read_ctl(&host, ctl);
+            if (e != hipSuccess || host.level[q % 3] >= kLevels) break;   // the last queued round found the growth over
+            if (q > (int64_t(1) << 30)) { r = fail(SDFK_ERR_INVALID, "%s: 2^30 rounds without an end", who); break; }
+        }
+        if (r || e != hipSuccess) break;
+        unsigned long long oriented = host.seeds;
+        for (int l = 0; l < kLevels; l++) oriented += host.per_level[l];
+        if (oriented >= host.valid || (int64_t)host.seeds >= max_seeds) break;
+        if (q > (int64_t(1) << 30)) { r = fail(SDFK_ERR_INVALID, "%s: 2^30 rounds without an end", who); break; }
+    }
+    if (!r && e == hipSuccess) {
+        ProfScope ps("k_or_finish");
+        hipLaunchKernelGGL(k_or_finish, dim3(blocks), dim3(kBlock), 0, g.stream, n, normals, stamp, sgn, ctl);
+        e = hipGetLastError();
+        if (e == hipSuccess && stats) {
+            e = read_ctl(&host, ctl);
+            stats[0] = (int64_t)host.rounds;
+            stats[1] = (int64_t)host.seeds;
+            stats[2] = (int64_t)host.flipped;
+            stats[3] = (int64_t)host.unreached;
+            stats[4] = n - (int64_t)host.valid;
+            for (int l = 0; l < kLevels; l++) stats[5 + l] = (int64_t)host.per_level[l];
+        }
+    }
+    dev_free(rows); dev_free(stamp); dev_free(sgn); dev_free(ctl);   // (stream-ordered pool)
+    if (r) return r;
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return SDFK_OK;
+}
+
+int check_orient(const sdfk_points* s, int32_t k, float max_distance, int32_t max_seeds, const void* normals, int64_t stats[9])
+{
+    static const char* who = "sdfk_points_orient_normals";
+    if (int r = require_init()) return r;
+    if (!s) return fail(SDFK_ERR_INVALID, "%s: null point set", who);
+    if (k < kMinK || k > kMaxK) return fail(SDFK_ERR_INVALID, "%s: k = %d is outside [%d, %d]", who, (int)k, kMinK, kMaxK);
+    if (!radius_is_valid(max_distance)) return fail(SDFK_ERR_INVALID, "%s: max_distance is negative or NaN", who);
+    if (max_seeds < 1) return fail(SDFK_ERR_INVALID, "%s: max_seeds = %d, at least 1 is needed", who, (int)max_seeds);
+    if (!normals) return fail(SDFK_ERR_INVALID, "%s: null normals", who);
+    if (stats)
+        for (int i = 0; i < 9; i++) stats[i] = 0;
+    return SDFK_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// entry points
+// ---------------------------------------------------------------------------------------------------------------------------
+extern "C" int sdfk_points_orient_normals_device(const sdfk_points* s, int32_t k, float max_distance, int32_t max_seeds, void* normals3_dev,
+                                                 int64_t stats[9])
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_orient(s, k, max_distance, max_seeds, normals3_dev, stats)) return r;
+    return orient(s, k, max_distance, max_seeds, (float*)normals3_dev, stats);
+}
+
+extern "C" int sdfk_points_orient_normals(const sdfk_points* s, int32_t k, float max_distance, int32_t max_seeds, float* normals3, int64_t stats[9])
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_orient(s, k, max_distance, max_seeds, normals3, stats)) return r;
+    const size_t bytes = (size_t)s->n * 3 * sizeof(float);
+    float* nd = nullptr;
+    int r = dev_alloc((void**)&nd, bytes);
+    hipError_t e = hipSuccess;
+    if (!r) e = hipMemcpyAsync(nd, normals3, bytes, hipMemcpyHostToDevice, g.stream);
+    if (!r && e == hipSuccess) r = orient(s, k, max_distance, max_seeds, nd, stats);
+    if (!r && e == hipSuccess) e = hipMemcpyAsync(normals3, nd, bytes, hipMemcpyDeviceToHost, g.stream);
+    const hipError_t es = hipStreamSynchronize(g.stream);
+    dev_free(nd);
+    if (r) return r;
+    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_orient_normals: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    return SDFK_OK;
+}

@@ -3,8 +3,8 @@ entry points sdfk_points_* / sdfk_icp_* (include/sdfkit_hip.h, csrc/lib_points.h
 
 Vector3 is a float32 numpy array of 3; a span of Vector3 is an (n, 3) float32 array.  The search is exact (the static
 point of least d2, ties to the lowest insertion index; SearchKNearest and
-SearchRadius extend it to the k nearest and to all within a radius, in the same (d2, index) order; EstimateNormals and ToVoxels
-turn the points into normals and a signed distance volume); the structure behind it is a grid of cell lists on the device,
+SearchRadius extend it to the k nearest and to all within a radius, in the same (d2, index) order; EstimateNormals, OrientNormals
+and ToVoxels turn the points into normals, orient them consistently and make a signed distance volume); the structure behind it is a grid of cell lists on the device,
 so the reference's tree internals -- Left, Right, SplitValue, IsLeaf -- are not provided.  SplitAxis is kept as given.
 """
 import ctypes as C
@@ -107,8 +107,8 @@ class KdTree:
         covariance and the surface variation lmin / (l0 + l1 + l2) (include/sdfkit_hip.h, "Point clouds").  A point with fewer
         than 3 neighbours, or all of them equal, gets (0, 0, 0) and 0.
         viewpoint: one Vector3, or one per point -- each normal is turned towards it.  Without one the component of largest
-        magnitude is made positive, which is NOT a consistent orientation of a closed surface: propagating one along a spanning
-        tree of the neighbourhood graph is out of scope here; scans know their sensor position, meshes their normals."""
+        magnitude is made positive, which is NOT a consistent orientation of a closed surface: OrientNormals makes one of these
+        normals afterwards."""
         n = self.TotalPoints
         view = None if viewpoint is None else _points(viewpoint)
         nrm = np.empty((n, 3), f32)
@@ -116,6 +116,23 @@ class KdTree:
         N.check(N.lib().sdfk_points_normals(self._h, int(k), float(f32(maxDistance)), _ptr(view), 0 if view is None else len(view),
                                             _ptr(nrm), _ptr(var)))
         return nrm, var
+
+    def OrientNormals(self, normals, k=8, maxDistance=np.inf, maxSeeds=64, stats=None):
+        """Extension: `normals` (one per static point) with the sign of some flipped, so that neighbouring normals agree and the top
+        of every connected piece points up -> (n, 3) float32, bit-identical to the input up to sign (the input is not modified).
+        A deterministic region growing over the k-nearest graph (2 <= k <= 64, no farther than maxDistance), confident edges first,
+        from at most maxSeeds seeds (include/sdfkit_hip.h, "Point clouds: a consistent orientation").  Normals that are not finite
+        or all zero are left alone, and so are those no seed reached.  It trusts that the k nearest of a point lie on the same
+        sheet of the surface.  stats: a dict that receives rounds, seeds, flipped, unreached, invalid, levels (a list of 4)."""
+        nrm = _points(normals).copy()
+        if len(nrm) != self.TotalPoints:
+            raise ValueError("one normal per static point (normals)")
+        st = (C.c_int64 * 9)()
+        N.check(N.lib().sdfk_points_orient_normals(self._h, int(k), float(f32(maxDistance)), int(maxSeeds), _ptr(nrm), st))
+        if stats is not None:
+            stats.update(rounds=int(st[0]), seeds=int(st[1]), flipped=int(st[2]), unreached=int(st[3]), invalid=int(st[4]),
+                         levels=[int(v) for v in st[5:9]])
+        return nrm
 
     def ToVoxels(self, normals, min, max, nx, ny, nz, k=8, maxDistance=np.inf, clipToBounds=False, stats=None):
         """Extension: the point cloud with `normals` (one per static point, pointing outside) as a signed distance volume at the

@@ -100,7 +100,7 @@ namespace SdfKit
         /// <summary>Extension: a normal per static point (insertion order) from its k nearest (3..64, itself included, no farther than
         /// maxDistance): the eigenvector of the least eigenvalue of the neighbourhood's covariance, and the surface variation
         /// lmin / (l0 + l1 + l2).  viewpoints: empty (the largest component is made positive -- not a consistent orientation of
-        /// a closed surface, which is out of scope), one for all points, or one per point; each normal is turned towards its
+        /// a closed surface: OrientNormals makes one afterwards), one for all points, or one per point; each normal is turned towards its
         /// viewpoint.  Degenerate neighbourhoods give (0, 0, 0) and 0.</summary>
         public unsafe void EstimateNormals (int k, Span<Vector3> normals, Span<float> variation, ReadOnlySpan<Vector3> viewpoints = default,
                                             float maxDistance = float.PositiveInfinity)
@@ -112,6 +112,25 @@ namespace SdfKit
                 throw new ArgumentException ("Output spans are shorter than the static points");
             fixed (Vector3* v = viewpoints) fixed (Vector3* o = normals) fixed (float* w = variation)
                 Native.Check (Native.sdfk_points_normals (handle, k, maxDistance, (float*)v, viewpoints.Length, (float*)o, w));
+        }
+
+        /// <summary>Extension: flips the sign of some of `normals` (one per static point, in place) so that neighbouring normals agree
+        /// and the top of every connected piece points up: a deterministic region growing over the k-nearest graph (k in 2..64, no
+        /// farther than maxDistance), confident edges first, from at most maxSeeds seeds.  Normals that are not finite or all zero,
+        /// and those no seed reached, are left alone.  Returns the stats: rounds, seeds, flipped, unreached, invalid and the
+        /// points oriented at each of the four levels.</summary>
+        public unsafe long[] OrientNormals (Span<Vector3> normals, int k = 8, float maxDistance = float.PositiveInfinity, int maxSeeds = 64)
+        {
+            if (k < 2 || k > 64)
+                throw new ArgumentOutOfRangeException (nameof (k), "k must be in 2..64");
+            if (maxSeeds < 1)
+                throw new ArgumentOutOfRangeException (nameof (maxSeeds), "maxSeeds must be at least 1");
+            if (normals.Length != TotalPoints)
+                throw new ArgumentException ("One normal per static point", nameof (normals));
+            var stats = new long[9];
+            fixed (Vector3* nrm = normals) fixed (long* st = stats)
+                Native.Check (Native.sdfk_points_orient_normals (handle, k, maxDistance, maxSeeds, (float*)nrm, st));
+            return stats;
         }
 
         /// <summary>Extension: the static points with one outward normal each as a signed distance volume: the blend of the

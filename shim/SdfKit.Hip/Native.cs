@@ -115,6 +115,9 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_points_to_volume(IntPtr points, float* normals3, IntPtr volume, int k, float maxDistance, long* stats4);
         [DllImport(Lib)] public static extern int sdfk_points_to_volume_device(IntPtr points, IntPtr normals3Dev, IntPtr volume, int k, float maxDistance,
                                                                                long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_points_orient_normals(IntPtr points, int k, float maxDistance, int maxSeeds, float* normals3, long* stats9);
+        [DllImport(Lib)] public static extern int sdfk_points_orient_normals_device(IntPtr points, int k, float maxDistance, int maxSeeds, IntPtr normals3Dev,
+                                                                                    long* stats9);
         [DllImport(Lib)] public static extern void sdfk_points_free(IntPtr points);
         [DllImport(Lib)] public static extern int sdfk_icp_register(IntPtr points, ref SdfkIcpParams prm, float* points3, long n, float* total16, out int iterations);
         [DllImport(Lib)] public static extern int sdfk_icp_register_device(IntPtr points, ref SdfkIcpParams prm, IntPtr points3Dev, long n, float* total16,
