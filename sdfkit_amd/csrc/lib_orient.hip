@@ -1,8 +1,8 @@
 // lib_orient.hip -- a consistent orientation of point-cloud normals (sdfk_points_orient_normals*): a parallel, deterministic
 // region growing over the k-nearest graph, confident edges first.  Contract: include/sdfkit_hip.h, "Point clouds: a consistent
 // orientation"; the decisions (validity, dot, the seed's order and sign, one point's choice from its row, the level rule):
-// points_orient.h, checked on the host; the walk and the bounded lists: points_walk.h / points_knn.h, shared with
-// lib_points_knn.hip and lib_pointcloud.hip.
+// points_orient.h, checked on the host; the walk, the tiers and the bounded lists: points_walk.h / points_knn.h, shared with every
+// query of the KdTree.
 //
 //   k_or_rows<CAP>   one lane per static point: its k nearest exactly as k_pts_knn<CAP> finds them (the same tiers), written once
 //                    for the call as SLOT-MAJOR rows (slot * n + point; -1 from the count on): in a round lane i reads slot s of
@@ -34,7 +34,7 @@ namespace {
 using namespace sdfk_walk;
 using namespace sdfk_orient;
 
-constexpr int kBatch = 32;   // rounds queued between two reads of the control block (tests/test_gpu_orient.py BATCH restates it: keep them equal)
+constexpr int kBatch = 32;   // rounds queued between two reads of the control block (tests/test_gpu_orient.py BATCH repeats it: keep them equal)
 
 struct Ctl {
     unsigned long long seed_key;             // k_or_seed_find's maximum; 0: no candidate (cleared by k_or_seed_apply)
@@ -45,16 +45,6 @@ struct Ctl {
     int level[3];                            // ring by launch number: the level launch q ran at (kLevels: growth over)
     unsigned count[3];                       // ring: the points launch q oriented
 };
-
-template <int CAP>
-constexpr int block_of() { return CAP == 8 ? kBlock : kLdsBlock; }
-template <int CAP>
-constexpr int lds_keys() { return CAP == 8 ? 1 : CAP * kLdsBlock; }   // (the register tier keeps no keys in LDS)
-
-__device__ __forceinline__ void load3(const float* a, int64_t i, float out[3])
-{
-    out[0] = a[3 * i]; out[1] = a[3 * i + 1]; out[2] = a[3 * i + 2];
-}
 
 __device__ __forceinline__ unsigned wave_count(bool flag) { return (unsigned)__popcll(__ballot(flag)); }
 
@@ -211,12 +201,9 @@ int orient(const sdfk_points* s, int k, float max_distance, int64_t max_seeds, f
     if (!r && e == hipSuccess) {
         ProfScope ps("k_or_rows");
         const float d2b = radius_d2_bound(max_distance);
-        switch (tier_of(k)) {
-        case 8: hipLaunchKernelGGL(k_or_rows<8>, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, normals, rows, stamp, sgn, ctl); break;
-        case 16: hipLaunchKernelGGL(k_or_rows<16>, dim3(grid_of(n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, normals, rows, stamp, sgn, ctl); break;
-        case 32: hipLaunchKernelGGL(k_or_rows<32>, dim3(grid_of(n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, normals, rows, stamp, sgn, ctl); break;
-        default: hipLaunchKernelGGL(k_or_rows<64>, dim3(grid_of(n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, normals, rows, stamp, sgn, ctl); break;
-        }
+        launch_tier(k, n, [&](auto cap, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL(k_or_rows<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, normals, rows, stamp, sgn, ctl);
+        });
         e = hipGetLastError();
     }
     const unsigned blocks = grid_of(n, kBlock);
@@ -301,16 +288,8 @@ extern "C" int sdfk_points_orient_normals(const sdfk_points* s, int32_t k, float
     StateScope in_owner_context(s ? s->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (int r = check_orient(s, k, max_distance, max_seeds, normals3, stats)) return r;
-    const size_t bytes = (size_t)s->n * 3 * sizeof(float);
-    float* nd = nullptr;
-    int r = dev_alloc((void**)&nd, bytes);
-    hipError_t e = hipSuccess;
-    if (!r) e = hipMemcpyAsync(nd, normals3, bytes, hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) r = orient(s, k, max_distance, max_seeds, nd, stats);
-    if (!r && e == hipSuccess) e = hipMemcpyAsync(normals3, nd, bytes, hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(nd);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_orient_normals: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    Staged st;
+    float* nd = st.inout(normals3, (size_t)s->n * 3);
+    st.run([&] { return orient(s, k, max_distance, max_seeds, nd, stats); });
+    return st.finish("sdfk_points_orient_normals");
 }

@@ -1,7 +1,7 @@
 // lib_pointcloud.hip -- the KdTree's point cloud as geometry: normals (sdfk_points_normals*) and signed distance volumes
 // (sdfk_points_to_volume*).  Contract: include/sdfkit_hip.h, "Point clouds: normals and volumes"; the arithmetic (covariance,
 // Jacobi eigenvectors, orientation, the blend of tangent-plane distances, the fill of one line): points_normals.h, checked on the
-// host; the walk and the bounded lists: points_walk.h / points_knn.h, shared with lib_points_knn.hip.
+// host; the walk, the tiers and the bounded lists: points_walk.h / points_knn.h, shared with every query of the KdTree.
 //
 //   k_pc_normals<CAP>   one lane per static point: its k nearest (itself included) exactly as k_pts_knn<CAP> finds them -- CAP = 8
 //                       in registers, 16 / 32 / 64 a heap in LDS, one wave per block --, then two passes over the list (mean,
@@ -24,16 +24,6 @@ namespace {
 
 using namespace sdfk_walk;
 using namespace sdfk_pc;
-
-template <int CAP>
-constexpr int block_of() { return CAP == 8 ? kBlock : kLdsBlock; }
-template <int CAP>
-constexpr int lds_keys() { return CAP == 8 ? 1 : CAP * kLdsBlock; }   // (the register tier keeps no keys in LDS)
-
-__device__ __forceinline__ void load3(const float* __restrict__ a, int64_t i, float out[3])
-{
-    out[0] = a[3 * i]; out[1] = a[3 * i + 1]; out[2] = a[3 * i + 2];
-}
 
 // ---- normals -------------------------------------------------------------------------------------------------------------------
 struct NormalsArgs {
@@ -183,12 +173,9 @@ int normals_launch(const sdfk_points* s, int k, float d2_bound, const float* vie
     NormalsArgs A{s->xyz, s->n, k, d2_bound, view_dev, n_view, normals_dev, variation_dev, cand.dev};
     {
         ProfScope ps("k_pc_normals");
-        switch (tier_of(k)) {
-        case 8: hipLaunchKernelGGL(k_pc_normals<8>, dim3(grid_of(s->n, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
-        case 16: hipLaunchKernelGGL(k_pc_normals<16>, dim3(grid_of(s->n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
-        case 32: hipLaunchKernelGGL(k_pc_normals<32>, dim3(grid_of(s->n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
-        default: hipLaunchKernelGGL(k_pc_normals<64>, dim3(grid_of(s->n, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
-        }
+        launch_tier(k, s->n, [&](auto cap, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL(k_pc_normals<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, A);
+        });
     }
     hipError_t e = hipGetLastError();
     const hipError_t ec = cand.end(s, s->n);
@@ -232,12 +219,9 @@ int to_volume(const sdfk_points* s, const float* normals_dev, sdfk_volume* v, in
                      k, radius_d2_bound(max_distance), max_distance, known, cand.dev};
         {
             ProfScope ps("k_pc_volume");
-            switch (tier_of(k)) {
-            case 8: hipLaunchKernelGGL(k_pc_volume<8>, dim3(grid_of(nvox, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
-            case 16: hipLaunchKernelGGL(k_pc_volume<16>, dim3(grid_of(nvox, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
-            case 32: hipLaunchKernelGGL(k_pc_volume<32>, dim3(grid_of(nvox, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
-            default: hipLaunchKernelGGL(k_pc_volume<64>, dim3(grid_of(nvox, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, A); break;
-            }
+            launch_tier(k, nvox, [&](auto cap, dim3 grid, dim3 block) {
+                hipLaunchKernelGGL(k_pc_volume<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, A);
+            });
         }
         e = hipGetLastError();
         if (e == hipSuccess) {
@@ -301,26 +285,12 @@ extern "C" int sdfk_points_normals(const sdfk_points* s, int32_t k, float max_di
     if (int r = check_normals(s, k, max_distance, viewpoints3, n_viewpoints)) return r;
     for (int64_t i = 0; i < 3 * n_viewpoints; i++)
         if (!std::isfinite(viewpoints3[i])) return fail(SDFK_ERR_INVALID, "sdfk_points_normals: viewpoint %lld has a NaN or infinite coordinate", (long long)(i / 3));
-    const int64_t n = s->n;
-    float* vd = nullptr;
-    float* nd = nullptr;
-    float* wd = nullptr;
-    int r = SDFK_OK;
-    if (n_viewpoints) r = dev_alloc((void**)&vd, (size_t)n_viewpoints * 3 * sizeof(float));
-    if (!r && normals3) r = dev_alloc((void**)&nd, (size_t)n * 3 * sizeof(float));
-    if (!r && variation) r = dev_alloc((void**)&wd, (size_t)n * sizeof(float));
-    hipError_t e = hipSuccess;
-    if (!r && vd) e = hipMemcpyAsync(vd, viewpoints3, (size_t)n_viewpoints * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) r = normals_launch(s, k, radius_d2_bound(max_distance), vd, n_viewpoints, nd, wd);
-    if (!r && e == hipSuccess && nd) e = hipMemcpyAsync(normals3, nd, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && wd) e = hipMemcpyAsync(variation, wd, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(vd);
-    dev_free(nd);
-    dev_free(wd);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_normals: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    Staged st;
+    const float* vd = st.in(viewpoints3, (size_t)n_viewpoints * 3);
+    float* nd = st.out(normals3, (size_t)s->n * 3);
+    float* wd = st.out(variation, (size_t)s->n);
+    st.run([&] { return normals_launch(s, k, radius_d2_bound(max_distance), vd, n_viewpoints, nd, wd); });
+    return st.finish("sdfk_points_normals");
 }
 
 extern "C" int sdfk_points_to_volume_device(const sdfk_points* s, const void* normals3_dev, sdfk_volume* v, int32_t k, float max_distance,
@@ -337,14 +307,8 @@ extern "C" int sdfk_points_to_volume(const sdfk_points* s, const float* normals3
     StateScope in_owner_context(s ? s->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (int r = check_volume(s, normals3, v, k, max_distance)) return r;
-    float* nd = nullptr;
-    int r = dev_alloc((void**)&nd, (size_t)s->n * 3 * sizeof(float));
-    hipError_t e = hipSuccess;
-    if (!r) e = hipMemcpyAsync(nd, normals3, (size_t)s->n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) r = to_volume(s, nd, v, k, max_distance, stats);
-    const hipError_t es = hipStreamSynchronize(g.stream);   // (the caller's array is not retained)
-    dev_free(nd);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_to_volume: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    Staged st;
+    const float* nd = st.in(normals3, (size_t)s->n * 3);   // (the caller's array is not retained)
+    st.run([&] { return to_volume(s, nd, v, k, max_distance, stats); });
+    return st.finish("sdfk_points_to_volume");
 }

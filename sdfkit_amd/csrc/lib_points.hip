@@ -5,8 +5,9 @@
 //   bounds (+ the non-finite check) -> cell key per point and per-cell counts (integer atomics) -> exclusive scan -> scatter into
 //   float4 (x, y, z, bits(index)) in cell order, so that one 16-byte load gives a candidate.
 // In-cell order comes from the atomics and varies from build to build; the (d2, index) rule makes every result independent of it.
-// Query: one lane per query; cells in growing Chebyshev shells around the query's cell (clamped to the grid), stopping when a
-// conservative f32 lower bound on the distance of every unvisited cell exceeds the best d2.  Queries run in the caller's order:
+// Query: one lane per query on the shell walk that every query of the KdTree runs (points_walk.h): cells in growing Chebyshev
+// shells around the query's cell (clamped to the grid); k_pts_search's visitor keeps the least (d2, index) and stops the walk when
+// the conservative f32 lower bound on the d2 of every unvisited cell exceeds it.  Queries run in the caller's order:
 // processing them in the order of a coarse counting sort of their cells was measured slower for mesh vertices, whose order is
 // already spatially coherent, and 5 % faster only for random queries (profiles/points_ab_query_order.txt).  Grid sizing and cell
 // assignment: points_grid.h.
@@ -20,6 +21,7 @@
 #include "device_scan.h"
 #include "points_grid.h"
 #include "points_set.h"
+#include "points_walk.h"
 #include "icp_solve.h"
 
 #include <cfloat>
@@ -111,97 +113,40 @@ struct SearchOut {
 struct IcpState;
 __device__ __forceinline__ bool icp_stopped(const IcpState* S, int iter);
 
-__device__ __forceinline__ float lb_sq(const float gap[3][2], const float base2[3])
-{
-    float best = INFINITY;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const float rest = base2[(a + 1) % 3] + base2[(a + 2) % 3];
-        const float gm = fminf(gap[a][0], gap[a][1]);
-        best = fminf(best, gm * gm + rest);
+// what the walk keeps for the nearest point: the least (d2, index) and that point's coordinates
+struct NearestVisitor {
+    float best;
+    int bi;
+    float bx, by, bz;
+    __device__ __forceinline__ void take(float d2, const float4& s)
+    {
+        const int id = __float_as_int(s.w);
+        if (d2 < best || (d2 == best && id < bi)) { best = d2; bi = id; bx = s.x; by = s.y; bz = s.z; }
     }
-    return best;
-}
+    // (the FLT_MAX bound is the k-nearest rule's for "no radius", points_knn.h walk_done: a point counts iff d2 < +inf, so once the
+    // lower bound of every unvisited cell is +inf nothing that is left can be taken, found or not)
+    __device__ __forceinline__ bool done(float lb2) const { return lb2 * (1.0f - 0x1p-18f) > fminf(best, FLT_MAX); }
+};
 
-// One lane per query.  `icp` / `iter`: ICP iterations exit once the registration stopped.
-// lib_points_knn.hip restates this walk (lb_sq, slack, the shells, the 2^-18 margin) for the k-nearest and radius queries: a change
-// to any of them here has to be made there too (tests: k = 1 of sdfk_points_knn equals this kernel bit for bit).
+// One lane per query.  `icp` / `iter`: ICP iterations exit once the registration stopped.  A query without a nearest point
+// (non-finite, or every d2 overflows) gets index -1, distance FLT_MAX and the first static point (fx, fy, fz).
 __global__ __launch_bounds__(kBlock) void k_pts_search(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
                                                        float fx, float fy, float fz, const float* __restrict__ queries, int64_t nq,
                                                        SearchOut O, const IcpState* icp, int iter)
 {
     if (icp && icp_stopped(icp, iter)) return;
     const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool active = t < nq;   // (every lane stays for the candidate count's shuffle)
-    const int64_t qi = active ? t : 0;
-    const float qx = active ? queries[3 * qi] : NAN, qy = active ? queries[3 * qi + 1] : NAN, qz = active ? queries[3 * qi + 2] : NAN;
-    float best = INFINITY;
-    int bi = -1;
-    float bx = fx, by = fy, bz = fz;
+    const sdfk_walk::Query q = sdfk_walk::load_query(queries, t, nq);
+    NearestVisitor v{INFINITY, -1, fx, fy, fz};
     unsigned long long ncand = 0;
-    if (isfinite(qx) && isfinite(qy) && isfinite(qz)) {
-        const float q[3] = {qx, qy, qz};
-        int c[3];
-        (void)key_of(G, qx, qy, qz, &c[0], &c[1], &c[2]);
-        const float slack = G.slack + fmaxf(fabsf(qx), fmaxf(fabsf(qy), fabsf(qz))) * 0x1p-20f;
-        float base2[3];
-        int rmax = 0;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            const float out = fmaxf(fmaxf(G.lo[a] - q[a], q[a] - G.hi[a]) - slack, 0.0f);
-            base2[a] = out * out;
-            rmax = max(rmax, max(c[a], G.dim[a] - 1 - c[a]));
-        }
-        const int gx = G.dim[0], gy = G.dim[1];
-        for (int r = 0; r <= rmax; r++) {
-            const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, G.dim[2] - 1);
-            const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, gy - 1);
-            const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, gx - 1);
-            for (int z = z0; z <= z1; z++) {
-                const bool zf = z == c[2] - r || z == c[2] + r;
-                for (int y = y0; y <= y1; y++) {
-                    const bool full = zf || y == c[1] - r || y == c[1] + r;
-                    const uint32_t row = ((uint32_t)z * (uint32_t)gy + (uint32_t)y) * (uint32_t)gx;
-                    // a full row of the shell is one contiguous range of the sorted points; otherwise its two end cells
-                    for (int part = 0; part < (full ? 1 : 2); part++) {
-                        int xa, xb;
-                        if (full) { xa = x0; xb = x1; }
-                        else {
-                            xa = xb = part == 0 ? c[0] - r : c[0] + r;
-                            if (xa < 0 || xa >= gx) continue;
-                        }
-                        const uint32_t j0 = starts[row + (uint32_t)xa], j1 = starts[row + (uint32_t)xb + 1];
-                        ncand += j1 - j0;
-                        for (uint32_t j = j0; j < j1; j++) {
-                            const float4 s = sorted[j];
-                            const float dx = qx - s.x, dy = qy - s.y, dz = qz - s.z;
-                            const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-                            const int id = __float_as_int(s.w);
-                            if (d2 < best || (d2 == best && id < bi)) { best = d2; bi = id; bx = s.x; by = s.y; bz = s.z; }
-                        }
-                    }
-                }
-            }
-            // every unvisited cell lies beyond shell r along some axis: the least distance it can have, made conservative
-            float gap[3][2];
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                gap[a][0] = c[a] - r - 1 >= 0 ? fmaxf(q[a] - (G.lo[a] + (float)(c[a] - r) * G.h) - slack, 0.0f) : INFINITY;
-                gap[a][1] = c[a] + r + 1 < G.dim[a] ? fmaxf((G.lo[a] + (float)(c[a] + r + 1) * G.h) - q[a] - slack, 0.0f) : INFINITY;
-            }
-            if (lb_sq(gap, base2) * (1.0f - 0x1p-18f) > best) break;
-        }
-    }
-    const float dist = bi < 0 ? FLT_MAX : (float)__builtin_sqrt((double)best);   // (correctly rounded sqrtf)
-    if (O.candidates) {
-        for (int o = 32; o > 0; o >>= 1) ncand += __shfl_down(ncand, o);
-        if ((threadIdx.x & 63) == 0) atomicAdd(O.candidates, ncand);
-    }
-    if (!active) return;
-    if (O.index) O.index[qi] = bi;
-    if (O.distance) O.distance[qi] = dist;
-    if (O.nearest3) { O.nearest3[3 * qi] = bx; O.nearest3[3 * qi + 1] = by; O.nearest3[3 * qi + 2] = bz; }
-    if (O.cor) O.cor[qi] = make_float4(bx, by, bz, dist);
+    if (q.finite) ncand = sdfk_walk::shell_walk(sorted, starts, G, q.x, q.y, q.z, v);
+    const float dist = v.bi < 0 ? FLT_MAX : (float)__builtin_sqrt((double)v.best);   // (correctly rounded sqrtf)
+    sdfk_walk::add_candidates(O.candidates, ncand);   // (every lane stays for the shuffle)
+    if (t >= nq) return;
+    if (O.index) O.index[t] = v.bi;
+    if (O.distance) O.distance[t] = dist;
+    if (O.nearest3) { O.nearest3[3 * t] = v.bx; O.nearest3[3 * t + 1] = v.by; O.nearest3[3 * t + 2] = v.bz; }
+    if (O.cor) O.cor[t] = make_float4(v.bx, v.by, v.bz, dist);
 }
 
 // ---- ICP --------------------------------------------------------------------------------------------------------------------
@@ -540,7 +485,7 @@ unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlock - 
 // ---------------------------------------------------------------------------------------------------------------------------
 // the handle
 // ---------------------------------------------------------------------------------------------------------------------------
-// struct sdfk_points: points_set.h (shared with lib_points_knn.hip)
+// struct sdfk_points: points_set.h (shared with the other query files)
 
 namespace {
 
@@ -625,28 +570,18 @@ int points_build(sdfk_points* s, const char* who)
 // Queues the search of nq device queries (caller order in and out).  `icp`/`iter`: the launch of an ICP iteration.
 int points_search_launch(const sdfk_points* s, const float* q, int64_t nq, SearchOut O, const IcpState* icp, int iter)
 {
-    unsigned long long* cand = nullptr;
-    int r = SDFK_OK;
-    if (g.prof_on && !icp) {
-        r = dev_alloc((void**)&cand, sizeof(unsigned long long));
-        if (!r && hipMemsetAsync(cand, 0, sizeof(unsigned long long), g.stream) != hipSuccess) r = fail(SDFK_ERR_HIP, "points search: memset");
-        if (r) { dev_free(cand); return r; }
-        O.candidates = cand;
-    }
+    sdfk_walk::Candidates cand;   // (not counted for ICP's launches)
+    if (!icp)
+        if (int r = cand.begin()) return r;
+    O.candidates = cand.dev;
     {
         ProfScope ps("k_pts_search");
         hipLaunchKernelGGL(k_pts_search, dim3(grid1(nq)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, s->first[0], s->first[1],
                            s->first[2], q, nq, O, icp, iter);
     }
     hipError_t e = hipGetLastError();
-    if (cand) {
-        unsigned long long c = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&c, cand, sizeof c, hipMemcpyDeviceToHost, g.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-        const_cast<sdfk_points*>(s)->last_candidates = (int64_t)c;
-        const_cast<sdfk_points*>(s)->last_queries = nq;
-        dev_free(cand);
-    }
+    const hipError_t ec = cand.end(s, nq);
+    if (e == hipSuccess) e = ec;
     if (e != hipSuccess) return fail(SDFK_ERR_HIP, "points search: %s", hipGetErrorString(e));
     return SDFK_OK;
 }
@@ -861,28 +796,11 @@ extern "C" int sdfk_points_search(const sdfk_points* s, const float* queries3, i
     if (!s || n < 0 || (n > 0 && !queries3)) return fail(SDFK_ERR_INVALID, "sdfk_points_search: null / negative argument");
     if (n >= (int64_t(1) << 32)) return fail(SDFK_ERR_INVALID, "sdfk_points_search: 2^32 queries or more");
     if (n == 0) return SDFK_OK;
-    float* qd = nullptr;
-    int32_t* id = nullptr;
-    float* dd = nullptr;
-    float* nd = nullptr;
-    int r = dev_alloc((void**)&qd, (size_t)n * 3 * sizeof(float));
-    if (!r && index) r = dev_alloc((void**)&id, (size_t)n * sizeof(int32_t));
-    if (!r && distance) r = dev_alloc((void**)&dd, (size_t)n * sizeof(float));
-    if (!r && nearest3) r = dev_alloc((void**)&nd, (size_t)n * 3 * sizeof(float));
-    hipError_t e = hipSuccess;
-    if (!r) e = hipMemcpyAsync(qd, queries3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) r = points_search_launch(s, qd, n, SearchOut{id, dd, nd, nullptr, nullptr}, nullptr, 0);
-    if (!r && e == hipSuccess && id) e = hipMemcpyAsync(index, id, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && dd) e = hipMemcpyAsync(distance, dd, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && nd) e = hipMemcpyAsync(nearest3, nd, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(qd);
-    dev_free(id);
-    dev_free(dd);
-    dev_free(nd);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_search: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    Staged st;
+    const float* qd = st.in(queries3, (size_t)n * 3);
+    const SearchOut O{st.out(index, (size_t)n), st.out(distance, (size_t)n), st.out(nearest3, (size_t)n * 3), nullptr, nullptr};
+    st.run([&] { return points_search_launch(s, qd, n, O, nullptr, 0); });
+    return st.finish("sdfk_points_search");
 }
 
 extern "C" int sdfk_icp_register_device(sdfk_points* s, const sdfk_icp_params* prm, void* points3_dev, int64_t n, float total[16],
@@ -901,17 +819,10 @@ extern "C" int sdfk_icp_register(sdfk_points* s, const sdfk_icp_params* prm, flo
     if (int r = icp_check(s, prm, points3, n, total, iterations)) return r;
     for (int64_t i = 0; i < 3 * n; i++)   // (as static sets are: nothing is touched)
         if (!std::isfinite(points3[i])) return fail(SDFK_ERR_INVALID, "sdfk_icp_register: dynamic point %lld has a NaN or infinite coordinate", (long long)(i / 3));
-    float* pd = nullptr;
-    int r = dev_alloc((void**)&pd, (size_t)n * 3 * sizeof(float));
-    hipError_t e = hipSuccess;
-    if (!r) e = hipMemcpyAsync(pd, points3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) r = icp_run(s, prm, nullptr, pd, n, total, iterations);
-    if (!r && e == hipSuccess) e = hipMemcpyAsync(points3, pd, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(pd);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_icp_register: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    Staged st;
+    float* pd = st.inout(points3, (size_t)n * 3);
+    st.run([&] { return icp_run(s, prm, nullptr, pd, n, total, iterations); });
+    return st.finish("sdfk_icp_register");
 }
 
 extern "C" int sdfk_icp_register_plane_device(sdfk_points* s, const sdfk_icp_params* prm, const void* normals3_dev, void* points3_dev, int64_t n,
@@ -935,27 +846,18 @@ extern "C" int sdfk_icp_register_plane(sdfk_points* s, const sdfk_icp_params* pr
         if (!std::isfinite(points3[i])) return fail(SDFK_ERR_INVALID, "sdfk_icp_register_plane: dynamic point %lld has a NaN or infinite coordinate", (long long)(i / 3));
     for (int64_t i = 0; i < 3 * s->n; i++)
         if (!std::isfinite(normals3[i])) return fail(SDFK_ERR_INVALID, "sdfk_icp_register_plane: normal %lld has a NaN or infinite component", (long long)(i / 3));
-    float* pd = nullptr;
-    float* nd = nullptr;
-    int r = dev_alloc((void**)&pd, (size_t)n * 3 * sizeof(float));
-    if (!r) r = dev_alloc((void**)&nd, (size_t)s->n * 3 * sizeof(float));
-    hipError_t e = hipSuccess;
-    if (!r) e = hipMemcpyAsync(pd, points3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) e = hipMemcpyAsync(nd, normals3, (size_t)s->n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    float tot[16];
+    Staged st;
+    float* pd = st.inout(points3, (size_t)n * 3);
+    const float* nd = st.in(normals3, (size_t)s->n * 3);
+    float tot[16];   // (the caller's results are written once everything, the copy back included, succeeded)
     int32_t iters = 0;
-    int64_t st[4] = {0, 0, 0, 0};
-    if (!r && e == hipSuccess) r = icp_run(s, prm, nd, pd, n, tot, &iters, st);
-    if (!r && e == hipSuccess) e = hipMemcpyAsync(points3, pd, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(pd);
-    dev_free(nd);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_icp_register_plane: %s", hipGetErrorString(e != hipSuccess ? e : es));
+    int64_t stt[4] = {0, 0, 0, 0};
+    st.run([&] { return icp_run(s, prm, nd, pd, n, tot, &iters, stt); });
+    if (int r = st.finish("sdfk_icp_register_plane")) return r;
     for (int q = 0; q < 16; q++) total[q] = tot[q];
     *iterations = iters;
     if (stats)
-        for (int q = 0; q < 4; q++) stats[q] = st[q];
+        for (int q = 0; q < 4; q++) stats[q] = stt[q];
     return SDFK_OK;
 }
 

@@ -2,8 +2,8 @@
 // cell lists that lib_points.hip builds.  Contract: include/sdfkit_hip.h, "k nearest / within a radius"; the arithmetic (packed
 // (d2, index) keys, bounded lists, radius predicate, stopping rule): points_knn.h, checked on the host.
 //
-// One lane per query, the shell walk of k_pts_search with the same `starts` / `sorted` reads; what differs is what a candidate
-// meets and when the walk stops:
+// One lane per query on the family's one shell walk (points_walk.h), the walk k_pts_search runs too; a kernel is the visitor it
+// hands the walk -- what a candidate meets and when the walk stops:
 //   k_pts_knn<CAP>       the k least keys within the radius bound; stops when the lower bound of every unvisited cell exceeds the
 //                        k-th key's d2 (+inf until k are held) or the radius bound.  CAP = 8: a sorted list in registers; CAP = 16 /
 //                        32 / 64: a max-heap in LDS, slot-major (slot * 64 + lane: conflict-free across the wave), ordered in place
@@ -33,53 +33,24 @@ struct KnnOut {
 };
 
 template <int CAP>
-__global__ __launch_bounds__(CAP == 8 ? kBlock : kLdsBlock) void k_pts_knn(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts,
-                                                                            Grid G, const float* __restrict__ queries, int64_t nq, int k,
-                                                                            float d2_bound, KnnOut O)
+__global__ __launch_bounds__(block_of<CAP>()) void k_pts_knn(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
+                                                              const float* __restrict__ queries, int64_t nq, int k, float d2_bound, KnnOut O)
 {
-    constexpr int B = CAP == 8 ? kBlock : kLdsBlock;
-    const int64_t t = (int64_t)blockIdx.x * B + threadIdx.x;
+    __shared__ uint64_t s_keys[lds_keys<CAP>()];
+    const int64_t t = (int64_t)blockIdx.x * block_of<CAP>() + threadIdx.x;
     const Query q = load_query(queries, t, nq);
-    unsigned long long ncand = 0;
-    int n_found = 0;
-    if constexpr (CAP == 8) {
-        KnnVisitor<SortedList<8>> v;
-        v.list.init(k);
-        v.bound_key = pack_key(d2_bound, -1);
-        v.d2_bound = d2_bound;
-        if (q.finite) ncand = shell_walk(sorted, starts, G, q.x, q.y, q.z, v);
-        n_found = v.list.count();
-        if (t < nq) {
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                if (i < k) {
-                    const uint64_t key = v.list.at(i);
-                    const bool real = key < kKeyInf;
-                    if (O.index) O.index[t * k + i] = real ? key_index(key) : -1;
-                    if (O.distance) O.distance[t * k + i] = real ? sqrt_rn(key_d2(key)) : FLT_MAX;
-                }
-            }
-        }
-    } else {
-        __shared__ uint64_t s_keys[CAP * kLdsBlock];
-        KnnVisitor<HeapList<LdsSlots>> v;
-        v.list.s.base = &s_keys[threadIdx.x];
-        v.list.init(k);
-        v.bound_key = pack_key(d2_bound, -1);
-        v.d2_bound = d2_bound;
-        if (q.finite) ncand = shell_walk(sorted, starts, G, q.x, q.y, q.z, v);
-        v.list.finish();
-        n_found = v.list.count();
-        if (t < nq) {
-            for (int i = 0; i < k; i++) {
-                const uint64_t key = v.list.at(i);
-                const bool real = key < kKeyInf;
-                if (O.index) O.index[t * k + i] = real ? key_index(key) : -1;
-                if (O.distance) O.distance[t * k + i] = real ? sqrt_rn(key_d2(key)) : FLT_MAX;
-            }
-        }
+    Neighbours<CAP> nb;
+    const unsigned long long ncand = nb.collect(sorted, starts, G, q, k, d2_bound, s_keys);
+    if (t < nq) {
+        int32_t* const irow = O.index ? O.index + t * k : nullptr;
+        float* const drow = O.distance ? O.distance + t * k : nullptr;
+        nb.each_slot(k, [&](int i, uint64_t key) {
+            const bool real = key < kKeyInf;
+            if (irow) irow[i] = real ? key_index(key) : -1;
+            if (drow) drow[i] = real ? sqrt_rn(key_d2(key)) : FLT_MAX;
+        });
+        if (O.found) O.found[t] = nb.m;
     }
-    if (t < nq && O.found) O.found[t] = n_found;
     add_candidates(O.candidates, ncand);
 }
 
@@ -87,7 +58,7 @@ __global__ __launch_bounds__(CAP == 8 ? kBlock : kLdsBlock) void k_pts_knn(const
 struct CountVisitor {
     float d2_bound;
     unsigned long long n;
-    __device__ __forceinline__ void take(float d2, int) { n += within(d2, d2_bound) ? 1u : 0u; }
+    __device__ __forceinline__ void take(float d2, const float4&) { n += within(d2, d2_bound) ? 1u : 0u; }
     __device__ __forceinline__ bool done(float lb2) const { return walk_done(lb2, kKeyInf, d2_bound); }
 };
 
@@ -130,10 +101,10 @@ struct FillVisitor {
     Segment<WITH_D2> seg;
     float d2_bound;
     int64_t n, cap;   // written so far, the segment's length (a segment is never overrun, whatever the offsets say)
-    __device__ __forceinline__ void take(float d2, int id)
+    __device__ __forceinline__ void take(float d2, const float4& s)
     {
         if (within(d2, d2_bound) && n < cap) {
-            seg.index[n] = id;
+            seg.index[n] = __float_as_int(s.w);
             if constexpr (WITH_D2) seg.d2bits[n] = f32_bits(d2);
             n++;
         }
@@ -167,7 +138,6 @@ __global__ __launch_bounds__(kBlock) void k_pts_radius_fill(const float4* __rest
     add_candidates(candidates, ncand);
 }
 
-
 // ---- launches ----------------------------------------------------------------------------------------------------------------
 
 int knn_launch(const sdfk_points* s, const float* q, int64_t nq, int k, float d2_bound, KnnOut O)
@@ -177,20 +147,9 @@ int knn_launch(const sdfk_points* s, const float* q, int64_t nq, int k, float d2
     O.candidates = cand.dev;
     {
         ProfScope ps("k_pts_knn");
-        switch (tier_of(k)) {
-        case 8:
-            hipLaunchKernelGGL(k_pts_knn<8>, dim3(grid_of(nq, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, q, nq, k, d2_bound, O);
-            break;
-        case 16:
-            hipLaunchKernelGGL(k_pts_knn<16>, dim3(grid_of(nq, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, q, nq, k, d2_bound, O);
-            break;
-        case 32:
-            hipLaunchKernelGGL(k_pts_knn<32>, dim3(grid_of(nq, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, q, nq, k, d2_bound, O);
-            break;
-        default:
-            hipLaunchKernelGGL(k_pts_knn<64>, dim3(grid_of(nq, kLdsBlock)), dim3(kLdsBlock), 0, g.stream, s->sorted, s->starts, s->G, q, nq, k, d2_bound, O);
-            break;
-        }
+        launch_tier(k, nq, [&](auto cap, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL(k_pts_knn<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, q, nq, k, d2_bound, O);
+        });
     }
     hipError_t e = hipGetLastError();
     const hipError_t ec = cand.end(s, nq);
@@ -265,11 +224,6 @@ int check_radius(const sdfk_points* s, const void* queries, int64_t n, float rad
     return SDFK_OK;
 }
 
-hipError_t upload_queries(float* qd, const float* queries3, int64_t n)
-{
-    return hipMemcpyAsync(qd, queries3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -292,29 +246,12 @@ extern "C" int sdfk_points_knn(const sdfk_points* s, const float* queries3, int6
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (int r = check_knn(s, queries3, n, k, max_distance)) return r;
     if (n == 0) return SDFK_OK;
-    float* qd = nullptr;
-    int32_t* id = nullptr;
-    float* dd = nullptr;
-    int32_t* fd = nullptr;
     const size_t nk = (size_t)n * (size_t)k;
-    int r = dev_alloc((void**)&qd, (size_t)n * 3 * sizeof(float));
-    if (!r && index) r = dev_alloc((void**)&id, nk * sizeof(int32_t));
-    if (!r && distance) r = dev_alloc((void**)&dd, nk * sizeof(float));
-    if (!r && found) r = dev_alloc((void**)&fd, (size_t)n * sizeof(int32_t));
-    hipError_t e = hipSuccess;
-    if (!r) e = upload_queries(qd, queries3, n);
-    if (!r && e == hipSuccess) r = knn_launch(s, qd, n, k, radius_d2_bound(max_distance), KnnOut{id, dd, fd, nullptr});
-    if (!r && e == hipSuccess && id) e = hipMemcpyAsync(index, id, nk * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && dd) e = hipMemcpyAsync(distance, dd, nk * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && fd) e = hipMemcpyAsync(found, fd, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(qd);
-    dev_free(id);
-    dev_free(dd);
-    dev_free(fd);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_knn: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    Staged st;
+    const float* qd = st.in(queries3, (size_t)n * 3);
+    const KnnOut O{st.out(index, nk), st.out(distance, nk), st.out(found, (size_t)n), nullptr};
+    st.run([&] { return knn_launch(s, qd, n, k, radius_d2_bound(max_distance), O); });
+    return st.finish("sdfk_points_knn");
 }
 
 extern "C" int sdfk_points_radius_count_device(const sdfk_points* s, const void* queries3_dev, int64_t n, float radius, void* offsets_dev)
@@ -338,20 +275,11 @@ extern "C" int sdfk_points_radius_count(const sdfk_points* s, const float* queri
         offsets[0] = 0;
         return SDFK_OK;
     }
-    float* qd = nullptr;
-    int64_t* od = nullptr;
-    int r = dev_alloc((void**)&qd, (size_t)n * 3 * sizeof(float));
-    if (!r) r = dev_alloc((void**)&od, (size_t)(n + 1) * sizeof(int64_t));
-    hipError_t e = hipSuccess;
-    if (!r) e = upload_queries(qd, queries3, n);
-    if (!r && e == hipSuccess) r = count_launch(s, qd, n, radius_d2_bound(radius), od);
-    if (!r && e == hipSuccess) e = hipMemcpyAsync(offsets, od, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(qd);
-    dev_free(od);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_radius_count: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    Staged st;
+    const float* qd = st.in(queries3, (size_t)n * 3);
+    int64_t* od = st.out(offsets, (size_t)n + 1);
+    st.run([&] { return count_launch(s, qd, n, radius_d2_bound(radius), od); });
+    return st.finish("sdfk_points_radius_count");
 }
 
 extern "C" int sdfk_points_radius_fill_device(const sdfk_points* s, const void* queries3_dev, int64_t n, float radius, const void* offsets_dev,
@@ -379,26 +307,11 @@ extern "C" int sdfk_points_radius_fill(const sdfk_points* s, const float* querie
         if (offsets[i + 1] < offsets[i]) return fail(SDFK_ERR_INVALID, "sdfk_points_radius_fill: offsets do not ascend (at query %lld)", (long long)i);
     if (total == 0) return SDFK_OK;
     if (!index) return fail(SDFK_ERR_INVALID, "sdfk_points_radius_fill: null index");
-    float* qd = nullptr;
-    int64_t* od = nullptr;
-    int32_t* id = nullptr;
-    float* dd = nullptr;
-    int r = dev_alloc((void**)&qd, (size_t)n * 3 * sizeof(float));
-    if (!r) r = dev_alloc((void**)&od, (size_t)(n + 1) * sizeof(int64_t));
-    if (!r) r = dev_alloc((void**)&id, (size_t)total * sizeof(int32_t));
-    if (!r && distance) r = dev_alloc((void**)&dd, (size_t)total * sizeof(float));
-    hipError_t e = hipSuccess;
-    if (!r) e = upload_queries(qd, queries3, n);
-    if (!r && e == hipSuccess) e = hipMemcpyAsync(od, offsets, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) r = fill_launch(s, qd, n, radius_d2_bound(radius), od, id, dd);
-    if (!r && e == hipSuccess) e = hipMemcpyAsync(index, id, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && dd) e = hipMemcpyAsync(distance, dd, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(qd);
-    dev_free(od);
-    dev_free(id);
-    dev_free(dd);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_radius_fill: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    Staged st;
+    const float* qd = st.in(queries3, (size_t)n * 3);
+    const int64_t* od = st.in(offsets, (size_t)n + 1);
+    int32_t* id = st.out(index, (size_t)total);
+    float* dd = st.out(distance, (size_t)total);
+    st.run([&] { return fill_launch(s, qd, n, radius_d2_bound(radius), od, id, dd); });
+    return st.finish("sdfk_points_radius_fill");
 }

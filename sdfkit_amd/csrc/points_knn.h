@@ -63,7 +63,7 @@ SDFK_KNN_HD bool within(float d2, float d2_bound) { return d2 <= d2_bound; }   /
 SDFK_KNN_HD bool radius_is_valid(float r) { return r >= 0.0f; }                // (false for NaN and negative radii)
 
 // ---- the stopping rule ---------------------------------------------------------------------------------------------------------
-// lb2: the conservative lower bound of d2 over every unvisited cell (lib_points.hip's lb_sq).  The walk stops once that bound, with
+// lb2: the conservative lower bound of d2 over every unvisited cell (points_walk.h's lb_sq).  The walk stops once that bound, with
 // the search's 2^-18 margin, exceeds both what the list would still take (the d2 of its worst key; +inf until k are held) and the
 // radius bound.  Strictly: a cell at exactly the worst d2 may hold an equal d2 with a lower index.
 SDFK_KNN_HD bool walk_done(float lb2, uint64_t worst, float d2_bound) { return lb2 * (1.0f - 0x1p-18f) > fminf(key_d2(worst), d2_bound); }

@@ -1,7 +1,9 @@
-// points_walk.h -- the device side that every neighbourhood kernel of the KdTree shares (lib_points_knn.hip: k nearest, within a
-// radius; lib_pointcloud.hip: normals, point clouds as volumes): the shell walk over the grid of sorted cell lists that
-// lib_points.hip builds, the visitor that keeps the k least keys, the LDS storage of the heap tiers, and the candidate counter
-// of a profiled call.  The arithmetic of keys, lists and the stopping rule is points_knn.h's.  hipcc only.
+// points_walk.h -- the owner of the KdTree's shell walk: the one walk over the grid of sorted cell lists that lib_points.hip builds,
+// with its conservative lower bound, run by every query kernel (lib_points.hip: nearest point, ICP; lib_points_knn.hip: k nearest,
+// within a radius; lib_pointcloud.hip: normals, volumes; lib_orient.hip: neighbour rows) through a visitor.  Also what the
+// k-nearest kernels share: the visitor that keeps the k least keys, the LDS storage of the heap tiers, the launch of a kernel's
+// tier for k, and the candidate counter of a profiled call.  The arithmetic of keys, lists and the k-nearest stopping rule is
+// points_knn.h's.  hipcc only.
 #pragma once
 #include "lib_internal.h"
 #include "points_knn.h"
@@ -19,7 +21,8 @@ using namespace sdfk_knn;
 constexpr int kBlock = 256;     // the register tier and the radius kernels
 constexpr int kLdsBlock = 64;   // the LDS tiers: one wave per block
 
-// the conservative lower bound of lib_points.hip (lb_sq), restated
+// the conservative lower bound of d2 over the unvisited cells: beyond the shell along one axis (the nearer of its two gaps) and
+// outside the box along the other two
 __device__ __forceinline__ float lb_sq(const float gap[3][2], const float base2[3])
 {
     float best = INFINITY;
@@ -32,8 +35,9 @@ __device__ __forceinline__ float lb_sq(const float gap[3][2], const float base2[
     return best;
 }
 
-// The shell walk of k_pts_search for a finite query: V::take(d2, index) per candidate, V::done(lb2) after each shell.
-// Returns the number of candidates.
+// The walk of a finite query: one lane, cells in growing Chebyshev shells around the query's cell (clamped to the grid).
+// V::take(d2, s) per candidate s = (x, y, z, bits(index)); V::done(lb2) after each shell, lb2 the lower bound of d2 over every
+// unvisited cell.  Returns the number of candidates.
 template <class V>
 __device__ __forceinline__ unsigned long long shell_walk(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, const Grid& G,
                                                          float qx, float qy, float qz, V& v)
@@ -73,7 +77,7 @@ __device__ __forceinline__ unsigned long long shell_walk(const float4* __restric
                     ncand += j1 - j0;
                     for (uint32_t j = j0; j < j1; j++) {
                         const float4 s = sorted[j];
-                        v.take(dist2(qx, qy, qz, s.x, s.y, s.z), __float_as_int(s.w));
+                        v.take(dist2(qx, qy, qz, s.x, s.y, s.z), s);
                     }
                 }
             }
@@ -110,6 +114,11 @@ __device__ __forceinline__ Query load_query(const float* __restrict__ queries, i
     return q;
 }
 
+__device__ __forceinline__ void load3(const float* __restrict__ a, int64_t i, float out[3])
+{
+    out[0] = a[3 * i]; out[1] = a[3 * i + 1]; out[2] = a[3 * i + 2];
+}
+
 // ---- k nearest ---------------------------------------------------------------------------------------------------------------
 struct LdsSlots {   // slot-major keys of one lane
     uint64_t* base;   // &s_keys[lane]
@@ -122,9 +131,9 @@ struct KnnVisitor {
     L list;
     uint64_t bound_key;   // (radius bound, index all ones): the greatest key within the radius
     float d2_bound;
-    __device__ __forceinline__ void take(float d2, int id)
+    __device__ __forceinline__ void take(float d2, const float4& s)
     {
-        const uint64_t key = pack_key(d2, id);
+        const uint64_t key = pack_key(d2, __float_as_int(s.w));
         if (key <= bound_key && key < list.worst()) list.insert(key);
     }
     __device__ __forceinline__ bool done(float lb2) const { return walk_done(lb2, list.worst(), d2_bound); }
@@ -165,6 +174,18 @@ struct Neighbours {
                 if (!f(v.list.at(i))) break;
         }
     }
+    // f(i, key) for the slots i < k of an output row: the neighbours in order, then kKeyInf (constant i in the register tier)
+    template <class F>
+    __device__ __forceinline__ void each_slot(int k, F&& f) const
+    {
+        if constexpr (CAP == 8) {
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                if (i < k) f(i, v.list.at(i));
+        } else {
+            for (int i = 0; i < k; i++) f(i, v.list.at(i));
+        }
+    }
     __device__ __forceinline__ uint64_t last() const   // the m-th key (m >= 1)
     {
         if constexpr (CAP == 8) {
@@ -178,6 +199,28 @@ struct Neighbours {
 };
 
 inline unsigned grid_of(int64_t n, int block) { return (unsigned)std::max<int64_t>(1, (n + block - 1) / block); }
+
+// a tiered kernel's block, and the keys its block holds in LDS
+template <int CAP>
+constexpr int block_of() { return CAP == 8 ? kBlock : kLdsBlock; }
+template <int CAP>
+constexpr int lds_keys() { return CAP == 8 ? 1 : CAP * kLdsBlock; }   // (the register tier keeps no keys in LDS)
+
+// The launch of a tiered kernel for k over n lanes: launch(cap, grid, block) with cap an std::integral_constant<int, CAP>.
+template <class F>
+inline void launch_tier(int k, int64_t n, F&& launch)
+{
+    auto go = [&](auto cap) {
+        constexpr int B = block_of<decltype(cap)::value>();
+        launch(cap, dim3(grid_of(n, B)), dim3(B));
+    };
+    switch (tier_of(k)) {
+    case 8: go(std::integral_constant<int, 8>{}); break;
+    case 16: go(std::integral_constant<int, 16>{}); break;
+    case 32: go(std::integral_constant<int, 32>{}); break;
+    default: go(std::integral_constant<int, 64>{}); break;
+    }
+}
 
 // the candidate counter of a profiled call (sdfk_points_stats[3..4]); null when profiling is off
 struct Candidates {

@@ -351,6 +351,56 @@ def test_profiled_calls_report_candidates(cube):
     assert 1 <= per_query[0] < per_query[1] and per_query[1] >= 64 and per_query[2] > 20_000 * 4.18 * 0.1 ** 3 * 0.5
 
 
+def _candidates_of_search_and_k1(tree, queries):
+    L = N.lib()
+    N.check(L.sdfk_profile_enable(1))
+    try:
+        tree.SearchMany(queries)
+        search = tree.stats()
+        tree.SearchKNearest(queries, 1)
+        knn = tree.stats()
+    finally:
+        N.check(L.sdfk_profile_enable(0))
+    print("candidates / queries: SearchMany", search["candidates"], search["queries"], " SearchKNearest(k=1)", knn["candidates"], knn["queries"])
+    assert search["queries"] == knn["queries"] == len(queries)
+    return search["candidates"], knn["candidates"]
+
+
+def test_search_and_k1_walk_the_same_candidates(cube):
+    """One shell walk and one stopping rule serve both kernels: on the cube's queries and its four bad queries SearchMany and
+    SearchKNearest(k = 1) report the same candidates.  (3e38, 3e38, 3e38), whose d2 to every point overflows, is the query
+    that tells: a search without the k-nearest rule's FLT_MAX bound walks all 20 000 points for it.)"""
+    tree, P, Q = cube
+    bad = np.array([[np.nan, 0, 0], [0, np.inf, 0], [3e38, 3e38, 3e38], [5, 5, 5]], f32)
+    search, knn = _candidates_of_search_and_k1(tree, np.concatenate([Q, bad]))
+    assert search == knn and search >= len(Q)
+
+
+def test_host_search_and_knn_with_null_outputs(cube):
+    """Any subset of the outputs of the staged host forms: what was asked for equals the call with every output, bitwise."""
+    tree, P, Q = cube
+    L = N.lib()
+    bad = np.array([[np.nan, 0, 0], [0, np.inf, 0], [3e38, 3e38, 3e38], [5, 5, 5]], f32)
+    Qb = np.ascontiguousarray(np.concatenate([Q[:997], bad]))
+    n, k = len(Qb), 9
+
+    def call(entry, extra, shapes, want):
+        outs = [np.full(shape, 7, dtype) if w else None for (shape, dtype), w in zip(shapes, want)]
+        N.check(entry(tree.handle, Qb.ctypes.data, n, *extra, *[o.ctypes.data if o is not None else None for o in outs]))
+        return outs
+
+    for entry, extra, shapes in ((L.sdfk_points_search, (), [((n,), np.int32), ((n,), f32), ((n, 3), f32)]),
+                                 (L.sdfk_points_knn, (k, np.inf), [((n, k), np.int32), ((n, k), f32), ((n,), np.int32)])):
+        full = call(entry, extra, shapes, (True, True, True))
+        assert (full[0][-4:-1] == -1).all() and (full[0][:-4] >= 0).all()   # (the call compared against did its work)
+        for want in ((True, False, False), (False, True, False), (True, True, False), (False, False, False)):
+            got = call(entry, extra, shapes, want)
+            for g, f, w in zip(got, full, want):
+                assert (g is None) == (not w)
+                if w:
+                    assert np.array_equal(g.view(np.uint8), f.view(np.uint8))
+
+
 # ---- refusals ----
 def test_refusals(cube):
     tree, P, Q = cube
