@@ -816,6 +816,55 @@ public:
         }
         return normals;
     }
+    // Extensions (sdfkit_hip.h, "Point clouds: filters").  Neither changes the tree: make a new KdTree from the result.
+    struct Downsampled {
+        std::vector<Vector3> Points;    // one per occupied voxel, the centroid of its members; voxels in the order of their lowest member
+        std::vector<int32_t> Counts;    // the members of each voxel
+        std::vector<int32_t> Group;     // per static point: the index of its voxel in Points
+    };
+    // One point per occupied voxel of the lattice of edge voxelSize anchored at origin.  A voxelSize below the spacing of the cloud
+    // returns the points as they are.
+    Downsampled VoxelDownsample(float voxelSize, Vector3 origin = Vector3{0.0f, 0.0f, 0.0f}) const
+    {
+        Downsampled r;
+        const size_t n = (size_t)TotalPoints();
+        r.Points.resize(n);
+        r.Counts.resize(n);
+        r.Group.resize(n);
+        int64_t m = 0;
+        Check(sdfk_points_voxel_downsample(h_, voxelSize, &origin.X, &r.Points[0].X, r.Counts.data(), r.Group.data(), &m));
+        r.Points.resize((size_t)m);
+        r.Counts.resize((size_t)m);
+        return r;
+    }
+    struct OutlierStats { int64_t Kept = 0, Removed = 0, Isolated = 0; double Mu = 0, Sigma = 0, Threshold = 0; };
+    struct Inliers {
+        std::vector<Vector3> Points;        // the kept points, in insertion order
+        std::vector<int32_t> Indices;       // their indices, ascending
+        std::vector<float> MeanDistance;    // per static point: the mean distance to its k nearest (itself not counted); +inf: isolated
+    };
+    // The static points whose mean distance to their k nearest (2 <= k <= 64, no farther than maxDistance) is at most
+    // mu + stdRatio * sigma over the cloud; a point without a neighbour within maxDistance is isolated and never kept.
+    Inliers RemoveStatisticalOutliers(int k, float stdRatio, float maxDistance = std::numeric_limits<float>::infinity(),
+                                      OutlierStats* stats = nullptr) const
+    {
+        Inliers r;
+        const size_t n = (size_t)TotalPoints();
+        r.Points.resize(n);
+        r.Indices.resize(n);
+        r.MeanDistance.resize(n);
+        int64_t kept = 0, st[6] = {0, 0, 0, 0, 0, 0};
+        Check(sdfk_points_outliers(h_, k, stdRatio, maxDistance, r.MeanDistance.data(), nullptr, r.Indices.data(), &r.Points[0].X, &kept, st));
+        r.Points.resize((size_t)kept);
+        r.Indices.resize((size_t)kept);
+        if (stats) {
+            stats->Kept = st[0]; stats->Removed = st[1]; stats->Isolated = st[2];
+            std::memcpy(&stats->Mu, &st[3], sizeof(double));
+            std::memcpy(&stats->Sigma, &st[4], sizeof(double));
+            std::memcpy(&stats->Threshold, &st[5], sizeof(double));
+        }
+        return r;
+    }
     struct VolumeStats { int64_t Known = 0, Unknown = 0, Candidates = 0, Queries = 0; };
     // The cloud with one outward normal per static point as a signed distance volume: the blend of the tangent-plane distances of the
     // k nearest points within maxDistance; voxels beyond get +-maxDistance (give a band, then Voxels::Redistance, for a full field).

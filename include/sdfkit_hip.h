@@ -38,7 +38,8 @@ extern "C" {
                                    SDFK_OP_SIN .. SDFK_OP_ATAN2 (19-23), accepted by every entry point that takes an op list;
                                    sdfk_points_knn* / sdfk_points_radius_* (KdTree: k nearest, within a radius);
                                    sdfk_points_normals* / sdfk_points_to_volume* (point clouds: normals, signed distance volumes);
-                                   sdfk_points_orient_normals* (point clouds: a consistent orientation of the normals) */
+                                   sdfk_points_orient_normals* (point clouds: a consistent orientation of the normals);
+                                   sdfk_points_voxel_downsample* / sdfk_points_outliers* (point clouds: filters) */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -687,6 +688,56 @@ int sdfk_points_orient_normals(const sdfk_points* s, int32_t k, float max_distan
                                int64_t stats[9]);
 int sdfk_points_orient_normals_device(const sdfk_points* s, int32_t k, float max_distance, int32_t max_seeds, void* normals3_dev,
                                       int64_t stats[9]);
+/* ---- Point clouds: filters (extension) ------------------------------------------------------------------------------------------
+ * Merged scans cover a surface several times over at uneven density, and one stray return stretches the search grid, turns a normal
+ * and puts a blob into a volume.  Two filters of the static points p_i (insertion order, n of them) of a set; neither changes the
+ * set: the caller makes a new one from the result.  Each is ONE function of its inputs, its arithmetic written once for device and
+ * host in csrc/points_filter.h (binary64 from the f32 inputs, one rounding per written operation, no contraction), restated in
+ * tests/points_filter_model.py and compared bit for bit.
+ *
+ * sdfk_points_voxel_downsample: one output point per occupied voxel of the lattice of edge `voxel_size` anchored at `origin` (NULL:
+ * (0, 0, 0)), the centroid of the voxel's members.
+ * 1. Key: the voxel of p_i along axis a is k_a = floor(((double)p_a - (double)o_a) / (double)size), an integer-valued binary64.  It
+ *    is monotone in p_a, so the least and greatest voxel of an axis, kmin_a and kmax_a, are those of the set's bounding box.
+ *    SDFK_ERR_INVALID, outputs untouched: a NULL set; a size that is not finite or <= 0; a non-finite origin; an axis with
+ *    kmax_a - kmin_a >= 2^21.  The packed key is (k_z - kmin_z) << 42 | (k_y - kmin_y) << 21 | (k_x - kmin_x); two points share a
+ *    voxel iff their keys are equal.  (-0.0 and +0.0 share a voxel.)
+ * 2. Groups: the members of a voxel are taken in ascending insertion index, and the voxels are output in the order of their lowest
+ *    member.  A size below the spacing of the cloud therefore returns the input in order.
+ * 3. Centroid, per axis, binary64: the members are cut into chunks of 32 consecutive members in ascending index (the last may be
+ *    short); a chunk is summed sequentially from +0.0, the f32 coordinates widened first; the chunk sums are added sequentially, in
+ *    order, to +0.0; centroid_a = (float)(sum_a / (double)count).  (A voxel of a million points is 31250 serial additions, not a
+ *    million: the chunks are summed side by side.  A lone member comes back bit for bit, except that a coordinate -0.0 comes back
+ *    as +0.0: +0.0 + -0.0.)
+ * 4. Outputs, the caller's, each of capacity n, any NULL: points_out m x 3 f32; counts m x int32, the members of each voxel; group
+ *    n x int32, the output index of every input point (the hook for averaging normals or colours).  *m (may be NULL) receives the
+ *    number of voxels.  Entries from m on are left as they were.
+ * The host form is synchronous.  The device form takes device arrays, runs on the library stream and has finished when it returns
+ * (it reads m on the way).  Temporaries of a call, freed at its end: 40 n bytes and 24 bytes per chunk.
+ *
+ * sdfk_points_outliers: the statistical outlier rule -- a point whose mean distance to its neighbours is far above the cloud's.
+ * 1. Row: the sdfk_points_knn row of p_i for (k, max_distance), 2 <= k <= 64: the same order, d2 formula and max_distance rule.  Its
+ *    first entry has distance 0 -- the point itself or a duplicate of lower index -- and is dropped.  mean_i = (the sum of
+ *    (double)distance_j over the rest, in row order, from 0.0) / (found - 1).  found < 2: the point is ISOLATED, mean_i = +inf; it
+ *    takes no part in the statistics and is never kept.
+ * 2. Statistics over the c points that are not isolated, binary64, summed in the order of sdfk_icp_register's step 1 (strides of
+ *    65536, the halving trees; a point that takes no part adds nothing): mu = sum(mean_i) / c; sigma = sqrt(sum((mean_i - mu)^2) / c),
+ *    the two-pass form; thr = mu + (double)std_ratio * sigma.  A point is KEPT iff it is not isolated and mean_i <= thr.  c = 0:
+ *    nothing is kept and mu = sigma = thr = 0.0.
+ * 3. Outputs, the caller's, each of capacity n, any NULL: mean_distance n x f32, (float)mean_i; keep n x uint8; index_out the kept
+ *    indices, ascending; points_out the kept points, ready for sdfk_points_create[_device].  *n_kept (may be NULL) receives their
+ *    number.  stats (may be NULL): [0] kept, [1] removed (not isolated, above thr), [2] isolated, [3..5] the bits of mu, sigma, thr.
+ *    Entries of index_out / points_out from n_kept on are left as they were.
+ * 4. SDFK_ERR_INVALID: a NULL set; k outside [2, 64]; a std_ratio that is NaN or negative; a NaN or negative max_distance.
+ * Host and device forms as above; both have finished when they return.  Temporaries: 12 n bytes. */
+int sdfk_points_voxel_downsample(const sdfk_points* s, float voxel_size, const float origin[3], float* points_out /* n*3 */,
+                                 int32_t* counts /* n */, int32_t* group /* n */, int64_t* m);
+int sdfk_points_voxel_downsample_device(const sdfk_points* s, float voxel_size, const float origin[3] /* host */, void* points_out_dev,
+                                        void* counts_dev, void* group_dev, int64_t* m);
+int sdfk_points_outliers(const sdfk_points* s, int32_t k, float std_ratio, float max_distance, float* mean_distance /* n */, uint8_t* keep /* n */,
+                         int32_t* index_out /* n */, float* points_out /* n*3 */, int64_t* n_kept, int64_t stats[6]);
+int sdfk_points_outliers_device(const sdfk_points* s, int32_t k, float std_ratio, float max_distance, void* mean_distance_dev, void* keep_dev,
+                                void* index_out_dev, void* points_out_dev, int64_t* n_kept, int64_t stats[6]);
 /* IterativeClosestPoint.RegisterPoints (IterativeClosestPoint.cs:53-196): rigidly moves the caller's points (in place) onto the
  * static set and returns the total transform (row-major M11..M44, System.Numerics row-vector convention) and the number of
  * iterations run.  Each iteration is the reference's: nearest static point of every point, the piecewise distMax from the

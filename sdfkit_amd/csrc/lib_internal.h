@@ -9,6 +9,7 @@
 //   mc_kernels.hip   the marching-cubes kernels (declared in mc_kernels.h)
 //   lib_points.hip   KdTree / IterativeClosestPoint: the grid search structure, exact nearest-point search, ICP
 //   lib_trimesh.hip  triangle-mesh distance: exact closest-triangle search, crossing parity, Mesh -> Voxels
+//   lib_points_filter.hip  KdTree filters: voxel downsample (stable radix sort, segment sums), statistical outliers
 // Build: sdfkit_amd/build.py (the nine units in parallel, then one link with csrc/exports.map).  gfx950 only; there is no CPU path.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -18,6 +18,7 @@
 // With a normal per static point the same loop runs the point-to-plane metric: kept count and mean -> the 28 sums of the 6x6 normal
 // equations -> a one-lane eigen-solve and Cayley step ("ICP, point to plane" below).
 #include "lib_internal.h"
+#include "device_reduce.h"
 #include "device_scan.h"
 #include "points_grid.h"
 #include "points_set.h"
@@ -163,22 +164,9 @@ struct IcpState {
 
 __device__ __forceinline__ bool icp_stopped(const IcpState* S, int iter) { return S->stop && S->iters <= iter; }
 
-// fixed-order block sum of K doubles per thread; thread 0 gets the block's totals
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*s)[kBlock])
-{
-#pragma unroll
-    for (int j = 0; j < K; j++) s[j][threadIdx.x] = v[j];
-    __syncthreads();
-    for (int o = kBlock / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o)
-#pragma unroll
-            for (int j = 0; j < K; j++) s[j][threadIdx.x] += s[j][threadIdx.x + o];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int j = 0; j < K; j++) v[j] = s[j][0];
-}
+// fixed-order block sum of K doubles per thread: device_reduce.h
+using sdfk_reduce::block_sum;
+static_assert(kBlock == sdfk_reduce::kReduceBlock, "the reductions run in blocks of device_reduce.h's size");
 
 struct IcpArgs {
     float* points;        // n x 3, moved in place

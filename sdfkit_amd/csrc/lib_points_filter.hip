@@ -1,0 +1,590 @@
+// lib_points_filter.hip -- the KdTree's two filters: sdfk_points_voxel_downsample* (one centroid per occupied voxel of a
+// world-anchored lattice) and sdfk_points_outliers* (the statistical outlier rule over the k-nearest rows).  Contract:
+// include/sdfkit_hip.h, "Point clouds: filters"; the arithmetic (voxel, range check, packed key, chunked centroid sum, row mean,
+// threshold, keep rule): points_filter.h, checked on the host; the walk, the tiers and the bounded lists: points_walk.h /
+// points_knn.h, shared with every query of the KdTree; the integer scan: device_scan.h.
+//
+// Downsample:
+//   k_vf_keys      one lane per point: (packed key, insertion index) as one 16-byte record.
+//   k_rs_hist      a stable LSD radix sort of the records, 8-bit digits, only the digits the three ranges can set (the host knows
+//   k_rs_scatter   them): per pass the digit counts of every tile of kSortTile records (LDS counters; integer adds, order-free),
+//                  digit-major, one exclusive scan over all of them, then the scatter.  A tile is 4 waves x 8 rounds of 64
+//                  consecutive records; wave w owns the w-th quarter of the tile.  In a round the lanes of equal digit find each
+//                  other with 8 ballots; a lane's rank is the wave's running count of its digit (LDS, one row per wave, touched by
+//                  that wave only, in program order) plus the peers in lower lanes -- so equal digits keep their order within the
+//                  wave, the wave rows are prefixed in wave order, and the tiles in tile order by the scan: the sort is stable, and
+//                  from the identity it leaves every voxel's members in ascending index.  One 16-byte store per record.
+//   k_vf_heads     head flag of every sorted position (its key differs from the one before), and the same flag at the member's
+//                  insertion index: a voxel's head is its lowest member.  Two scans: segment numbers in key order, and output
+//                  numbers in the order of the lowest members.  The host reads m here.
+//   k_vf_starts    the start of every segment.
+//   k_vf_chunks    one lane per chunk of 32 members: its three sums (a lane per sorted position; chunk starts go on).
+//   k_vf_finish    one lane per sorted position: group of its point; at a head the chunk sums in order, the centroid, the count.
+// Outliers:
+//   k_of_mean<CAP> one lane per static point on the shell walk (the tiers of k_pts_knn): the row's mean distance in binary64.
+//   k_of_sum / k_of_var / k_of_thr   the ICP's fixed-order reductions (256 blocks x 256 threads, halving trees): sum and count,
+//                  squared deviations, then mu, sigma and the threshold.
+//   k_of_flags     keep byte, flag and (float)mean; a scan; k_of_scatter writes the kept indices and points.
+#include "lib_internal.h"
+#include "device_reduce.h"
+#include "device_scan.h"
+#include "points_filter.h"
+#include "points_knn.h"
+#include "points_set.h"
+#include "points_walk.h"
+
+namespace {
+
+using namespace sdfk_walk;
+using namespace sdfk_filter;
+
+// ---- flag -> scan ------------------------------------------------------------------------------------------------------------
+// the exclusive scan of buf[0 .. n) in place, buf[n] = the total (both filters' compaction)
+int scan_flags(uint32_t* buf, int64_t n)
+{
+    uint32_t* aux = nullptr;
+    if (int r = dev_alloc((void**)&aux, (size_t)(sdfk_scan::scan_blocks(n) + 1) * sizeof(uint32_t))) return r;
+    sdfk_scan::scan_launch<uint32_t>(buf, n, aux, g.stream);
+    dev_free(aux);   // (stream-ordered pool)
+    HIPCHK(hipGetLastError());
+    return SDFK_OK;
+}
+
+hipError_t read_back(void* host, const void* dev, size_t bytes)
+{
+    hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, g.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    return e;
+}
+
+// ---- the radix sort ----------------------------------------------------------------------------------------------------------
+constexpr int kSortBlock = 256;
+constexpr int kSortRounds = 8;                                // rounds of 64 records per wave
+constexpr int kSortTile = kSortBlock * kSortRounds;           // 2048 records (tests/test_gpu_points_filter.py TILE repeats it)
+constexpr int kSortWave = 64 * kSortRounds;                   // a wave's contiguous part of the tile
+
+struct alignas(16) Rec {
+    unsigned long long key;
+    uint32_t index, pad;
+};
+
+__global__ __launch_bounds__(kBlock) void k_vf_keys(const float* __restrict__ xyz, int64_t n, Lattice L, Rec* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    out[i] = Rec{voxel_key(L, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]), (uint32_t)i, 0u};
+}
+
+// hist[digit * ntiles + tile] = records of the tile with that digit
+__global__ __launch_bounds__(kSortBlock) void k_rs_hist(const Rec* __restrict__ in, int64_t n, int shift, uint32_t ntiles, uint32_t* __restrict__ hist)
+{
+    __shared__ uint32_t s_cnt[256];
+    s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * kSortTile;
+    for (int j = 0; j < kSortRounds; j++) {
+        const int64_t i = base + j * kSortBlock + threadIdx.x;
+        if (i < n) atomicAdd(&s_cnt[(unsigned)(in[i].key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[(size_t)threadIdx.x * ntiles + blockIdx.x] = s_cnt[threadIdx.x];
+}
+
+// offs: the scanned histogram
+__global__ __launch_bounds__(kSortBlock) void k_rs_scatter(const Rec* __restrict__ in, Rec* __restrict__ out, int64_t n, int shift, uint32_t ntiles,
+                                                           const uint32_t* __restrict__ offs)
+{
+    __shared__ uint32_t s_wave[4][256];   // [wave][digit]: the wave's running count, then its first destination
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int j = 0; j < 4; j++) s_wave[j][threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t wbase = (int64_t)blockIdx.x * kSortTile + (int64_t)w * kSortWave + lane;
+    const unsigned long long lower = (1ull << lane) - 1ull;
+    Rec r[kSortRounds];
+    uint32_t rank[kSortRounds];
+#pragma unroll
+    for (int j = 0; j < kSortRounds; j++) {
+        const int64_t i = wbase + j * 64;
+        const bool valid = i < n;
+        r[j] = valid ? in[i] : Rec{0ull, 0u, 0u};
+        const unsigned digit = (unsigned)(r[j].key >> shift) & 255u;
+        unsigned long long peers = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; b++) {
+            const bool bit = (digit >> b) & 1u;
+            const unsigned long long has = __ballot(valid && bit);
+            peers &= bit ? has : ~has;
+        }
+        const uint32_t before = valid ? s_wave[w][digit] : 0u;
+        __builtin_amdgcn_wave_barrier();   // (every peer has read the count before the first of them raises it)
+        const uint32_t below = (uint32_t)__popcll(peers & lower);
+        if (valid && below == 0) s_wave[w][digit] = before + (uint32_t)__popcll(peers);
+        __builtin_amdgcn_wave_barrier();
+        rank[j] = before + below;
+    }
+    __syncthreads();
+    {
+        const unsigned d = threadIdx.x;   // one digit per lane: the waves' counts -> the first destination of each wave's run
+        uint32_t run = offs[(size_t)d * ntiles + blockIdx.x];
+        for (int j = 0; j < 4; j++) {
+            const uint32_t c = s_wave[j][d];
+            s_wave[j][d] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kSortRounds; j++) {
+        const int64_t i = wbase + j * 64;
+        if (i < n) {
+            const unsigned digit = (unsigned)(r[j].key >> shift) & 255u;
+            const uint32_t dest = s_wave[w][digit] + rank[j];
+            if (dest < n) out[dest] = r[j];   // (always: the histogram counted these same records)
+        }
+    }
+}
+
+// Sorts the n records of a by key, stably, through the passes of `mask`; -> the buffer that holds the result (a or b).
+int radix_sort(Rec* a, Rec* b, int64_t n, unsigned mask, Rec** sorted)
+{
+    *sorted = a;
+    if (!mask) return SDFK_OK;
+    const uint32_t ntiles = (uint32_t)((n + kSortTile - 1) / kSortTile);
+    const int64_t nh = (int64_t)ntiles * 256;
+    uint32_t* hist = nullptr;
+    if (int r = dev_alloc((void**)&hist, (size_t)(nh + 1) * sizeof(uint32_t))) return r;
+    int r = SDFK_OK;
+    for (int d = 0; d < 8 && !r; d++) {
+        if (!(mask >> d & 1u)) continue;
+        ProfScope ps("k_rs_pass");
+        hipLaunchKernelGGL(k_rs_hist, dim3(ntiles), dim3(kSortBlock), 0, g.stream, a, n, 8 * d, ntiles, hist);
+        r = scan_flags(hist, nh);
+        if (r) break;
+        hipLaunchKernelGGL(k_rs_scatter, dim3(ntiles), dim3(kSortBlock), 0, g.stream, a, b, n, 8 * d, ntiles, hist);
+        std::swap(a, b);
+    }
+    dev_free(hist);
+    *sorted = a;
+    return r;
+}
+
+// ---- voxel downsample --------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool is_head(const Rec* __restrict__ s, int64_t j) { return j == 0 || s[j].key != s[j - 1].key; }
+
+__global__ __launch_bounds__(kBlock) void k_vf_heads(const Rec* __restrict__ s, int64_t n, uint32_t* __restrict__ seg, uint32_t* __restrict__ first)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t h = is_head(s, j) ? 1u : 0u;
+    seg[j] = h;
+    first[s[j].index] = h;   // (every index once: the array is written whole)
+}
+
+// seg: scanned.  start[0 .. m]: the sorted position each segment begins at, start[m] = n.
+__global__ __launch_bounds__(kBlock) void k_vf_starts(const Rec* __restrict__ s, int64_t n, const uint32_t* __restrict__ seg, uint32_t m,
+                                                      uint32_t* __restrict__ start)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    if (is_head(s, j) && seg[j] < m) start[seg[j]] = (uint32_t)j;
+    if (j == 0) start[m] = (uint32_t)n;
+}
+
+// the slot of chunk q of segment `sid`, which starts at sorted position hs: ascending over all chunks, below n / 32 + m + 1
+__device__ __forceinline__ int64_t chunk_slot(uint32_t hs, uint32_t sid, uint32_t q) { return (int64_t)(hs >> 5) + sid + q; }
+
+__global__ __launch_bounds__(kBlock) void k_vf_chunks(const Rec* __restrict__ s, int64_t n, const uint32_t* __restrict__ seg,
+                                                      const uint32_t* __restrict__ start, uint32_t m, const float* __restrict__ xyz,
+                                                      double* __restrict__ csum, int64_t slots)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t sid = seg[j] + (is_head(s, j) ? 1u : 0u) - 1u;
+    if (sid >= m) return;
+    const uint32_t hs = start[sid], end = start[sid + 1];
+    const uint32_t rel = (uint32_t)j - hs;
+    if (rel % kChunk != 0 || end > n) return;
+    const int count = (int)min((uint32_t)kChunk, end - (uint32_t)j);
+    Sum3 sum;
+    for (int t = 0; t < count; t++) {
+        const int64_t id = s[j + t].index;
+        sum.add_point(xyz[3 * id], xyz[3 * id + 1], xyz[3 * id + 2]);
+    }
+    const int64_t slot = chunk_slot(hs, sid, rel / kChunk);
+    if (slot < slots)
+        for (int a = 0; a < 3; a++) csum[3 * slot + a] = sum.v[a];
+}
+
+// first: scanned (first[i] of a voxel's lowest member i = the voxel's output number)
+__global__ __launch_bounds__(kBlock) void k_vf_finish(const Rec* __restrict__ s, int64_t n, const uint32_t* __restrict__ seg,
+                                                      const uint32_t* __restrict__ start, uint32_t m, const uint32_t* __restrict__ first,
+                                                      const double* __restrict__ csum, int64_t slots, float* __restrict__ points_out,
+                                                      int32_t* __restrict__ counts, int32_t* __restrict__ group)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const bool head = is_head(s, j);
+    const uint32_t sid = seg[j] + (head ? 1u : 0u) - 1u;
+    if (sid >= m) return;
+    const uint32_t hs = start[sid], end = start[sid + 1];
+    if (hs >= n || end > n) return;
+    const uint32_t o = first[s[hs].index];
+    if (o >= m) return;
+    if (group) group[s[j].index] = (int32_t)o;
+    if (!head) return;
+    const int64_t count = (int64_t)end - (int64_t)hs;
+    if (counts) counts[o] = (int32_t)count;
+    if (points_out) {
+        const int64_t chunks = chunks_of(count), base = chunk_slot(hs, sid, 0);
+        Sum3 total;
+        for (int64_t q = 0; q < chunks && base + q < slots; q++) total.add_sum(&csum[3 * (base + q)]);
+        for (int a = 0; a < 3; a++) points_out[3 * (int64_t)o + a] = centroid_of(total.v[a], count);
+    }
+}
+
+unsigned grid1(int64_t n) { return grid_of(n, kBlock); }
+
+struct DownArgs {
+    Lattice L;
+    unsigned mask;   // the sort's passes
+};
+
+int check_downsample(const sdfk_points* s, float size, const float origin[3], DownArgs* A)
+{
+    static const char* who = "sdfk_points_voxel_downsample";
+    if (int r = require_init()) return r;
+    if (!s) return fail(SDFK_ERR_INVALID, "%s: null point set", who);
+    if (!size_is_valid(size)) return fail(SDFK_ERR_INVALID, "%s: the voxel size is not a finite positive number", who);
+    const float zero[3] = {0.0f, 0.0f, 0.0f};
+    const float* o = origin ? origin : zero;
+    if (!origin_is_valid(o)) return fail(SDFK_ERR_INVALID, "%s: the origin is not finite", who);
+    int bits[3];
+    A->L.size = size;
+    for (int a = 0; a < 3; a++) {
+        A->L.origin[a] = o[a];
+        // the voxel of a coordinate is monotone in it and the box's corners are coordinates of points: the extreme voxels
+        const double kmin = voxel_of(s->G.lo[a], o[a], size), kmax = voxel_of(s->G.hi[a], o[a], size);
+        if (!span_is_valid(kmin, kmax))
+            return fail(SDFK_ERR_INVALID, "%s: the points span 2^21 voxels or more along axis %d (a larger voxel size is needed)", who, a);
+        A->L.kmin[a] = kmin;
+        bits[a] = span_bits(kmin, kmax);
+    }
+    A->mask = digit_mask(bits);
+    return SDFK_OK;
+}
+
+// everything on the device; *m_out is read on the way (the call is synchronous)
+int downsample(const sdfk_points* s, const DownArgs& A, float* points_out, int32_t* counts, int32_t* group, int64_t* m_out)
+{
+    static const char* who = "sdfk_points_voxel_downsample";
+    const int64_t n = s->n;
+    Rec* ra = nullptr;
+    Rec* rb = nullptr;
+    Rec* sorted = nullptr;
+    uint32_t* seg = nullptr;
+    uint32_t* first = nullptr;
+    uint32_t* start = nullptr;
+    double* csum = nullptr;
+    hipError_t e = hipSuccess;
+    uint32_t m = 0;
+    int r = dev_alloc((void**)&ra, (size_t)n * sizeof(Rec));
+    if (!r) r = dev_alloc((void**)&rb, (size_t)n * sizeof(Rec));
+    if (!r) r = dev_alloc((void**)&seg, (size_t)(n + 1) * sizeof(uint32_t));
+    if (!r) r = dev_alloc((void**)&first, (size_t)(n + 1) * sizeof(uint32_t));
+    if (!r) {
+        ProfScope ps("k_vf_keys");
+        hipLaunchKernelGGL(k_vf_keys, dim3(grid1(n)), dim3(kBlock), 0, g.stream, s->xyz, n, A.L, ra);
+    }
+    if (!r) r = radix_sort(ra, rb, n, A.mask, &sorted);
+    if (!r) {
+        ProfScope ps("k_vf_heads");
+        hipLaunchKernelGGL(k_vf_heads, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, first);
+        r = scan_flags(seg, n);
+        if (!r) r = scan_flags(first, n);
+    }
+    if (!r) e = read_back(&m, seg + n, sizeof m);
+    const int64_t slots = n / kChunk + (int64_t)m + 2;
+    if (!r && e == hipSuccess) r = dev_alloc((void**)&start, (size_t)(m + 1) * sizeof(uint32_t));
+    if (!r && e == hipSuccess && points_out) r = dev_alloc((void**)&csum, (size_t)slots * 3 * sizeof(double));
+    if (!r && e == hipSuccess) {
+        ProfScope ps("k_vf_centroids");
+        hipLaunchKernelGGL(k_vf_starts, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, m, start);
+        if (points_out)
+            hipLaunchKernelGGL(k_vf_chunks, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, s->xyz, csum, slots);
+        hipLaunchKernelGGL(k_vf_finish, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, first, csum, slots, points_out, counts, group);
+        e = hipGetLastError();
+    }
+    if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);   // (the call returns when finished)
+    dev_free(ra); dev_free(rb); dev_free(seg); dev_free(first); dev_free(start); dev_free(csum);
+    if (r) return r;
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (m_out) *m_out = (int64_t)m;
+    return SDFK_OK;
+}
+
+// ---- statistical outliers ----------------------------------------------------------------------------------------------------
+constexpr int kRedBlocks = 256;   // the ICP's reduction grid (lib_points.hip): the summation order depends on n only
+
+struct OfState {
+    double part[kRedBlocks][3];   // per-block partials: sum of the means, their count, sum of squared deviations
+    double mu, sigma, thr, c;
+};
+
+using sdfk_reduce::block_sum;   // the ICP's fixed-order block sum
+static_assert(kBlock == sdfk_reduce::kReduceBlock, "the reductions run in blocks of device_reduce.h's size");
+
+// ... and its sum of the 256 partials (lib_points.hip reduce_parts): each added to a 0.0 of its own, then the same tree
+template <int K, int OFF>
+__device__ __forceinline__ void reduce_parts(const OfState* S, double (&out)[K], double (*s)[kBlock])
+{
+#pragma unroll
+    for (int j = 0; j < K; j++) out[j] = 0.0;
+    for (int b = threadIdx.x; b < kRedBlocks; b += kBlock)
+#pragma unroll
+        for (int j = 0; j < K; j++) out[j] += S->part[b][OFF + j];
+    block_sum<K>(out, s);
+}
+
+template <int CAP>
+__global__ __launch_bounds__(block_of<CAP>()) void k_of_mean(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
+                                                              const float* __restrict__ xyz, int64_t n, int k, float d2_bound,
+                                                              double* __restrict__ mean)
+{
+    __shared__ uint64_t s_keys[lds_keys<CAP>()];
+    const int64_t t = (int64_t)blockIdx.x * block_of<CAP>() + threadIdx.x;
+    const Query q = load_query(xyz, t, n);
+    Neighbours<CAP> nb;
+    (void)nb.collect(sorted, starts, G, q, k, d2_bound, s_keys);
+    if (t >= n) return;
+    double sum = 0.0;
+    int slot = 0;
+    nb.each([&](uint64_t key) {
+        if (slot > 0) sum = sum + (double)sqrt_rn(key_d2(key));   // (the first entry, distance 0, is dropped)
+        slot++;
+        return true;
+    });
+    mean[t] = row_mean(sum, nb.m);
+}
+
+__global__ __launch_bounds__(kBlock) void k_of_sum(const double* __restrict__ mean, int64_t n, OfState* S)
+{
+    __shared__ double s[2][kBlock];
+    double v[2] = {0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)kRedBlocks * kBlock) {
+        const double m = mean[i];
+        if (!is_isolated(m)) { v[0] += m; v[1] += 1.0; }
+    }
+    block_sum<2>(v, s);
+    if (threadIdx.x == 0) { S->part[blockIdx.x][0] = v[0]; S->part[blockIdx.x][1] = v[1]; }
+}
+
+__global__ __launch_bounds__(kBlock) void k_of_var(const double* __restrict__ mean, int64_t n, OfState* S)
+{
+    __shared__ double s[2][kBlock];
+    double t[2];
+    reduce_parts<2, 0>(S, t, s);   // (every block alike)
+    const double mu = threshold_of(t[0], 0.0, t[1], 0.0f).mu;
+    __syncthreads();   // (s is reused)
+    double v[1] = {0.0};
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)kRedBlocks * kBlock) {
+        const double m = mean[i];
+        if (!is_isolated(m)) {
+            const double d = m - mu;
+            v[0] += d * d;
+        }
+    }
+    block_sum<1>(v, s);
+    if (threadIdx.x == 0) S->part[blockIdx.x][2] = v[0];
+}
+
+__global__ __launch_bounds__(kBlock) void k_of_thr(OfState* S, float std_ratio)
+{
+    __shared__ double s[3][kBlock];
+    double t[3];
+    reduce_parts<3, 0>(S, t, s);
+    if (threadIdx.x != 0) return;
+    const Threshold T = threshold_of(t[0], t[2], t[1], std_ratio);
+    S->mu = T.mu; S->sigma = T.sigma; S->thr = T.thr; S->c = t[1];
+}
+
+__global__ __launch_bounds__(kBlock) void k_of_flags(const double* __restrict__ mean, int64_t n, const OfState* __restrict__ S,
+                                                     float* __restrict__ mean_distance, uint8_t* __restrict__ keep, uint32_t* __restrict__ flag)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const double m = mean[i];
+    const bool kp = is_kept(m, S->thr);
+    if (mean_distance) mean_distance[i] = (float)m;
+    if (keep) keep[i] = kp ? 1 : 0;
+    flag[i] = kp ? 1u : 0u;
+}
+
+// flag: scanned
+__global__ __launch_bounds__(kBlock) void k_of_scatter(const double* __restrict__ mean, int64_t n, const OfState* __restrict__ S,
+                                                       const uint32_t* __restrict__ flag, const float* __restrict__ xyz,
+                                                       int32_t* __restrict__ index_out, float* __restrict__ points_out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n || !is_kept(mean[i], S->thr)) return;
+    const int64_t o = flag[i];
+    if (o >= n) return;
+    if (index_out) index_out[o] = (int32_t)i;
+    if (points_out)
+        for (int a = 0; a < 3; a++) points_out[3 * o + a] = xyz[3 * i + a];
+}
+
+int64_t f64_bits(double x)
+{
+    int64_t u;
+    memcpy(&u, &x, sizeof u);
+    return u;
+}
+
+int check_outliers(const sdfk_points* s, int32_t k, float std_ratio, float max_distance)
+{
+    static const char* who = "sdfk_points_outliers";
+    if (int r = require_init()) return r;
+    if (!s) return fail(SDFK_ERR_INVALID, "%s: null point set", who);
+    if (k < 2 || k > kMaxK) return fail(SDFK_ERR_INVALID, "%s: k = %d is outside [2, %d]", who, (int)k, kMaxK);
+    if (!ratio_is_valid(std_ratio)) return fail(SDFK_ERR_INVALID, "%s: std_ratio is negative or NaN", who);
+    if (!radius_is_valid(max_distance)) return fail(SDFK_ERR_INVALID, "%s: max_distance is negative or NaN", who);
+    return SDFK_OK;
+}
+
+int outliers(const sdfk_points* s, int k, float std_ratio, float max_distance, float* mean_distance, uint8_t* keep, int32_t* index_out,
+             float* points_out, int64_t* n_kept, int64_t stats[6])
+{
+    static const char* who = "sdfk_points_outliers";
+    const int64_t n = s->n;
+    double* mean = nullptr;
+    uint32_t* flag = nullptr;
+    OfState* S = nullptr;
+    hipError_t e = hipSuccess;
+    int r = dev_alloc((void**)&mean, (size_t)n * sizeof(double));
+    if (!r) r = dev_alloc((void**)&flag, (size_t)(n + 1) * sizeof(uint32_t));
+    if (!r) r = dev_alloc((void**)&S, sizeof(OfState));
+    if (!r) {
+        ProfScope ps("k_of_mean");
+        const float d2b = radius_d2_bound(max_distance);
+        launch_tier(k, n, [&](auto cap, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL(k_of_mean<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, mean);
+        });
+    }
+    if (!r) {
+        ProfScope ps("k_of_stats");
+        hipLaunchKernelGGL(k_of_sum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, mean, n, S);
+        hipLaunchKernelGGL(k_of_var, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, mean, n, S);
+        hipLaunchKernelGGL(k_of_thr, dim3(1), dim3(kBlock), 0, g.stream, S, std_ratio);
+    }
+    if (!r) {
+        ProfScope ps("k_of_compact");
+        hipLaunchKernelGGL(k_of_flags, dim3(grid1(n)), dim3(kBlock), 0, g.stream, mean, n, S, mean_distance, keep, flag);
+        r = scan_flags(flag, n);
+        if (!r && (index_out || points_out))
+            hipLaunchKernelGGL(k_of_scatter, dim3(grid1(n)), dim3(kBlock), 0, g.stream, mean, n, S, flag, s->xyz, index_out, points_out);
+        if (!r) e = hipGetLastError();
+    }
+    uint32_t kept = 0;
+    double st[4] = {0, 0, 0, 0};   // mu, sigma, thr, c
+    if (!r && e == hipSuccess) e = hipMemcpyAsync(st, &S->mu, sizeof st, hipMemcpyDeviceToHost, g.stream);
+    if (!r && e == hipSuccess) e = read_back(&kept, flag + n, sizeof kept);   // (synchronises: the call returns when finished)
+    dev_free(mean); dev_free(flag); dev_free(S);
+    if (r) return r;
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (n_kept) *n_kept = (int64_t)kept;
+    if (stats) {
+        const int64_t c = (int64_t)st[3];
+        stats[0] = (int64_t)kept;
+        stats[1] = c - (int64_t)kept;
+        stats[2] = n - c;
+        stats[3] = f64_bits(st[0]);
+        stats[4] = f64_bits(st[1]);
+        stats[5] = f64_bits(st[2]);
+    }
+    return SDFK_OK;
+}
+
+// the first `count` values of a device array into the caller's (nothing when either is null)
+template <class T>
+hipError_t copy_out(T* host, const T* dev, size_t count)
+{
+    if (!host || !dev || !count) return hipSuccess;
+    return hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, g.stream);
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// entry points
+// ---------------------------------------------------------------------------------------------------------------------------
+extern "C" int sdfk_points_voxel_downsample_device(const sdfk_points* s, float voxel_size, const float origin[3], void* points_out_dev,
+                                                   void* counts_dev, void* group_dev, int64_t* m)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    DownArgs A;
+    if (int r = check_downsample(s, voxel_size, origin, &A)) return r;
+    return downsample(s, A, (float*)points_out_dev, (int32_t*)counts_dev, (int32_t*)group_dev, m);
+}
+
+extern "C" int sdfk_points_voxel_downsample(const sdfk_points* s, float voxel_size, const float origin[3], float* points_out, int32_t* counts,
+                                            int32_t* group, int64_t* m)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    DownArgs A;
+    if (int r = check_downsample(s, voxel_size, origin, &A)) return r;
+    const size_t n = (size_t)s->n;
+    Staged st;
+    float* points_d = points_out ? st.scratch<float>(n * 3) : nullptr;
+    int32_t* counts_d = counts ? st.scratch<int32_t>(n) : nullptr;
+    int32_t* group_d = st.out(group, n);
+    int64_t found = 0;
+    st.run([&] {
+        if (int r = downsample(s, A, points_d, counts_d, group_d, &found)) return r;
+        hipError_t e = copy_out(points_out, points_d, (size_t)found * 3);   // (the m voxels only: the rest of the caller's arrays stays)
+        if (e == hipSuccess) e = copy_out(counts, counts_d, (size_t)found);
+        return e == hipSuccess ? SDFK_OK : fail(SDFK_ERR_HIP, "sdfk_points_voxel_downsample: %s", hipGetErrorString(e));
+    });
+    const int r = st.finish("sdfk_points_voxel_downsample");
+    if (!r && m) *m = found;
+    return r;
+}
+
+extern "C" int sdfk_points_outliers_device(const sdfk_points* s, int32_t k, float std_ratio, float max_distance, void* mean_distance_dev,
+                                           void* keep_dev, void* index_out_dev, void* points_out_dev, int64_t* n_kept, int64_t stats[6])
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_outliers(s, k, std_ratio, max_distance)) return r;
+    return outliers(s, k, std_ratio, max_distance, (float*)mean_distance_dev, (uint8_t*)keep_dev, (int32_t*)index_out_dev, (float*)points_out_dev,
+                    n_kept, stats);
+}
+
+extern "C" int sdfk_points_outliers(const sdfk_points* s, int32_t k, float std_ratio, float max_distance, float* mean_distance, uint8_t* keep,
+                                    int32_t* index_out, float* points_out, int64_t* n_kept, int64_t stats[6])
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_outliers(s, k, std_ratio, max_distance)) return r;
+    const size_t n = (size_t)s->n;
+    Staged st;
+    float* mean_d = st.out(mean_distance, n);
+    uint8_t* keep_d = st.out(keep, n);
+    int32_t* index_d = index_out ? st.scratch<int32_t>(n) : nullptr;
+    float* points_d = points_out ? st.scratch<float>(n * 3) : nullptr;
+    int64_t kept = 0, stv[6] = {0, 0, 0, 0, 0, 0};
+    st.run([&] {
+        if (int r = outliers(s, k, std_ratio, max_distance, mean_d, keep_d, index_d, points_d, &kept, stv)) return r;
+        hipError_t e = copy_out(index_out, index_d, (size_t)kept);   // (the kept ones only)
+        if (e == hipSuccess) e = copy_out(points_out, points_d, (size_t)kept * 3);
+        return e == hipSuccess ? SDFK_OK : fail(SDFK_ERR_HIP, "sdfk_points_outliers: %s", hipGetErrorString(e));
+    });
+    const int r = st.finish("sdfk_points_outliers");
+    if (!r) {
+        if (n_kept) *n_kept = kept;
+        if (stats)
+            for (int i = 0; i < 6; i++) stats[i] = stv[i];
+    }
+    return r;
+}

@@ -1,5 +1,5 @@
 // points_set.h -- the handle behind sdfk_points_* (KdTree): the static points and their search grid, built by lib_points.hip and
-// read by every query of the family (lib_points.hip, lib_points_knn.hip, lib_pointcloud.hip, lib_orient.hip) through the walk of
+// read by every query of the family (lib_points.hip, lib_points_knn.hip, lib_pointcloud.hip, lib_orient.hip, lib_points_filter.hip) through the walk of
 // points_walk.h; and Staged, the device copies of the arrays of a query's host form.
 #pragma once
 #include "lib_internal.h"

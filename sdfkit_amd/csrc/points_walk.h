@@ -1,6 +1,6 @@
 // points_walk.h -- the owner of the KdTree's shell walk: the one walk over the grid of sorted cell lists that lib_points.hip builds,
 // with its conservative lower bound, run by every query kernel (lib_points.hip: nearest point, ICP; lib_points_knn.hip: k nearest,
-// within a radius; lib_pointcloud.hip: normals, volumes; lib_orient.hip: neighbour rows) through a visitor.  Also what the
+// within a radius; lib_pointcloud.hip: normals, volumes; lib_orient.hip: neighbour rows; lib_points_filter.hip: mean neighbour distances) through a visitor.  Also what the
 // k-nearest kernels share: the visitor that keeps the k least keys, the LDS storage of the heap tiers, the launch of a kernel's
 // tier for k, and the candidate counter of a profiled call.  The arithmetic of keys, lists and the k-nearest stopping rule is
 // points_knn.h's.  hipcc only.

@@ -4,7 +4,8 @@ entry points sdfk_points_* / sdfk_icp_* (include/sdfkit_hip.h, csrc/lib_points.h
 Vector3 is a float32 numpy array of 3; a span of Vector3 is an (n, 3) float32 array.  The search is exact (the static
 point of least d2, ties to the lowest insertion index; SearchKNearest and
 SearchRadius extend it to the k nearest and to all within a radius, in the same (d2, index) order; EstimateNormals, OrientNormals
-and ToVoxels turn the points into normals, orient them consistently and make a signed distance volume); the structure behind it is a grid of cell lists on the device,
+and ToVoxels turn the points into normals, orient them consistently and make a signed distance volume; VoxelDownsample and
+RemoveStatisticalOutliers thin merged scans and drop stray points); the structure behind it is a grid of cell lists on the device,
 so the reference's tree internals -- Left, Right, SplitValue, IsLeaf -- are not provided.  SplitAxis is kept as given.
 """
 import ctypes as C
@@ -133,6 +134,42 @@ class KdTree:
             stats.update(rounds=int(st[0]), seeds=int(st[1]), flipped=int(st[2]), unreached=int(st[3]), invalid=int(st[4]),
                          levels=[int(v) for v in st[5:9]])
         return nrm
+
+    def VoxelDownsample(self, voxelSize, origin=(0, 0, 0)):
+        """Extension: one point per occupied voxel of the lattice of edge voxelSize anchored at origin, the centroid of the voxel's
+        members -> (points (m, 3) float32, counts (m,) int32, group (n,) int32): the voxels in the order of their lowest member,
+        how many points each holds, and the output index of every static point (for averaging normals or colours the same way).
+        A voxelSize below the spacing of the cloud returns the points as they are.  The tree is not changed: make a new KdTree
+        from the result.  Refused: a voxelSize that is not finite and positive, a non-finite origin, a cloud spanning 2^21 voxels
+        or more along an axis (include/sdfkit_hip.h, "Point clouds: filters")."""
+        n = self.TotalPoints
+        o = np.ascontiguousarray(np.asarray(origin, dtype=f32).reshape(3))
+        pts = np.empty((n, 3), f32)
+        cnt = np.empty(n, np.int32)
+        group = np.empty(n, np.int32)
+        m = C.c_int64()
+        N.check(N.lib().sdfk_points_voxel_downsample(self._h, float(f32(voxelSize)), _ptr(o), _ptr(pts), _ptr(cnt), _ptr(group), C.byref(m)))
+        return pts[:m.value].copy(), cnt[:m.value].copy(), group
+
+    def RemoveStatisticalOutliers(self, k, stdRatio, maxDistance=np.inf, stats=None):
+        """Extension: the static points whose mean distance to their k nearest (the point itself not counted; 2 <= k <= 64, no
+        farther than maxDistance) is at most mu + stdRatio * sigma, mu and sigma the mean and standard deviation of that mean
+        distance over the cloud -> (points (kept, 3) float32, indices (kept,) int32 ascending, meanDistance (n,) float32).  A point
+        with no neighbour within maxDistance is isolated: its meanDistance is +inf, it takes no part in mu and sigma and is never
+        kept.  The tree is not changed: make a new KdTree from the result.  stats: a dict that receives kept, removed, isolated,
+        mu, sigma, threshold (include/sdfkit_hip.h, "Point clouds: filters")."""
+        n = self.TotalPoints
+        pts = np.empty((n, 3), f32)
+        idx = np.empty(n, np.int32)
+        mean = np.empty(n, f32)
+        kept = C.c_int64()
+        st = (C.c_int64 * 6)()
+        N.check(N.lib().sdfk_points_outliers(self._h, int(k), float(f32(stdRatio)), float(f32(maxDistance)), _ptr(mean), None, _ptr(idx), _ptr(pts),
+                                             C.byref(kept), st))
+        if stats is not None:
+            mu, sigma, thr = np.array(st[3:6], np.int64).view(np.float64)
+            stats.update(kept=int(st[0]), removed=int(st[1]), isolated=int(st[2]), mu=float(mu), sigma=float(sigma), threshold=float(thr))
+        return pts[:kept.value].copy(), idx[:kept.value].copy(), mean
 
     def ToVoxels(self, normals, min, max, nx, ny, nz, k=8, maxDistance=np.inf, clipToBounds=False, stats=None):
         """Extension: the point cloud with `normals` (one per static point, pointing outside) as a signed distance volume at the

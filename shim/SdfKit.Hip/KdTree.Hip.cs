@@ -133,6 +133,53 @@ namespace SdfKit
             return stats;
         }
 
+        /// <summary>Extension: one point per occupied voxel of the lattice of edge voxelSize anchored at origin, the centroid of the
+        /// voxel's members, voxels in the order of their lowest member.  counts: the members of each voxel; group: per static point
+        /// the index of its voxel in the result (for averaging normals or colours the same way).  A voxelSize below the spacing of
+        /// the cloud returns the points as they are.  The tree is not changed: make a new KdTree from the result.</summary>
+        public unsafe Vector3[] VoxelDownsample (float voxelSize, out int[] counts, out int[] group, Vector3 origin = default)
+        {
+            if (!(voxelSize > 0) || float.IsInfinity (voxelSize))
+                throw new ArgumentOutOfRangeException (nameof (voxelSize), "voxelSize must be finite and positive");
+            int n = TotalPoints;
+            var points = new Vector3[n];
+            var cnt = new int[n];
+            group = new int[n];
+            long m = 0;
+            fixed (Vector3* p = points) fixed (int* c = cnt) fixed (int* g = group)
+                Native.Check (Native.sdfk_points_voxel_downsample (handle, voxelSize, (float*)&origin, (float*)p, c, g, &m));
+            Array.Resize (ref points, (int)m);
+            Array.Resize (ref cnt, (int)m);
+            counts = cnt;
+            return points;
+        }
+
+        /// <summary>Extension: the static points whose mean distance to their k nearest (k in 2..64, the point itself not counted, no
+        /// farther than maxDistance) is at most mu + stdRatio * sigma, mu and sigma taken over the cloud.  indices: the kept
+        /// indices, ascending; meanDistance: per static point, +inf for an isolated one (no neighbour within maxDistance), which is
+        /// never kept; stats: kept, removed, isolated and the bits of mu, sigma and the threshold (BitConverter.Int64BitsToDouble).
+        /// The tree is not changed: make a new KdTree from the result.</summary>
+        public unsafe Vector3[] RemoveStatisticalOutliers (int k, float stdRatio, out int[] indices, out float[] meanDistance, out long[] stats,
+                                                           float maxDistance = float.PositiveInfinity)
+        {
+            if (k < 2 || k > 64)
+                throw new ArgumentOutOfRangeException (nameof (k), "k must be in 2..64");
+            if (!(stdRatio >= 0))
+                throw new ArgumentOutOfRangeException (nameof (stdRatio), "stdRatio must not be negative");
+            int n = TotalPoints;
+            var points = new Vector3[n];
+            var idx = new int[n];
+            meanDistance = new float[n];
+            stats = new long[6];
+            long kept = 0;
+            fixed (Vector3* p = points) fixed (int* i = idx) fixed (float* d = meanDistance) fixed (long* st = stats)
+                Native.Check (Native.sdfk_points_outliers (handle, k, stdRatio, maxDistance, d, null, i, (float*)p, &kept, st));
+            Array.Resize (ref points, (int)kept);
+            Array.Resize (ref idx, (int)kept);
+            indices = idx;
+            return points;
+        }
+
         /// <summary>Extension: the static points with one outward normal each as a signed distance volume: the blend of the
         /// tangent-plane distances of the k nearest points (1..64) within maxDistance at every cell centre; voxels farther away
         /// get +-maxDistance, the sign carried over from the known ones.  Give a band, then Voxels.Redistance, for a full field.</summary>

@@ -118,6 +118,13 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_points_orient_normals(IntPtr points, int k, float maxDistance, int maxSeeds, float* normals3, long* stats9);
         [DllImport(Lib)] public static extern int sdfk_points_orient_normals_device(IntPtr points, int k, float maxDistance, int maxSeeds, IntPtr normals3Dev,
                                                                                     long* stats9);
+        [DllImport(Lib)] public static extern int sdfk_points_voxel_downsample(IntPtr points, float voxelSize, float* origin3, float* pointsOut, int* counts, int* group, long* m);
+        [DllImport(Lib)] public static extern int sdfk_points_voxel_downsample_device(IntPtr points, float voxelSize, float* origin3, IntPtr pointsOutDev, IntPtr countsDev,
+            IntPtr groupDev, long* m);
+        [DllImport(Lib)] public static extern int sdfk_points_outliers(IntPtr points, int k, float stdRatio, float maxDistance, float* meanDistance, byte* keep, int* indexOut,
+            float* pointsOut, long* nKept, long* stats6);
+        [DllImport(Lib)] public static extern int sdfk_points_outliers_device(IntPtr points, int k, float stdRatio, float maxDistance, IntPtr meanDistanceDev, IntPtr keepDev,
+            IntPtr indexOutDev, IntPtr pointsOutDev, long* nKept, long* stats6);
         [DllImport(Lib)] public static extern void sdfk_points_free(IntPtr points);
         [DllImport(Lib)] public static extern int sdfk_icp_register(IntPtr points, ref SdfkIcpParams prm, float* points3, long n, float* total16, out int iterations);
         [DllImport(Lib)] public static extern int sdfk_icp_register_device(IntPtr points, ref SdfkIcpParams prm, IntPtr points3Dev, long n, float* total16,
