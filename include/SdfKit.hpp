@@ -816,11 +816,30 @@ public:
         }
         return normals;
     }
+    // Extension (sdfkit_hip.h, "Point clouds: colours"): the colour at every query from `colors` (one per static point; any three
+    // floats -- normals can be averaged the same way): the blend of the k nearest points' colours within maxDistance, weighted as
+    // ToVoxels weights their distances; k = 1: the nearest point's colour.  A query with no point within maxDistance: (0, 0, 0), Found 0.
+    struct SampledColors {
+        std::vector<Vector3> Colors;    // per query
+        std::vector<int32_t> Found;     // per query: the neighbours that took part
+    };
+    SampledColors SampleColors(const std::vector<Vector3>& queries, const std::vector<Vector3>& colors, int k = 8,
+                               float maxDistance = std::numeric_limits<float>::infinity()) const
+    {
+        if ((int64_t)colors.size() != (int64_t)TotalPoints()) throw std::invalid_argument("one colour per static point (colors)");
+        SampledColors r;
+        r.Colors.resize(queries.size());
+        r.Found.resize(queries.size());
+        Check(sdfk_points_blend_colors(h_, &colors[0].X, reinterpret_cast<const float*>(queries.data()), (int64_t)queries.size(), k, maxDistance,
+                                       reinterpret_cast<float*>(r.Colors.data()), r.Found.data()));
+        return r;
+    }
     // Extensions (sdfkit_hip.h, "Point clouds: filters").  Neither changes the tree: make a new KdTree from the result.
     struct Downsampled {
         std::vector<Vector3> Points;    // one per occupied voxel, the centroid of its members; voxels in the order of their lowest member
         std::vector<int32_t> Counts;    // the members of each voxel
         std::vector<int32_t> Group;     // per static point: the index of its voxel in Points
+        std::vector<Vector3> Colors;    // one per voxel, the mean of its members' colours; empty when no colours were given
     };
     // One point per occupied voxel of the lattice of edge voxelSize anchored at origin.  A voxelSize below the spacing of the cloud
     // returns the points as they are.
@@ -837,6 +856,24 @@ public:
         r.Counts.resize((size_t)m);
         return r;
     }
+    // ... with one colour per static point (or a normal, or anything else to average): Colors holds every voxel's mean.
+    Downsampled VoxelDownsample(float voxelSize, const std::vector<Vector3>& colors, Vector3 origin = Vector3{0.0f, 0.0f, 0.0f}) const
+    {
+        if ((int64_t)colors.size() != (int64_t)TotalPoints()) throw std::invalid_argument("one colour per static point (colors)");
+        Downsampled r;
+        const size_t n = (size_t)TotalPoints();
+        r.Points.resize(n);
+        r.Counts.resize(n);
+        r.Group.resize(n);
+        r.Colors.resize(n);
+        int64_t m = 0;
+        Check(sdfk_points_voxel_downsample_colors(h_, voxelSize, &origin.X, &colors[0].X, &r.Points[0].X, r.Counts.data(), r.Group.data(),
+                                                  &r.Colors[0].X, &m));
+        r.Points.resize((size_t)m);
+        r.Counts.resize((size_t)m);
+        r.Colors.resize((size_t)m);
+        return r;
+    }
     struct OutlierStats { int64_t Kept = 0, Removed = 0, Isolated = 0; double Mu = 0, Sigma = 0, Threshold = 0; };
     struct Inliers {
         std::vector<Vector3> Points;        // the kept points, in insertion order
@@ -844,7 +881,8 @@ public:
         std::vector<float> MeanDistance;    // per static point: the mean distance to its k nearest (itself not counted); +inf: isolated
     };
     // The static points whose mean distance to their k nearest (2 <= k <= 64, no farther than maxDistance) is at most
-    // mu + stdRatio * sigma over the cloud; a point without a neighbour within maxDistance is isolated and never kept.
+    // mu + stdRatio * sigma over the cloud; a point without a neighbour within maxDistance is isolated and never kept.  The kept
+    // points' colours are colors[Indices[i]].
     Inliers RemoveStatisticalOutliers(int k, float stdRatio, float maxDistance = std::numeric_limits<float>::infinity(),
                                       OutlierStats* stats = nullptr) const
     {
@@ -876,13 +914,28 @@ public:
         if (clipToBounds) v.ClipToBounds();
         return v;
     }
-    void SampleInto(Voxels& v, const std::vector<Vector3>& normals, int k = 8, float maxDistance = std::numeric_limits<float>::infinity(),
+    // ... with one colour per static point: the volume's colours are SampleColors at every cell centre (zero where no point lies
+    // within maxDistance), which Redistance copies and ToMesh interpolates onto the vertices.
+    Voxels ToVoxels(const std::vector<Vector3>& normals, const std::vector<Vector3>& colors, Vector3 min, Vector3 max, int nx, int ny, int nz,
+                    int k = 8, float maxDistance = std::numeric_limits<float>::infinity(), bool clipToBounds = false,
                     VolumeStats* stats = nullptr) const
     {
+        Voxels v(min, max, nx, ny, nz);
+        SampleInto(v, normals, k, maxDistance, stats, &colors);
+        if (clipToBounds) v.ClipToBounds();
+        return v;
+    }
+    // colors: null leaves the volume's colours alone; otherwise they are overwritten (a volume without colour storage gets it)
+    void SampleInto(Voxels& v, const std::vector<Vector3>& normals, int k = 8, float maxDistance = std::numeric_limits<float>::infinity(),
+                    VolumeStats* stats = nullptr, const std::vector<Vector3>* colors = nullptr) const
+    {
         if ((int64_t)normals.size() != (int64_t)TotalPoints()) throw std::invalid_argument("one normal per static point (normals)");
+        if (colors && (int64_t)colors->size() != (int64_t)TotalPoints()) throw std::invalid_argument("one colour per static point (colors)");
+        if (colors) v.Ensure(true);   // (a device copy without colour storage is dropped: every voxel of it is written below)
         if (v.hostNewer_) v.Sync(); else v.Ensure(v.hasColors_);   // (host edits go up first; the colours stay what they are)
         int64_t st[4] = {0, 0, 0, 0};
-        Check(sdfk_points_to_volume(h_, &normals[0].X, v.h_, k, maxDistance, stats ? st : nullptr));
+        if (colors) Check(sdfk_points_to_volume_colors(h_, &normals[0].X, &(*colors)[0].X, v.h_, k, maxDistance, stats ? st : nullptr));
+        else Check(sdfk_points_to_volume(h_, &normals[0].X, v.h_, k, maxDistance, stats ? st : nullptr));
         if (stats) { stats->Known = st[0]; stats->Unknown = st[1]; stats->Candidates = st[2]; stats->Queries = st[3]; }
         v.values_.clear();
         v.hostNewer_ = false;

@@ -39,7 +39,9 @@ extern "C" {
                                    sdfk_points_knn* / sdfk_points_radius_* (KdTree: k nearest, within a radius);
                                    sdfk_points_normals* / sdfk_points_to_volume* (point clouds: normals, signed distance volumes);
                                    sdfk_points_orient_normals* (point clouds: a consistent orientation of the normals);
-                                   sdfk_points_voxel_downsample* / sdfk_points_outliers* (point clouds: filters) */
+                                   sdfk_points_voxel_downsample* / sdfk_points_outliers* (point clouds: filters);
+                                   sdfk_points_blend_colors* / sdfk_points_to_volume_colors* / sdfk_points_voxel_downsample_colors* (point
+                                   clouds: per-point colours) */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -635,7 +637,7 @@ int sdfk_points_radius_fill_device(const sdfk_points* s, const void* queries3_de
  *    otherwise -- an open scan, a band thinner than the sampling -- it is deterministic, not meaningful.
  * 5. stats (may be NULL; reading them synchronises): [0] known voxels, [1] unknown voxels, [2] candidates and [3] queries of the
  *    call when sdfk_profile_enable(1) is on (else 0; sdfk_points_stats[3..4] report them too).
- * 6. Colours are left as they are.  Cached sign bits of the volume are dropped, as for a write through sdfk_volume_device_ptrs.
+ * 6. Colours are left as they are (sdfk_points_to_volume_colors, below, writes them from per-point colours).  Cached sign bits of the volume are dropped, as for a write through sdfk_volume_device_ptrs.
  * The plain forms take host arrays and are synchronous; the _device forms take device arrays and are asynchronous on the library
  * stream (unless stats or profiling make them wait). */
 int sdfk_points_normals(const sdfk_points* s, int32_t k, float max_distance, const float* viewpoints3, int64_t n_viewpoints,
@@ -710,7 +712,7 @@ int sdfk_points_orient_normals_device(const sdfk_points* s, int32_t k, float max
  *    million: the chunks are summed side by side.  A lone member comes back bit for bit, except that a coordinate -0.0 comes back
  *    as +0.0: +0.0 + -0.0.)
  * 4. Outputs, the caller's, each of capacity n, any NULL: points_out m x 3 f32; counts m x int32, the members of each voxel; group
- *    n x int32, the output index of every input point (the hook for averaging normals or colours).  *m (may be NULL) receives the
+ *    n x int32, the output index of every input point (the hook for averaging further per-point data; sdfk_points_voxel_downsample_colors, below, does it on the device).  *m (may be NULL) receives the
  *    number of voxels.  Entries from m on are left as they were.
  * The host form is synchronous.  The device form takes device arrays, runs on the library stream and has finished when it returns
  * (it reads m on the way).  Temporaries of a call, freed at its end: 40 n bytes and 24 bytes per chunk.
@@ -738,6 +740,60 @@ int sdfk_points_outliers(const sdfk_points* s, int32_t k, float std_ratio, float
                          int32_t* index_out /* n */, float* points_out /* n*3 */, int64_t* n_kept, int64_t stats[6]);
 int sdfk_points_outliers_device(const sdfk_points* s, int32_t k, float std_ratio, float max_distance, void* mean_distance_dev, void* keep_dev,
                                 void* index_out_dev, void* points_out_dev, int64_t* n_kept, int64_t stats[6]);
+/* ---- Point clouds: colours (extension) ------------------------------------------------------------------------------------------
+ * The rest of the library moves colour and distance together (programs write Colors next to Values, sdfk_trimesh_to_volume blends
+ * vertex colours, sdfk_volume_redistance copies them, the mesher interpolates them onto vertices); these calls do it for point
+ * clouds, so that a coloured scan becomes a coloured mesh without leaving the device, and a mesh made any other way can be
+ * re-coloured from a scan.  A "colour" is three f32 per static point, in insertion order (colors3, n x 3).  Nothing is clamped and
+ * nothing is checked for finiteness, and nothing is specific to RGB: normals averaged through the same calls are as legitimate.
+ * Each call is ONE function of its inputs, its arithmetic written once for device and host in csrc/points_color.h (binary64 from the
+ * f32 inputs, + - * / only, one rounding per written operation, no contraction, one rounding to f32 per result), restated in
+ * tests/pointcloud_color_model.py and compared bit for bit.
+ *
+ * sdfk_points_blend_colors: the colour at every query x, 1 <= k <= 64, max_distance by the rule of sdfk_points_knn (+inf allowed):
+ * 1. Row: the sdfk_points_knn row of x for (k, max_distance): the same order, d2 and bound; m = the number found.  A point's normal
+ *    plays no part (there is none here), so no neighbour is skipped.  A query with a non-finite coordinate finds nothing.
+ * 2. m == 0: the colour is (+0, +0, +0) and found = 0.
+ * 3. Cut-off: h2 is that of sdfk_points_to_volume's step 2: the d2 of neighbour k - 1 when m == k, else the greatest d2 within
+ *    max_distance (FLT_MAX for +inf).
+ * 4. When h2 > 0, over the neighbours in row order: t = (double)d2_j / (double)h2, u = 1 - t, w = u u, W += w, and per channel c
+ *    S_c += w * (double)c_jc -- three separate sums, each from +0.0.
+ * 5. W > 0: out_c = (float)(S_c / W).  Otherwise (h2 == 0; k == 1; every d2 equal to h2): out_c is the first neighbour's channel, bit
+ *    for bit -- so k = 1 is nearest-point colouring.  As with the distances, a neighbour enters or leaves the set with weight 0.
+ * 6. Outputs, each may be NULL: colors_out n x 3 f32, found n x int32.  SDFK_ERR_INVALID: a NULL set, NULL colors3, k outside
+ *    [1, 64], a NaN or negative max_distance.
+ * The host form is synchronous; the _device form is asynchronous on the library stream, as sdfk_points_knn_device.
+ *
+ * sdfk_points_to_volume_colors: sdfk_points_to_volume with colors3.  The volume must have colour storage (SDFK_ERR_INVALID
+ * otherwise, and for NULL colors3).  Values and stats are bit for bit what sdfk_points_to_volume gives for the same arguments.
+ * Colors, in the volume's padded-row layout: at every voxel the function above at the cell centre for the same (k, max_distance) --
+ * one walk per voxel, its neighbour list feeding both blends.  A voxel with no point within max_distance gets zero colours (as
+ * beyond sdfk_trimesh_to_volume's band); a colour is defined wherever a point was found, also where every neighbour lacks a normal
+ * and the value is unknown.  Colours are not filled beyond the band: a mesh vertex gets a sound colour when both voxels of its edge
+ * found a point, which is the case under the condition step 4 of sdfk_points_to_volume states (a band of at least a voxel's
+ * diagonal, points no sparser than the band).  Cached sign bits are dropped, as there.  Host and _device forms as there.
+ *
+ * sdfk_points_voxel_downsample_colors: sdfk_points_voxel_downsample with colors3 in and colors_out (capacity n x 3; m rows written,
+ * may be NULL).  points_out, counts, group and *m are bit for bit those of sdfk_points_voxel_downsample (one sort serves both).
+ * colors_out, per channel: the members' mean by exactly the rule of the centroid (filters, step 3): chunks of 32 members in
+ * ascending index, each summed sequentially from +0.0; the chunk sums added in order; (float)(sum / (double)count).  (A lone
+ * member's channel -0.0 comes back as +0.0, as a coordinate does.)  SDFK_ERR_INVALID as there, and for NULL colors3.  Host and
+ * device forms as there; temporaries: those of sdfk_points_voxel_downsample and 24 more bytes per chunk.
+ * sdfk_points_outliers needs no such form: it returns the kept indices, and the kept colours are colors3[index_out[i]]. */
+int sdfk_points_blend_colors(const sdfk_points* s, const float* colors3 /* n*3 */, const float* queries3, int64_t n_queries, int32_t k,
+                             float max_distance, float* colors_out /* n_queries*3 */, int32_t* found /* n_queries */);
+int sdfk_points_blend_colors_device(const sdfk_points* s, const void* colors3_dev, const void* queries3_dev, int64_t n_queries, int32_t k,
+                                    float max_distance, void* colors_out_dev, void* found_dev);
+int sdfk_points_to_volume_colors(const sdfk_points* s, const float* normals3, const float* colors3, sdfk_volume* v, int32_t k,
+                                 float max_distance, int64_t stats[4]);
+int sdfk_points_to_volume_colors_device(const sdfk_points* s, const void* normals3_dev, const void* colors3_dev, sdfk_volume* v, int32_t k,
+                                        float max_distance, int64_t stats[4]);
+int sdfk_points_voxel_downsample_colors(const sdfk_points* s, float voxel_size, const float origin[3], const float* colors3 /* n*3 */,
+                                        float* points_out /* n*3 */, int32_t* counts /* n */, int32_t* group /* n */,
+                                        float* colors_out /* n*3 */, int64_t* m);
+int sdfk_points_voxel_downsample_colors_device(const sdfk_points* s, float voxel_size, const float origin[3] /* host */,
+                                               const void* colors3_dev, void* points_out_dev, void* counts_dev, void* group_dev,
+                                               void* colors_out_dev, int64_t* m);
 /* IterativeClosestPoint.RegisterPoints (IterativeClosestPoint.cs:53-196): rigidly moves the caller's points (in place) onto the
  * static set and returns the total transform (row-major M11..M44, System.Numerics row-vector convention) and the number of
  * iterations run.  Each iteration is the reference's: nearest static point of every point, the piecewise distMax from the

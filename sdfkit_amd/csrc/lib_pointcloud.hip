@@ -1,18 +1,24 @@
-// lib_pointcloud.hip -- the KdTree's point cloud as geometry: normals (sdfk_points_normals*) and signed distance volumes
-// (sdfk_points_to_volume*).  Contract: include/sdfkit_hip.h, "Point clouds: normals and volumes"; the arithmetic (covariance,
-// Jacobi eigenvectors, orientation, the blend of tangent-plane distances, the fill of one line): points_normals.h, checked on the
-// host; the walk, the tiers and the bounded lists: points_walk.h / points_knn.h, shared with every query of the KdTree.
+// lib_pointcloud.hip -- the KdTree's point cloud as geometry: normals (sdfk_points_normals*), signed distance volumes
+// (sdfk_points_to_volume*) and per-point colours at queries and in volumes (sdfk_points_blend_colors*,
+// sdfk_points_to_volume_colors*).  Contract: include/sdfkit_hip.h, "Point clouds: normals and volumes" and "Point clouds:
+// colours"; the arithmetic (covariance, Jacobi eigenvectors, orientation, the blend of tangent-plane distances, the fill of one
+// line): points_normals.h, (the blend of colours): points_color.h, both checked on the host; the walk, the tiers and the bounded
+// lists: points_walk.h / points_knn.h, shared with every query of the KdTree.
 //
 //   k_pc_normals<CAP>   one lane per static point: its k nearest (itself included) exactly as k_pts_knn<CAP> finds them -- CAP = 8
 //                       in registers, 16 / 32 / 64 a heap in LDS, one wave per block --, then two passes over the list (mean,
 //                       covariance; the neighbours' coordinates gathered from the insertion-order array) and the binary64 eigen
 //                       step, all in the same lane.
-//   k_pc_volume<CAP>    one lane per voxel: the k nearest of the cell centre, the blend over them (coordinates and normals
-//                       gathered), the value and a sign byte (0: unknown).
+//   k_pc_volume<CAP, COLOR>  one lane per voxel: the k nearest of the cell centre, the blend over them (coordinates and normals
+//                       gathered), the value and a sign byte (0: unknown).  COLOR: the same list feeds the colour blend as well
+//                       (colours gathered; every voxel's colour is written, zero where nothing was found); without it the kernel is
+//                       what it was before colours.
+//   k_pc_colors<CAP>    one lane per query: its k nearest, the colour blend over them, the colour and the number found.
 //   k_pc_fill<AXIS>     one lane per line of sign bytes along z, then y, then x: unknown voxels take the sign carried along the
 //                       line and the value +-max_distance.  Lines along z are walked by neighbouring lanes nz bytes apart
 //                       (uncoalesced; the array is one byte per voxel and each line stays in cache), the other two coalesce.
 #include "lib_internal.h"
+#include "points_color.h"
 #include "points_knn.h"
 #include "points_normals.h"
 #include "points_set.h"
@@ -86,9 +92,11 @@ struct VolumeArgs {
     float d2_bound, max_distance;
     unsigned long long* known;        // null: not counted
     unsigned long long* candidates;
+    const float* colors3;    // COLOR: one colour per static point
+    float* colors_out;       // COLOR: the volume's colours, rows padded as the values'
 };
 
-template <int CAP>
+template <int CAP, bool COLOR>
 __global__ __launch_bounds__(block_of<CAP>()) void k_pc_volume(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
                                                                 VolumeArgs A)
 {
@@ -109,6 +117,7 @@ __global__ __launch_bounds__(block_of<CAP>()) void k_pc_volume(const float4* __r
     bool known = false;
     if (active) {
         Blend b;
+        sdfk_color::Blend cb;
         if (nb.m > 0) {
             const float h2 = cutoff_d2(nb.m, A.k, key_d2(nb.last()), A.d2_bound);
             nb.each([&](uint64_t key) {
@@ -116,8 +125,19 @@ __global__ __launch_bounds__(block_of<CAP>()) void k_pc_volume(const float4* __r
                 load3(A.xyz, key_index(key), p);
                 load3(A.normals, key_index(key), nr);
                 b.add(x, p, nr, key_d2(key), h2);
+                if constexpr (COLOR) {
+                    float c[3];
+                    load3(A.colors3, key_index(key), c);
+                    cb.add(c, key_d2(key), h2);
+                }
                 return true;
             });
+        }
+        if constexpr (COLOR) {
+            float rgb[3];
+            cb.result(rgb);
+            const size_t o = (size_t)row * A.pitch + kz;
+            for (int a = 0; a < 3; a++) A.colors_out[3 * o + a] = rgb[a];
         }
         known = b.known();
         signed char s = 0;
@@ -165,7 +185,78 @@ __global__ __launch_bounds__(kBlock) void k_pc_fill(signed char* __restrict__ sg
         }
 }
 
+// ---- colours at queries --------------------------------------------------------------------------------------------------------
+struct ColorArgs {
+    const float* colors3;    // one colour per static point, insertion order
+    const float* queries;
+    int64_t nq;
+    int k;
+    float d2_bound;
+    float* colors_out;       // nq x 3, may be null
+    int32_t* found;          // nq, may be null
+    unsigned long long* candidates;
+};
+
+template <int CAP>
+__global__ __launch_bounds__(block_of<CAP>()) void k_pc_colors(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
+                                                                ColorArgs A)
+{
+    __shared__ uint64_t s_keys[lds_keys<CAP>()];
+    const int64_t t = (int64_t)blockIdx.x * block_of<CAP>() + threadIdx.x;
+    const Query q = load_query(A.queries, t, A.nq);
+    Neighbours<CAP> nb;
+    const unsigned long long ncand = nb.collect(sorted, starts, G, q, A.k, A.d2_bound, s_keys);
+    if (t < A.nq) {
+        sdfk_color::Blend cb;
+        if (nb.m > 0) {
+            const float h2 = cutoff_d2(nb.m, A.k, key_d2(nb.last()), A.d2_bound);
+            nb.each([&](uint64_t key) {
+                float c[3];
+                load3(A.colors3, key_index(key), c);
+                cb.add(c, key_d2(key), h2);
+                return true;
+            });
+        }
+        if (A.colors_out) {
+            float rgb[3];
+            cb.result(rgb);
+            A.colors_out[3 * t] = rgb[0]; A.colors_out[3 * t + 1] = rgb[1]; A.colors_out[3 * t + 2] = rgb[2];
+        }
+        if (A.found) A.found[t] = nb.m;
+    }
+    add_candidates(A.candidates, ncand);
+}
+
 // ---- launches ----------------------------------------------------------------------------------------------------------------
+int colors_launch(const sdfk_points* s, ColorArgs A)
+{
+    Candidates cand;
+    if (int r = cand.begin()) return r;
+    A.candidates = cand.dev;
+    {
+        ProfScope ps("k_pc_colors");
+        launch_tier(A.k, A.nq, [&](auto cap, dim3 grid, dim3 block) {
+            hipLaunchKernelGGL(k_pc_colors<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, A);
+        });
+    }
+    hipError_t e = hipGetLastError();
+    const hipError_t ec = cand.end(s, A.nq);
+    if (e == hipSuccess) e = ec;
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_blend_colors: %s", hipGetErrorString(e));
+    return SDFK_OK;
+}
+
+int check_colors(const sdfk_points* s, const void* colors3, const void* queries, int64_t n, int32_t k, float max_distance)
+{
+    static const char* who = "sdfk_points_blend_colors";
+    if (int r = require_init()) return r;
+    if (!s || !colors3 || n < 0 || (n > 0 && !queries)) return fail(SDFK_ERR_INVALID, "%s: null / negative argument", who);
+    if (n >= (int64_t(1) << 32)) return fail(SDFK_ERR_INVALID, "%s: 2^32 queries or more", who);
+    if (k < 1 || k > kMaxK) return fail(SDFK_ERR_INVALID, "%s: k = %d is outside [1, %d]", who, (int)k, kMaxK);
+    if (!radius_is_valid(max_distance)) return fail(SDFK_ERR_INVALID, "%s: max_distance is negative or NaN", who);
+    return SDFK_OK;
+}
+
 int normals_launch(const sdfk_points* s, int k, float d2_bound, const float* view_dev, int64_t n_view, float* normals_dev, float* variation_dev)
 {
     Candidates cand;
@@ -196,9 +287,10 @@ int check_normals(const sdfk_points* s, int32_t k, float max_distance, const voi
     return SDFK_OK;
 }
 
-int to_volume(const sdfk_points* s, const float* normals_dev, sdfk_volume* v, int k, float max_distance, int64_t stats[4])
+// colors_dev: null for the colourless call (the volume's colours stay), else one colour per static point and v has colour storage
+int to_volume(const sdfk_points* s, const float* normals_dev, const float* colors_dev, sdfk_volume* v, int k, float max_distance, int64_t stats[4])
 {
-    static const char* who = "sdfk_points_to_volume";
+    const char* who = colors_dev ? "sdfk_points_to_volume_colors" : "sdfk_points_to_volume";
     resolve_dependents(v);   // (a queued mesh may still read the old values)
     volume_values_changed(v);
     float d[3], m[3], outside;
@@ -216,11 +308,14 @@ int to_volume(const sdfk_points* s, const float* normals_dev, sdfk_volume* v, in
     if (!r && e == hipSuccess) r = cand.begin();
     if (!r && e == hipSuccess) {
         VolumeArgs A{s->xyz, normals_dev, v->values, sgn, v->nx, v->ny, v->nz, v->pitch(), v->z0, m[0], m[1], m[2], d[0], d[1], d[2],
-                     k, radius_d2_bound(max_distance), max_distance, known, cand.dev};
+                     k, radius_d2_bound(max_distance), max_distance, known, cand.dev, colors_dev, colors_dev ? v->colors : nullptr};
         {
             ProfScope ps("k_pc_volume");
             launch_tier(k, nvox, [&](auto cap, dim3 grid, dim3 block) {
-                hipLaunchKernelGGL(k_pc_volume<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, A);
+                if (colors_dev)
+                    hipLaunchKernelGGL((k_pc_volume<decltype(cap)::value, true>), grid, block, 0, g.stream, s->sorted, s->starts, s->G, A);
+                else
+                    hipLaunchKernelGGL((k_pc_volume<decltype(cap)::value, false>), grid, block, 0, g.stream, s->sorted, s->starts, s->G, A);
             });
         }
         e = hipGetLastError();
@@ -251,15 +346,24 @@ int to_volume(const sdfk_points* s, const float* normals_dev, sdfk_volume* v, in
     return SDFK_OK;
 }
 
-int check_volume(const sdfk_points* s, const void* normals, const sdfk_volume* v, int32_t k, float max_distance)
+int check_volume(const sdfk_points* s, const void* normals, const sdfk_volume* v, int32_t k, float max_distance,
+                 const char* who = "sdfk_points_to_volume")
 {
-    static const char* who = "sdfk_points_to_volume";
     if (int r = require_init()) return r;
     if (!s || !v || !normals) return fail(SDFK_ERR_INVALID, "%s: null argument", who);
     if (k < 1 || k > kMaxK) return fail(SDFK_ERR_INVALID, "%s: k = %d is outside [1, %d]", who, (int)k, kMaxK);
     if (!(max_distance > 0.0f)) return fail(SDFK_ERR_INVALID, "%s: max_distance must be > 0 (+inf: no band)", who);
     if (v->elided || !v->values) return fail(SDFK_ERR_INVALID, "%s: the volume has no storage", who);
     if (v->owner != s->owner) return fail(SDFK_ERR_INVALID, "%s: the volume belongs to another device context", who);
+    return SDFK_OK;
+}
+
+int check_volume_colors(const sdfk_points* s, const void* normals, const void* colors3, const sdfk_volume* v, int32_t k, float max_distance)
+{
+    static const char* who = "sdfk_points_to_volume_colors";
+    if (int r = check_volume(s, normals, v, k, max_distance, who)) return r;
+    if (!colors3) return fail(SDFK_ERR_INVALID, "%s: null colours", who);
+    if (!v->colors) return fail(SDFK_ERR_INVALID, "%s: the volume was created without colours", who);
     return SDFK_OK;
 }
 
@@ -299,7 +403,7 @@ extern "C" int sdfk_points_to_volume_device(const sdfk_points* s, const void* no
     StateScope in_owner_context(s ? s->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (int r = check_volume(s, normals3_dev, v, k, max_distance)) return r;
-    return to_volume(s, (const float*)normals3_dev, v, k, max_distance, stats);
+    return to_volume(s, (const float*)normals3_dev, nullptr, v, k, max_distance, stats);
 }
 
 extern "C" int sdfk_points_to_volume(const sdfk_points* s, const float* normals3, sdfk_volume* v, int32_t k, float max_distance, int64_t stats[4])
@@ -309,6 +413,54 @@ extern "C" int sdfk_points_to_volume(const sdfk_points* s, const float* normals3
     if (int r = check_volume(s, normals3, v, k, max_distance)) return r;
     Staged st;
     const float* nd = st.in(normals3, (size_t)s->n * 3);   // (the caller's array is not retained)
-    st.run([&] { return to_volume(s, nd, v, k, max_distance, stats); });
+    st.run([&] { return to_volume(s, nd, nullptr, v, k, max_distance, stats); });
     return st.finish("sdfk_points_to_volume");
+}
+
+extern "C" int sdfk_points_to_volume_colors_device(const sdfk_points* s, const void* normals3_dev, const void* colors3_dev, sdfk_volume* v, int32_t k,
+                                                   float max_distance, int64_t stats[4])
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_volume_colors(s, normals3_dev, colors3_dev, v, k, max_distance)) return r;
+    return to_volume(s, (const float*)normals3_dev, (const float*)colors3_dev, v, k, max_distance, stats);
+}
+
+extern "C" int sdfk_points_to_volume_colors(const sdfk_points* s, const float* normals3, const float* colors3, sdfk_volume* v, int32_t k,
+                                            float max_distance, int64_t stats[4])
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_volume_colors(s, normals3, colors3, v, k, max_distance)) return r;
+    Staged st;
+    const float* nd = st.in(normals3, (size_t)s->n * 3);   // (the caller's arrays are not retained)
+    const float* cd = st.in(colors3, (size_t)s->n * 3);
+    st.run([&] { return to_volume(s, nd, cd, v, k, max_distance, stats); });
+    return st.finish("sdfk_points_to_volume_colors");
+}
+
+extern "C" int sdfk_points_blend_colors_device(const sdfk_points* s, const void* colors3_dev, const void* queries3_dev, int64_t n, int32_t k,
+                                               float max_distance, void* colors_out_dev, void* found_dev)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_colors(s, colors3_dev, queries3_dev, n, k, max_distance)) return r;
+    if (n == 0) return SDFK_OK;
+    return colors_launch(s, ColorArgs{(const float*)colors3_dev, (const float*)queries3_dev, n, k, radius_d2_bound(max_distance), (float*)colors_out_dev,
+                                      (int32_t*)found_dev, nullptr});
+}
+
+extern "C" int sdfk_points_blend_colors(const sdfk_points* s, const float* colors3, const float* queries3, int64_t n, int32_t k, float max_distance,
+                                        float* colors_out, int32_t* found)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = check_colors(s, colors3, queries3, n, k, max_distance)) return r;
+    if (n == 0) return SDFK_OK;
+    Staged st;
+    const float* cd = st.in(colors3, (size_t)s->n * 3);
+    const float* qd = st.in(queries3, (size_t)n * 3);
+    const ColorArgs A{cd, qd, n, k, radius_d2_bound(max_distance), st.out(colors_out, (size_t)n * 3), st.out(found, (size_t)n), nullptr};
+    st.run([&] { return colors_launch(s, A); });
+    return st.finish("sdfk_points_blend_colors");
 }

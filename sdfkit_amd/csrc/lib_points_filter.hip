@@ -1,7 +1,8 @@
 // lib_points_filter.hip -- the KdTree's two filters: sdfk_points_voxel_downsample* (one centroid per occupied voxel of a
-// world-anchored lattice) and sdfk_points_outliers* (the statistical outlier rule over the k-nearest rows).  Contract:
-// include/sdfkit_hip.h, "Point clouds: filters"; the arithmetic (voxel, range check, packed key, chunked centroid sum, row mean,
-// threshold, keep rule): points_filter.h, checked on the host; the walk, the tiers and the bounded lists: points_walk.h /
+// world-anchored lattice; sdfk_points_voxel_downsample_colors*: and the members' mean colour) and sdfk_points_outliers* (the
+// statistical outlier rule over the k-nearest rows).  Contract: include/sdfkit_hip.h, "Point clouds: filters" and "Point clouds:
+// colours"; the arithmetic (voxel, range check, packed key, chunked centroid sum, row mean, threshold, keep rule): points_filter.h,
+// (the mean colour): points_color.h, both checked on the host; the walk, the tiers and the bounded lists: points_walk.h /
 // points_knn.h, shared with every query of the KdTree; the integer scan: device_scan.h.
 //
 // Downsample:
@@ -20,6 +21,8 @@
 //   k_vf_starts    the start of every segment.
 //   k_vf_chunks    one lane per chunk of 32 members: its three sums (a lane per sorted position; chunk starts go on).
 //   k_vf_finish    one lane per sorted position: group of its point; at a head the chunk sums in order, the centroid, the count.
+//   k_vc_chunks    with colours only: the same segments and chunk slots, the three sums of the members' colours;
+//   k_vc_finish    at a head the chunk sums in order and the mean colour.  The sort and the segments are the centroids'.
 // Outliers:
 //   k_of_mean<CAP> one lane per static point on the shell walk (the tiers of k_pts_knn): the row's mean distance in binary64.
 //   k_of_sum / k_of_var / k_of_thr   the ICP's fixed-order reductions (256 blocks x 256 threads, halving trees): sum and count,
@@ -28,6 +31,7 @@
 #include "lib_internal.h"
 #include "device_reduce.h"
 #include "device_scan.h"
+#include "points_color.h"
 #include "points_filter.h"
 #include "points_knn.h"
 #include "points_set.h"
@@ -242,6 +246,45 @@ __global__ __launch_bounds__(kBlock) void k_vf_finish(const Rec* __restrict__ s,
     }
 }
 
+// the colours of the same segments: one lane per chunk of 32 members, as k_vf_chunks
+__global__ __launch_bounds__(kBlock) void k_vc_chunks(const Rec* __restrict__ s, int64_t n, const uint32_t* __restrict__ seg,
+                                                      const uint32_t* __restrict__ start, uint32_t m, const float* __restrict__ colors3,
+                                                      double* __restrict__ csum, int64_t slots)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t sid = seg[j] + (is_head(s, j) ? 1u : 0u) - 1u;
+    if (sid >= m) return;
+    const uint32_t hs = start[sid], end = start[sid + 1];
+    const uint32_t rel = (uint32_t)j - hs;
+    if (rel % kChunk != 0 || end > n) return;
+    const int count = (int)min((uint32_t)kChunk, end - (uint32_t)j);
+    const Sum3 sum = sdfk_color::chunk_sum(colors3, count, [&](int t) { return (int64_t)s[j + t].index; });
+    const int64_t slot = chunk_slot(hs, sid, rel / kChunk);
+    if (slot < slots)
+        for (int a = 0; a < 3; a++) csum[3 * slot + a] = sum.v[a];
+}
+
+// one lane per sorted position; a head writes its voxel's mean colour
+__global__ __launch_bounds__(kBlock) void k_vc_finish(const Rec* __restrict__ s, int64_t n, const uint32_t* __restrict__ seg,
+                                                      const uint32_t* __restrict__ start, uint32_t m, const uint32_t* __restrict__ first,
+                                                      const double* __restrict__ csum, int64_t slots, float* __restrict__ colors_out)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n || !is_head(s, j)) return;
+    const uint32_t sid = seg[j];
+    if (sid >= m) return;
+    const uint32_t hs = start[sid], end = start[sid + 1];
+    if (hs >= n || end > n || end <= hs) return;
+    const uint32_t o = first[s[hs].index];
+    if (o >= m) return;
+    const int64_t count = (int64_t)end - (int64_t)hs, base = chunk_slot(hs, sid, 0);
+    if (base + chunks_of(count) > slots) return;   // (never: the slots were sized for every chunk)
+    float rgb[3];
+    sdfk_color::group_mean(count, [&](int64_t q) { return &csum[3 * (base + q)]; }, rgb);
+    for (int a = 0; a < 3; a++) colors_out[3 * (int64_t)o + a] = rgb[a];
+}
+
 unsigned grid1(int64_t n) { return grid_of(n, kBlock); }
 
 struct DownArgs {
@@ -273,10 +316,11 @@ int check_downsample(const sdfk_points* s, float size, const float origin[3], Do
     return SDFK_OK;
 }
 
-// everything on the device; *m_out is read on the way (the call is synchronous)
-int downsample(const sdfk_points* s, const DownArgs& A, float* points_out, int32_t* counts, int32_t* group, int64_t* m_out)
+// everything on the device; *m_out is read on the way (the call is synchronous).  colors3 / colors_out: both or neither.
+int downsample(const sdfk_points* s, const DownArgs& A, float* points_out, int32_t* counts, int32_t* group, int64_t* m_out,
+               const float* colors3 = nullptr, float* colors_out = nullptr)
 {
-    static const char* who = "sdfk_points_voxel_downsample";
+    const char* who = colors3 ? "sdfk_points_voxel_downsample_colors" : "sdfk_points_voxel_downsample";
     const int64_t n = s->n;
     Rec* ra = nullptr;
     Rec* rb = nullptr;
@@ -285,6 +329,7 @@ int downsample(const sdfk_points* s, const DownArgs& A, float* points_out, int32
     uint32_t* first = nullptr;
     uint32_t* start = nullptr;
     double* csum = nullptr;
+    double* ccsum = nullptr;
     hipError_t e = hipSuccess;
     uint32_t m = 0;
     int r = dev_alloc((void**)&ra, (size_t)n * sizeof(Rec));
@@ -306,16 +351,21 @@ int downsample(const sdfk_points* s, const DownArgs& A, float* points_out, int32
     const int64_t slots = n / kChunk + (int64_t)m + 2;
     if (!r && e == hipSuccess) r = dev_alloc((void**)&start, (size_t)(m + 1) * sizeof(uint32_t));
     if (!r && e == hipSuccess && points_out) r = dev_alloc((void**)&csum, (size_t)slots * 3 * sizeof(double));
+    if (!r && e == hipSuccess && colors_out) r = dev_alloc((void**)&ccsum, (size_t)slots * 3 * sizeof(double));
     if (!r && e == hipSuccess) {
         ProfScope ps("k_vf_centroids");
         hipLaunchKernelGGL(k_vf_starts, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, m, start);
         if (points_out)
             hipLaunchKernelGGL(k_vf_chunks, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, s->xyz, csum, slots);
         hipLaunchKernelGGL(k_vf_finish, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, first, csum, slots, points_out, counts, group);
+        if (colors_out) {
+            hipLaunchKernelGGL(k_vc_chunks, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, colors3, ccsum, slots);
+            hipLaunchKernelGGL(k_vc_finish, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, first, ccsum, slots, colors_out);
+        }
         e = hipGetLastError();
     }
     if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);   // (the call returns when finished)
-    dev_free(ra); dev_free(rb); dev_free(seg); dev_free(first); dev_free(start); dev_free(csum);
+    dev_free(ra); dev_free(rb); dev_free(seg); dev_free(first); dev_free(start); dev_free(csum); dev_free(ccsum);
     if (r) return r;
     if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     if (m_out) *m_out = (int64_t)m;
@@ -547,6 +597,45 @@ extern "C" int sdfk_points_voxel_downsample(const sdfk_points* s, float voxel_si
         return e == hipSuccess ? SDFK_OK : fail(SDFK_ERR_HIP, "sdfk_points_voxel_downsample: %s", hipGetErrorString(e));
     });
     const int r = st.finish("sdfk_points_voxel_downsample");
+    if (!r && m) *m = found;
+    return r;
+}
+
+extern "C" int sdfk_points_voxel_downsample_colors_device(const sdfk_points* s, float voxel_size, const float origin[3], const void* colors3_dev,
+                                                          void* points_out_dev, void* counts_dev, void* group_dev, void* colors_out_dev, int64_t* m)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    DownArgs A;
+    if (int r = check_downsample(s, voxel_size, origin, &A)) return r;
+    if (!colors3_dev) return fail(SDFK_ERR_INVALID, "sdfk_points_voxel_downsample_colors: null colours");
+    return downsample(s, A, (float*)points_out_dev, (int32_t*)counts_dev, (int32_t*)group_dev, m, (const float*)colors3_dev, (float*)colors_out_dev);
+}
+
+extern "C" int sdfk_points_voxel_downsample_colors(const sdfk_points* s, float voxel_size, const float origin[3], const float* colors3,
+                                                   float* points_out, int32_t* counts, int32_t* group, float* colors_out, int64_t* m)
+{
+    StateScope in_owner_context(s ? s->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    DownArgs A;
+    if (int r = check_downsample(s, voxel_size, origin, &A)) return r;
+    if (!colors3) return fail(SDFK_ERR_INVALID, "sdfk_points_voxel_downsample_colors: null colours");
+    const size_t n = (size_t)s->n;
+    Staged st;
+    const float* colors_in = st.in(colors3, n * 3);
+    float* points_d = points_out ? st.scratch<float>(n * 3) : nullptr;
+    int32_t* counts_d = counts ? st.scratch<int32_t>(n) : nullptr;
+    float* colors_d = colors_out ? st.scratch<float>(n * 3) : nullptr;
+    int32_t* group_d = st.out(group, n);
+    int64_t found = 0;
+    st.run([&] {
+        if (int r = downsample(s, A, points_d, counts_d, group_d, &found, colors_in, colors_d)) return r;
+        hipError_t e = copy_out(points_out, points_d, (size_t)found * 3);   // (the m voxels only: the rest of the caller's arrays stays)
+        if (e == hipSuccess) e = copy_out(counts, counts_d, (size_t)found);
+        if (e == hipSuccess) e = copy_out(colors_out, colors_d, (size_t)found * 3);
+        return e == hipSuccess ? SDFK_OK : fail(SDFK_ERR_HIP, "sdfk_points_voxel_downsample_colors: %s", hipGetErrorString(e));
+    });
+    const int r = st.finish("sdfk_points_voxel_downsample_colors");
     if (!r && m) *m = found;
     return r;
 }

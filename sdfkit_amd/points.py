@@ -5,7 +5,8 @@ Vector3 is a float32 numpy array of 3; a span of Vector3 is an (n, 3) float32 ar
 point of least d2, ties to the lowest insertion index; SearchKNearest and
 SearchRadius extend it to the k nearest and to all within a radius, in the same (d2, index) order; EstimateNormals, OrientNormals
 and ToVoxels turn the points into normals, orient them consistently and make a signed distance volume; VoxelDownsample and
-RemoveStatisticalOutliers thin merged scans and drop stray points); the structure behind it is a grid of cell lists on the device,
+RemoveStatisticalOutliers thin merged scans and drop stray points; SampleColors, ToVoxels(colors=) and VoxelDownsample(colors=)
+carry per-point colours along); the structure behind it is a grid of cell lists on the device,
 so the reference's tree internals -- Left, Right, SplitValue, IsLeaf -- are not provided.  SplitAxis is kept as given.
 """
 import ctypes as C
@@ -26,6 +27,14 @@ def _points(points):
 
 def _ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None and a.size else C.c_void_p()
+
+
+def _per_point(a, n, what):
+    """One Vector3 per static point (colours, or anything else averaged like them)."""
+    a = _points(a)
+    if len(a) != n:
+        raise ValueError(f"one {what} per static point ({what}s)")
+    return a
 
 
 class KdTree:
@@ -102,6 +111,21 @@ class KdTree:
             N.check(N.lib().sdfk_points_radius_fill(self._h, _ptr(q), n, r, _ptr(off), _ptr(idx), _ptr(dist)))
         return off, idx, dist
 
+    def SampleColors(self, queries, colors, k=8, maxDistance=np.inf):
+        """Extension: the colour at every query from `colors` (one Vector3 per static point): the blend of the k nearest points'
+        colours within maxDistance, weighted as ToVoxels weights their distances (k = 1: the nearest point's colour)
+        -> (colors (n, 3) float32, found (n,) int32); a query with no point within maxDistance gets (0, 0, 0) and found 0
+        (include/sdfkit_hip.h, "Point clouds: colours").  It re-colours the vertices of any mesh from a scan.  Nothing is specific
+        to RGB and nothing is clamped: normals can be averaged the same way.  1 <= k <= 64."""
+        q = _points(queries)
+        col = _per_point(colors, self.TotalPoints, "colour")
+        n = len(q)
+        out = np.empty((n, 3), f32)
+        found = np.empty(n, np.int32)
+        # (n == 0 still goes to the library: it is what refuses a bad k or maxDistance)
+        N.check(N.lib().sdfk_points_blend_colors(self._h, _ptr(col), _ptr(q), n, int(k), float(f32(maxDistance)), _ptr(out), _ptr(found)))
+        return out, found
+
     def EstimateNormals(self, k, viewpoint=None, maxDistance=np.inf):
         """Extension: a normal per static point from its k nearest (itself included; 3 <= k <= 64, no farther than maxDistance)
         -> (normals (n, 3) float32, variation (n,) float32): the eigenvector of the least eigenvalue of the neighbourhood's
@@ -135,10 +159,12 @@ class KdTree:
                          levels=[int(v) for v in st[5:9]])
         return nrm
 
-    def VoxelDownsample(self, voxelSize, origin=(0, 0, 0)):
+    def VoxelDownsample(self, voxelSize, origin=(0, 0, 0), colors=None):
         """Extension: one point per occupied voxel of the lattice of edge voxelSize anchored at origin, the centroid of the voxel's
         members -> (points (m, 3) float32, counts (m,) int32, group (n,) int32): the voxels in the order of their lowest member,
-        how many points each holds, and the output index of every static point (for averaging normals or colours the same way).
+        how many points each holds, and the output index of every static point (for averaging further per-point data).
+        colors: one Vector3 per static point (colours, or normals); the result then has a fourth element, (m, 3) float32: the
+        members' mean per voxel, summed in the order of the centroid.
         A voxelSize below the spacing of the cloud returns the points as they are.  The tree is not changed: make a new KdTree
         from the result.  Refused: a voxelSize that is not finite and positive, a non-finite origin, a cloud spanning 2^21 voxels
         or more along an axis (include/sdfkit_hip.h, "Point clouds: filters")."""
@@ -148,6 +174,12 @@ class KdTree:
         cnt = np.empty(n, np.int32)
         group = np.empty(n, np.int32)
         m = C.c_int64()
+        if colors is not None:
+            col = _per_point(colors, n, "colour")
+            out = np.empty((n, 3), f32)
+            N.check(N.lib().sdfk_points_voxel_downsample_colors(self._h, float(f32(voxelSize)), _ptr(o), _ptr(col), _ptr(pts), _ptr(cnt), _ptr(group),
+                                                                _ptr(out), C.byref(m)))
+            return pts[:m.value].copy(), cnt[:m.value].copy(), group, out[:m.value].copy()
         N.check(N.lib().sdfk_points_voxel_downsample(self._h, float(f32(voxelSize)), _ptr(o), _ptr(pts), _ptr(cnt), _ptr(group), C.byref(m)))
         return pts[:m.value].copy(), cnt[:m.value].copy(), group
 
@@ -156,7 +188,8 @@ class KdTree:
         farther than maxDistance) is at most mu + stdRatio * sigma, mu and sigma the mean and standard deviation of that mean
         distance over the cloud -> (points (kept, 3) float32, indices (kept,) int32 ascending, meanDistance (n,) float32).  A point
         with no neighbour within maxDistance is isolated: its meanDistance is +inf, it takes no part in mu and sigma and is never
-        kept.  The tree is not changed: make a new KdTree from the result.  stats: a dict that receives kept, removed, isolated,
+        kept.  Per-point data of the kept points, colours for one, is colors[indices].  The tree is not changed: make a new KdTree
+        from the result.  stats: a dict that receives kept, removed, isolated,
         mu, sigma, threshold (include/sdfkit_hip.h, "Point clouds: filters")."""
         n = self.TotalPoints
         pts = np.empty((n, 3), f32)
@@ -171,28 +204,37 @@ class KdTree:
             stats.update(kept=int(st[0]), removed=int(st[1]), isolated=int(st[2]), mu=float(mu), sigma=float(sigma), threshold=float(thr))
         return pts[:kept.value].copy(), idx[:kept.value].copy(), mean
 
-    def ToVoxels(self, normals, min, max, nx, ny, nz, k=8, maxDistance=np.inf, clipToBounds=False, stats=None):
+    def ToVoxels(self, normals, min, max, nx, ny, nz, k=8, maxDistance=np.inf, clipToBounds=False, stats=None, colors=None):
         """Extension: the point cloud with `normals` (one per static point, pointing outside) as a signed distance volume at the
         cell centres of Voxels(min, max, nx, ny, nz): a blend of the tangent-plane distances (x - p) . n of the k nearest points
         within maxDistance.  Voxels with no point within maxDistance get +-maxDistance, the sign carried over from the known
         ones -- right when the band of known voxels covers a closed surface.  Give a band of a few voxels and call
-        Voxels.Redistance() on the result for a full field.  stats: a dict that receives known, unknown, candidates, queries."""
+        Voxels.Redistance() on the result for a full field.  stats: a dict that receives known, unknown, candidates, queries.
+        colors: one Vector3 per static point; the volume's Colors are then the same blend of the neighbours' colours (SampleColors
+        at every cell centre; zero where no point lies within maxDistance), which Redistance copies and ToMesh interpolates."""
         from .api import Voxels
         vox = Voxels(min, max, nx, ny, nz)
-        self.SampleInto(vox, normals, k, maxDistance, stats)
+        self.SampleInto(vox, normals, k, maxDistance, stats, colors)
         if clipToBounds:
             vox.ClipToBounds()
         return vox
 
-    def SampleInto(self, voxels, normals, k=8, maxDistance=np.inf, stats=None):
-        """ToVoxels into an existing Voxels (its colours are left alone)."""
+    def SampleInto(self, voxels, normals, k=8, maxDistance=np.inf, stats=None, colors=None):
+        """ToVoxels into an existing Voxels.  Without colors its colours are left alone; with them (one per static point) they are
+        overwritten, and a volume made without colour storage gets it."""
         nrm = _points(normals)
         if len(nrm) != self.TotalPoints:
             raise ValueError("one normal per static point (normals)")
+        col = None if colors is None else _per_point(colors, self.TotalPoints, "colour")
+        if col is not None:
+            voxels._ensure_device(True)   # (a device copy without colour storage is dropped: every voxel of it is written below)
         # values the host may have edited go up first: the call writes the distances only, the colours stay what they were
         h = voxels._sync_to_device() if voxels._host_values is not None else voxels._ensure_device(voxels._has_colors)
         st = (C.c_int64 * 4)() if stats is not None else None
-        N.check(N.lib().sdfk_points_to_volume(self._h, _ptr(nrm), h, int(k), float(f32(maxDistance)), st))
+        if col is not None:
+            N.check(N.lib().sdfk_points_to_volume_colors(self._h, _ptr(nrm), _ptr(col), h, int(k), float(f32(maxDistance)), st))
+        else:
+            N.check(N.lib().sdfk_points_to_volume(self._h, _ptr(nrm), h, int(k), float(f32(maxDistance)), st))
         voxels._host_values = voxels._host_colors = None   # the device copy is now the truth
         voxels._version += 1
         if stats is not None:

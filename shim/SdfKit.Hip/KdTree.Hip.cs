@@ -135,8 +135,8 @@ namespace SdfKit
 
         /// <summary>Extension: one point per occupied voxel of the lattice of edge voxelSize anchored at origin, the centroid of the
         /// voxel's members, voxels in the order of their lowest member.  counts: the members of each voxel; group: per static point
-        /// the index of its voxel in the result (for averaging normals or colours the same way).  A voxelSize below the spacing of
-        /// the cloud returns the points as they are.  The tree is not changed: make a new KdTree from the result.</summary>
+        /// the index of its voxel in the result (for averaging further per-point data; the overload with colors does it on the
+        /// device).  A voxelSize below the spacing of the cloud returns the points as they are.  The tree is not changed: make a new KdTree from the result.</summary>
         public unsafe Vector3[] VoxelDownsample (float voxelSize, out int[] counts, out int[] group, Vector3 origin = default)
         {
             if (!(voxelSize > 0) || float.IsInfinity (voxelSize))
@@ -154,10 +154,53 @@ namespace SdfKit
             return points;
         }
 
+        /// <summary>Extension: VoxelDownsample with one colour per static point (or a normal, or anything else to average):
+        /// colorsOut holds every voxel's mean, summed in the order of the centroid.</summary>
+        public unsafe Vector3[] VoxelDownsample (float voxelSize, ReadOnlySpan<Vector3> colors, out int[] counts, out int[] group, out Vector3[] colorsOut,
+                                                 Vector3 origin = default)
+        {
+            if (!(voxelSize > 0) || float.IsInfinity (voxelSize))
+                throw new ArgumentOutOfRangeException (nameof (voxelSize), "voxelSize must be finite and positive");
+            int n = TotalPoints;
+            if (colors.Length != n)
+                throw new ArgumentException ("One colour per static point", nameof (colors));
+            var points = new Vector3[n];
+            var col = new Vector3[n];
+            var cnt = new int[n];
+            group = new int[n];
+            long m = 0;
+            fixed (Vector3* ci = colors) fixed (Vector3* p = points) fixed (int* c = cnt) fixed (int* g = group) fixed (Vector3* co = col)
+                Native.Check (Native.sdfk_points_voxel_downsample_colors (handle, voxelSize, (float*)&origin, (float*)ci, (float*)p, c, g, (float*)co, &m));
+            Array.Resize (ref points, (int)m);
+            Array.Resize (ref cnt, (int)m);
+            Array.Resize (ref col, (int)m);
+            counts = cnt;
+            colorsOut = col;
+            return points;
+        }
+
+        /// <summary>Extension: the colour at every query from colors (one per static point; any three floats -- normals can be
+        /// averaged the same way): the blend of the k nearest points' colours (1..64) within maxDistance, weighted as ToVoxels
+        /// weights their distances; k = 1: the nearest point's colour.  A query with no point within maxDistance gets (0, 0, 0)
+        /// and found 0.  It re-colours the vertices of any mesh from a scan.</summary>
+        public unsafe void SampleColors (ReadOnlySpan<Vector3> queries, ReadOnlySpan<Vector3> colors, Span<Vector3> colorsOut, Span<int> found, int k = 8,
+                                         float maxDistance = float.PositiveInfinity)
+        {
+            if (k < 1 || k > 64)
+                throw new ArgumentOutOfRangeException (nameof (k), "k must be in 1..64");
+            if (colors.Length != TotalPoints)
+                throw new ArgumentException ("One colour per static point", nameof (colors));
+            if (colorsOut.Length < queries.Length || found.Length < queries.Length)
+                throw new ArgumentException ("Output spans are shorter than the queries");
+            fixed (Vector3* q = queries) fixed (Vector3* c = colors) fixed (Vector3* o = colorsOut) fixed (int* f = found)
+                Native.Check (Native.sdfk_points_blend_colors (handle, (float*)c, (float*)q, queries.Length, k, maxDistance, (float*)o, f));
+        }
+
         /// <summary>Extension: the static points whose mean distance to their k nearest (k in 2..64, the point itself not counted, no
         /// farther than maxDistance) is at most mu + stdRatio * sigma, mu and sigma taken over the cloud.  indices: the kept
         /// indices, ascending; meanDistance: per static point, +inf for an isolated one (no neighbour within maxDistance), which is
         /// never kept; stats: kept, removed, isolated and the bits of mu, sigma and the threshold (BitConverter.Int64BitsToDouble).
+        /// The kept points' colours are colors[indices[i]].
         /// The tree is not changed: make a new KdTree from the result.</summary>
         public unsafe Vector3[] RemoveStatisticalOutliers (int k, float stdRatio, out int[] indices, out float[] meanDistance, out long[] stats,
                                                            float maxDistance = float.PositiveInfinity)
@@ -192,6 +235,17 @@ namespace SdfKit
             return v;
         }
 
+        /// <summary>Extension: ToVoxels with one colour per static point: the volume's Colors are SampleColors at every cell centre
+        /// (zero where no point lies within maxDistance), which Redistance copies and ToMesh interpolates onto the vertices.</summary>
+        public Voxels ToVoxels (ReadOnlySpan<Vector3> normals, ReadOnlySpan<Vector3> colors, Vector3 min, Vector3 max, int nx, int ny, int nz, int k = 8,
+                                float maxDistance = float.PositiveInfinity, bool clipToBounds = false)
+        {
+            var v = new Voxels (min, max, nx, ny, nz);
+            v.SamplePoints (this, normals, colors, k, maxDistance);
+            if (clipToBounds) v.ClipToBounds ();
+            return v;
+        }
+
         public void Dispose ()
         {
             if (handle != IntPtr.Zero) {
@@ -214,6 +268,21 @@ namespace SdfKit
             IntPtr v = hostMayBeNewer ? SyncToDevice () : EnsureDevice (deviceHasColors);
             fixed (Vector3* nrm = normals)
                 Native.Check (Native.sdfk_points_to_volume (points.Handle, (float*)nrm, v, k, maxDistance, null));
+            deviceIsNewer = true; hostMayBeNewer = false;
+        }
+
+        /// <summary>... and its colours from one colour per static point; a device twin without colour storage gets it.</summary>
+        public unsafe void SamplePoints (KdTree points, ReadOnlySpan<Vector3> normals, ReadOnlySpan<Vector3> colors, int k = 8,
+                                         float maxDistance = float.PositiveInfinity)
+        {
+            if (normals.Length != points.TotalPoints)
+                throw new ArgumentException ("One normal per static point", nameof (normals));
+            if (colors.Length != points.TotalPoints)
+                throw new ArgumentException ("One colour per static point", nameof (colors));
+            EnsureDevice (true);   // (a twin without colour storage is dropped: every voxel of it is written below)
+            IntPtr v = hostMayBeNewer ? SyncToDevice () : EnsureDevice (true);
+            fixed (Vector3* nrm = normals) fixed (Vector3* col = colors)
+                Native.Check (Native.sdfk_points_to_volume_colors (points.Handle, (float*)nrm, (float*)col, v, k, maxDistance, null));
             deviceIsNewer = true; hostMayBeNewer = false;
         }
     }

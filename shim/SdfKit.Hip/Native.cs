@@ -125,6 +125,19 @@ namespace SdfKit.Hip
             float* pointsOut, long* nKept, long* stats6);
         [DllImport(Lib)] public static extern int sdfk_points_outliers_device(IntPtr points, int k, float stdRatio, float maxDistance, IntPtr meanDistanceDev, IntPtr keepDev,
             IntPtr indexOutDev, IntPtr pointsOutDev, long* nKept, long* stats6);
+        // point clouds: per-point colours (KdTree.Hip.cs)
+        [DllImport(Lib)] public static extern int sdfk_points_blend_colors(IntPtr points, float* colors3, float* queries3, long nQueries, int k, float maxDistance,
+            float* colorsOut, int* found);
+        [DllImport(Lib)] public static extern int sdfk_points_blend_colors_device(IntPtr points, IntPtr colors3Dev, IntPtr queries3Dev, long nQueries, int k,
+            float maxDistance, IntPtr colorsOutDev, IntPtr foundDev);
+        [DllImport(Lib)] public static extern int sdfk_points_to_volume_colors(IntPtr points, float* normals3, float* colors3, IntPtr volume, int k, float maxDistance,
+            long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_points_to_volume_colors_device(IntPtr points, IntPtr normals3Dev, IntPtr colors3Dev, IntPtr volume, int k,
+            float maxDistance, long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_points_voxel_downsample_colors(IntPtr points, float voxelSize, float* origin3, float* colors3, float* pointsOut,
+            int* counts, int* group, float* colorsOut, long* m);
+        [DllImport(Lib)] public static extern int sdfk_points_voxel_downsample_colors_device(IntPtr points, float voxelSize, float* origin3, IntPtr colors3Dev,
+            IntPtr pointsOutDev, IntPtr countsDev, IntPtr groupDev, IntPtr colorsOutDev, long* m);
         [DllImport(Lib)] public static extern void sdfk_points_free(IntPtr points);
         [DllImport(Lib)] public static extern int sdfk_icp_register(IntPtr points, ref SdfkIcpParams prm, float* points3, long n, float* total16, out int iterations);
         [DllImport(Lib)] public static extern int sdfk_icp_register_device(IntPtr points, ref SdfkIcpParams prm, IntPtr points3Dev, long n, float* total16,
