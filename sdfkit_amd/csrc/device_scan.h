@@ -1,8 +1,9 @@
-// device_scan.h -- the exclusive prefix scan of the grid builds (lib_points.hip, lib_trimesh.hip): counts[0..m) -> starts[0..m]
-// in place, starts[m] = the total.  Blocks of kScanItems values (256 lanes x 8), the block totals scanned by one block, then the
-// block offsets added.  Integer types only: the result does not depend on the order of anything.
+// device_scan.h -- the exclusive prefix scan of the counting sorts and compactions (lib_points.hip, lib_points_filter.hip,
+// lib_points_knn.hip, lib_trimesh.hip): counts[0..m) -> starts[0..m] in place, starts[m] = the total.  Blocks of kScanItems values
+// (256 lanes x 8), the block totals scanned by one block, then the block offsets added.  Integer types only: the result does not
+// depend on the order of anything.  scan() is the one call: it owns the scratch of the block totals.  hipcc only.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "lib_internal.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -78,14 +79,21 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_add(T* __restrict__ buf, in
     if (blockIdx.x == 0 && threadIdx.x == 0) buf[m] = *grand;
 }
 
-// Queues the scan of buf[0..m) on `stream`; aux holds at least scan_blocks(m) + 1 values.
+// Queues the scan of buf[0..m) on g.stream, the scan_blocks(m) + 1 values of its scratch taken from the stream-ordered pool and
+// returned to it: SDFK_OK, or the failure as "<who>: <error string>".
 template <typename T>
-inline void scan_launch(T* buf, int64_t m, T* aux, hipStream_t stream)
+inline int scan(T* buf, int64_t m, const char* who)
 {
     const int64_t nb = scan_blocks(m);
-    hipLaunchKernelGGL(k_scan_blocks<T>, dim3((unsigned)nb), dim3(kScanBlock), 0, stream, buf, m, aux);
-    hipLaunchKernelGGL(k_scan_sums<T>, dim3(1), dim3(kScanBlock), 0, stream, aux, nb, aux + nb);
-    hipLaunchKernelGGL(k_scan_add<T>, dim3((unsigned)nb), dim3(kScanBlock), 0, stream, buf, m, aux, aux + nb);
+    T* aux = nullptr;   // the block totals, then the grand total
+    if (int r = dev_alloc((void**)&aux, (size_t)(nb + 1) * sizeof(T))) return r;
+    hipLaunchKernelGGL(k_scan_blocks<T>, dim3((unsigned)nb), dim3(kScanBlock), 0, g.stream, buf, m, aux);
+    hipLaunchKernelGGL(k_scan_sums<T>, dim3(1), dim3(kScanBlock), 0, g.stream, aux, nb, aux + nb);
+    hipLaunchKernelGGL(k_scan_add<T>, dim3((unsigned)nb), dim3(kScanBlock), 0, g.stream, buf, m, aux, aux + nb);
+    dev_free(aux);   // (stream-ordered pool)
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return SDFK_OK;
 }
 
 }  // namespace sdfk_scan

@@ -2,7 +2,7 @@
 // region growing over the k-nearest graph, confident edges first.  Contract: include/sdfkit_hip.h, "Point clouds: a consistent
 // orientation"; the decisions (validity, dot, the seed's order and sign, one point's choice from its row, the level rule):
 // points_orient.h, checked on the host; the walk, the tiers and the bounded lists: points_walk.h / points_knn.h, shared with every
-// query of the KdTree.
+// query of the KdTree; the reads of the control block: points_set.h read_back.
 //
 //   k_or_rows<CAP>   one lane per static point: its k nearest exactly as k_pts_knn<CAP> finds them (the same tiers), written once
 //                    for the call as SLOT-MAJOR rows (slot * n + point; -1 from the count on): in a round lane i reads slot s of
@@ -176,13 +176,6 @@ __global__ __launch_bounds__(kBlock) void k_or_finish(int64_t n, float* __restri
     }
 }
 
-hipError_t read_ctl(Ctl* host, const Ctl* dev)
-{
-    hipError_t e = hipMemcpyAsync(host, dev, sizeof(Ctl), hipMemcpyDeviceToHost, g.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    return e;
-}
-
 int orient(const sdfk_points* s, int k, float max_distance, int64_t max_seeds, float* normals, int64_t stats[9])
 {
     static const char* who = "sdfk_points_orient_normals";
@@ -225,7 +218,7 @@ int orient(const sdfk_points* s, int k, float max_distance, int64_t max_seeds, f
                 }
                 e = hipGetLastError();
             }
-            if (e == hipSuccess) e = read_ctl(&host, ctl);
+            if (e == hipSuccess) e = read_back(&host, ctl, sizeof host);
             if (e != hipSuccess || host.level[q % 3] >= kLevels) break;   // the last queued round found the growth over
             if (q > (int64_t(1) << 30)) { r = fail(SDFK_ERR_INVALID, "%s: 2^30 rounds without an end", who); break; }
         }
@@ -240,7 +233,7 @@ int orient(const sdfk_points* s, int k, float max_distance, int64_t max_seeds, f
         hipLaunchKernelGGL(k_or_finish, dim3(blocks), dim3(kBlock), 0, g.stream, n, normals, stamp, sgn, ctl);
         e = hipGetLastError();
         if (e == hipSuccess && stats) {
-            e = read_ctl(&host, ctl);
+            e = read_back(&host, ctl, sizeof host);
             stats[0] = (int64_t)host.rounds;
             stats[1] = (int64_t)host.seeds;
             stats[2] = (int64_t)host.flipped;

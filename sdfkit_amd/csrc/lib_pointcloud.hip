@@ -2,8 +2,8 @@
 // (sdfk_points_to_volume*) and per-point colours at queries and in volumes (sdfk_points_blend_colors*,
 // sdfk_points_to_volume_colors*).  Contract: include/sdfkit_hip.h, "Point clouds: normals and volumes" and "Point clouds:
 // colours"; the arithmetic (covariance, Jacobi eigenvectors, orientation, the blend of tangent-plane distances, the fill of one
-// line): points_normals.h, (the blend of colours): points_color.h, both checked on the host; the walk, the tiers and the bounded
-// lists: points_walk.h / points_knn.h, shared with every query of the KdTree.
+// line): points_normals.h, (the blend of colours): points_color.h, both checked on the host; the walk, the tiers, the bounded
+// lists and the profiled launch (walk_launch): points_walk.h / points_knn.h, shared with every query of the KdTree.
 //
 //   k_pc_normals<CAP>   one lane per static point: its k nearest (itself included) exactly as k_pts_knn<CAP> finds them -- CAP = 8
 //                       in registers, 16 / 32 / 64 a heap in LDS, one wave per block --, then two passes over the list (mean,
@@ -230,20 +230,12 @@ __global__ __launch_bounds__(block_of<CAP>()) void k_pc_colors(const float4* __r
 // ---- launches ----------------------------------------------------------------------------------------------------------------
 int colors_launch(const sdfk_points* s, ColorArgs A)
 {
-    Candidates cand;
-    if (int r = cand.begin()) return r;
-    A.candidates = cand.dev;
-    {
-        ProfScope ps("k_pc_colors");
+    return walk_launch(s, A.nq, "k_pc_colors", "sdfk_points_blend_colors", [&](unsigned long long* counter) {
+        A.candidates = counter;
         launch_tier(A.k, A.nq, [&](auto cap, dim3 grid, dim3 block) {
             hipLaunchKernelGGL(k_pc_colors<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, A);
         });
-    }
-    hipError_t e = hipGetLastError();
-    const hipError_t ec = cand.end(s, A.nq);
-    if (e == hipSuccess) e = ec;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_blend_colors: %s", hipGetErrorString(e));
-    return SDFK_OK;
+    });
 }
 
 int check_colors(const sdfk_points* s, const void* colors3, const void* queries, int64_t n, int32_t k, float max_distance)
@@ -259,20 +251,12 @@ int check_colors(const sdfk_points* s, const void* colors3, const void* queries,
 
 int normals_launch(const sdfk_points* s, int k, float d2_bound, const float* view_dev, int64_t n_view, float* normals_dev, float* variation_dev)
 {
-    Candidates cand;
-    if (int r = cand.begin()) return r;
-    NormalsArgs A{s->xyz, s->n, k, d2_bound, view_dev, n_view, normals_dev, variation_dev, cand.dev};
-    {
-        ProfScope ps("k_pc_normals");
+    return walk_launch(s, s->n, "k_pc_normals", "sdfk_points_normals", [&](unsigned long long* counter) {
+        const NormalsArgs A{s->xyz, s->n, k, d2_bound, view_dev, n_view, normals_dev, variation_dev, counter};
         launch_tier(k, s->n, [&](auto cap, dim3 grid, dim3 block) {
             hipLaunchKernelGGL(k_pc_normals<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, A);
         });
-    }
-    hipError_t e = hipGetLastError();
-    const hipError_t ec = cand.end(s, s->n);
-    if (e == hipSuccess) e = ec;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_normals: %s", hipGetErrorString(e));
-    return SDFK_OK;
+    });
 }
 
 int check_normals(const sdfk_points* s, int32_t k, float max_distance, const void* view, int64_t n_view)
@@ -304,36 +288,28 @@ int to_volume(const sdfk_points* s, const float* normals_dev, const float* color
         r = dev_alloc((void**)&known, sizeof(unsigned long long));
         if (!r) e = hipMemsetAsync(known, 0, sizeof(unsigned long long), g.stream);
     }
-    Candidates cand;
-    if (!r && e == hipSuccess) r = cand.begin();
-    if (!r && e == hipSuccess) {
-        VolumeArgs A{s->xyz, normals_dev, v->values, sgn, v->nx, v->ny, v->nz, v->pitch(), v->z0, m[0], m[1], m[2], d[0], d[1], d[2],
-                     k, radius_d2_bound(max_distance), max_distance, known, cand.dev, colors_dev, colors_dev ? v->colors : nullptr};
-        {
-            ProfScope ps("k_pc_volume");
+    if (!r && e == hipSuccess)
+        r = walk_launch(s, nvox, "k_pc_volume", who, [&](unsigned long long* counter) {
+            const VolumeArgs A{s->xyz, normals_dev, v->values, sgn, v->nx, v->ny, v->nz, v->pitch(), v->z0, m[0], m[1], m[2], d[0], d[1], d[2],
+                               k, radius_d2_bound(max_distance), max_distance, known, counter, colors_dev, colors_dev ? v->colors : nullptr};
             launch_tier(k, nvox, [&](auto cap, dim3 grid, dim3 block) {
                 if (colors_dev)
                     hipLaunchKernelGGL((k_pc_volume<decltype(cap)::value, true>), grid, block, 0, g.stream, s->sorted, s->starts, s->G, A);
                 else
                     hipLaunchKernelGGL((k_pc_volume<decltype(cap)::value, false>), grid, block, 0, g.stream, s->sorted, s->starts, s->G, A);
             });
-        }
+        });
+    if (!r && e == hipSuccess) {
+        ProfScope ps("k_pc_fill");
+        const int nx = v->nx, ny = v->ny, nz = v->nz, pitch = v->pitch();
+        hipLaunchKernelGGL(k_pc_fill<2>, dim3(grid_of((int64_t)nx * ny, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
+        hipLaunchKernelGGL(k_pc_fill<1>, dim3(grid_of((int64_t)nx * nz, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
+        hipLaunchKernelGGL(k_pc_fill<0>, dim3(grid_of((int64_t)ny * nz, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
         e = hipGetLastError();
-        if (e == hipSuccess) {
-            ProfScope ps("k_pc_fill");
-            const int nx = v->nx, ny = v->ny, nz = v->nz, pitch = v->pitch();
-            hipLaunchKernelGGL(k_pc_fill<2>, dim3(grid_of((int64_t)nx * ny, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
-            hipLaunchKernelGGL(k_pc_fill<1>, dim3(grid_of((int64_t)nx * nz, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
-            hipLaunchKernelGGL(k_pc_fill<0>, dim3(grid_of((int64_t)ny * nz, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
-            e = hipGetLastError();
-        }
-        const hipError_t ec = cand.end(s, nvox);
-        if (e == hipSuccess) e = ec;
     }
     if (!r && e == hipSuccess && stats) {
         unsigned long long c = 0;
-        e = hipMemcpyAsync(&c, known, sizeof c, hipMemcpyDeviceToHost, g.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+        e = read_back(&c, known, sizeof c);
         stats[0] = (int64_t)c;
         stats[1] = nvox - (int64_t)c;
         stats[2] = g.prof_on ? s->last_candidates : 0;

@@ -5,15 +5,16 @@
 //   bounds (+ the non-finite check) -> cell key per point and per-cell counts (integer atomics) -> exclusive scan -> scatter into
 //   float4 (x, y, z, bits(index)) in cell order, so that one 16-byte load gives a candidate.
 // In-cell order comes from the atomics and varies from build to build; the (d2, index) rule makes every result independent of it.
-// Query: one lane per query on the shell walk that every query of the KdTree runs (points_walk.h): cells in growing Chebyshev
-// shells around the query's cell (clamped to the grid); k_pts_search's visitor keeps the least (d2, index) and stops the walk when
-// the conservative f32 lower bound on the d2 of every unvisited cell exceeds it.  Queries run in the caller's order:
+// Query: one lane per query on the shell walk that every query of the KdTree runs (points_walk.h, walk_launch): cells in growing
+// Chebyshev shells around the query's cell (clamped to the grid); k_pts_search's visitor keeps the least (d2, index) and stops
+// the walk when the conservative f32 lower bound on the d2 of every unvisited cell exceeds it.  Queries run in the caller's order:
 // processing them in the order of a coarse counting sort of their cells was measured slower for mesh vertices, whose order is
 // already spatially coherent, and 5 % faster only for random queries (profiles/points_ab_query_order.txt).  Grid sizing and cell
 // assignment: points_grid.h.
 // ICP: per iteration search -> sum of d, then of (d - mean)^2 -> filtered sums (count, p, q) -> centred C -> a one-lane solve (f64 SVD, the
-// reference's f32 Matrix4x4 steps, convergence, running total) -> the step applied to the points.  Every reduction is f64 in a
-// fixed order (per-block partials of a fixed grid, then one block), with no float atomics: results are bitwise reproducible.
+// reference's f32 Matrix4x4 steps, convergence, running total) -> the step applied to the points.  Every reduction is f64 in the
+// fixed order of device_reduce.h (per-block partials of its fixed grid, then one block), with no float atomics: results are bitwise
+// reproducible.
 // Everything after the reductions (the distMax rule, the filter, the solve, the Matrix4x4 steps) is icp_solve.h, shared with the host.
 // With a normal per static point the same loop runs the point-to-plane metric: kept count and mean -> the 28 sums of the 6x6 normal
 // equations -> a one-lane eigen-solve and Cayley step ("ICP, point to plane" below).
@@ -30,11 +31,30 @@
 namespace {
 
 using namespace sdfk_points_grid;   // Grid, cell_of, key_of, grid_for_box; kMaxCells, kMaxAxisCells
-
-constexpr int kBlock = 256;
-constexpr int kRedBlocks = 256;   // partials of every ICP reduction: a fixed grid, so the summation order depends on n only
+using sdfk_walk::grid_of;
+using sdfk_walk::kBlock;
+using namespace sdfk_reduce;        // the fixed-order reductions of the ICP, both levels
+static_assert(kBlock == kReduceBlock, "the reductions run in blocks of device_reduce.h's size");
 
 // ---- build ------------------------------------------------------------------------------------------------------------------
+// the box so far and another: least of the three minima, greatest of the three maxima and of the non-finite count or flag
+__device__ __forceinline__ void bounds_merge(float* r, const float* o, int stride)
+{
+    for (int j = 0; j < 3; j++) r[j * stride] = fminf(r[j * stride], o[j * stride]);
+    for (int j = 3; j < 7; j++) r[j * stride] = fmaxf(r[j * stride], o[j * stride]);   // (any non-finite point: > 0)
+}
+
+// the block's box of its threads' boxes -> s[0 .. 6][0]
+__device__ __forceinline__ void bounds_tree(const float (&r)[7], float (*s)[kBlock])
+{
+    for (int j = 0; j < 7; j++) s[j][threadIdx.x] = r[j];
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) bounds_merge(&s[0][threadIdx.x], &s[0][threadIdx.x + o], kBlock);
+        __syncthreads();
+    }
+}
+
 // per-block min / max of each coordinate and the number of non-finite points -> part[block][8]
 __global__ __launch_bounds__(kBlock) void k_pts_bounds(const float* __restrict__ p, int64_t n, float* __restrict__ part)
 {
@@ -46,16 +66,7 @@ __global__ __launch_bounds__(kBlock) void k_pts_bounds(const float* __restrict__
         r[0] = fminf(r[0], x); r[1] = fminf(r[1], y); r[2] = fminf(r[2], z);
         r[3] = fmaxf(r[3], x); r[4] = fmaxf(r[4], y); r[5] = fmaxf(r[5], z);
     }
-    for (int j = 0; j < 7; j++) s[j][threadIdx.x] = r[j];
-    __syncthreads();
-    for (int o = kBlock / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            for (int j = 0; j < 3; j++) s[j][threadIdx.x] = fminf(s[j][threadIdx.x], s[j][threadIdx.x + o]);
-            for (int j = 3; j < 6; j++) s[j][threadIdx.x] = fmaxf(s[j][threadIdx.x], s[j][threadIdx.x + o]);
-            s[6][threadIdx.x] = fmaxf(s[6][threadIdx.x], s[6][threadIdx.x + o]);   // (any non-finite point: > 0)
-        }
-        __syncthreads();
-    }
+    bounds_tree(r, s);
     if (threadIdx.x < 7) part[blockIdx.x * 8 + threadIdx.x] = s[threadIdx.x][0];
 }
 
@@ -63,20 +74,8 @@ __global__ __launch_bounds__(kBlock) void k_pts_bounds_final(const float* __rest
 {
     __shared__ float s[7][kBlock];
     float r[7] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY, 0.0f};
-    for (int b = threadIdx.x; b < blocks; b += kBlock) {
-        for (int j = 0; j < 3; j++) r[j] = fminf(r[j], part[b * 8 + j]);
-        for (int j = 3; j < 6; j++) r[j] = fmaxf(r[j], part[b * 8 + j]);
-        r[6] = fmaxf(r[6], part[b * 8 + 6]);
-    }
-    for (int j = 0; j < 7; j++) s[j][threadIdx.x] = r[j];
-    __syncthreads();
-    for (int o = kBlock / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            for (int j = 0; j < 3; j++) s[j][threadIdx.x] = fminf(s[j][threadIdx.x], s[j][threadIdx.x + o]);
-            for (int j = 3; j < 7; j++) s[j][threadIdx.x] = fmaxf(s[j][threadIdx.x], s[j][threadIdx.x + o]);
-        }
-        __syncthreads();
-    }
+    for (int b = threadIdx.x; b < blocks; b += kBlock) bounds_merge(r, part + b * 8, 1);
+    bounds_tree(r, s);
     if (threadIdx.x < 7) out[threadIdx.x] = s[threadIdx.x][0];
 }
 
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void k_pts_search(const float4* __restrict_
 
 // ---- ICP --------------------------------------------------------------------------------------------------------------------
 struct IcpState {
-    double part[kRedBlocks][9];   // per-block partial sums of the current reduction
+    double part[kReduceBlocks][9];   // per-block partial sums of the current reduction
     double dist_mean;             // this iteration's distance mean (f64)
     float dist_max;               // this iteration's filter
     double pmean[3], qmean[3];    // filtered means (f64)
@@ -164,10 +163,6 @@ struct IcpState {
 
 __device__ __forceinline__ bool icp_stopped(const IcpState* S, int iter) { return S->stop && S->iters <= iter; }
 
-// fixed-order block sum of K doubles per thread: device_reduce.h
-using sdfk_reduce::block_sum;
-static_assert(kBlock == sdfk_reduce::kReduceBlock, "the reductions run in blocks of device_reduce.h's size");
-
 struct IcpArgs {
     float* points;        // n x 3, moved in place
     const float4* cor;    // nearest static point + distance per point
@@ -177,27 +172,13 @@ struct IcpArgs {
     IcpState* S;
 };
 
-// one block: the partials of the last pass (columns OFF .. OFF + K - 1) -> `out` (fixed order: thread t sums partials t,
-// t + 256, ..., then a tree): the same result in every block that calls it
-template <int K, int OFF = 0>
-__device__ __forceinline__ void reduce_parts(const IcpState* S, double (&out)[K], double (*s)[kBlock])
-{
-#pragma unroll
-    for (int j = 0; j < K; j++) out[j] = 0.0;
-    for (int b = threadIdx.x; b < kRedBlocks; b += kBlock)
-#pragma unroll
-        for (int j = 0; j < K; j++) out[j] += S->part[b][OFF + j];
-    block_sum<K>(out, s);
-}
-
 // pass 1: sum d -> part[b][0]
 __global__ __launch_bounds__(kBlock) void k_icp_dsum(IcpArgs A, int iter)
 {
     if (icp_stopped(A.S, iter)) return;
     __shared__ double s[1][kBlock];
-    double v[1] = {0.0};
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) v[0] += A.cor[i].w;
-    block_sum<1>(v, s);
+    double v[1];
+    grid_sum(A.n, v, s, [&](int64_t i, double* acc) { acc[0] += A.cor[i].w; });
     if (threadIdx.x == 0) A.S->part[blockIdx.x][0] = v[0];
 }
 
@@ -208,15 +189,14 @@ __global__ __launch_bounds__(kBlock) void k_icp_dvar(IcpArgs A, int iter)
     if (icp_stopped(A.S, iter)) return;
     __shared__ double s[1][kBlock];
     double m[1];
-    reduce_parts<1, 0>(A.S, m, s);
+    sum_partials(A.S->part, 0, m, s);
     const double mean = m[0] / (double)A.n;
     __syncthreads();   // (s is reused)
-    double v[1] = {0.0};
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
+    double v[1];
+    grid_sum(A.n, v, s, [&](int64_t i, double* acc) {
         const double d = (double)A.cor[i].w - mean;
-        v[0] += d * d;
-    }
-    block_sum<1>(v, s);
+        acc[0] += d * d;
+    });
     if (threadIdx.x == 0) {
         A.S->part[blockIdx.x][1] = v[0];
         if (blockIdx.x == 0) A.S->dist_mean = mean;
@@ -228,7 +208,7 @@ __global__ __launch_bounds__(kBlock) void k_icp_dstats(IcpArgs A, int iter)
     if (icp_stopped(A.S, iter)) return;
     __shared__ double s[1][kBlock];
     double r[1];
-    reduce_parts<1, 1>(A.S, r, s);
+    sum_partials(A.S->part, 1, r, s);
     if (threadIdx.x != 0) return;
     A.S->dist_max = sdfk_icp::dist_max(A.S->dist_mean, r[0], (double)A.n, A.good);   // (icp_solve.h)
 }
@@ -239,16 +219,15 @@ __global__ __launch_bounds__(kBlock) void k_icp_fsum(IcpArgs A, int iter)
     if (icp_stopped(A.S, iter)) return;
     __shared__ double s[7][kBlock];
     const float dmax = A.S->dist_max;
-    double v[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
+    double v[7];
+    grid_sum(A.n, v, s, [&](int64_t i, double* acc) {
         const float4 c = A.cor[i];
         if (sdfk_icp::kept(c.w, dmax)) {
-            v[0] += 1.0;
-            v[1] += A.points[3 * i]; v[2] += A.points[3 * i + 1]; v[3] += A.points[3 * i + 2];
-            v[4] += c.x; v[5] += c.y; v[6] += c.z;
+            acc[0] += 1.0;
+            acc[1] += A.points[3 * i]; acc[2] += A.points[3 * i + 1]; acc[3] += A.points[3 * i + 2];
+            acc[4] += c.x; acc[5] += c.y; acc[6] += c.z;
         }
-    }
-    block_sum<7>(v, s);
+    });
     if (threadIdx.x == 0)
         for (int j = 0; j < 7; j++) A.S->part[blockIdx.x][j] = v[j];
 }
@@ -258,7 +237,7 @@ __global__ __launch_bounds__(kBlock) void k_icp_means(IcpArgs A, int iter)
     if (icp_stopped(A.S, iter)) return;
     __shared__ double s[7][kBlock];
     double r[7];
-    reduce_parts<7>(A.S, r, s);
+    sum_partials(A.S->part, 0, r, s);
     if (threadIdx.x != 0) return;
     for (int j = 0; j < 3; j++) { A.S->pmean[j] = r[1 + j] / r[0]; A.S->qmean[j] = r[4 + j] / r[0]; }
 }
@@ -271,8 +250,8 @@ __global__ __launch_bounds__(kBlock) void k_icp_csum(IcpArgs A, int iter)
     const float dmax = A.S->dist_max;
     const double pm0 = A.S->pmean[0], pm1 = A.S->pmean[1], pm2 = A.S->pmean[2];
     const double qm0 = A.S->qmean[0], qm1 = A.S->qmean[1], qm2 = A.S->qmean[2];
-    double v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
+    double v[9];
+    grid_sum(A.n, v, s, [&](int64_t i, double* acc) {
         const float4 c = A.cor[i];
         if (sdfk_icp::kept(c.w, dmax)) {
             const double p[3] = {A.points[3 * i] - pm0, A.points[3 * i + 1] - pm1, A.points[3 * i + 2] - pm2};
@@ -280,10 +259,9 @@ __global__ __launch_bounds__(kBlock) void k_icp_csum(IcpArgs A, int iter)
 #pragma unroll
             for (int a = 0; a < 3; a++)
 #pragma unroll
-                for (int b = 0; b < 3; b++) v[3 * a + b] += p[a] * q[b];
+                for (int b = 0; b < 3; b++) acc[3 * a + b] += p[a] * q[b];
         }
-    }
-    block_sum<9>(v, s);
+    });
     if (threadIdx.x == 0)
         for (int j = 0; j < 9; j++) A.S->part[blockIdx.x][j] = v[j];
 }
@@ -294,7 +272,7 @@ __global__ __launch_bounds__(kBlock) void k_icp_solve(IcpArgs A, int iter)
     if (icp_stopped(A.S, iter)) return;
     __shared__ double s[9][kBlock];
     double Cs[9];
-    reduce_parts<9>(A.S, Cs, s);
+    sum_partials(A.S->part, 0, Cs, s);
     if (threadIdx.x != 0) return;
     IcpState* S = A.S;
     float step[16], tot[16];
@@ -338,7 +316,7 @@ constexpr int kPlaneCols = 28;
 constexpr int kPlaneGroup = 7;
 
 struct IcpPlane {
-    double part[kRedBlocks][kPlaneCols];   // per-block partial sums of the current reduction
+    double part[kReduceBlocks][kPlaneCols];   // per-block partial sums of the current reduction
     double count;                          // kept points of this iteration
     double rsq;                            // sum of r^2 over them, before the step
     int retained;                          // eigenvalues the solve retained
@@ -361,32 +339,20 @@ __device__ __forceinline__ bool plane_cor(const IcpArgs& A, const IcpPlaneArgs& 
     return sdfk_icp::kept_plane(id, c.w, dmax, nrm);
 }
 
-template <int K>
-__device__ __forceinline__ void reduce_plane_parts(const IcpPlane* P, int off, double (&out)[K], double (*s)[kBlock])
-{
-#pragma unroll
-    for (int j = 0; j < K; j++) out[j] = 0.0;
-    for (int b = threadIdx.x; b < kRedBlocks; b += kBlock)
-#pragma unroll
-        for (int j = 0; j < K; j++) out[j] += P->part[b][off + j];
-    block_sum<K>(out, s);
-}
-
 // count and sum p of the kept points
 __global__ __launch_bounds__(kBlock) void k_icpp_centre(IcpArgs A, IcpPlaneArgs B, int iter)
 {
     if (icp_stopped(A.S, iter)) return;
     __shared__ double s[4][kBlock];
     const float dmax = A.S->dist_max;
-    double v[4] = {0, 0, 0, 0};
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
+    double v[4];
+    grid_sum(A.n, v, s, [&](int64_t i, double* acc) {
         float q[3], nrm[3];
         if (plane_cor(A, B, i, dmax, q, nrm)) {
-            v[0] += 1.0;
-            v[1] += A.points[3 * i]; v[2] += A.points[3 * i + 1]; v[3] += A.points[3 * i + 2];
+            acc[0] += 1.0;
+            acc[1] += A.points[3 * i]; acc[2] += A.points[3 * i + 1]; acc[3] += A.points[3 * i + 2];
         }
-    }
-    block_sum<4>(v, s);
+    });
     if (threadIdx.x == 0)
         for (int j = 0; j < 4; j++) B.P->part[blockIdx.x][j] = v[j];
 }
@@ -396,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void k_icpp_mean(IcpArgs A, IcpPlaneArgs B,
     if (icp_stopped(A.S, iter)) return;
     __shared__ double s[4][kBlock];
     double r[4];
-    reduce_plane_parts<4>(B.P, 0, r, s);
+    sum_partials(B.P->part, 0, r, s);
     if (threadIdx.x != 0) return;
     for (int j = 0; j < 3; j++) A.S->pmean[j] = r[1 + j] / r[0];
     B.P->count = r[0];
@@ -409,12 +375,10 @@ __global__ __launch_bounds__(kBlock) void k_icpp_nsum(IcpArgs A, IcpPlaneArgs B,
     __shared__ double s[kPlaneGroup][kBlock];
     const float dmax = A.S->dist_max;
     const double pm[3] = {A.S->pmean[0], A.S->pmean[1], A.S->pmean[2]};
-    double v[kPlaneCols / kPlaneGroup][kPlaneGroup];
-#pragma unroll
-    for (int c = 0; c < kPlaneCols; c++) v[c / kPlaneGroup][c % kPlaneGroup] = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < A.n; i += (int64_t)kRedBlocks * kBlock) {
+    double v[kPlaneCols];
+    grid_accumulate(A.n, v, [&](int64_t i, double* acc) {
         float q[3], nrm[3];
-        if (!plane_cor(A, B, i, dmax, q, nrm)) continue;
+        if (!plane_cor(A, B, i, dmax, q, nrm)) return;
         const float p[3] = {A.points[3 * i], A.points[3 * i + 1], A.points[3 * i + 2]};
         double J[6], r;
         sdfk_icp::plane_row(p, q, nrm, pm, J, &r);
@@ -422,16 +386,19 @@ __global__ __launch_bounds__(kBlock) void k_icpp_nsum(IcpArgs A, IcpPlaneArgs B,
 #pragma unroll
         for (int a = 0; a < 6; a++)
 #pragma unroll
-            for (int b = a; b < 6; b++) { v[c / kPlaneGroup][c % kPlaneGroup] += J[a] * J[b]; c++; }
+            for (int b = a; b < 6; b++) acc[c++] += J[a] * J[b];
 #pragma unroll
-        for (int a = 0; a < 6; a++) { v[c / kPlaneGroup][c % kPlaneGroup] += J[a] * r; c++; }
-        v[c / kPlaneGroup][c % kPlaneGroup] += r * r;
-    }
+        for (int a = 0; a < 6; a++) acc[c++] += J[a] * r;
+        acc[c] += r * r;
+    });
 #pragma unroll
-    for (int gq = 0; gq < kPlaneCols / kPlaneGroup; gq++) {
-        block_sum<kPlaneGroup>(v[gq], s);
+    for (int c0 = 0; c0 < kPlaneCols; c0 += kPlaneGroup) {
+        double grp[kPlaneGroup];
+#pragma unroll
+        for (int j = 0; j < kPlaneGroup; j++) grp[j] = v[c0 + j];
+        block_sum(grp, s);
         if (threadIdx.x == 0)
-            for (int j = 0; j < kPlaneGroup; j++) B.P->part[blockIdx.x][gq * kPlaneGroup + j] = v[gq][j];
+            for (int j = 0; j < kPlaneGroup; j++) B.P->part[blockIdx.x][c0 + j] = grp[j];
         __syncthreads();   // (s is reused)
     }
 }
@@ -444,7 +411,7 @@ __global__ __launch_bounds__(kBlock) void k_icpp_solve(IcpArgs A, IcpPlaneArgs B
     double red[kPlaneCols / kPlaneGroup][kPlaneGroup];
 #pragma unroll
     for (int gq = 0; gq < kPlaneCols / kPlaneGroup; gq++) {
-        reduce_plane_parts<kPlaneGroup>(B.P, gq * kPlaneGroup, red[gq], s);
+        sum_partials(B.P->part, gq * kPlaneGroup, red[gq], s);
         __syncthreads();   // (s is reused)
     }
     if (threadIdx.x != 0) return;
@@ -466,8 +433,6 @@ __global__ __launch_bounds__(kBlock) void k_icpp_solve(IcpArgs A, IcpPlaneArgs B
     S->stop = conv || iter + 1 >= A.max_iters;
 }
 
-unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock); }
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -485,13 +450,6 @@ void points_release(sdfk_points* s)
     s->xyz = nullptr;
     s->sorted = nullptr;
     s->starts = nullptr;
-}
-
-int scan_launch(uint32_t* buf, int64_t m, uint32_t* aux /* >= nb + 1 */)
-{
-    sdfk_scan::scan_launch<uint32_t>(buf, m, aux, g.stream);
-    HIPCHK(hipGetLastError());
-    return SDFK_OK;
 }
 
 // (Re)builds the search structure of s from s->xyz (synchronises: the host reads the bounding box to size the grid).  Refuses
@@ -522,9 +480,7 @@ int points_build(sdfk_points* s, const char* who)
 
     s->G = grid_for_box(box, box + 3, n);
     s->cells = (int64_t)s->G.dim[0] * s->G.dim[1] * s->G.dim[2];
-    const int64_t nb = sdfk_scan::scan_blocks(s->cells + 1);
     uint32_t* keys = nullptr;
-    uint32_t* aux = nullptr;
     uint32_t* cursor = nullptr;
     dev_free(s->sorted);
     dev_free(s->starts);
@@ -533,22 +489,20 @@ int points_build(sdfk_points* s, const char* who)
     r = dev_alloc((void**)&s->sorted, (size_t)n * sizeof(float4));
     if (!r) r = dev_alloc((void**)&s->starts, (size_t)(s->cells + 1) * sizeof(uint32_t));
     if (!r) r = dev_alloc((void**)&keys, (size_t)n * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&aux, (size_t)(nb + 2) * sizeof(uint32_t));
     if (!r) r = dev_alloc((void**)&cursor, (size_t)(s->cells + 1) * sizeof(uint32_t));
     if (!r) {
         ProfScope ps("k_pts_build");
         e = hipMemsetAsync(s->starts, 0, (size_t)(s->cells + 1) * sizeof(uint32_t), g.stream);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_pts_count, dim3(grid1(n)), dim3(kBlock), 0, g.stream, s->xyz, n, s->G, keys, s->starts);
-            r = scan_launch(s->starts, s->cells, aux);
+            hipLaunchKernelGGL(k_pts_count, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, s->xyz, n, s->G, keys, s->starts);
+            r = sdfk_scan::scan(s->starts, s->cells, who);
         }
         if (!r && e == hipSuccess) e = hipMemcpyAsync(cursor, s->starts, (size_t)s->cells * sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream);
         if (!r && e == hipSuccess)
-            hipLaunchKernelGGL(k_pts_scatter, dim3(grid1(n)), dim3(kBlock), 0, g.stream, s->xyz, n, keys, cursor, s->sorted);
+            hipLaunchKernelGGL(k_pts_scatter, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, s->xyz, n, keys, cursor, s->sorted);
         if (e == hipSuccess) e = hipGetLastError();
     }
     dev_free(keys);
-    dev_free(aux);
     dev_free(cursor);
     if (r) return r;
     if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
@@ -558,20 +512,11 @@ int points_build(sdfk_points* s, const char* who)
 // Queues the search of nq device queries (caller order in and out).  `icp`/`iter`: the launch of an ICP iteration.
 int points_search_launch(const sdfk_points* s, const float* q, int64_t nq, SearchOut O, const IcpState* icp, int iter)
 {
-    sdfk_walk::Candidates cand;   // (not counted for ICP's launches)
-    if (!icp)
-        if (int r = cand.begin()) return r;
-    O.candidates = cand.dev;
-    {
-        ProfScope ps("k_pts_search");
-        hipLaunchKernelGGL(k_pts_search, dim3(grid1(nq)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, s->first[0], s->first[1],
+    return sdfk_walk::walk_launch(s, nq, "k_pts_search", "points search", [&](unsigned long long* counter) {
+        O.candidates = counter;
+        hipLaunchKernelGGL(k_pts_search, dim3(grid_of(nq, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, s->first[0], s->first[1],
                            s->first[2], q, nq, O, icp, iter);
-    }
-    hipError_t e = hipGetLastError();
-    const hipError_t ec = cand.end(s, nq);
-    if (e == hipSuccess) e = ec;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "points search: %s", hipGetErrorString(e));
-    return SDFK_OK;
+    }, /* counted = */ !icp);   // (not counted for ICP's launches)
 }
 
 int points_make(const void* pts, int64_t n, bool device, sdfk_points** out)
@@ -659,21 +604,21 @@ int icp_run(sdfk_points* s, const sdfk_icp_params* prm, const float* normals_dev
                 r = points_search_launch(s, pts_dev, n, O, S, it);
                 if (r) break;
                 ProfScope ps(plane ? "k_icpp_step" : "k_icp_step");
-                hipLaunchKernelGGL(k_icp_dsum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
-                hipLaunchKernelGGL(k_icp_dvar, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
+                launch_grid_sum(k_icp_dsum, g.stream, A, it);
+                launch_grid_sum(k_icp_dvar, g.stream, A, it);
                 hipLaunchKernelGGL(k_icp_dstats, dim3(1), dim3(kBlock), 0, g.stream, A, it);
                 if (plane) {
-                    hipLaunchKernelGGL(k_icpp_centre, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, B, it);
+                    launch_grid_sum(k_icpp_centre, g.stream, A, B, it);
                     hipLaunchKernelGGL(k_icpp_mean, dim3(1), dim3(kBlock), 0, g.stream, A, B, it);
-                    hipLaunchKernelGGL(k_icpp_nsum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, B, it);
+                    launch_grid_sum(k_icpp_nsum, g.stream, A, B, it);
                     hipLaunchKernelGGL(k_icpp_solve, dim3(1), dim3(kBlock), 0, g.stream, A, B, it);
                 } else {
-                    hipLaunchKernelGGL(k_icp_fsum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
+                    launch_grid_sum(k_icp_fsum, g.stream, A, it);
                     hipLaunchKernelGGL(k_icp_means, dim3(1), dim3(kBlock), 0, g.stream, A, it);
-                    hipLaunchKernelGGL(k_icp_csum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, A, it);
+                    launch_grid_sum(k_icp_csum, g.stream, A, it);
                     hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(kBlock), 0, g.stream, A, it);
                 }
-                hipLaunchKernelGGL(k_icp_apply, dim3(grid1(n)), dim3(kBlock), 0, g.stream, A, it);
+                hipLaunchKernelGGL(k_icp_apply, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, A, it);
                 e = hipGetLastError();
             }
             if (r || e != hipSuccess) break;

@@ -3,7 +3,7 @@
 // statistical outlier rule over the k-nearest rows).  Contract: include/sdfkit_hip.h, "Point clouds: filters" and "Point clouds:
 // colours"; the arithmetic (voxel, range check, packed key, chunked centroid sum, row mean, threshold, keep rule): points_filter.h,
 // (the mean colour): points_color.h, both checked on the host; the walk, the tiers and the bounded lists: points_walk.h /
-// points_knn.h, shared with every query of the KdTree; the integer scan: device_scan.h.
+// points_knn.h, shared with every query of the KdTree; the integer scan of the sort and of both compactions: device_scan.h.
 //
 // Downsample:
 //   k_vf_keys      one lane per point: (packed key, insertion index) as one 16-byte record.
@@ -25,8 +25,8 @@
 //   k_vc_finish    at a head the chunk sums in order and the mean colour.  The sort and the segments are the centroids'.
 // Outliers:
 //   k_of_mean<CAP> one lane per static point on the shell walk (the tiers of k_pts_knn): the row's mean distance in binary64.
-//   k_of_sum / k_of_var / k_of_thr   the ICP's fixed-order reductions (256 blocks x 256 threads, halving trees): sum and count,
-//                  squared deviations, then mu, sigma and the threshold.
+//   k_of_sum / k_of_var / k_of_thr   the fixed-order reductions of device_reduce.h, as the ICP's: sum and count, squared
+//                  deviations, then mu, sigma and the threshold.
 //   k_of_flags     keep byte, flag and (float)mean; a scan; k_of_scatter writes the kept indices and points.
 #include "lib_internal.h"
 #include "device_reduce.h"
@@ -41,25 +41,6 @@ namespace {
 
 using namespace sdfk_walk;
 using namespace sdfk_filter;
-
-// ---- flag -> scan ------------------------------------------------------------------------------------------------------------
-// the exclusive scan of buf[0 .. n) in place, buf[n] = the total (both filters' compaction)
-int scan_flags(uint32_t* buf, int64_t n)
-{
-    uint32_t* aux = nullptr;
-    if (int r = dev_alloc((void**)&aux, (size_t)(sdfk_scan::scan_blocks(n) + 1) * sizeof(uint32_t))) return r;
-    sdfk_scan::scan_launch<uint32_t>(buf, n, aux, g.stream);
-    dev_free(aux);   // (stream-ordered pool)
-    HIPCHK(hipGetLastError());
-    return SDFK_OK;
-}
-
-hipError_t read_back(void* host, const void* dev, size_t bytes)
-{
-    hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, g.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    return e;
-}
 
 // ---- the radix sort ----------------------------------------------------------------------------------------------------------
 constexpr int kSortBlock = 256;
@@ -149,7 +130,7 @@ __global__ __launch_bounds__(kSortBlock) void k_rs_scatter(const Rec* __restrict
 }
 
 // Sorts the n records of a by key, stably, through the passes of `mask`; -> the buffer that holds the result (a or b).
-int radix_sort(Rec* a, Rec* b, int64_t n, unsigned mask, Rec** sorted)
+int radix_sort(Rec* a, Rec* b, int64_t n, unsigned mask, Rec** sorted, const char* who)
 {
     *sorted = a;
     if (!mask) return SDFK_OK;
@@ -162,7 +143,7 @@ int radix_sort(Rec* a, Rec* b, int64_t n, unsigned mask, Rec** sorted)
         if (!(mask >> d & 1u)) continue;
         ProfScope ps("k_rs_pass");
         hipLaunchKernelGGL(k_rs_hist, dim3(ntiles), dim3(kSortBlock), 0, g.stream, a, n, 8 * d, ntiles, hist);
-        r = scan_flags(hist, nh);
+        r = sdfk_scan::scan(hist, nh, who);
         if (r) break;
         hipLaunchKernelGGL(k_rs_scatter, dim3(ntiles), dim3(kSortBlock), 0, g.stream, a, b, n, 8 * d, ntiles, hist);
         std::swap(a, b);
@@ -285,8 +266,6 @@ __global__ __launch_bounds__(kBlock) void k_vc_finish(const Rec* __restrict__ s,
     for (int a = 0; a < 3; a++) colors_out[3 * (int64_t)o + a] = rgb[a];
 }
 
-unsigned grid1(int64_t n) { return grid_of(n, kBlock); }
-
 struct DownArgs {
     Lattice L;
     unsigned mask;   // the sort's passes
@@ -338,14 +317,14 @@ int downsample(const sdfk_points* s, const DownArgs& A, float* points_out, int32
     if (!r) r = dev_alloc((void**)&first, (size_t)(n + 1) * sizeof(uint32_t));
     if (!r) {
         ProfScope ps("k_vf_keys");
-        hipLaunchKernelGGL(k_vf_keys, dim3(grid1(n)), dim3(kBlock), 0, g.stream, s->xyz, n, A.L, ra);
+        hipLaunchKernelGGL(k_vf_keys, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, s->xyz, n, A.L, ra);
     }
-    if (!r) r = radix_sort(ra, rb, n, A.mask, &sorted);
+    if (!r) r = radix_sort(ra, rb, n, A.mask, &sorted, who);
     if (!r) {
         ProfScope ps("k_vf_heads");
-        hipLaunchKernelGGL(k_vf_heads, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, first);
-        r = scan_flags(seg, n);
-        if (!r) r = scan_flags(first, n);
+        hipLaunchKernelGGL(k_vf_heads, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, sorted, n, seg, first);
+        r = sdfk_scan::scan(seg, n, who);
+        if (!r) r = sdfk_scan::scan(first, n, who);
     }
     if (!r) e = read_back(&m, seg + n, sizeof m);
     const int64_t slots = n / kChunk + (int64_t)m + 2;
@@ -354,13 +333,13 @@ int downsample(const sdfk_points* s, const DownArgs& A, float* points_out, int32
     if (!r && e == hipSuccess && colors_out) r = dev_alloc((void**)&ccsum, (size_t)slots * 3 * sizeof(double));
     if (!r && e == hipSuccess) {
         ProfScope ps("k_vf_centroids");
-        hipLaunchKernelGGL(k_vf_starts, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, m, start);
+        hipLaunchKernelGGL(k_vf_starts, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, sorted, n, seg, m, start);
         if (points_out)
-            hipLaunchKernelGGL(k_vf_chunks, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, s->xyz, csum, slots);
-        hipLaunchKernelGGL(k_vf_finish, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, first, csum, slots, points_out, counts, group);
+            hipLaunchKernelGGL(k_vf_chunks, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, s->xyz, csum, slots);
+        hipLaunchKernelGGL(k_vf_finish, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, first, csum, slots, points_out, counts, group);
         if (colors_out) {
-            hipLaunchKernelGGL(k_vc_chunks, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, colors3, ccsum, slots);
-            hipLaunchKernelGGL(k_vc_finish, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, first, ccsum, slots, colors_out);
+            hipLaunchKernelGGL(k_vc_chunks, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, colors3, ccsum, slots);
+            hipLaunchKernelGGL(k_vc_finish, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, first, ccsum, slots, colors_out);
         }
         e = hipGetLastError();
     }
@@ -373,27 +352,13 @@ int downsample(const sdfk_points* s, const DownArgs& A, float* points_out, int32
 }
 
 // ---- statistical outliers ----------------------------------------------------------------------------------------------------
-constexpr int kRedBlocks = 256;   // the ICP's reduction grid (lib_points.hip): the summation order depends on n only
+using namespace sdfk_reduce;   // the fixed-order reductions, both levels
+static_assert(kBlock == kReduceBlock, "the reductions run in blocks of device_reduce.h's size");
 
 struct OfState {
-    double part[kRedBlocks][3];   // per-block partials: sum of the means, their count, sum of squared deviations
+    double part[kReduceBlocks][3];   // per-block partials: sum of the means, their count, sum of squared deviations
     double mu, sigma, thr, c;
 };
-
-using sdfk_reduce::block_sum;   // the ICP's fixed-order block sum
-static_assert(kBlock == sdfk_reduce::kReduceBlock, "the reductions run in blocks of device_reduce.h's size");
-
-// ... and its sum of the 256 partials (lib_points.hip reduce_parts): each added to a 0.0 of its own, then the same tree
-template <int K, int OFF>
-__device__ __forceinline__ void reduce_parts(const OfState* S, double (&out)[K], double (*s)[kBlock])
-{
-#pragma unroll
-    for (int j = 0; j < K; j++) out[j] = 0.0;
-    for (int b = threadIdx.x; b < kRedBlocks; b += kBlock)
-#pragma unroll
-        for (int j = 0; j < K; j++) out[j] += S->part[b][OFF + j];
-    block_sum<K>(out, s);
-}
 
 template <int CAP>
 __global__ __launch_bounds__(block_of<CAP>()) void k_of_mean(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,
@@ -419,12 +384,11 @@ __global__ __launch_bounds__(block_of<CAP>()) void k_of_mean(const float4* __res
 __global__ __launch_bounds__(kBlock) void k_of_sum(const double* __restrict__ mean, int64_t n, OfState* S)
 {
     __shared__ double s[2][kBlock];
-    double v[2] = {0.0, 0.0};
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)kRedBlocks * kBlock) {
+    double v[2];
+    grid_sum(n, v, s, [&](int64_t i, double* acc) {
         const double m = mean[i];
-        if (!is_isolated(m)) { v[0] += m; v[1] += 1.0; }
-    }
-    block_sum<2>(v, s);
+        if (!is_isolated(m)) { acc[0] += m; acc[1] += 1.0; }
+    });
     if (threadIdx.x == 0) { S->part[blockIdx.x][0] = v[0]; S->part[blockIdx.x][1] = v[1]; }
 }
 
@@ -432,18 +396,17 @@ __global__ __launch_bounds__(kBlock) void k_of_var(const double* __restrict__ me
 {
     __shared__ double s[2][kBlock];
     double t[2];
-    reduce_parts<2, 0>(S, t, s);   // (every block alike)
+    sum_partials(S->part, 0, t, s);   // (every block alike)
     const double mu = threshold_of(t[0], 0.0, t[1], 0.0f).mu;
     __syncthreads();   // (s is reused)
-    double v[1] = {0.0};
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)kRedBlocks * kBlock) {
+    double v[1];
+    grid_sum(n, v, s, [&](int64_t i, double* acc) {
         const double m = mean[i];
         if (!is_isolated(m)) {
             const double d = m - mu;
-            v[0] += d * d;
+            acc[0] += d * d;
         }
-    }
-    block_sum<1>(v, s);
+    });
     if (threadIdx.x == 0) S->part[blockIdx.x][2] = v[0];
 }
 
@@ -451,7 +414,7 @@ __global__ __launch_bounds__(kBlock) void k_of_thr(OfState* S, float std_ratio)
 {
     __shared__ double s[3][kBlock];
     double t[3];
-    reduce_parts<3, 0>(S, t, s);
+    sum_partials(S->part, 0, t, s);
     if (threadIdx.x != 0) return;
     const Threshold T = threshold_of(t[0], t[2], t[1], std_ratio);
     S->mu = T.mu; S->sigma = T.sigma; S->thr = T.thr; S->c = t[1];
@@ -522,16 +485,16 @@ int outliers(const sdfk_points* s, int k, float std_ratio, float max_distance, f
     }
     if (!r) {
         ProfScope ps("k_of_stats");
-        hipLaunchKernelGGL(k_of_sum, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, mean, n, S);
-        hipLaunchKernelGGL(k_of_var, dim3(kRedBlocks), dim3(kBlock), 0, g.stream, mean, n, S);
+        launch_grid_sum(k_of_sum, g.stream, mean, n, S);
+        launch_grid_sum(k_of_var, g.stream, mean, n, S);
         hipLaunchKernelGGL(k_of_thr, dim3(1), dim3(kBlock), 0, g.stream, S, std_ratio);
     }
     if (!r) {
         ProfScope ps("k_of_compact");
-        hipLaunchKernelGGL(k_of_flags, dim3(grid1(n)), dim3(kBlock), 0, g.stream, mean, n, S, mean_distance, keep, flag);
-        r = scan_flags(flag, n);
+        hipLaunchKernelGGL(k_of_flags, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, mean, n, S, mean_distance, keep, flag);
+        r = sdfk_scan::scan(flag, n, who);
         if (!r && (index_out || points_out))
-            hipLaunchKernelGGL(k_of_scatter, dim3(grid1(n)), dim3(kBlock), 0, g.stream, mean, n, S, flag, s->xyz, index_out, points_out);
+            hipLaunchKernelGGL(k_of_scatter, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, mean, n, S, flag, s->xyz, index_out, points_out);
         if (!r) e = hipGetLastError();
     }
     uint32_t kept = 0;

@@ -2,8 +2,8 @@
 // cell lists that lib_points.hip builds.  Contract: include/sdfkit_hip.h, "k nearest / within a radius"; the arithmetic (packed
 // (d2, index) keys, bounded lists, radius predicate, stopping rule): points_knn.h, checked on the host.
 //
-// One lane per query on the family's one shell walk (points_walk.h), the walk k_pts_search runs too; a kernel is the visitor it
-// hands the walk -- what a candidate meets and when the walk stops:
+// One lane per query on the family's one shell walk (points_walk.h), the walk k_pts_search runs too, launched as every walk kernel
+// is (walk_launch); a kernel is the visitor it hands the walk -- what a candidate meets and when the walk stops:
 //   k_pts_knn<CAP>       the k least keys within the radius bound; stops when the lower bound of every unvisited cell exceeds the
 //                        k-th key's d2 (+inf until k are held) or the radius bound.  CAP = 8: a sorted list in registers; CAP = 16 /
 //                        32 / 64: a max-heap in LDS, slot-major (slot * 64 + lane: conflict-free across the wave), ordered in place
@@ -22,7 +22,7 @@
 
 namespace {
 
-using namespace sdfk_walk;   // the shell walk, the k-nearest visitor, the LDS slots, the candidate counter
+using namespace sdfk_walk;   // the shell walk, the k-nearest visitor, the LDS slots, the profiled launch
 
 // ---- k nearest ---------------------------------------------------------------------------------------------------------------
 struct KnnOut {
@@ -142,62 +142,36 @@ __global__ __launch_bounds__(kBlock) void k_pts_radius_fill(const float4* __rest
 
 int knn_launch(const sdfk_points* s, const float* q, int64_t nq, int k, float d2_bound, KnnOut O)
 {
-    Candidates cand;
-    if (int r = cand.begin()) return r;
-    O.candidates = cand.dev;
-    {
-        ProfScope ps("k_pts_knn");
+    return walk_launch(s, nq, "k_pts_knn", "sdfk_points_knn", [&](unsigned long long* counter) {
+        O.candidates = counter;
         launch_tier(k, nq, [&](auto cap, dim3 grid, dim3 block) {
             hipLaunchKernelGGL(k_pts_knn<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, q, nq, k, d2_bound, O);
         });
-    }
-    hipError_t e = hipGetLastError();
-    const hipError_t ec = cand.end(s, nq);
-    if (e == hipSuccess) e = ec;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_knn: %s", hipGetErrorString(e));
-    return SDFK_OK;
+    });
 }
 
 // offsets_dev[0 .. nq]: the counts, scanned in place
 int count_launch(const sdfk_points* s, const float* q, int64_t nq, float d2_bound, int64_t* offsets_dev)
 {
+    static const char* who = "sdfk_points_radius_count";
     unsigned long long* off = reinterpret_cast<unsigned long long*>(offsets_dev);
-    unsigned long long* aux = nullptr;
-    if (int r = dev_alloc((void**)&aux, (size_t)(sdfk_scan::scan_blocks(nq) + 1) * sizeof(unsigned long long))) return r;
-    Candidates cand;
-    if (int r = cand.begin()) { dev_free(aux); return r; }
-    {
-        ProfScope ps("k_pts_radius_count");
+    return walk_launch(s, nq, "k_pts_radius_count", who, [&](unsigned long long* counter) {
         hipLaunchKernelGGL(k_pts_radius_count, dim3(grid_of(nq, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, q, nq, d2_bound, off,
-                           cand.dev);
-        sdfk_scan::scan_launch<unsigned long long>(off, nq, aux, g.stream);
-    }
-    dev_free(aux);   // (stream-ordered pool)
-    hipError_t e = hipGetLastError();
-    const hipError_t ec = cand.end(s, nq);
-    if (e == hipSuccess) e = ec;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_radius_count: %s", hipGetErrorString(e));
-    return SDFK_OK;
+                           counter);
+        return sdfk_scan::scan(off, nq, who);
+    });
 }
 
 int fill_launch(const sdfk_points* s, const float* q, int64_t nq, float d2_bound, const int64_t* offsets_dev, int32_t* index, float* distance)
 {
-    Candidates cand;
-    if (int r = cand.begin()) return r;
-    {
-        ProfScope ps("k_pts_radius_fill");
+    return walk_launch(s, nq, "k_pts_radius_fill", "sdfk_points_radius_fill", [&](unsigned long long* counter) {
         if (distance)
             hipLaunchKernelGGL(k_pts_radius_fill<true>, dim3(grid_of(nq, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, q, nq,
-                               d2_bound, offsets_dev, index, distance, cand.dev);
+                               d2_bound, offsets_dev, index, distance, counter);
         else
             hipLaunchKernelGGL(k_pts_radius_fill<false>, dim3(grid_of(nq, kBlock)), dim3(kBlock), 0, g.stream, s->sorted, s->starts, s->G, s->xyz, q, nq,
-                               d2_bound, offsets_dev, index, distance, cand.dev);
-    }
-    hipError_t e = hipGetLastError();
-    const hipError_t ec = cand.end(s, nq);
-    if (e == hipSuccess) e = ec;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_points_radius_fill: %s", hipGetErrorString(e));
-    return SDFK_OK;
+                               d2_bound, offsets_dev, index, distance, counter);
+    });
 }
 
 int check_queries(const sdfk_points* s, const void* queries, int64_t n, const char* who)

@@ -2,8 +2,8 @@
 // parity along z.  Contract: include/sdfkit_hip.h, "Triangle-mesh distance".  Arithmetic: trimesh_sdf.h (shared with a host test).
 //
 // Build (create): the triangles are validated and packed on the device (vertices + f32 AABB, 64 bytes each), then binned into
-// every cell of a uniform grid (points_grid.h, sized from the triangle count) that their AABB overlaps, by count, scan and
-// scatter.  Two prefix arrays describe the cells: `starts` in x-fastest order (a run of x cells is one contiguous range of the
+// every cell of a uniform grid (points_grid.h, sized from the triangle count) that their AABB overlaps, by count, scan
+// (device_scan.h) and scatter.  Two prefix arrays describe the cells: `starts` in x-fastest order (a run of x cells is one contiguous range of the
 // sorted list) and `ystarts` in y-fastest order (a run of y cells can be tested for emptiness with two loads).
 // Search: one lane per query, cells in growing Chebyshev shells, each shell as its six faces: z and y faces as x runs, x faces as
 // y runs skipped when empty.  It stops when a conservative f32 lower bound on every unvisited cell exceeds the best d2 (or the
@@ -35,19 +35,6 @@ struct TriPack {
 };
 
 unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, int64_t(1) << 30)); }
-
-// buf[0..m) -> exclusive prefix, buf[m] = total (device_scan.h)
-template <typename T>
-int scan(T* buf, int64_t m, const char* who)
-{
-    T* aux = nullptr;
-    if (int r = dev_alloc((void**)&aux, (size_t)(sdfk_scan::scan_blocks(m) + 1) * sizeof(T))) return r;
-    sdfk_scan::scan_launch<T>(buf, m, aux, g.stream);
-    dev_free(aux);   // (stream-ordered pool)
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return SDFK_OK;
-}
 
 // ---- build ------------------------------------------------------------------------------------------------------------------
 // flags[0]: indices out of range, flags[1]: non-finite vertex coordinates
@@ -516,7 +503,7 @@ int trimesh_build(sdfk_trimesh* t)
     if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     if (entries >= (1ull << 32)) return fail(SDFK_ERR_INVALID, "%s: 2^32 triangle-cell pairs or more", who);
     t->entries = (int64_t)entries;
-    r = scan<uint32_t>(t->starts, t->cells, who);
+    r = sdfk_scan::scan(t->starts, t->cells, who);
     if (!r) r = dev_alloc((void**)&t->list, (size_t)std::max<int64_t>(t->entries, 1) * sizeof(uint32_t));
     if (!r) r = dev_alloc((void**)&cursor, (size_t)t->cells * sizeof(uint32_t));
     if (!r) r = dev_alloc((void**)&t->ystarts, (size_t)(t->cells + 1) * sizeof(uint32_t));
@@ -529,7 +516,7 @@ int trimesh_build(sdfk_trimesh* t)
             e = hipGetLastError();
         }
     }
-    if (!r && e == hipSuccess) r = scan<uint32_t>(t->ystarts, t->cells, who);
+    if (!r && e == hipSuccess) r = sdfk_scan::scan(t->ystarts, t->cells, who);
     if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);   // (the cursor goes back to the pool; the caller's arrays are not retained)
     dev_free(cursor);
     if (r) return r;
@@ -623,7 +610,7 @@ int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band)
         ProfScope ps("k_tm_cross");
         hipLaunchKernelGGL(k_tm_items, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->tri, nt, Q, box, items);
         e = hipGetLastError();
-        if (e == hipSuccess) r = scan<unsigned long long>(items, nt, who);
+        if (e == hipSuccess) r = sdfk_scan::scan(items, nt, who);
         if (!r && e == hipSuccess) e = hipMemcpyAsync(&n_items, items + nt, sizeof n_items, hipMemcpyDeviceToHost, g.stream);
         if (!r && e == hipSuccess) e = hipMemsetAsync(col, 0, (size_t)(ncol + 1) * sizeof(uint32_t), g.stream);
         if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);
@@ -631,7 +618,7 @@ int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band)
             hipLaunchKernelGGL(k_tm_cross<0>, dim3(grid_items(n_items)), dim3(kBlock), 0, g.stream, t->tri, nt, Q, box, items, n_items, col, nullptr);
             e = hipGetLastError();
         }
-        if (!r && e == hipSuccess) r = scan<uint32_t>(col, ncol, who);
+        if (!r && e == hipSuccess) r = sdfk_scan::scan(col, ncol, who);
         if (!r && e == hipSuccess) e = hipMemcpyAsync(&n_cross, col + ncol, sizeof n_cross, hipMemcpyDeviceToHost, g.stream);
         if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);
         if (!r && e == hipSuccess) r = dev_alloc((void**)&zrec, (size_t)std::max<uint32_t>(n_cross, 1) * sizeof(double));

@@ -1,6 +1,7 @@
 // points_set.h -- the handle behind sdfk_points_* (KdTree): the static points and their search grid, built by lib_points.hip and
 // read by every query of the family (lib_points.hip, lib_points_knn.hip, lib_pointcloud.hip, lib_orient.hip, lib_points_filter.hip) through the walk of
-// points_walk.h; and Staged, the device copies of the arrays of a query's host form.
+// points_walk.h; and what owns the copies between host and device on g.stream: Staged, the device copies of the arrays of a query's
+// host form, and read_back, a device value the host needs on the way.
 #pragma once
 #include "lib_internal.h"
 #include "points_grid.h"
@@ -18,6 +19,14 @@ struct sdfk_points {
     float first[3] = {0, 0, 0};
     int64_t last_candidates = 0, last_queries = 0;   // of the last profiled query call, whichever kind
 };
+
+// `bytes` of device memory into the host's, synchronised
+inline hipError_t read_back(void* host, const void* dev, size_t bytes)
+{
+    hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, g.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    return e;
+}
 
 // The device copies of a host form's arrays on g.stream.  Nothing more is queued after the first failure; finish() copies the
 // outputs back, synchronises -- on failure too -- before any buffer is freed, and reports: an SDFK_ERR_* of an allocation or of

@@ -1,9 +1,10 @@
 // points_walk.h -- the owner of the KdTree's shell walk: the one walk over the grid of sorted cell lists that lib_points.hip builds,
 // with its conservative lower bound, run by every query kernel (lib_points.hip: nearest point, ICP; lib_points_knn.hip: k nearest,
-// within a radius; lib_pointcloud.hip: normals, volumes; lib_orient.hip: neighbour rows; lib_points_filter.hip: mean neighbour distances) through a visitor.  Also what the
-// k-nearest kernels share: the visitor that keeps the k least keys, the LDS storage of the heap tiers, the launch of a kernel's
-// tier for k, and the candidate counter of a profiled call.  The arithmetic of keys, lists and the k-nearest stopping rule is
-// points_knn.h's.  hipcc only.
+// within a radius; lib_pointcloud.hip: normals, volumes; lib_orient.hip: neighbour rows; lib_points_filter.hip: mean neighbour
+// distances) through a visitor.  Also what the k-nearest kernels share: the visitor that keeps the k least keys, the LDS storage of
+// the heap tiers and the launch of a kernel's tier for k; the one grid computation of the family (grid_of); and walk_launch, the
+// launch of a walk kernel under its span with the candidate counter of a profiled call.  The arithmetic of keys, lists and the
+// k-nearest stopping rule is points_knn.h's.  hipcc only.
 #pragma once
 #include "lib_internal.h"
 #include "points_knn.h"
@@ -222,32 +223,39 @@ inline void launch_tier(int k, int64_t n, F&& launch)
     }
 }
 
-// the candidate counter of a profiled call (sdfk_points_stats[3..4]); null when profiling is off
-struct Candidates {
+// The launch of a walk kernel (or of the tiers of one): launch(counter) queues it under the span `name`, counter being the device
+// word its lanes add their candidates to -- null unless profiling is on (and `counted`), when the call zeroes it before, and reads
+// it into sdfk_points_stats[3..4] with the nq queries after (which synchronises).  launch returns nothing, or the SDFK_ERR_* of
+// what it queued besides.  SDFK_OK or the failure as "<who>: <error string>": the launch's HIP error before the counter's, then
+// what launch returned.
+template <class F>
+inline int walk_launch(const sdfk_points* s, int64_t nq, const char* name, const char* who, F&& launch, bool counted = true)
+{
     unsigned long long* dev = nullptr;
-    int begin()
-    {
-        if (!g.prof_on) return SDFK_OK;
+    if (counted && g.prof_on) {
         if (int r = dev_alloc((void**)&dev, sizeof(unsigned long long))) return r;
         if (hipMemsetAsync(dev, 0, sizeof(unsigned long long), g.stream) != hipSuccess) {
             dev_free(dev);
-            dev = nullptr;
             return fail(SDFK_ERR_HIP, "points query: memset");
         }
-        return SDFK_OK;
     }
-    hipError_t end(const sdfk_points* s, int64_t nq)   // (synchronises, as the profiled search does)
+    int r = SDFK_OK;
     {
-        if (!dev) return hipSuccess;
+        ProfScope ps(name);
+        if constexpr (std::is_void<decltype(launch(dev))>::value) launch(dev);
+        else r = launch(dev);
+    }
+    hipError_t e = hipGetLastError();
+    if (dev) {
         unsigned long long c = 0;
-        hipError_t e = hipMemcpyAsync(&c, dev, sizeof c, hipMemcpyDeviceToHost, g.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+        const hipError_t ec = read_back(&c, dev, sizeof c);
         const_cast<sdfk_points*>(s)->last_candidates = (int64_t)c;
         const_cast<sdfk_points*>(s)->last_queries = nq;
         dev_free(dev);
-        dev = nullptr;
-        return e;
+        if (e == hipSuccess) e = ec;
     }
-};
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return r;
+}
 
 }  // namespace sdfk_walk

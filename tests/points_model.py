@@ -122,7 +122,7 @@ def register(static, points, max_iterations=100, good=f32(0.01), max_t=f32(1e-4)
 
 
 # ---- the bit-exact model: the device's reduction order and csrc/icp_solve.h, operation by operation ----
-RED_BLOCKS, RED_THREADS = 256, 256            # the reduction grid of lib_points.hip: a grid stride of 65536
+RED_BLOCKS, RED_THREADS = 256, 256            # the reduction grid of csrc/device_reduce.h: a grid stride of 65536
 f64 = np.float64
 
 
