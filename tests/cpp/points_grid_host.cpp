@@ -2,9 +2,15 @@
 // the same functions the kernels call) on the boxes that stress it: every cell index of every coordinate -- the box's ends,
 // values just outside, NaN, infinities -- lies in [0, dim), every key in [0, cells), the cell counts stay within their bounds,
 // and cells are monotone along each axis.  Prints "grid ok" and exits 0, or the first failure and exits 1.
+//
+//   points_grid_host cells IN OUT   the grid and the cells of given coordinates, for tests/test_points_walk_model.py to compare
+//                                   the numpy restatement (tests/meshsdf_cases.py grid_for_box / cell_of) with, bit for bit.
+//                                   IN: f32 lo[3], hi[3]; i64 n, m; m x 3 f32 coordinates (any value).
+//                                   OUT: i32 dim[3]; f32 h, inv_h, slack; m x 3 i32 cells (cell_of per axis).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <random>
 #include <vector>
@@ -46,8 +52,34 @@ static void check_box(const char* what, float lo[3], float hi[3], int64_t n)
     printf("%-34s n = %-11lld dim = %d x %d x %d\n", what, (long long)n, G.dim[0], G.dim[1], G.dim[2]);
 }
 
-int main()
+static int cells_mode(const char* in_path, const char* out_path)
 {
+    FILE* f = fopen(in_path, "rb");
+    if (!f) { printf("cannot read %s\n", in_path); return 1; }
+    float box[6];
+    int64_t nm[2];
+    if (fread(box, sizeof(float), 6, f) != 6 || fread(nm, sizeof(int64_t), 2, f) != 2 || nm[1] < 0) { printf("short input\n"); fclose(f); return 1; }
+    std::vector<float> x((size_t)nm[1] * 3);
+    if (fread(x.data(), sizeof(float), x.size(), f) != x.size()) { printf("short input\n"); fclose(f); return 1; }
+    fclose(f);
+    const Grid G = grid_for_box(box, box + 3, nm[0]);
+    std::vector<int32_t> cells(x.size());
+    for (size_t i = 0; i < x.size(); i++) cells[i] = cell_of(x[i], G.lo[i % 3], G.inv_h, G.dim[i % 3]);
+    f = fopen(out_path, "wb");
+    if (!f) { printf("cannot write %s\n", out_path); return 1; }
+    const int32_t dim[3] = {G.dim[0], G.dim[1], G.dim[2]};
+    const float hs[3] = {G.h, G.inv_h, G.slack};
+    fwrite(dim, sizeof(int32_t), 3, f);
+    fwrite(hs, sizeof(float), 3, f);
+    fwrite(cells.data(), sizeof(int32_t), cells.size(), f);
+    fclose(f);
+    printf("cells ok\n");
+    return 0;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc == 4 && !strcmp(argv[1], "cells")) return cells_mode(argv[2], argv[3]);
     {   // a line of 20 000 000 points on x in [0, 1]: the single-axis request exceeds 2^24 cells
         float lo[3] = {0, 0, 0}, hi[3] = {1, 0, 0};
         check_box("line x [0,1], 2e7 points", lo, hi, 20000000);

@@ -60,10 +60,13 @@ def mesh_grid(V, T):
 
 
 def cell_of(G, X):
-    """points_grid.h cell_of per axis, f32 as there: (n, 3) coordinates -> (n, 3) cells."""
+    """points_grid.h cell_of per axis, f32 as there: (n, 3) coordinates -> (n, 3) cells.  fmaxf / fminf return the other operand
+    of a NaN (np.fmax / np.fmin; np.maximum would hand the NaN on), so a NaN -- a NaN coordinate, or 0 * inf where inv_h has
+    overflowed -- lands in cell 0; the truncation comes after the clamp."""
     X = np.asarray(X, f32).reshape(-1, 3)
-    t = (X - G["lo"][None]) * G["inv_h"]
-    t = np.minimum(np.maximum(t, f32(0)), f32(K_MAX_AXIS))
+    with np.errstate(all="ignore"):
+        t = (X - G["lo"][None]) * G["inv_h"]
+    t = np.fmin(np.fmax(t, f32(0)), f32(K_MAX_AXIS))
     return np.minimum(t.astype(np.int64), np.asarray(G["dim"], np.int64)[None] - 1)
 
 
