@@ -781,7 +781,7 @@ public:
     // Extensions (sdfkit_hip.h, "Point clouds: normals and volumes").
     struct Normals {
         std::vector<Vector3> Normal;     // per static point; (0, 0, 0) where the neighbourhood is degenerate
-        std::vector<float> Variation;    // lmin / (l0 + l1 + l2)
+        std::vector<float> Variation;    // max(lmin, 0) / (l0 + l1 + l2): never negative, +0 on an exact plane
     };
     // A normal per static point from its k nearest (3 <= k <= 64), turned towards the viewpoints: none (the largest component is
     // made positive -- not a consistent orientation of a closed surface: OrientNormals makes one afterwards), one, or one per point.

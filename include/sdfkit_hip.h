@@ -611,7 +611,10 @@ int sdfk_points_radius_fill_device(const sdfk_points* s, const void* queries3_de
  *    d = ((w0 - p0) n0 + (w1 - p1) n1) + (w2 - p2) n2; d < 0 flips n.  With no viewpoint, or d exactly 0, the component of n of
  *    largest magnitude is made positive (ties: the lowest axis).  That is NOT a consistent orientation of a closed surface; one
  *    without a viewpoint is sdfk_points_orient_normals' (below), applied to these normals afterwards.
- * 5. normal = n rounded to f32; variation = (float)(l_min / ((l_0 + l_1) + l_2)) (surface variation: 0 on a plane, up to 1/3).
+ * 5. normal = n rounded to f32; variation = (float)(max(l_min, 0) / ((l_0 + l_1) + l_2)) (surface variation: 0 on a plane, up to
+ *    1/3).  The covariance is positive semi-definite, so an l_min below zero is rounding noise (an exactly planar neighbourhood,
+ *    which every three points are, ends there as often as not): it counts as zero and the variation is +0.0, never negative.
+ *    Only the numerator is clamped; the denominator is the sum of the diagonal as it stands.
  * 6. Degenerate: m < 3, or (c00 + c11) + c22 == 0: normal = (0, 0, 0), variation = 0.  A collinear neighbourhood gives a
  *    deterministic but meaningless direction.
  * 7. SDFK_ERR_INVALID: k outside [3, 64], a NaN or negative max_distance, n_viewpoints not 0, 1 or the number of static points, a

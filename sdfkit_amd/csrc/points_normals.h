@@ -106,7 +106,8 @@ struct Eigen3 {
 // ---- one point's normal --------------------------------------------------------------------------------------------------------
 // From the finished covariance of m neighbours: degenerate (m < 3 or trace == 0): normal = (0, 0, 0), variation = 0.  Otherwise
 // n = column least() of V, normalised: len = sqrt((n0 n0 + n1 n1) + n2 n2), n_a = n_a / len; oriented (below); normal = (float)n_a;
-// variation = (float)(l_min / ((l_0 + l_1) + l_2)), l the diagonal after the sweeps.
+// variation = (float)(max(l_min, 0) / ((l_0 + l_1) + l_2)), l the diagonal after the sweeps: the covariance is positive semi-definite, so
+// an l_min below zero is rounding noise (every exactly planar neighbourhood, three points among them) and counts as zero.
 // Orientation.  With a viewpoint w: d = ((w0 - p0) n0 + (w1 - p1) n1) + (w2 - p2) n2 (binary64, w and p widened first); d < 0
 // flips n, d > 0 keeps it.  Without a viewpoint, or when d is neither (exactly 0, or NaN from a non-finite viewpoint of the
 // unchecked device form): the component of largest magnitude is made positive, ties to the lowest axis.
@@ -139,6 +140,7 @@ SDFK_PC_HD void normal_of(const Cov& C, int m, const float pi[3], bool has_viewp
         flip = big < 0.0;
     }
     for (int a = 0; a < 3; a++) normal[a] = (float)(flip ? -n[a] : n[a]);
+    if (lmin < 0.0) lmin = 0.0;
     *variation = (float)(lmin / ((E.a[0][0] + E.a[1][1]) + E.a[2][2]));
 }
 

@@ -129,7 +129,8 @@ class KdTree:
     def EstimateNormals(self, k, viewpoint=None, maxDistance=np.inf):
         """Extension: a normal per static point from its k nearest (itself included; 3 <= k <= 64, no farther than maxDistance)
         -> (normals (n, 3) float32, variation (n,) float32): the eigenvector of the least eigenvalue of the neighbourhood's
-        covariance and the surface variation lmin / (l0 + l1 + l2) (include/sdfkit_hip.h, "Point clouds").  A point with fewer
+        covariance and the surface variation max(lmin, 0) / (l0 + l1 + l2), never negative and exactly +0 where rounding leaves lmin
+        below zero, as on an exact plane (include/sdfkit_hip.h, "Point clouds").  A point with fewer
         than 3 neighbours, or all of them equal, gets (0, 0, 0) and 0.
         viewpoint: one Vector3, or one per point -- each normal is turned towards it.  Without one the component of largest
         magnitude is made positive, which is NOT a consistent orientation of a closed surface: OrientNormals makes one of these

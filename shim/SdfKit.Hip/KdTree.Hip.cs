@@ -99,7 +99,7 @@ namespace SdfKit
 
         /// <summary>Extension: a normal per static point (insertion order) from its k nearest (3..64, itself included, no farther than
         /// maxDistance): the eigenvector of the least eigenvalue of the neighbourhood's covariance, and the surface variation
-        /// lmin / (l0 + l1 + l2).  viewpoints: empty (the largest component is made positive -- not a consistent orientation of
+        /// max(lmin, 0) / (l0 + l1 + l2), never negative (exactly +0 on an exact plane).  viewpoints: empty (the largest component is made positive -- not a consistent orientation of
         /// a closed surface: OrientNormals makes one afterwards), one for all points, or one per point; each normal is turned towards its
         /// viewpoint.  Degenerate neighbourhoods give (0, 0, 0) and 0.</summary>
         public unsafe void EstimateNormals (int k, Span<Vector3> normals, Span<float> variation, ReadOnlySpan<Vector3> viewpoints = default,

@@ -8,6 +8,7 @@
 //                                        OUT (f32): per case known (0 / 1), value
 //   points_normals_host fill    IN OUT   IN (i32): nx, ny, nz, then nx * ny * nz signs (z fastest) -> OUT (i32): the signs after the
 //                                        passes along z, y, x (a volume without a sign: all +1), then the number of entries filled
+//   points_normals_host sign    IN OUT   IN (f32): known values -> OUT (i32): the sign each hands to the far fill
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -104,6 +105,11 @@ int main(int argc, char** argv)
                     for (int i = 0; i < nx; i++) { s[((size_t)i * ny + j) * nz + k] = 1; filled++; }
         std::vector<int32_t> out(s.begin(), s.end());
         out.push_back(filled);
+        write_all(argv[3], out);
+    } else if (!strcmp(mode, "sign")) {
+        const auto in = read_all<float>(argv[2]);
+        std::vector<int32_t> out;
+        for (float v : in) out.push_back(sign_of(v));
         write_all(argv[3], out);
     } else
         return 2;

@@ -120,7 +120,7 @@ def normals_from_neighbours(P, idx, found, viewpoint=None):
             d = ((w[:, 0] - P64[:, 0]) * nv[:, 0] + (w[:, 1] - P64[:, 1]) * nv[:, 1]) + (w[:, 2] - P64[:, 2]) * nv[:, 2]
             flip = np.where((d < 0.0) | (d > 0.0), d < 0.0, flip)
         nv = np.where(flip[:, None], -nv, nv)
-        variation = lmin / ((a[0][0] + a[1][1]) + a[2][2])
+        variation = np.where(lmin < 0.0, 0.0, lmin) / ((a[0][0] + a[1][1]) + a[2][2])   # (a negative l_min is rounding noise: +0.0)
     degenerate = (found < 3) | (trace == 0.0)
     normals = np.where(degenerate[:, None], 0.0, nv).astype(f32)
     return normals, np.where(degenerate, 0.0, variation).astype(f32)
