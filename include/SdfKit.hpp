@@ -325,11 +325,21 @@ struct Sdfs {   // Sdf.cs:118-215 (batched delegates that only assign .W leave c
 // ---------------------------------------------------------------------------------------
 // Mesh (Mesh.cs:8-64)
 // ---------------------------------------------------------------------------------------
+// MeshSdf::SamplePoints / Mesh::SamplePoints (not in the reference): per sample the point, the unit face normal, the blended colour
+// (empty when the mesh has none), the triangle and the barycentric weights of its three vertices as the colour blend used them.
+struct MeshSamples {
+    std::vector<Vector3> Points, Normals, Colors;
+    std::vector<int32_t> Triangles;
+    std::vector<Vector3> Weights;
+};
+
 class Mesh {
 public:
     std::vector<Vector3> Vertices, Colors, Normals;
     std::vector<int32_t> Triangles;
     Vector3 Min, Max;
+    // n points on the triangles in proportion to area (MeshSdf(*this).SamplePoints)
+    inline MeshSamples SamplePoints(int64_t n, uint64_t seed = 0, bool stratified = true) const;
     Vector3 Center() const { return (Min + Max) * 0.5f; }
     Vector3 Size() const { return Max - Min; }
     float Radius() const { return (Max - Min).Length() * 0.5f; }
@@ -1096,6 +1106,25 @@ public:
         v.hostNewer_ = false;
         v.version_++;
     }
+    // n points on the triangles in proportion to area (sdfk_trimesh_sample: one stated function of the mesh, n, seed and the mode).
+    // stratified: one sample per equal share of the total area, in triangle order; otherwise independent draws.  Normals: the unit
+    // face normals of the winding (b - a) x (c - a).  A mesh in which no triangle has an area is refused.
+    MeshSamples SamplePoints(int64_t n, uint64_t seed = 0, bool stratified = true) const
+    {
+        MeshSamples s;
+        const int32_t flags = stratified ? SDFK_TRIMESH_SAMPLE_STRATIFIED : 0;
+        if (n < 0 || n >= (int64_t(1) << 31))   // (the library refuses it: nothing is allocated for it first)
+            Check(sdfk_trimesh_sample(h_, n, seed, flags, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        const size_t m = n > 0 ? (size_t)n : 0;
+        s.Points.resize(m); s.Normals.resize(m); s.Triangles.resize(m); s.Weights.resize(m);
+        if (hasColors_) s.Colors.resize(m);
+        Check(sdfk_trimesh_sample(h_, n, seed, flags, &s.Points.data()->X, &s.Normals.data()->X,
+                                  hasColors_ ? &s.Colors.data()->X : nullptr, s.Triangles.data(), &s.Weights.data()->X, sampleStats_));
+        return s;
+    }
+    // triangles of non-zero sampling weight and the total weight (the largest triangle has 2^32), as the last SamplePoints read them
+    int64_t SampledTriangles() const { return sampleStats_[0]; }
+    int64_t SampleTotalWeight() const { return sampleStats_[1]; }
     sdfk_trimesh* Handle() const { return h_; }
 
 private:
@@ -1106,7 +1135,10 @@ private:
     }
     sdfk_trimesh* h_ = nullptr;
     bool hasColors_ = false;
+    mutable int64_t sampleStats_[2] = {0, 0};
 };
+
+inline MeshSamples Mesh::SamplePoints(int64_t n, uint64_t seed, bool stratified) const { return MeshSdf(*this).SamplePoints(n, seed, stratified); }
 
 struct FloatData {   // VectorData.cs:137-280; indexer is (x, y)
     int Width = 0, Height = 0;

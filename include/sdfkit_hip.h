@@ -936,6 +936,42 @@ int sdfk_trimesh_to_volume(const sdfk_trimesh* t, sdfk_volume* v, float max_dist
 int sdfk_trimesh_stats(const sdfk_trimesh* t, int64_t stats[8]);
 void sdfk_trimesh_free(sdfk_trimesh* t);
 
+/* ---- Triangle meshes: sampling (Mesh.SamplePoints: Mesh -> points) ------------------------------------------------------------
+ * n points on the triangles of a mesh, in proportion to area, each with its face normal, blended colour, triangle index and
+ * barycentric weights.  ONE function of (mesh, n, seed, flags), computed by csrc/trimesh_sample.h (no contraction); everything
+ * that is accumulated is an integer, so no result depends on a summation order and every output is reproducible bit for bit.
+ * Weights: for triangle t with f32 vertices a, b, c widened to binary64: e1 = b - a, e2 = c - a, n = e1 x e2 (each product
+ * rounded, then one subtraction), A2 = (n.x n.x + n.y n.y) + n.z n.z; A2max = the largest A2;
+ * w_t = (uint64)(sqrt(A2_t / A2max) * 2^32) (one division, one correctly rounded root, an exact scaling, truncation), so
+ * w_t <= 2^32 and the total stays below 2^63.  A triangle whose area is below 2^-32 of the largest one gets weight 0 and is never
+ * sampled.  W = the exclusive 64-bit integer scan of w, W[nt] = total.  A mesh in which no triangle has an area (A2max == 0) is
+ * refused with SDFK_ERR_INVALID ("no triangle has an area"); the handle stays usable for everything else.
+ * Draws: splitmix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31 (mod 2^64).
+ * Sample s takes h_j = splitmix(seed + (3 s + j + 1) * 0x9E3779B97F4A7C15), j = 0, 1, 2: no state is carried, and without
+ * SDFK_TRIMESH_SAMPLE_STRATIFIED sample s does not depend on n.
+ * Triangle: flags = 0: r = mulhi64(h0, total).  SDFK_TRIMESH_SAMPLE_STRATIFIED: lo_s = floor(s total / n), computed as
+ * (total / n) s + ((total % n) s) / n, and r = lo_s + mulhi64(h0, lo_{s+1} - lo_s): one sample per stratum of the total, so
+ * triangle t is drawn n w_t / total times to within less than 2, and the output follows the triangle order.  The triangle is the
+ * unique t with W[t] <= r < W[t + 1].
+ * Position: k1 = h1 >> 11, k2 = h2 >> 11; if k1 + k2 > 2^53 both are replaced by 2^53 - k; k0 = 2^53 - k1 - k2 (>= 0).  The
+ * weights w_i = k_i 2^-53 are exact in binary64 and sum to 1.
+ * Outputs per sample (each may be NULL): points3 = (float)((w0 a + w1 b) + w2 c) per axis, in binary64; normals3 =
+ * (float)(n_k / sqrt(A2)), the unit face normal of the winding (b - a) x (c - a) -- on the meshes sdfk_march makes this agrees in
+ * sign with the vertex normals; colors3 = the f32 blend of sdfk_trimesh_to_volume ((ca wa + cb wb) + cc wc, weights rounded to
+ * f32), zeros when the mesh has no colours; triangle = t (int32); weights3 = (float)w0, (float)w1, (float)w2, the weights of that
+ * blend, with which a caller blends any other per-vertex attribute to the same bits.
+ * stats (may be NULL): stats[0] = triangles of non-zero weight, stats[1] = the total weight.
+ * Refused with SDFK_ERR_INVALID: n outside [0, 2^31), unknown flag bits, a mesh without area.  n = 0 returns SDFK_OK and touches
+ * nothing.  The weights, A2max and the scan are made once per handle, by its first sampling call, which synchronises to read the
+ * total and the refusal; W (8 bytes per triangle plus one) stays on the handle until sdfk_trimesh_free.  After that,
+ * sdfk_trimesh_sample_device (caller-owned device buffers) only queues work on the library stream, so sample ->
+ * sdfk_points_create_device -> sdfk_icp_register_device never touches the host.  sdfk_trimesh_sample: host arrays, synchronous. */
+#define SDFK_TRIMESH_SAMPLE_STRATIFIED 1
+int sdfk_trimesh_sample(sdfk_trimesh* t, int64_t n, uint64_t seed, int32_t flags, float* points3, float* normals3, float* colors3,
+                        int32_t* triangle, float* weights3, int64_t stats[2]);
+int sdfk_trimesh_sample_device(sdfk_trimesh* t, int64_t n, uint64_t seed, int32_t flags, void* points3_dev, void* normals3_dev,
+                               void* colors3_dev, void* triangle_dev, void* weights3_dev, int64_t stats[2]);
+
 /* ---- Redistancing (Voxels.Redistance) ---------------------------------------------------------------------------------------
  * dst gets a signed distance to the iso-surface of src, with src's sign at every voxel: a first-order Eikonal solve (Godunov
  * upwind, Jacobi sweeps to the fixed point -- the fast iterative method family, Jeong & Whitaker 2008).  src is not modified

@@ -152,6 +152,8 @@ SIGNATURES = {
     "sdfk_trimesh_closest_device": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "sdfk_trimesh_to_volume": (C.c_int, [_vp, _vp, C.c_float]),
     "sdfk_trimesh_stats": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "sdfk_trimesh_sample": (C.c_int, [_vp, _i64, C.c_uint64, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "sdfk_trimesh_sample_device": (C.c_int, [_vp, _i64, C.c_uint64, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "sdfk_trimesh_free": (None, [_vp]),
     "sdfk_volume_redistance": (C.c_int, [_vp, _vp, C.c_float, C.c_float, C.POINTER(_i64)]),
     "sdfk_icp_register": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),

@@ -754,6 +754,12 @@ class Mesh:
         from .meshsdf import MeshSdf
         return MeshSdf(self).ToVoxels(min, max, nx, ny, nz, maxDistance, clipToBounds)
 
+    def SamplePoints(self, n, seed=0, stratified=True):
+        """n points on the mesh in proportion to area, with face normals, blended colours, triangle indices and barycentric
+        weights (sdfkit_amd.meshsdf.MeshSdf.SamplePoints) -> MeshSamples."""
+        from .meshsdf import MeshSdf
+        return MeshSdf(self).SamplePoints(n, seed, stratified)
+
     def WriteObj(self, path_or_file):
         """Mesh.WriteObj (Mesh.cs:66-97): `v`, then `vn`, then `f a//a b//b c//c`, 1-based."""
         own = isinstance(path_or_file, str)

@@ -12,10 +12,14 @@
 // (triangle, column) item, the items of all triangles flattened by a scan, so a triangle over 10^5 columns is spread over 10^5
 // lanes -- count, scan, write: crossing records grouped by column.  The volume pass runs one lane per voxel (z fastest) and
 // counts the crossings of its column below it.
+// Sample (sdfk_trimesh_sample; arithmetic: trimesh_sample.h): the first call makes the integer weights of the triangles (area over
+// the largest area, in units of 2^-32) and their exclusive 64-bit scan W, kept on the handle; every call runs one lane per sample:
+// three stateless draws, a binary search over W, one TriPack gather, the stores.
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "points_grid.h"
 #include "trimesh_sdf.h"
+#include "trimesh_sample.h"
 
 #include <cfloat>
 
@@ -23,6 +27,7 @@ namespace {
 
 using namespace sdfk_points_grid;   // Grid, cell_of, grid_for_box
 using namespace sdfk_trimesh_sdf;
+namespace smp = sdfk_trimesh_smp;
 
 constexpr int kBlock = 256;
 
@@ -416,6 +421,96 @@ __global__ __launch_bounds__(kBlock) void k_tm_volume(SearchGrid S, VolArgs A)
     }
 }
 
+// ---- sampling ---------------------------------------------------------------------------------------------------------------
+constexpr int kAreaParts = 1024;
+
+// A2 per triangle and the per-block max -> part[block]; then one block -> part[kAreaParts] (a max is order-free)
+__global__ __launch_bounds__(kBlock) void k_tm_area2(const TriPack* __restrict__ tri, int64_t nt, double* __restrict__ a2, double* __restrict__ part,
+                                                     int final_pass)
+{
+    __shared__ double s[kBlock];
+    double r = 0.0;
+    if (!final_pass) {
+        for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < nt; t += (int64_t)gridDim.x * kBlock) {
+            float a[3], b[3], c[3];
+            double n[3];
+            load_tri(tri[t], a, b, c);
+            const double v = smp::area2(a, b, c, n);
+            a2[t] = v;
+            r = fmax(r, v);
+        }
+    } else {
+        for (int64_t b = threadIdx.x; b < nt; b += kBlock) r = fmax(r, part[b]);   // (nt = the number of partials here)
+    }
+    s[threadIdx.x] = r;
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + o]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[final_pass ? kAreaParts : (int64_t)blockIdx.x] = s[0];
+}
+
+// the integer weights (0 everywhere when no triangle has an area) and the number of non-zero ones
+__global__ __launch_bounds__(kBlock) void k_tm_sample_weights(const double* __restrict__ a2, int64_t nt, const double* __restrict__ a2max,
+                                                              unsigned long long* __restrict__ w, unsigned long long* __restrict__ nonzero)
+{
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const double m = *a2max;
+    unsigned long long n = 0;
+    if (t < nt) {
+        const unsigned long long v = m > 0.0 ? smp::weight(a2[t], m) : 0ull;
+        w[t] = v;
+        n = v ? 1ull : 0ull;
+    }
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(nonzero, n);
+}
+
+struct SampleArgs {
+    const TriPack* tri;
+    const unsigned long long* W;   // nt + 1: W[nt] is the total, read here and not on the host
+    int64_t nt;
+    const int32_t* idx;
+    const float* mesh_colors;      // null: the mesh has none (colours are zero)
+    int64_t n;
+    uint64_t seed;
+    int stratified;
+    float* points;
+    float* normals;
+    float* colors;
+    int32_t* triangle;
+    float* weights;
+};
+
+__global__ __launch_bounds__(kBlock) void k_tm_sample(SampleArgs A)
+{
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= A.n) return;
+    const uint64_t total = A.W[A.nt];
+    const uint64_t h0 = smp::draw(A.seed, (uint64_t)s, 0), h1 = smp::draw(A.seed, (uint64_t)s, 1), h2 = smp::draw(A.seed, (uint64_t)s, 2);
+    const uint64_t r = smp::pick(h0, (uint64_t)s, (uint64_t)A.n, total, A.stratified != 0);
+    const int64_t t = smp::find_triangle(A.W, A.nt, r);
+    float a[3], b[3], c[3];
+    load_tri(A.tri[t], a, b, c);
+    const smp::Sample S = smp::sample_on(a, b, c, h1, h2);
+    if (A.points)
+        for (int k = 0; k < 3; k++) A.points[3 * s + k] = S.point[k];
+    if (A.normals)
+        for (int k = 0; k < 3; k++) A.normals[3 * s + k] = S.normal[k];
+    if (A.colors) {
+        float rgb[3] = {0.0f, 0.0f, 0.0f};
+        if (A.mesh_colors) {
+            const int32_t* v = A.idx + 3 * t;
+            smp::blend_colour(A.mesh_colors + 3 * (int64_t)v[0], A.mesh_colors + 3 * (int64_t)v[1], A.mesh_colors + 3 * (int64_t)v[2], S.w, rgb);
+        }
+        for (int k = 0; k < 3; k++) A.colors[3 * s + k] = rgb[k];
+    }
+    if (A.triangle) A.triangle[s] = (int32_t)t;
+    if (A.weights)
+        for (int k = 0; k < 3; k++) A.weights[3 * s + k] = S.weights[k];
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -434,6 +529,8 @@ struct sdfk_trimesh {
     int64_t cells = 0, entries = 0;
     Grid G{};
     int64_t last_candidates = 0, last_queries = 0, last_crossings = 0;
+    unsigned long long* sample_W = nullptr;   // nt + 1: the exclusive scan of the sampling weights (made by the first sampling call)
+    int64_t sample_nonzero = 0, sample_total = 0;
 };
 
 namespace {
@@ -441,7 +538,8 @@ namespace {
 void trimesh_release(sdfk_trimesh* t)
 {
     dev_free(t->vertices); dev_free(t->colors); dev_free(t->idx); dev_free(t->tri);
-    dev_free(t->list); dev_free(t->starts); dev_free(t->ystarts);
+    dev_free(t->list); dev_free(t->starts); dev_free(t->ystarts); dev_free(t->sample_W);
+    t->sample_W = nullptr;
     t->vertices = t->colors = nullptr; t->idx = nullptr; t->tri = nullptr; t->list = t->starts = t->ystarts = nullptr;
 }
 
@@ -657,6 +755,80 @@ int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band)
     return SDFK_OK;
 }
 
+// The sampling weights and their scan, once per handle: synchronises to read the total and the refusal.
+int sample_prepare(sdfk_trimesh* t, const char* who)
+{
+    if (t->sample_W) return SDFK_OK;
+    const int64_t nt = t->nt;
+    const unsigned bb = (unsigned)std::min<int64_t>(kAreaParts, (nt + kBlock - 1) / kBlock);
+    unsigned long long* W = nullptr;
+    double* a2 = nullptr;
+    double* part = nullptr;
+    unsigned long long* nonzero = nullptr;
+    int r = dev_alloc((void**)&W, (size_t)(nt + 1) * sizeof(unsigned long long));
+    if (!r) r = dev_alloc((void**)&a2, (size_t)nt * sizeof(double));
+    if (!r) r = dev_alloc((void**)&part, (size_t)(kAreaParts + 1) * sizeof(double));
+    if (!r) r = dev_alloc((void**)&nonzero, sizeof(unsigned long long));
+    hipError_t e = hipSuccess;
+    struct { double a2max; unsigned long long nonzero, total; } host{};
+    if (!r) {
+        e = hipMemsetAsync(nonzero, 0, sizeof(unsigned long long), g.stream);
+        if (e == hipSuccess) {
+            {
+                ProfScope ps("k_tm_area2");
+                hipLaunchKernelGGL(k_tm_area2, dim3(bb), dim3(kBlock), 0, g.stream, t->tri, nt, a2, part, 0);
+                hipLaunchKernelGGL(k_tm_area2, dim3(1), dim3(kBlock), 0, g.stream, t->tri, (int64_t)bb, a2, part, 1);
+            }
+            ProfScope ps("k_tm_sample_weights");
+            hipLaunchKernelGGL(k_tm_sample_weights, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, a2, nt, part + kAreaParts, W, nonzero);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) r = sdfk_scan::scan(W, nt, who);
+        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.a2max, part + kAreaParts, sizeof(double), hipMemcpyDeviceToHost, g.stream);
+        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.nonzero, nonzero, sizeof(unsigned long long), hipMemcpyDeviceToHost, g.stream);
+        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.total, W + nt, sizeof(unsigned long long), hipMemcpyDeviceToHost, g.stream);
+        if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    }
+    dev_free(a2); dev_free(part); dev_free(nonzero);
+    if (!r && e != hipSuccess) r = fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (!r && !(host.a2max > 0.0)) r = fail(SDFK_ERR_INVALID, "%s: no triangle has an area", who);
+    if (r) { dev_free(W); return r; }
+    t->sample_W = W;
+    t->sample_nonzero = (int64_t)host.nonzero;
+    t->sample_total = (int64_t)host.total;
+    return SDFK_OK;
+}
+
+int sample_check(const sdfk_trimesh* t, int64_t n, int32_t flags, const char* who)
+{
+    if (int r = require_init()) return r;
+    if (!t) return fail(SDFK_ERR_INVALID, "%s: null argument", who);
+    if (n < 0 || n >= (int64_t(1) << 31)) return fail(SDFK_ERR_INVALID, "%s: n must be in [0, 2^31)", who);
+    if (flags & ~SDFK_TRIMESH_SAMPLE_STRATIFIED) return fail(SDFK_ERR_INVALID, "%s: unknown flag bits", who);
+    return SDFK_OK;
+}
+
+int sample_launch(const sdfk_trimesh* t, int64_t n, uint64_t seed, int32_t flags, float* points, float* normals, float* colors, int32_t* triangle,
+                  float* weights, const char* who)
+{
+    const SampleArgs A{t->tri, t->sample_W, t->nt, t->idx, t->colors, n, seed, flags & SDFK_TRIMESH_SAMPLE_STRATIFIED, points, normals, colors,
+                       triangle, weights};
+    {
+        ProfScope ps("k_tm_sample");
+        hipLaunchKernelGGL(k_tm_sample, dim3(grid1(n)), dim3(kBlock), 0, g.stream, A);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return SDFK_OK;
+}
+
+void sample_stats(const sdfk_trimesh* t, int64_t stats[2])
+{
+    if (!stats) return;
+    stats[0] = t->sample_nonzero;
+    stats[1] = t->sample_total;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -725,6 +897,56 @@ extern "C" int sdfk_trimesh_to_volume(const sdfk_trimesh* t, sdfk_volume* v, flo
     if (!t || !v) return fail(SDFK_ERR_INVALID, "sdfk_trimesh_to_volume: null argument");
     if (!(max_distance >= 0.0f)) return fail(SDFK_ERR_INVALID, "sdfk_trimesh_to_volume: max_distance must be >= 0 (+inf: exact everywhere)");
     return to_volume(t, v, max_distance);
+}
+
+extern "C" int sdfk_trimesh_sample_device(sdfk_trimesh* t, int64_t n, uint64_t seed, int32_t flags, void* points3_dev, void* normals3_dev,
+                                          void* colors3_dev, void* triangle_dev, void* weights3_dev, int64_t stats[2])
+{
+    static const char* who = "sdfk_trimesh_sample";
+    StateScope in_owner_context(t ? t->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = sample_check(t, n, flags, who)) return r;
+    if (n == 0) return SDFK_OK;
+    if (int r = sample_prepare(t, who)) return r;
+    sample_stats(t, stats);
+    return sample_launch(t, n, seed, flags, (float*)points3_dev, (float*)normals3_dev, (float*)colors3_dev, (int32_t*)triangle_dev,
+                         (float*)weights3_dev, who);
+}
+
+extern "C" int sdfk_trimesh_sample(sdfk_trimesh* t, int64_t n, uint64_t seed, int32_t flags, float* points3, float* normals3, float* colors3,
+                                   int32_t* triangle, float* weights3, int64_t stats[2])
+{
+    static const char* who = "sdfk_trimesh_sample";
+    StateScope in_owner_context(t ? t->owner : nullptr);
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    if (int r = sample_check(t, n, flags, who)) return r;
+    if (n == 0) return SDFK_OK;
+    if (int r = sample_prepare(t, who)) return r;
+    sample_stats(t, stats);
+    float* pd = nullptr;
+    float* nd = nullptr;
+    float* cd = nullptr;
+    int32_t* td = nullptr;
+    float* wd = nullptr;
+    const size_t n3 = (size_t)n * 3 * sizeof(float);
+    int r = SDFK_OK;
+    if (points3) r = dev_alloc((void**)&pd, n3);
+    if (!r && normals3) r = dev_alloc((void**)&nd, n3);
+    if (!r && colors3) r = dev_alloc((void**)&cd, n3);
+    if (!r && triangle) r = dev_alloc((void**)&td, (size_t)n * sizeof(int32_t));
+    if (!r && weights3) r = dev_alloc((void**)&wd, n3);
+    hipError_t e = hipSuccess;
+    if (!r) r = sample_launch(t, n, seed, flags, pd, nd, cd, td, wd, who);
+    if (!r && pd) e = hipMemcpyAsync(points3, pd, n3, hipMemcpyDeviceToHost, g.stream);
+    if (!r && e == hipSuccess && nd) e = hipMemcpyAsync(normals3, nd, n3, hipMemcpyDeviceToHost, g.stream);
+    if (!r && e == hipSuccess && cd) e = hipMemcpyAsync(colors3, cd, n3, hipMemcpyDeviceToHost, g.stream);
+    if (!r && e == hipSuccess && td) e = hipMemcpyAsync(triangle, td, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
+    if (!r && e == hipSuccess && wd) e = hipMemcpyAsync(weights3, wd, n3, hipMemcpyDeviceToHost, g.stream);
+    const hipError_t es = hipStreamSynchronize(g.stream);
+    dev_free(pd); dev_free(nd); dev_free(cd); dev_free(td); dev_free(wd);
+    if (r) return r;
+    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
+    return SDFK_OK;
 }
 
 extern "C" int sdfk_trimesh_stats(const sdfk_trimesh* t, int64_t stats[8])

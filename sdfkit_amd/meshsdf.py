@@ -1,16 +1,24 @@
 """Triangle meshes as signed distance fields over the C ABI entry points sdfk_trimesh_* (include/sdfkit_hip.h,
-csrc/lib_trimesh.hip): the exact closest triangle of arbitrary points, and signed distance volumes (Mesh -> Voxels).
+csrc/lib_trimesh.hip): the exact closest triangle of arbitrary points, signed distance volumes (Mesh -> Voxels), and points
+sampled on the triangles in proportion to area (Mesh -> points).
 
 The distance is exact (binary64 closest point, ties to the lowest triangle index); the sign is the parity of the mesh's
 crossings along z, meaningful for closed meshes (nested shells included) and deterministic for any mesh.
 """
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
 from . import _native as N
 
 f32 = np.float32
+
+SAMPLE_STRATIFIED = 1   # SDFK_TRIMESH_SAMPLE_STRATIFIED
+
+# MeshSdf.SamplePoints: Points (n, 3) f32, Normals (n, 3) f32 (unit face normals), Colors (n, 3) f32 or None, Triangles (n,) int32,
+# Weights (n, 3) f32 (the barycentric weights of the triangle's three vertices, as the colour blend used them)
+MeshSamples = namedtuple("MeshSamples", "Points Normals Colors Triangles Weights")
 
 
 def _ptr(a):
@@ -83,6 +91,38 @@ class MeshSdf:
         voxels._host_values = voxels._host_colors = None   # the device copy is now the truth
         voxels._version += 1
         return voxels
+
+    def SamplePoints(self, n, seed=0, stratified=True):
+        """n points on the triangles, in proportion to area (sdfk_trimesh_sample: one stated function of the mesh, n, seed and
+        the mode, the same bits on every run) -> MeshSamples.  Normals are the unit face normals of the winding (b - a) x (c - a),
+        which on marching-cubes meshes point the way the vertex normals do; Colors the blended vertex colours (None when the mesh
+        has none); any other per-vertex attribute blends as attr[tri[Triangles]] weighted by Weights.  stratified: one sample per
+        equal share of the total area (every triangle gets its share to within two samples, and the output follows the triangle
+        order); otherwise independent draws, and sample s does not depend on n.  A triangle whose area is below 2^-32 of the largest
+        one is never sampled; a mesh in which no triangle has an area is refused."""
+        n, seed, flags = int(n), C.c_uint64(int(seed) & (2 ** 64 - 1)), SAMPLE_STRATIFIED if stratified else 0
+        if not 0 <= n < 2 ** 31:   # (the library refuses it: nothing is allocated for it first)
+            N.check(N.lib().sdfk_trimesh_sample(self._h, n, seed, flags, None, None, None, None, None, None))
+        pts, nrm, wts = np.empty((n, 3), f32), np.empty((n, 3), f32), np.empty((n, 3), f32)
+        tri = np.empty(n, np.int32)
+        cols = np.empty((n, 3), f32) if self.Colors is not None else None
+        N.check(N.lib().sdfk_trimesh_sample(self._h, n, seed, flags, _ptr(pts), _ptr(nrm), _ptr(cols) if cols is not None else C.c_void_p(),
+                                            _ptr(tri), _ptr(wts), None))
+        return MeshSamples(pts, nrm, cols, tri, wts)
+
+    def SamplePointsDevice(self, n, seed, stratified, points_dev, normals_dev=None, colors_dev=None, triangles_dev=None, weights_dev=None):
+        """SamplePoints into caller-owned device memory (raw pointers; None: that output is not wanted): after the handle's first
+        sampling call this only queues work on the library stream."""
+        N.check(N.lib().sdfk_trimesh_sample_device(self._h, int(n), C.c_uint64(int(seed) & (2 ** 64 - 1)), SAMPLE_STRATIFIED if stratified else 0,
+                                                   *[C.c_void_p(p) if p else C.c_void_p() for p in (points_dev, normals_dev, colors_dev,
+                                                                                                   triangles_dev, weights_dev)], None))
+
+    def sample_stats(self):
+        """{"sampled_triangles": triangles of non-zero sampling weight, "total_weight": the sum of the integer weights (the largest
+        triangle has 2^32)}; makes the weights when no sampling call has."""
+        s = (C.c_int64 * 2)()
+        N.check(N.lib().sdfk_trimesh_sample(self._h, 1, C.c_uint64(0), 0, None, None, None, None, None, s))
+        return {"sampled_triangles": int(s[0]), "total_weight": int(s[1])}
 
     def stats(self):
         """sdfk_trimesh_stats: grid, triangles, binned pairs, candidates / queries of the last profiled call, crossings."""

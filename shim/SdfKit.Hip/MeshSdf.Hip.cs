@@ -1,6 +1,8 @@
 // MeshSdf.Hip.cs -- triangle meshes as signed distance fields over sdfk_trimesh_* (include/sdfkit_hip.h).  Not in the reference,
 // which converts SDF -> Voxels -> Mesh only: MeshSdf and Mesh.ToVoxels add the way back.  Distances are exact (binary64 closest
 // point, ties to the lowest triangle index); the sign is the parity of crossings along z, right for closed meshes.
+// SamplePoints (sdfk_trimesh_sample) turns a mesh into a point cloud: points in proportion to area with face normals, colours,
+// triangle indices and barycentric weights, one stated function of the mesh, n, the seed and the mode.
 // UNCOMPILED HERE (no .NET in the build image); sdfkit_amd/meshsdf.py's MeshSdf is the same layer, tested.
 using System;
 using System.Numerics;
@@ -8,8 +10,21 @@ using SdfKit.Hip;
 
 namespace SdfKit
 {
+    /// <summary>MeshSdf.SamplePoints: per sample the point, the unit face normal, the blended colour (null when the mesh has none),
+    /// the triangle and the barycentric weights of its three vertices as the colour blend used them.</summary>
+    public sealed class MeshSamples
+    {
+        public Vector3[] Points = Array.Empty<Vector3> ();
+        public Vector3[] Normals = Array.Empty<Vector3> ();
+        public Vector3[]? Colors;
+        public int[] Triangles = Array.Empty<int> ();
+        public Vector3[] Weights = Array.Empty<Vector3> ();
+    }
+
     public class MeshSdf : IDisposable
     {
+        const int SampleStratified = 1;   // SDFK_TRIMESH_SAMPLE_STRATIFIED
+
         IntPtr handle;   // sdfk_trimesh*
         readonly bool hasColors;
 
@@ -58,6 +73,23 @@ namespace SdfKit
             return v;
         }
 
+        /// <summary>n points on the triangles in proportion to area.  stratified: one sample per equal share of the total area, in
+        /// triangle order; otherwise independent draws (sample s does not depend on n).  Normals are the unit face normals of the
+        /// winding (b - a) x (c - a).  A triangle below 2^-32 of the largest area is never sampled; a mesh without area is refused.</summary>
+        public unsafe MeshSamples SamplePoints (long n, ulong seed = 0, bool stratified = true)
+        {
+            if (n < 0 || n >= 1L << 31)   // (the library refuses it: nothing is allocated for it first)
+                Native.Check (Native.sdfk_trimesh_sample (handle, n, seed, stratified ? SampleStratified : 0, null, null, null, null, null, null));
+            var m = n;
+            var s = new MeshSamples { Points = new Vector3[m], Normals = new Vector3[m], Colors = hasColors ? new Vector3[m] : null,
+                                      Triangles = new int[m], Weights = new Vector3[m] };
+            fixed (Vector3* p = s.Points) fixed (Vector3* nr = s.Normals) fixed (Vector3* c = s.Colors) fixed (int* t = s.Triangles)
+            fixed (Vector3* w = s.Weights)
+                Native.Check (Native.sdfk_trimesh_sample (handle, n, seed, stratified ? SampleStratified : 0, (float*)p, (float*)nr, (float*)c, t,
+                                                          (float*)w, null));
+            return s;
+        }
+
         public void Dispose ()
         {
             if (handle != IntPtr.Zero) {
@@ -88,6 +120,13 @@ namespace SdfKit
         {
             using var m = new MeshSdf (mesh);
             return m.ToVoxels (min, max, nx, ny, nz, maxDistance, clipToBounds);
+        }
+
+        /// <summary>Mesh.SamplePoints: n points on the mesh in proportion to area (MeshSdf.SamplePoints).</summary>
+        public static MeshSamples SamplePoints (this Mesh mesh, long n, ulong seed = 0, bool stratified = true)
+        {
+            using var m = new MeshSdf (mesh);
+            return m.SamplePoints (n, seed, stratified);
         }
     }
 }

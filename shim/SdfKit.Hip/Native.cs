@@ -156,6 +156,11 @@ namespace SdfKit.Hip
                                                                               IntPtr distanceDev, IntPtr closest3Dev);
         [DllImport(Lib)] public static extern int sdfk_trimesh_to_volume(IntPtr trimesh, IntPtr volume, float maxDistance);
         [DllImport(Lib)] public static extern int sdfk_trimesh_stats(IntPtr trimesh, long* stats8);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_sample(IntPtr trimesh, long n, ulong seed, int flags, float* points3, float* normals3,
+                                                                      float* colors3, int* triangle, float* weights3, long* stats2);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_sample_device(IntPtr trimesh, long n, ulong seed, int flags, IntPtr points3Dev,
+                                                                             IntPtr normals3Dev, IntPtr colors3Dev, IntPtr triangleDev, IntPtr weights3Dev,
+                                                                             long* stats2);
         [DllImport(Lib)] public static extern void sdfk_trimesh_free(IntPtr trimesh);
         [DllImport(Lib)] public static extern int sdfk_volume_redistance(IntPtr src, IntPtr dst, float isoValue, float maxDistance, long* stats4);
         // several GPUs from ONE process (the managed host is one process): include/sdfkit_hip.h, "one process, several GPUs"
