@@ -1182,18 +1182,25 @@ public:
     Vec3Data Render() const { Vec3Data d; d.Width = w_; d.Height = h_; d.Values.resize((size_t)w_ * h_ * 3); Run(nullptr, d.Values.data()); return d; }
     FloatData RenderDepth() const { FloatData d; d.Width = w_; d.Height = h_; d.Values.resize((size_t)w_ * h_); Run(d.Values.data(), nullptr); return d; }
 
-private:
-    void Run(float* depth, float* rgb) const
+    // host part of GetCameraRays (RayMarcher.cs:97-112): the camera position and the inverse view-projection sdfk_raymarch takes
+    void Camera(float pos[3], Matrix4x4& vpi) const
     {
-        // host part of GetCameraRays (RayMarcher.cs:97-112)
-        Matrix4x4 cam, vpi;
+        Matrix4x4 cam;
         Matrix4x4::Invert(ViewTransform, cam);
-        const float pos[3] = {((0.0f * cam.M[0][0] + 0.0f * cam.M[1][0]) + 0.0f * cam.M[2][0]) + cam.M[3][0],
-                              ((0.0f * cam.M[0][1] + 0.0f * cam.M[1][1]) + 0.0f * cam.M[2][1]) + cam.M[3][1],
-                              ((0.0f * cam.M[0][2] + 0.0f * cam.M[1][2]) + 0.0f * cam.M[2][2]) + cam.M[3][2]};
+        pos[0] = ((0.0f * cam.M[0][0] + 0.0f * cam.M[1][0]) + 0.0f * cam.M[2][0]) + cam.M[3][0];
+        pos[1] = ((0.0f * cam.M[0][1] + 0.0f * cam.M[1][1]) + 0.0f * cam.M[2][1]) + cam.M[3][1];
+        pos[2] = ((0.0f * cam.M[0][2] + 0.0f * cam.M[1][2]) + 0.0f * cam.M[2][2]) + cam.M[3][2];
         const Matrix4x4 proj = Matrix4x4::CreatePerspectiveFieldOfView(VerticalFieldOfViewDegrees * 3.14159274f / 180.0f, (float)w_ / (float)h_,
                                                                        NearPlaneDistance, FarPlaneDistance);
         Matrix4x4::Invert(ViewTransform * proj, vpi);
+    }
+
+private:
+    void Run(float* depth, float* rgb) const
+    {
+        float pos[3];
+        Matrix4x4 vpi;
+        Camera(pos, vpi);
         EnsureInit();
         Check(sdfk_raymarch(sdf_.Program(), w_, h_, pos, &vpi.M[0][0], NearPlaneDistance, FarPlaneDistance, DepthIterations, depth, rgb));
     }

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import raymarch_cases as R
 from tests import scenes as S
 
 
@@ -59,20 +60,58 @@ def test_render_is_sky_where_nothing_is_hit_and_lit_where_something_is():
     assert (lit[:, 0] > 0.1).any()                                  # something is actually lit
 
 
-# ---- host-side camera arithmetic of the product mirror == the oracle's --------------------
+# ---- host-side camera arithmetic of the product mirrors == the oracle's ---------------------
+CAMERA_TABLE = [(*R.CAMERAS[c], w, h, *lens) for c in R.CAMERAS for lens in R.LENSES for (w, h) in ((33, 21), (1920, 1080))]
+
+
 @pytest.mark.parametrize("cam", [((0, 0, 5), (0, 0, 0), (0, 1, 0), 50, 30, 60.0, 1.0, 100.0),
                                  ((-2, 2, 4), (0, 0, 0), (0, 1, 0), 192, 108, 60.0, 1.0, 100.0),
-                                 ((3, -1, 2.5), (0.2, 0.1, -0.3), (0, 0, 1), 1920, 1080, 45.0, 0.5, 250.0)])
+                                 ((3, -1, 2.5), (0.2, 0.1, -0.3), (0, 0, 1), 1920, 1080, 45.0, 0.5, 250.0)] + CAMERA_TABLE)
 def test_camera_math_matches_oracle(cam):
+    """the Python mirror, over every camera x lens of tests/raymarch_cases.py too: the all-NaN matrices of `degenerate_up` and
+    the far = +inf branch of CreatePerspectiveFieldOfView included (NaN == NaN; finite values to the sign bit)"""
     from sdfkit_amd import Matrix4x4, RayMarcher
     pos, tgt, up, w, h, fov, near, far = cam
-    view = Matrix4x4.CreateLookAt(pos, tgt, up)
-    assert np.array_equal(view, O.look_at(pos, tgt, up))
-    rm = RayMarcher(w, h, None)
-    rm.ViewTransform, rm.VerticalFieldOfViewDegrees, rm.NearPlaneDistance, rm.FarPlaneDistance = view, fov, near, far
-    c, vpi = rm.camera()
+    with np.errstate(all="ignore"):
+        view = Matrix4x4.CreateLookAt(pos, tgt, up)
+        assert R.same_image(view, O.look_at(pos, tgt, up))
+        rm = RayMarcher(w, h, None)
+        rm.ViewTransform, rm.VerticalFieldOfViewDegrees, rm.NearPlaneDistance, rm.FarPlaneDistance = view, fov, near, far
+        c, vpi = rm.camera()
     oc, ovpi = O.ray_camera(view, fov, w, h, near, far)
-    assert np.array_equal(c, oc) and np.array_equal(vpi, ovpi)
+    assert R.same_image(c, oc) and R.same_image(vpi, ovpi)
+    if up == (0, 1, 0) and pos[0] == pos[2] == 0 and pos[1] != 0:
+        assert np.isnan(oc).all() and np.isnan(ovpi).all()
+    else:
+        assert np.isfinite(oc).all() and np.isfinite(ovpi).all()
+
+
+def test_cpp_camera_math_matches_oracle(tmp_path):
+    """SdfKit::Matrix4x4 and RayMarcher::Camera of include/SdfKit.hpp, built with g++ -ffp-contract=off and run on the CPU
+    (tests/cpp/raymarch_camera_host.cpp): the bits of the camera position and of the inverse view-projection"""
+    import os
+    import subprocess
+    from sdfkit_amd import _native as N
+    N.lib()  # makes sure libsdfkit_hip.so exists
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe, libdir = str(tmp_path / "raymarch_camera_host"), os.path.join(root, "sdfkit_amd")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(root, "include"),
+                           os.path.join(root, "tests", "cpp", "raymarch_camera_host.cpp"), "-o", exe,
+                           "-L", libdir, "-lsdfkit_hip", f"-Wl,-rpath,{libdir}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"])
+    lines = []
+    for pos, tgt, up, w, h, fov, near, far in CAMERA_TABLE:
+        words = np.array([*pos, *tgt, *up, fov, near, far], np.float32).view(np.uint32)
+        lines.append(" ".join(f"{x:08x}" for x in words) + f" {w} {h}")
+    p = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and f"{len(CAMERA_TABLE)} cases" in p.stderr, (p.returncode, p.stderr[-2000:])
+    got = np.array([[int(x, 16) for x in ln.split()] for ln in p.stdout.splitlines()], np.uint32).view(np.float32)
+    assert got.shape == (len(CAMERA_TABLE), 19)
+    nan_rows = 0
+    for row, (pos, tgt, up, w, h, fov, near, far) in zip(got, CAMERA_TABLE):
+        oc, ovpi = O.ray_camera(O.look_at(pos, tgt, up), fov, w, h, near, far)
+        assert R.same_image(row[:3], oc) and R.same_image(row[3:].reshape(4, 4), ovpi), (pos, tgt, up, w, h, fov, near, far)
+        nan_rows += bool(np.isnan(ovpi).all())
+    assert nan_rows == 2 * len(R.LENSES)      # `degenerate_up`, and nothing else
 
 
 def test_tga_writers(tmp_path):
