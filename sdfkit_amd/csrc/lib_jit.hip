@@ -2,6 +2,7 @@
 #include "lib_internal.h"
 
 #include "sample_codegen.h"
+#include "vol_pyramid.h"
 
 // ---------------------------------------------------------------------------
 // programs (JIT, counterpart of SdfExprCompiler.Compile, SdfExpr.cs:225-273)
@@ -262,52 +263,7 @@ extern "C" int sdfk_program_check_bound(const sdfk_op* ops, int32_t n_ops, const
 // One device allocation per program: the SdfkVol table, then per volume its Values (+ Colors) copied as they are (pitched rows),
 // then the min/max pyramid of every channel the program reads.  Built once, synchronously: a program is made once and used often.
 namespace {
-__host__ __device__ inline bool finite_f(float v) { return v - v == 0.0f; }
-// level 1 of a channel's pyramid from the voxels: cell c covers voxels [2c, 2c + 1] per axis (clipped); NaN when one is not finite
-__global__ void k_vol_pyr_base(const float* __restrict__ src, int stride, int nx, int ny, int nz, int pitch, int cx, int cy, int cz,
-                               float* __restrict__ out)
-{
-    const long total = (long)cx * cy * cz;
-    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < total; c += (long)gridDim.x * 256) {
-        const int k = (int)(c % cz);
-        const long t = c / cz;
-        const int j = (int)(t % cy), i = (int)(t / cy);
-        float lo = __builtin_inff(), hi = -__builtin_inff();
-        bool bad = false;
-        for (int q = 0; q < 8; q++) {
-            const int x = 2 * i + (q & 1), y = 2 * j + ((q >> 1) & 1), z = 2 * k + (q >> 2);
-            if (x >= nx || y >= ny || z >= nz) continue;
-            const float v = src[(((long)x * ny + y) * pitch + z) * stride];
-            bad |= !finite_f(v);
-            lo = __builtin_elementwise_minimum(lo, v);
-            hi = __builtin_elementwise_maximum(hi, v);
-        }
-        out[2 * c] = bad ? __builtin_nanf("") : lo;
-        out[2 * c + 1] = bad ? __builtin_nanf("") : hi;
-    }
-}
-// level L + 1 from level L: minimum / maximum of up to 8 cells (IEEE 754:2019: a poisoned cell poisons its parent)
-__global__ void k_vol_pyr_up(const float* __restrict__ in, int nx, int ny, int nz, float* __restrict__ out, int cx, int cy, int cz)
-{
-    const long total = (long)cx * cy * cz;
-    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < total; c += (long)gridDim.x * 256) {
-        const int k = (int)(c % cz);
-        const long t = c / cz;
-        const int j = (int)(t % cy), i = (int)(t / cy);
-        float lo = __builtin_inff(), hi = -__builtin_inff();
-        for (int q = 0; q < 8; q++) {
-            const int x = 2 * i + (q & 1), y = 2 * j + ((q >> 1) & 1), z = 2 * k + (q >> 2);
-            if (x >= nx || y >= ny || z >= nz) continue;
-            const long e = ((long)x * ny + y) * nz + z;
-            lo = __builtin_elementwise_minimum(lo, in[2 * e]);
-            hi = __builtin_elementwise_maximum(hi, in[2 * e + 1]);
-        }
-        out[2 * c] = lo;
-        out[2 * c + 1] = hi;
-    }
-}
 inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
-inline int cells(int n, int L) { return (int)(((long)n + (1l << L) - 1) >> L); }
 }  // namespace
 
 static int bind_volumes(sdfk_program* p, const sdfk_op* ops, int32_t n_ops, const sdfk_volume* const* vols, int32_t n_vol)
@@ -324,21 +280,15 @@ static int bind_volumes(sdfk_program* p, const sdfk_op* ops, int32_t n_ops, cons
         const sdfk_volume* v = vols[s];
         SdfkVol& T = table[(size_t)s];
         const int n[3] = {v->nx, v->ny, v->nz};
-        int top = 0;
         for (int a = 0; a < 3; a++) {
             T.n[a] = n[a];
             T.mn[a] = v->gmin[a];
             T.d[a] = (v->gmax[a] - v->gmin[a]) / (float)n[a];
             T.m[a] = v->gmin[a] + 0.5f * T.d[a];
-            while ((1l << top) < n[a]) top++;
         }
         T.pitch = v->pitch();
-        T.nlev = top;
-        long long cells_so_far = 0;
-        for (int L = 1; L <= top; L++) {
-            T.lev[L] = cells_so_far;
-            cells_so_far += (long long)cells(n[0], L) * cells(n[1], L) * cells(n[2], L);
-        }
+        const long long cells_so_far = vol_pyr_levels(n, &T.nlev, T.lev);
+        const int top = T.nlev;
         if (!used[s]) continue;
         val_off[s] = off;
         off = align256(off + v->nalloc() * sizeof(float));
@@ -366,17 +316,7 @@ static int bind_volumes(sdfk_program* p, const sdfk_op* ops, int32_t n_ops, cons
             T.pyr[ch] = P;
             const float* src = ch == 3 ? val : col + ch;
             const int stride = ch == 3 ? 1 : 3;
-            for (int L = 1; L <= T.nlev; L++) {
-                const int cx = cells(T.n[0], L), cy = cells(T.n[1], L), cz = cells(T.n[2], L);
-                const size_t nc = (size_t)cx * cy * cz;
-                if (L == 1)
-                    hipLaunchKernelGGL(k_vol_pyr_base, dim3(grid_for(nc)), dim3(256), 0, g.stream, src, stride, T.n[0], T.n[1], T.n[2], T.pitch,
-                                       cx, cy, cz, P + 2 * T.lev[1]);
-                else
-                    hipLaunchKernelGGL(k_vol_pyr_up, dim3(grid_for(nc)), dim3(256), 0, g.stream, P + 2 * T.lev[L - 1], cells(T.n[0], L - 1),
-                                       cells(T.n[1], L - 1), cells(T.n[2], L - 1), P + 2 * T.lev[L], cx, cy, cz);
-                HIPCHK(hipGetLastError());
-            }
+            HIPCHK(vol_pyr_build(src, stride, T.n, T.pitch, T.nlev, T.lev, P, g.stream));
         }
     }
     HIPCHK(hipMemcpyAsync(mem, table.data(), sizeof(SdfkVol) * (size_t)n_vol, hipMemcpyHostToDevice, g.stream));

@@ -3,9 +3,17 @@
 1. Device == host build == model: the text tests/test_interval_codegen.py cuts out of the generated sources, with a probe kernel
    appended (one lane per box writes sdf_interval, one lane per point writes sdf_eval), compiled by hipcc with the optimisation and
    contraction flags lib_jit.hip gives hiprtc, run as ONE child process under a time limit.  Every interval and point value is
-   bit-equal to the numpy models, which the CPU file proves bit-equal to the g++ build.  Volume-less programs only: a bound
-   program's K.V table and its device-built min/max pyramid cannot be reached without a new entry point; that is out of scope here
-   (the device pyramid is covered indirectly by the volume fields of 2).
+   bit-equal to the numpy models, which the CPU file proves bit-equal to the g++ build.  Bound programs included: the probe
+   uploads each volume of a record (pitched values and colours), builds the min/max pyramid of every channel ON THE DEVICE with
+   csrc/vol_pyramid.h -- the kernels and the launcher bind_volumes uses -- and points an SdfkVol table at it; the record's model
+   pyramid is read past.  The built pyramids come back and are bit-equal, level by level and NaN cell by NaN cell, to
+   voxel_sdf_model.pyramid; iv_vox_nearest / iv_vox_linear / iv_vox_box then read the device's pyramid, not the model's.
+   The volumes are those of the CPU file: the bound scenes, the edge volumes, and the shapes at which a level can go wrong (no
+   pyramid at all, a clipped last cell at every level, N = 1 and N = 2 axes, non-finite corner voxels with padded rows, one NaN
+   in a power of two, and 176 x 160 x 160, whose level 1 needs the second step of the base kernel's grid stride).
+   What this catches, established by reverting vol_pyramid.h locally and running once: see test_device_equals_host_build_equals_model.
+   What it does not reach -- bind_volumes' own layout (one pyramid per channel read, one block per slot) -- is
+   tests/test_gpu_voxel_cull.py's.
 2. Meshes that a one-ulp error changes: one-line fields on a 264 x 260 x 256 grid, isoValue set to the float just below the largest
    voxel of an interior 8 x 4 x 4 sub-box (only its extreme voxels lie above), and to the smallest voxel itself (`<= iso` is the
    tie): culled (mode 2) == sign-only (mode 1) == stored (mode 0), bit for bit, and different from the mesh at the neighbouring iso.
@@ -26,6 +34,7 @@ from sdfkit_amd.expr import MathF, Mod, Vec4, select_lt
 from tests import mathops_model as M
 from tests import scenes as S
 from tests import test_interval_codegen as T
+from tests import voxel_sdf_model as VM
 from tests.test_gpu_elide_volume import _kernels_launched, _same_mesh
 from tests.test_voxel_sdf_codegen import codegen  # noqa: F401  (a fixture)
 
@@ -38,13 +47,16 @@ PROBE_HEAD = r"""
 #include <cstdio>
 #include <cstring>
 #include <vector>
-typedef int (*interval_run_fn)(const float* k, int nbox, const float* b, float* iv, int npt, const float* p, float* w);
+#include "vol_pyramid.h"
+typedef int (*interval_run_fn)(const float* k, const void* V, int nbox, const float* b, float* iv, int npt, const float* p, float* w);
 // one lane per box and one lane per point: whole wavefronts of mixed operands (sdfk_sqrt's ballot takes both paths)
 #define INTERVAL_RUN(NK, SETV)                                                                                                 \
-    __global__ void probe(const float* k, int nbox, const float* b, float* iv, int npt, const float* p, float* w)              \
+    __global__ void probe(const float* k, const void* V, int nbox, const float* b, float* iv, int npt, const float* p, float* w) \
     {                                                                                                                          \
         SdfkK K = {};                                                                                                          \
         for (int i = 0; i < NK; i++) K.k[i] = k[i];                                                                            \
+        (void)V;                                                                                                               \
+        SETV                                                                                                                   \
         const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;                                                            \
         if (i < nbox) {                                                                                                        \
             sdfk_iv X, Y, Z;                                                                                                   \
@@ -58,14 +70,16 @@ typedef int (*interval_run_fn)(const float* k, int nbox, const float* b, float* 
             w[i] = W;                                                                                                          \
         }                                                                                                                      \
     }                                                                                                                          \
-    static int run(const float* k, int nbox, const float* b, float* iv, int npt, const float* p, float* w)                     \
+    static int run(const float* k, const void* V, int nbox, const float* b, float* iv, int npt, const float* p, float* w)      \
     {                                                                                                                          \
         const int n = nbox > npt ? nbox : npt;                                                                                 \
-        if (n > 0) hipLaunchKernelGGL(probe, dim3((n + 255) / 256), dim3(256), 0, 0, k, nbox, b, iv, npt, p, w);               \
+        if (n > 0) hipLaunchKernelGGL(probe, dim3((n + 255) / 256), dim3(256), 0, 0, k, V, nbox, b, iv, npt, p, w);            \
         return hipDeviceSynchronize() == hipSuccess ? 0 : 1;                                                                   \
     }
 """
 
+# IN: the records of tests/cpp/interval_host.cpp.  OUT, per record: per volume, per channel 0..3 (3 only without colours), the
+# pyramid the device built (levels 1..nlev, (lo, hi) per cell); then float iv[nbox][2], float w[npt].
 PROBE_MAIN = r"""
 static FILE* g_in;
 template <class T> static std::vector<T> rd(size_t n)
@@ -74,11 +88,17 @@ template <class T> static std::vector<T> rd(size_t n)
     if (n && fread(v.data(), sizeof(T), n, g_in) != n) { fprintf(stderr, "short read\n"); exit(2); }
     return v;
 }
-template <class T> static T* up(const std::vector<T>& v, size_t atleast)
+static std::vector<void*> g_dev;   // the device arrays of one record
+template <class T> static T* dev(size_t n)
 {
     T* d = nullptr;
-    const size_t n = v.size() > atleast ? v.size() : atleast;
     if (hipMalloc(&d, (n ? n : 1) * sizeof(T)) != hipSuccess) { fprintf(stderr, "hipMalloc\n"); exit(3); }
+    g_dev.push_back(d);
+    return d;
+}
+template <class T> static T* up(const std::vector<T>& v)
+{
+    T* d = dev<T>(v.size());
     if (v.size() && hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "hipMemcpy\n"); exit(3); }
     return d;
 }
@@ -93,14 +113,50 @@ int main(int argc, char** argv)
     for (;;) {
         int32_t h[5];
         if (fread(h, sizeof h, 1, g_in) != 1) break;
-        if (h[0] < 0 || h[0] >= nprog || h[2] != 0) { fprintf(stderr, "bad record\n"); return 2; }
-        std::vector<float> k = rd<float>((size_t)h[1]), b = rd<float>(6 * (size_t)h[3]), p = rd<float>(3 * (size_t)h[4]);
+        if (h[0] < 0 || h[0] >= nprog || h[2] < 0 || h[2] > 8) { fprintf(stderr, "bad record\n"); return 2; }
+        std::vector<float> k = rd<float>((size_t)h[1]);
+        const void* table = nullptr;
+#ifdef INTERVAL_HAS_VOLUMES
+        std::vector<SdfkVol> vols((size_t)h[2]);
+        for (SdfkVol& V : vols) {
+            memset(&V, 0, sizeof V);
+            std::vector<int32_t> q = rd<int32_t>(6);
+            std::vector<float> g = rd<float>(9);
+            if (q[0] < 1 || q[1] < 1 || q[2] < 1 || q[3] < q[2]) { fprintf(stderr, "bad volume\n"); return 2; }
+            for (int a = 0; a < 3; a++) { V.n[a] = q[a]; V.mn[a] = g[a]; V.d[a] = g[3 + a]; V.m[a] = g[6 + a]; }
+            V.pitch = q[3];
+            const size_t nalloc = (size_t)q[0] * q[1] * q[3];
+            float* val = up(rd<float>(nalloc));
+            float* col = q[4] ? up(rd<float>(3 * nalloc)) : nullptr;
+            V.val = val;
+            V.col = col;
+            const long long total = vol_pyr_levels(V.n, &V.nlev, V.lev);
+            if (V.nlev != q[5]) { fprintf(stderr, "nlev %d, the record has %d\n", V.nlev, q[5]); return 2; }
+            for (int ch = q[4] ? 0 : 3; ch < 4; ch++) {
+                for (int L = 1; L <= q[5]; L++) rd<float>(2 * (size_t)rd<int32_t>(1)[0]);   // (the model's pyramid: read past)
+                if (V.nlev == 0) continue;
+                std::vector<float> P(2 * (size_t)total);
+                float* dP = dev<float>(P.size());
+                if (hipMemset(dP, 0x55, P.size() * 4) != hipSuccess) return 3;   // (a cell nobody writes stays 1.46e13)
+                const float* src = ch == 3 ? val : col + ch;
+                if (vol_pyr_build(src, ch == 3 ? 1 : 3, V.n, V.pitch, V.nlev, V.lev, dP, 0) != hipSuccess) { fprintf(stderr, "vol_pyr_build\n"); return 3; }
+                if (hipMemcpy(P.data(), dP, P.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "pyramid kernels failed\n"); return 3; }
+                fwrite(P.data(), 4, P.size(), out);
+                V.pyr[ch] = dP;
+            }
+        }
+        table = up(vols);
+#else
+        if (h[2]) { fprintf(stderr, "built without volumes\n"); return 2; }
+#endif
+        std::vector<float> b = rd<float>(6 * (size_t)h[3]), p = rd<float>(3 * (size_t)h[4]);
         std::vector<float> iv(2 * (size_t)h[3]), w((size_t)h[4]);
-        float *dk = up(k, 1), *db = up(b, 0), *dp = up(p, 0), *div = up(iv, 0), *dw = up(w, 0);
-        if (kPrograms[h[0]](dk, h[3], db, div, h[4], dp, dw)) { fprintf(stderr, "kernel failed, program %d\n", h[0]); return 3; }
+        float *dk = up(k), *db = up(b), *dp = up(p), *div = up(iv), *dw = up(w);
+        if (kPrograms[h[0]](dk, table, h[3], db, div, h[4], dp, dw)) { fprintf(stderr, "kernel failed, program %d\n", h[0]); return 3; }
         if (iv.size() && hipMemcpy(iv.data(), div, iv.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return 3;
         if (w.size() && hipMemcpy(w.data(), dw, w.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return 3;
-        hipFree(dk); hipFree(db); hipFree(dp); hipFree(div); hipFree(dw);
+        for (void* d : g_dev) (void)hipFree(d);
+        g_dev.clear();
         fwrite(iv.data(), 4, iv.size(), out);
         fwrite(w.data(), 4, w.size(), out);
         n++;
@@ -112,44 +168,145 @@ int main(int argc, char** argv)
 """
 
 
-def test_device_equals_host_build_equals_model(gpu, codegen, tmp_path):
-    """Every volume-less program of the CPU file (catalogue, mathops scenes, the random DAGs, the domain-safe DAGs, one program per
-    opcode), on the same boxes and points: the device's sdf_interval and sdf_eval are bit-equal to the models.  Bound programs are
-    out of scope (see the module docstring)."""
+@pytest.fixture(scope="module")
+def probe(codegen, tmp_path_factory):
+    """(Text, executable) of every program of the CPU file -- catalogue, mathops scenes, the random DAGs, the domain-safe DAGs, the
+    bound scenes, one program per opcode and per edge volume -- built once"""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     assert os.path.exists(hipcc), "no hipcc"
-    programs = [p for p in T.whole_programs() + T.single_op_programs() if not p["vols"]]
-    t = T.Text(codegen, programs)
-    assert not t.vol
-    src = tmp_path / "probe.hip"
+    t = T.Text(codegen, T.whole_programs() + T.single_op_programs())
+    assert t.vol
+    d = tmp_path_factory.mktemp("interval_probe")
+    src, exe = d / "probe.hip", d / "probe"
     src.write_text(PROBE_HEAD + t.unit() + PROBE_MAIN)
-    exe = tmp_path / "probe"
     # -O3 -ffp-contract=off -DSDFK_SAMPLE_NT=1 -DSDFK_SAMPLE_RPW=kSampleRpw (lib_internal.h: 2): the options lib_jit.hip gives hiprtc
     c = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-DSDFK_KERNELS=0x200", "-DSDFK_SAMPLE_NT=1",
-                        "-DSDFK_SAMPLE_RPW=2", "-std=c++17", str(src), "-o", str(exe)], capture_output=True, text=True)
+                        "-DSDFK_SAMPLE_RPW=2", "-DINTERVAL_HAS_VOLUMES", "-std=c++17", "-I", os.path.join(T.ROOT, "sdfkit_amd", "csrc"),
+                        str(src), "-o", str(exe)], capture_output=True, text=True)
     assert c.returncode == 0, c.stderr[-4000:]
+    return t, str(exe)
+
+
+def _channels(vol):
+    return range(4) if vol[1] is not None else (3,)
+
+
+def _run_probe(exe, d, tag, recs, padding="nan"):
+    """one child process: [(pyramids {(volume, channel): flat floats}, iv [nbox, 2], w [npt])] per record"""
+    fin, fout = str(d / f"in_{tag}"), str(d / f"out_{tag}")
+    T.write_records(fin, recs, padding=padding)
+    r = subprocess.run(["timeout", "-k", "10", "300", exe, fin, fout], capture_output=True, text=True)
+    assert r.returncode == 0 and "interval ok" in r.stdout, (r.returncode, r.stdout, r.stderr)   # (nothing else touches the GPU after a failure here)
+    data, o, res = np.fromfile(fout, f32), 0, []
+    for _, _, vols, boxes, pts in recs:
+        pyr = {}
+        for vi, vol in enumerate(vols):
+            cells = sum(lo.size for lo, _ in VM.pyramid(vol[0])[1:])
+            for ch in (_channels(vol) if cells else ()):
+                pyr[(vi, ch)] = data[o:o + 2 * cells]
+                o += 2 * cells
+        nb, npt = len(boxes), len(pts)
+        res.append((pyr, data[o:o + 2 * nb].reshape(nb, 2), data[o + 2 * nb:o + 2 * nb + npt]))
+        o += 2 * nb + npt
+    assert o == len(data)
+    return res
+
+
+_MODEL_PYRAMIDS = {}
+
+
+def _model_pyramid(vol, ch):
+    """voxel_sdf_model.pyramid of a channel, computed once per volume: [(lo, hi)] for the levels 1..top"""
+    key = (id(vol), ch)
+    if key not in _MODEL_PYRAMIDS:
+        _MODEL_PYRAMIDS[key] = (vol, VM.pyramid(VM._channel(vol, ch))[1:])
+    return _MODEL_PYRAMIDS[key][1]
+
+
+def _assert_pyramids(name, vols, pyr):
+    """every level of every channel the device built, on bits (NaN == NaN): a poisoned cell must be poisoned, and no other"""
+    for vi, vol in enumerate(vols):
+        levels = _model_pyramid(vol, 3)
+        assert sorted(c for v, c in pyr if v == vi) == (list(_channels(vol)) if levels else []), (name, vi)
+        for ch in (_channels(vol) if levels else ()):
+            o = 0
+            for L, (lo, hi) in enumerate(_model_pyramid(vol, ch), 1):
+                got = pyr[(vi, ch)][o:o + 2 * lo.size].reshape(lo.shape + (2,))
+                o += 2 * lo.size
+                assert np.array_equal(np.isnan(got[..., 0]), np.isnan(lo)) and np.array_equal(np.isnan(got[..., 1]), np.isnan(hi)), \
+                    (name, vol[0].shape, ch, L, "the poisoned cells differ", np.argwhere(np.isnan(got[..., 0]) != np.isnan(lo))[:4])
+                bad = ~(T.bits_eq(got[..., 0], lo) & T.bits_eq(got[..., 1], hi))
+                assert not bad.any(), (name, vol[0].shape, ch, L, "device pyramid != model", np.argwhere(bad)[:4], got[bad][:4], lo[bad][:4], hi[bad][:4])
+            assert o == len(pyr[(vi, ch)])
+
+
+def _assert_values(p, B, pts, iv, w):
+    lo, hi = T.model_interval(p, B)
+    bad = ~(T.bits_eq(iv[:, 0], lo) & T.bits_eq(iv[:, 1], hi))
+    assert not bad.any(), (p["name"], "device interval != model", B[bad][:3], iv[bad][:3], lo[bad][:3], hi[bad][:3])
+    want = T.point_values(p, pts)
+    bad = ~T.bits_eq(w, want)
+    assert not bad.any(), (p["name"], "device sdf_eval != model", pts[bad][:3], w[bad][:3], want[bad][:3])
+
+
+def _records(t, select=lambda p: True):
     tables = T.edge_tables()
     recs, meta = [], []
-    for n, p in enumerate(programs):
+    for n, p in enumerate(t.programs):
+        if not select(p):
+            continue
         if p["name"] in tables:
             B = tables[p["name"]]
             pts = T.edge_points(p["name"], B[:4096]).reshape(-1, 3)
         else:
             B, nsub, ncoarse = T.program_boxes(p)
             pts = np.concatenate(T.program_points(p, B, nsub, ncoarse))
-        recs.append((n, t.cuts[n][3], [], B, pts))
-        meta.append((B, pts))
-    fin, fout = str(tmp_path / "in"), str(tmp_path / "out")
-    T.write_records(fin, recs)
-    r = subprocess.run(["timeout", "-k", "10", "300", str(exe), fin, fout], capture_output=True, text=True)
-    assert r.returncode == 0 and "interval ok" in r.stdout, (r.returncode, r.stdout, r.stderr)   # (nothing else touches the GPU after a failure here)
-    for p, (B, pts), (iv, w) in zip(programs, meta, T.read_results(fout, recs)):
-        lo, hi = T.model_interval(p, B)
-        bad = ~(T.bits_eq(iv[:, 0], lo) & T.bits_eq(iv[:, 1], hi))
-        assert not bad.any(), (p["name"], "device interval != model", B[bad][:3], iv[bad][:3], lo[bad][:3], hi[bad][:3])
-        want = T.point_values(p, pts)
-        bad = ~T.bits_eq(w, want)
-        assert not bad.any(), (p["name"], "device sdf_eval != model", pts[bad][:3], w[bad][:3], want[bad][:3])
+        recs.append((n, t.cuts[n][3], p["vols"], B, pts))
+        meta.append((p, B, pts))
+    return recs, meta
+
+
+def test_device_equals_host_build_equals_model(gpu, probe, tmp_path):
+    """Every program of the CPU file (catalogue, mathops scenes, the random DAGs, the domain-safe DAGs, the bound scenes, one program
+    per opcode and per edge volume), on the same boxes and points: the device's sdf_interval and sdf_eval are bit-equal to the
+    models, and so is every level of every pyramid the device built for a bound program's volumes.
+
+    What this catches, found by making each change in csrc/vol_pyramid.h (none reads outside an allocation), building and running
+    this test and test_row_padding_is_never_read once; both failed every time, on a pyramid comparison:
+      k_vol_pyr_up skips child q == 7              device pyramid != model at level 2 (bound_two_volumes' 12 x 10 x 14, first)
+      __builtin_elementwise_minimum -> fminf       the poisoned cells differ at level 2 (65 x 33 x 17, colour channel 1): lo loses
+                                                   the NaN, hi keeps it.  No mesh can show this one: iv_whole makes the interval
+                                                   unknown from hi alone, so tests/test_gpu_voxel_cull.py passes with it
+      k_vol_pyr_base without the `bad` poison      the poisoned cells differ at level 1 (the +-inf voxels of 13 x 6 x 21 and
+                                                   65 x 33 x 17; a NaN voxel poisons through minimum / maximum anyway).  No mesh of
+                                                   tests/test_gpu_voxel_cull.py shows it either: a read's result is clamped to its
+                                                   corners, so [c, inf] still contains it
+      lev[] starts one level late                  the probe's output no longer has the layout's size
+    (the fifth, channel 1's pyramid built from channel 0, is a change of bind_volumes: tests/test_gpu_voxel_cull.py)"""
+    t, exe = probe
+    assert sum(bool(p["vols"]) for p in t.programs) >= 3 + 2 * len(T.EDGE_VOLS)
+    recs, meta = _records(t)
+    for (p, B, pts), (pyr, iv, w) in zip(meta, _run_probe(exe, tmp_path, "all", recs)):
+        _assert_pyramids(p["name"], p["vols"], pyr)
+        _assert_values(p, B, pts, iv, w)
+
+
+def test_row_padding_is_never_read(gpu, probe, tmp_path):
+    """65 x 33 x 17 (rows of 17 in a pitch of 20), its values and colour channel 1 through both reads, run twice: the padding NaN, and
+    alternately +FLT_MAX and -FLT_MAX.  Both runs give the model's pyramid, intervals and point values, hence the same: a read into
+    the padding cannot hide behind a NaN that a minimum or a select then drops."""
+    t, exe = probe
+    vol = T.EDGE_VOLS[T.POISONED_VOL]
+    recs, meta = _records(t, lambda p: len(p["vols"]) == 1 and p["vols"][0] is vol)
+    assert len(recs) == 4 and T.volume_record(vol, "nan") != T.volume_record(vol, "fmax")
+    runs = {}
+    for padding in ("nan", "fmax"):   # (one child each; the second is not started when the first fails)
+        runs[padding] = _run_probe(exe, tmp_path, padding, recs, padding)
+        for (p, B, pts), (pyr, iv, w) in zip(meta, runs[padding]):
+            _assert_pyramids(p["name"] + " padding " + padding, p["vols"], pyr)
+            _assert_values(p, B, pts, iv, w)
+    for (pa, iva, wa), (pb, ivb, wb) in zip(runs["nan"], runs["fmax"]):
+        assert all(np.all(T.bits_eq(pa[k], pb[k])) for k in pa) and np.all(T.bits_eq(iva, ivb)) and np.all(T.bits_eq(wa, wb))
 
 
 # ---- meshes that a one-ulp error changes ----------------------------------------------------------------------------------------

@@ -114,6 +114,44 @@ EDGE_VOLS = [_random_volume((1, 2, 5), (-1.0, -0.5, 0.0), (1.0, 0.5, 2.0), False
              _random_volume((16, 8, 4), (0.0, 0.0, 0.0), (4.0, 2.0, 1.0), False, 13)]
 
 
+def _poisoned_volume():
+    """65 x 33 x 17 with colours (rows of 17 are padded to 20): +inf in the first voxel, NaN in the last one -- the clipped corner cell
+    of every level -- and -inf inside; a NaN in colour channel 1 somewhere else"""
+    vals, cols, mn, mx = _random_volume((65, 33, 17), (-2.0, -1.0, -0.5), (2.0, 1.0, 0.5), True, 24)
+    vals[0, 0, 0], vals[64, 32, 16], vals[40, 8, 3] = np.inf, np.nan, -np.inf
+    cols[10, 20, 5, 1] = np.nan
+    return (vals, cols, mn, mx)
+
+
+def _one_nan_volume():
+    """64 x 64 x 64, a power of two, with one NaN: its ancestors are poisoned at every level, and no other cell"""
+    vol = _random_volume((64, 64, 64), (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0), False, 25)
+    vol[0][37, 21, 50] = np.nan
+    return vol
+
+
+def _big_volume():
+    """176 x 160 x 160: level 1 has 88 x 80 x 80 = 563 200 cells, more than the 2048 x 256 lanes k_vol_pyr_base is launched with, so
+    the cells from x = 164 on are the second step of its grid stride.  A smooth field, distinct from voxel to voxel, and two
+    non-finite voxels, one of them in the second step."""
+    n, mn, mx = (176, 160, 160), (-1.1, -1.0, -1.0), (1.1, 1.0, 1.0)
+    px, py, pz = VM.grid_points(mn, mx, *n)
+    vals = (np.sqrt(px * px + py * py + pz * pz) - f32(0.9) + f32(0.0625) * px * py + f32(0.03125) * pz).astype(f32)
+    vals[170, 100, 33], vals[5, 150, 150] = np.nan, -np.inf
+    return (vals, None, mn, mx)
+
+
+# the smallest shapes at which a level of the min/max pyramid can go wrong: no pyramid at all (nlev == 0); 257 x 3 x 5, whose x cells
+# run 129, 65, 33, 17, 9, 5, 3, 2, 1 (a clipped last cell at every level) while y and z collapse early; an N = 1 and an N = 2 axis
+# with a long z; the three above.  BIG_VOL gets a handful of boxes instead of a vox_table.
+EDGE_VOLS += [_random_volume((1, 1, 1), (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0), False, 21),
+              _random_volume((257, 3, 5), (-2.0, -0.5, -1.0), (2.0, 0.5, 1.0), False, 22),
+              _random_volume((2, 1, 64), (-0.5, -0.25, -2.0), (0.5, 0.25, 2.0), False, 23),
+              _poisoned_volume(), _one_nan_volume(), _big_volume()]
+POISONED_VOL, BIG_VOL = 6, 8
+assert EDGE_VOLS[POISONED_VOL][0].shape == (65, 33, 17) and EDGE_VOLS[BIG_VOL][0].shape == (176, 160, 160)
+
+
 def single_op_programs():
     """one program per opcode: the operands are X, Y, Z or constants, so that the box IS the operand interval"""
     P = {}
@@ -189,35 +227,49 @@ class Text:
         return exe
 
 
-def volume_record(vol):
+_RECORDS = {}
+
+
+def volume_record(vol, padding="nan"):
+    """the record of a volume.  Rows are padded as the device lays them out; nobody may read the padding: it is NaN, or (padding ==
+    "fmax") alternately +FMAX and -FMAX, which a minimum or maximum that wrongly reads it cannot lose the way it loses a NaN."""
+    key = (id(vol), padding)
+    if key in _RECORDS and _RECORDS[key][0] is vol:
+        return _RECORDS[key][1]
     vals, cols, mn, _ = vol
     n = vals.shape
-    pitch = (n[2] + 3) & ~3   # (rows padded as the device lays them out; the padding is NaN: nobody may read it)
+    pitch = (n[2] + 3) & ~3
+
+    def padded(shape):
+        if padding == "nan":
+            return np.full(shape, np.nan, f32)
+        return np.where(np.arange(int(np.prod(shape))) % 2 == 0, FMAX, -FMAX).astype(f32).reshape(shape)
     d = VM.vol_d(vol)
     m = (np.asarray(mn, f32) + (f32(0.5) * d).astype(f32)).astype(f32)
     lv = VM.pyramid(vals)
-    pv = np.full(n[:2] + (pitch,), np.nan, f32)
+    pv = padded(n[:2] + (pitch,))
     pv[..., :n[2]] = vals
     b = struct.pack("<6i", *n, pitch, int(cols is not None), len(lv) - 1)
     b += np.concatenate([np.asarray(mn, f32), d, m]).astype(f32).tobytes() + pv.tobytes()
     if cols is not None:
-        pc = np.full(n[:2] + (pitch, 3), np.nan, f32)
+        pc = padded(n[:2] + (pitch, 3))
         pc[..., :n[2], :] = cols
         b += pc.tobytes()
     for ch in (range(4) if cols is not None else (3,)):
-        for lo, hi in VM.pyramid(VM._channel(vol, ch))[1:]:
+        for lo, hi in (lv if ch == 3 else VM.pyramid(VM._channel(vol, ch)))[1:]:
             b += struct.pack("<i", lo.size) + np.stack([lo, hi], -1).astype(f32).tobytes()
+    _RECORDS[key] = (vol, b)   # (the volumes are module constants, written once per build that is run)
     return b
 
 
-def write_records(path, recs, with_volumes=True):
+def write_records(path, recs, with_volumes=True, padding="nan"):
     """recs: (program index, constants, volumes, boxes [n, 6], points [m, 3])"""
     with open(path, "wb") as f:
         for prog, k, vols, boxes, pts in recs:
             f.write(struct.pack("<5i", prog, len(k), len(vols) if with_volumes else 0, len(boxes), len(pts)))
             f.write(np.asarray(k, f32).tobytes())
             for v in (vols if with_volumes else ()):
-                f.write(volume_record(v))
+                f.write(volume_record(v, padding))
             f.write(np.ascontiguousarray(boxes, f32).tobytes() + np.ascontiguousarray(pts, f32).tobytes())
 
 
@@ -703,12 +755,12 @@ def vox_table(vol, op):
     org = mn if op == VM.NEAREST else (mn + f32(0.5) * d).astype(f32)   # cell edges / cell centres: where the index maps step
     rows = []
     for span in (1, 2, 3, 4, 5, 8, 9, 16, 17):
-        for where in (0, 1, 2):
+        for where in (0, 1, 2, 3):   # the lower end, one cell in, the upper end, one cell short of the upper end
             for f0, f1 in ((0.25, 0.75), (0.0, 1.0), (0.0, 0.0)):
                 r = []
                 for a in range(3):
                     s = min(span, n[a])
-                    st = (0, min(1, n[a] - s), n[a] - s)[where]
+                    st = (0, min(1, n[a] - s), n[a] - s, max(n[a] - s - 1, 0))[where]
                     r += [org[a] + f32(st + f0) * d[a], org[a] + f32(st + s - 1 + f1) * d[a]]
                 rows.append(r)
     mxs = np.asarray(vol[3], f32)
@@ -719,6 +771,39 @@ def vox_table(vol, op):
             r = list(full)
             r[2 * a], r[2 * a + 1] = lo, hi
             rows.append(r)
+    return np.asarray(rows, f32)
+
+
+def interior_table(vol, op):
+    """small boxes (1 to 4 cells per axis) on a lattice inside POISONED_VOL, away from its corners: the non-finite corner voxels
+    poison the first and the last cell of every level, so most boxes of vox_table are unknown there; these are known"""
+    d, mn = VM.vol_d(vol), np.asarray(vol[2], f32)
+    org = mn if op == VM.NEAREST else (mn + f32(0.5) * d).astype(f32)
+    rows = []
+    for span in (1, 2, 3, 4):
+        for x in (9, 22, 35, 50):
+            for y, z in ((5, 5), (14, 9), (25, 12)):
+                for f0, f1 in ((0.25, 0.75), (0.0, 1.0), (0.0, 0.0)):
+                    r = []
+                    for a, st in enumerate((x, y, z)):
+                        r += [org[a] + f32(st + f0) * d[a], org[a] + f32(st + span - 1 + f1) * d[a]]
+                    rows.append(r)
+    return np.asarray(rows, f32)
+
+
+def big_table(vol, op):
+    """a handful of boxes for BIG_VOL: the whole volume (the top level), its upper half in x, boxes of 2, 3 and 5 cells in the second
+    step of the base kernel's grid stride (x >= 164) and at the lower corner, a box on each non-finite voxel"""
+    n = vol[0].shape
+    d, mn = VM.vol_d(vol), np.asarray(vol[2], f32)
+    org = mn if op == VM.NEAREST else (mn + f32(0.5) * d).astype(f32)
+    rows = []
+    for st, span in (((0, 0, 0), n), ((88, 0, 0), (88, 160, 160)), ((165, 3, 7), (2, 2, 2)), ((171, 150, 155), (3, 3, 3)), ((168, 70, 90), (5, 5, 5)),
+                     ((1, 2, 1), (3, 2, 3)), ((8, 0, 0), (80, 128, 128)), ((164, 128, 128), (12, 32, 32)), ((169, 99, 32), (3, 3, 3)), ((4, 149, 149), (2, 2, 2)), ((175, 159, 159), (1, 1, 1))):
+        r = []
+        for a in range(3):
+            r += [org[a] + f32(st[a] + 0.25) * d[a], org[a] + f32(st[a] + span[a] - 1 + 0.75) * d[a]]
+        rows.append(r)
     return np.asarray(rows, f32)
 
 
@@ -755,7 +840,8 @@ def edge_tables():
     for vi, vol in enumerate(EDGE_VOLS):
         for nm, op in (("nearest", VM.NEAREST), ("linear", VM.LINEAR)):
             for ch in ((3, 1) if vol[1] is not None else (3,)):
-                T[f"op_vox_{nm}_{vi}_{ch}"] = vox_table(vol, op)
+                T[f"op_vox_{nm}_{vi}_{ch}"] = (big_table(vol, op) if vi == BIG_VOL else vox_table(vol, op) if vi != POISONED_VOL else
+                                               np.concatenate([vox_table(vol, op), interior_table(vol, op)]))
     return T
 
 
