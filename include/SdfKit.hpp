@@ -333,11 +333,48 @@ struct MeshSamples {
     std::vector<Vector3> Weights;
 };
 
+// MeshSdf::Components / Mesh::Components (not in the reference): the connected components by index (two vertices with equal
+// positions and different indices are different vertices).  Labels are -1 for an unreferenced vertex and an index-degenerate
+// triangle; the per-component arrays have Count entries; AreaWeights sums the integer sampling weights of the component's triangles.
+struct MeshComponents {
+    int64_t Count = 0;
+    std::vector<int32_t> VertexLabels, TriangleLabels;
+    std::vector<int64_t> Triangles, Vertices, Edges, BoundaryEdges, NonManifoldEdges, OddEdges, InconsistentEdges, AreaWeights;
+    int64_t Rounds = 0, ShortcutLaunches = 0;   // what the labels took on the device
+    int64_t EulerCharacteristic(size_t c) const { return Vertices[c] - Edges[c] + Triangles[c]; }
+    bool IsWatertight(size_t c) const { return OddEdges[c] == 0; }   // (the condition under which ToVoxels' parity sign is well defined)
+    bool IsOriented(size_t c) const { return InconsistentEdges[c] == 0 && NonManifoldEdges[c] == 0; }
+};
+
+// MeshSdf::Topology / Mesh::Topology: the census of the whole mesh.  Triangles: those that are not index-degenerate; Vertices: referenced.
+struct MeshTopology {
+    int64_t Components = 0, Triangles = 0, Vertices = 0, Edges = 0, BoundaryEdges = 0, NonManifoldEdges = 0, OddEdges = 0, InconsistentEdges = 0,
+            DegenerateTriangles = 0;
+    int64_t EulerCharacteristic() const { return Vertices - Edges + Triangles; }
+    bool IsWatertight() const { return OddEdges == 0; }
+    bool IsOriented() const { return InconsistentEdges == 0 && NonManifoldEdges == 0; }
+};
+
+// MeshSdf::Select: the kept vertices' and triangles' old indices, the renumbered index array, the gathered positions and colours.
+struct MeshSelection {
+    std::vector<int32_t> VertexIndex, TriangleIndex, Triangles;
+    std::vector<Vector3> Vertices, Colors;
+};
+
 class Mesh {
 public:
     std::vector<Vector3> Vertices, Colors, Normals;
     std::vector<int32_t> Triangles;
     Vector3 Min, Max;
+    // connectivity by index (MeshSdf(*this).Components / Topology / Select); the Mesh-returning members gather Normals and re-measure
+    // Min / Max; a result without components is an empty Mesh
+    inline MeshComponents Components() const;
+    inline MeshTopology Topology() const;
+    inline Mesh SelectComponents(const std::vector<bool>& keep) const;
+    // kept iff Triangles >= minTriangles and (double)AreaWeight >= (double)minAreaFraction * (double)total
+    inline Mesh RemoveSmallComponents(int64_t minTriangles = 0, float minAreaFraction = 0.0f) const;
+    // the greatest AreaWeight; ties: more triangles, then the lower number
+    inline Mesh LargestComponent() const;
     // n points on the triangles in proportion to area (MeshSdf(*this).SamplePoints)
     inline MeshSamples SamplePoints(int64_t n, uint64_t seed = 0, bool stratified = true) const;
     Vector3 Center() const { return (Min + Max) * 0.5f; }
@@ -1077,6 +1114,8 @@ public:
         if (hasColors_ && colors.size() != vertices.size()) throw std::invalid_argument("one colour per vertex (colors)");
         Check(sdfk_trimesh_create(reinterpret_cast<const float*>(vertices.data()), (int64_t)vertices.size(), triangles.data(),
                                   (int64_t)triangles.size(), hasColors_ ? reinterpret_cast<const float*>(colors.data()) : nullptr, &h_));
+        nv_ = (int64_t)vertices.size();
+        nt_ = (int64_t)triangles.size() / 3;
     }
     explicit MeshSdf(const Mesh& m) : MeshSdf(m.Vertices, m.Triangles, AnyNonZero(m.Colors) ? m.Colors : std::vector<Vector3>{}) {}
     MeshSdf(const MeshSdf&) = delete;
@@ -1122,6 +1161,55 @@ public:
                                   hasColors_ ? &s.Colors.data()->X : nullptr, s.Triangles.data(), &s.Weights.data()->X, sampleStats_));
         return s;
     }
+    // The connected components by index with a row of counts each (sdfk_trimesh_components, sdfk_trimesh_topology).
+    MeshComponents Components() const
+    {
+        MeshComponents c;
+        int64_t nv = 0, nt = 0, stats[4] = {0, 0, 0, 0}, census[8];
+        Counts(&nv, &nt);
+        c.VertexLabels.resize((size_t)nv); c.TriangleLabels.resize((size_t)nt);
+        Check(sdfk_trimesh_components(h_, c.VertexLabels.data(), c.TriangleLabels.data(), &c.Count, stats));
+        std::vector<int64_t> rows((size_t)c.Count * 8);
+        Check(sdfk_trimesh_topology(h_, census, rows.data(), c.Count));
+        std::vector<int64_t>* cols[8] = {&c.Triangles, &c.Vertices, &c.Edges, &c.BoundaryEdges, &c.NonManifoldEdges, &c.OddEdges, &c.InconsistentEdges,
+                                         &c.AreaWeights};
+        for (int k = 0; k < 8; k++) {
+            cols[k]->resize((size_t)c.Count);
+            for (size_t i = 0; i < (size_t)c.Count; i++) (*cols[k])[i] = rows[8 * i + k];
+        }
+        c.Rounds = stats[0]; c.ShortcutLaunches = stats[1];
+        return c;
+    }
+    // The edge census of the whole mesh (sdfk_trimesh_topology).
+    MeshTopology Topology() const
+    {
+        int64_t census[8], nv = 0, nt = 0;
+        Counts(&nv, &nt);
+        Check(sdfk_trimesh_topology(h_, census, nullptr, 0));
+        MeshTopology t;
+        t.Components = census[0]; t.Vertices = census[1]; t.Edges = census[2]; t.BoundaryEdges = census[3]; t.NonManifoldEdges = census[4];
+        t.OddEdges = census[5]; t.InconsistentEdges = census[6]; t.DegenerateTriangles = census[7];
+        t.Triangles = nt - census[7];
+        return t;
+    }
+    // The sub-mesh of the components whose flag is set (sdfk_trimesh_select): one flag per component.
+    MeshSelection Select(const std::vector<bool>& keep) const
+    {
+        int64_t nv = 0, nt = 0, count = 0, kv = 0, kt = 0;
+        Counts(&nv, &nt);
+        Check(sdfk_trimesh_components(h_, nullptr, nullptr, &count, nullptr));
+        if ((int64_t)keep.size() != count) throw std::invalid_argument("one flag per component (keep)");
+        std::vector<uint8_t> k(keep.size() + 1, 0);   // (never empty: a NULL keep array is refused)
+        for (size_t i = 0; i < keep.size(); i++) k[i] = keep[i] ? 1 : 0;
+        MeshSelection s;
+        s.VertexIndex.resize((size_t)nv); s.TriangleIndex.resize((size_t)nt); s.Triangles.resize((size_t)nt * 3);
+        s.Vertices.resize((size_t)nv); s.Colors.resize((size_t)nv);
+        Check(sdfk_trimesh_select(h_, k.data(), s.VertexIndex.data(), s.TriangleIndex.data(), s.Triangles.data(), &s.Vertices.data()->X,
+                                  &s.Colors.data()->X, &kv, &kt));
+        s.VertexIndex.resize((size_t)kv); s.Vertices.resize((size_t)kv); s.Colors.resize((size_t)kv);
+        s.TriangleIndex.resize((size_t)kt); s.Triangles.resize((size_t)kt * 3);
+        return s;
+    }
     // triangles of non-zero sampling weight and the total weight (the largest triangle has 2^32), as the last SamplePoints read them
     int64_t SampledTriangles() const { return sampleStats_[0]; }
     int64_t SampleTotalWeight() const { return sampleStats_[1]; }
@@ -1133,12 +1221,58 @@ private:
         for (const Vector3& x : c) if (x.X != 0 || x.Y != 0 || x.Z != 0) return true;
         return false;
     }
+    void Counts(int64_t* nv, int64_t* nt) const { *nv = nv_; *nt = nt_; }
     sdfk_trimesh* h_ = nullptr;
     bool hasColors_ = false;
+    int64_t nv_ = 0, nt_ = 0;
     mutable int64_t sampleStats_[2] = {0, 0};
 };
 
 inline MeshSamples Mesh::SamplePoints(int64_t n, uint64_t seed, bool stratified) const { return MeshSdf(*this).SamplePoints(n, seed, stratified); }
+inline MeshComponents Mesh::Components() const { return MeshSdf(*this).Components(); }
+inline MeshTopology Mesh::Topology() const { return MeshSdf(*this).Topology(); }
+namespace detail {
+inline Mesh SelectedMesh(const Mesh& from, const MeshSdf& sdf, const std::vector<bool>& keep)
+{
+    MeshSelection s = sdf.Select(keep);
+    Mesh m;
+    m.Min = m.Max = Vector3(0, 0, 0);
+    if (s.VertexIndex.empty()) return m;
+    m.Normals.resize(s.VertexIndex.size());
+    for (size_t i = 0; i < s.VertexIndex.size(); i++)
+        m.Normals[i] = (size_t)s.VertexIndex[i] < from.Normals.size() ? from.Normals[(size_t)s.VertexIndex[i]] : Vector3(0, 0, 0);
+    m.Vertices = std::move(s.Vertices); m.Colors = std::move(s.Colors); m.Triangles = std::move(s.Triangles);
+    m.Min = m.Max = m.Vertices[0];
+    for (const Vector3& v : m.Vertices) {   // Measure (Mesh.cs:30-45)
+        m.Min = Vector3(std::min(m.Min.X, v.X), std::min(m.Min.Y, v.Y), std::min(m.Min.Z, v.Z));
+        m.Max = Vector3(std::max(m.Max.X, v.X), std::max(m.Max.Y, v.Y), std::max(m.Max.Z, v.Z));
+    }
+    return m;
+}
+}  // namespace detail
+inline Mesh Mesh::SelectComponents(const std::vector<bool>& keep) const { return detail::SelectedMesh(*this, MeshSdf(*this), keep); }
+inline Mesh Mesh::RemoveSmallComponents(int64_t minTriangles, float minAreaFraction) const
+{
+    MeshSdf sdf(*this);
+    const MeshComponents c = sdf.Components();
+    int64_t total = 0;
+    for (int64_t w : c.AreaWeights) total += w;
+    std::vector<bool> keep((size_t)c.Count);
+    for (size_t i = 0; i < keep.size(); i++)
+        keep[i] = c.Triangles[i] >= minTriangles && (double)c.AreaWeights[i] >= (double)minAreaFraction * (double)total;
+    return detail::SelectedMesh(*this, sdf, keep);
+}
+inline Mesh Mesh::LargestComponent() const
+{
+    MeshSdf sdf(*this);
+    const MeshComponents c = sdf.Components();
+    size_t best = 0;
+    for (size_t i = 1; i < (size_t)c.Count; i++)
+        if (c.AreaWeights[i] != c.AreaWeights[best] ? c.AreaWeights[i] > c.AreaWeights[best] : c.Triangles[i] > c.Triangles[best]) best = i;
+    std::vector<bool> keep((size_t)c.Count, false);
+    if (c.Count) keep[best] = true;
+    return detail::SelectedMesh(*this, sdf, keep);
+}
 
 struct FloatData {   // VectorData.cs:137-280; indexer is (x, y)
     int Width = 0, Height = 0;

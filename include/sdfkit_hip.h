@@ -41,7 +41,9 @@ extern "C" {
                                    sdfk_points_orient_normals* (point clouds: a consistent orientation of the normals);
                                    sdfk_points_voxel_downsample* / sdfk_points_outliers* (point clouds: filters);
                                    sdfk_points_blend_colors* / sdfk_points_to_volume_colors* / sdfk_points_voxel_downsample_colors* (point
-                                   clouds: per-point colours) */
+                                   clouds: per-point colours);
+                                   sdfk_trimesh_components* / sdfk_trimesh_topology* / sdfk_trimesh_select* (triangle meshes: components,
+                                   edge census, sub-meshes) */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -915,6 +917,8 @@ int sdfk_icp_register_plane_device(sdfk_points* s, const sdfk_icp_params* prm, c
  * passes through a projected edge or vertex.  Each crossing has a binary64 z (trimesh_sdf.h z_cross); voxel (i, j, k) is inside
  * iff the number of crossings with z < (double)z_k is odd, and its value is -d inside, d outside.  Parity needs no consistent
  * orientation and handles nested shells; it is meaningless (but deterministic) for open and self-intersecting meshes.
+ * The parity sign is well defined exactly when every undirected edge is used an even number of times, which is what
+ * sdfk_trimesh_topology reports as odd == 0 ("watertight", see "Triangle meshes: topology").
  * max_distance (>= 0; +inf: exact everywhere): voxels whose f32 distance exceeds it get +-max_distance with the exact sign (and
  * zero colours); every other voxel equals the +inf run bit for bit, colours included.  Without a band, large volumes far from a
  * fine mesh are slow (every voxel searches until its nearest triangle): give a band when only a shell around the surface is needed.  Colours, when the volume has them: the f32 blend of the nearest
@@ -945,7 +949,8 @@ void sdfk_trimesh_free(sdfk_trimesh* t);
  * w_t = (uint64)(sqrt(A2_t / A2max) * 2^32) (one division, one correctly rounded root, an exact scaling, truncation), so
  * w_t <= 2^32 and the total stays below 2^63.  A triangle whose area is below 2^-32 of the largest one gets weight 0 and is never
  * sampled.  W = the exclusive 64-bit integer scan of w, W[nt] = total.  A mesh in which no triangle has an area (A2max == 0) is
- * refused with SDFK_ERR_INVALID ("no triangle has an area"); the handle stays usable for everything else.
+ * refused with SDFK_ERR_INVALID ("no triangle has an area"); the handle stays usable for everything else (the topology
+ * calls read its weights as zeros).
  * Draws: splitmix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31 (mod 2^64).
  * Sample s takes h_j = splitmix(seed + (3 s + j + 1) * 0x9E3779B97F4A7C15), j = 0, 1, 2: no state is carried, and without
  * SDFK_TRIMESH_SAMPLE_STRATIFIED sample s does not depend on n.
@@ -971,6 +976,59 @@ int sdfk_trimesh_sample(sdfk_trimesh* t, int64_t n, uint64_t seed, int32_t flags
                         int32_t* triangle, float* weights3, int64_t stats[2]);
 int sdfk_trimesh_sample_device(sdfk_trimesh* t, int64_t n, uint64_t seed, int32_t flags, void* points3_dev, void* normals3_dev,
                                void* colors3_dev, void* triangle_dev, void* weights3_dev, int64_t stats[2]);
+
+/* ---- Triangle meshes: topology (Mesh.Components / Topology / SelectComponents: extensions) -------------------------------------
+ * The connectivity of the nv vertices and nt triangles (a, b, c) of a handle, as ONE function of the index array, computed by
+ * the decisions of csrc/trimesh_topology.h.  Connectivity is BY INDEX ONLY: two vertices with equal positions and different
+ * indices are different vertices (welding is not done here).  Every output is an integer and unique given the input: the device
+ * gives the same bits whatever order its atomics land in.
+ * A triangle with a repeated index (a == b, b == c or a == c) is index-degenerate: it connects nothing, contributes no edges,
+ * belongs to no component (label -1) and is counted once in the census.  Two vertices are adjacent iff some triangle that is not
+ * index-degenerate holds both; a vertex that no such triangle references has label -1.  The root of a component is its lowest
+ * vertex index; components are numbered 0 .. C-1 by ascending root.  vertex_component[v] is that number, triangle_component[t]
+ * the number of its first index.
+ * Edges: every triangle that is not index-degenerate gives the directed edges (a, b), (b, c), (c, a).  The undirected key of
+ * (u, v) is min << 32 | max; the edge is forward iff u < v.  An undirected edge used m times, f of them forward, is a boundary
+ * edge iff m == 1, non-manifold iff m >= 3, odd iff m is odd, inconsistent iff m == 2 && f != 1.  It belongs to the component of
+ * its vertices.
+ * Component row, 8 x int64: triangles, vertices, edges, boundary, non_manifold, odd, inconsistent, area_weight.  area_weight is
+ * the sum over the component's triangles of the integer sampling weight w_t of "Triangle meshes: sampling" (area over the largest
+ * area, in units of 2^-32); the weights are made if the handle has none yet, and here a mesh in which no triangle has an area
+ * gives zeros and is not refused.  There is no floating-point area: that would need a summation order.
+ * Census, 8 x int64: components, referenced vertices, distinct edges, boundary, non_manifold, odd, inconsistent, index-degenerate
+ * triangles.
+ * For the host to derive: Euler characteristic V - E + F; watertight: odd == 0 (exactly the condition under which
+ * sdfk_trimesh_to_volume's parity sign is well defined); oriented: inconsistent == 0 && non_manifold == 0.
+ * sdfk_trimesh_components: vertex_component (nv) and triangle_component (nt), either may be NULL; *n_components = C; stats[0] =
+ * hook rounds run, stats[1] = shortcut launches that worked, stats[2..3] = 0 (n_components and stats may be NULL).  The labels
+ * are made once per handle by hook-and-shortcut rounds (min-hooking by atomicMin, pointer jumping one jump per launch; at most
+ * nv + 1 hook rounds, else SDFK_ERR_INVALID, which no input reaches) and stay on it (4 bytes per vertex and per triangle) until
+ * sdfk_trimesh_free; the call that makes them synchronises, and frees its temporaries (9 nv + 4 bytes) at its end.
+ * sdfk_trimesh_topology: census is always complete; component_rows receives the rows of components 0 .. min(C, capacity) - 1,
+ * rows beyond `capacity` are not written; either may be NULL.  Temporaries, freed at the call's end: the edge records and their
+ * sort (2 x 16 x 3 nt bytes, sorted over only the key bytes nv can set), three uint32 arrays of 3 nt + 1, the rows.
+ * sdfk_trimesh_select: keep_component holds C bytes (non-zero: keep).  The kept vertices are exactly the vertices of the kept
+ * components, in ascending old index; the kept triangles come in ascending old index with their indices rewritten to the new
+ * numbering.  vertex_index_out (capacity nv) / triangle_index_out (nt): the old index of every kept item; triangles_out (3 nt);
+ * vertices_out / colors_out (3 nv): gathered, colours zeros when the mesh has none.  Label -1 is never kept, so index-degenerate
+ * triangles and unreferenced vertices disappear.  Entries beyond *nv_out / *nt_out are left as they were.  Any output may be
+ * NULL.  Keeping nothing gives 0 and 0, which is not an error.
+ * The plain forms take host arrays; the _device forms take caller-owned device buffers for the arrays (keep_component_dev
+ * included) and host pointers for the counts, census and stats; the outputs of sdfk_trimesh_select_device are ready for
+ * sdfk_trimesh_create_device.  The call that makes the labels and every topology and select call synchronise (the counts come
+ * back through pointers); sdfk_trimesh_components_device on a handle that has its labels only queues two copies on the library
+ * stream.
+ * Refused with SDFK_ERR_INVALID, outputs untouched: a NULL handle, a NULL keep_component, a negative capacity, and a handle with
+ * 2^32 / 3 triangles or more. */
+int sdfk_trimesh_components(sdfk_trimesh* t, int32_t* vertex_component, int32_t* triangle_component, int64_t* n_components, int64_t stats[4]);
+int sdfk_trimesh_components_device(sdfk_trimesh* t, void* vertex_component_dev, void* triangle_component_dev, int64_t* n_components,
+                                   int64_t stats[4]);
+int sdfk_trimesh_topology(sdfk_trimesh* t, int64_t census[8], int64_t* component_rows, int64_t capacity);
+int sdfk_trimesh_topology_device(sdfk_trimesh* t, int64_t census[8], void* component_rows_dev, int64_t capacity);
+int sdfk_trimesh_select(sdfk_trimesh* t, const uint8_t* keep_component, int32_t* vertex_index_out, int32_t* triangle_index_out,
+                        int32_t* triangles_out, float* vertices_out, float* colors_out, int64_t* nv_out, int64_t* nt_out);
+int sdfk_trimesh_select_device(sdfk_trimesh* t, const void* keep_component_dev, void* vertex_index_out_dev, void* triangle_index_out_dev,
+                               void* triangles_out_dev, void* vertices_out_dev, void* colors_out_dev, int64_t* nv_out, int64_t* nt_out);
 
 /* ---- Redistancing (Voxels.Redistance) ---------------------------------------------------------------------------------------
  * dst gets a signed distance to the iso-surface of src, with src's sign at every voxel: a first-order Eikonal solve (Godunov

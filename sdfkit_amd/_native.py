@@ -154,6 +154,12 @@ SIGNATURES = {
     "sdfk_trimesh_stats": (C.c_int, [_vp, C.POINTER(_i64)]),
     "sdfk_trimesh_sample": (C.c_int, [_vp, _i64, C.c_uint64, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "sdfk_trimesh_sample_device": (C.c_int, [_vp, _i64, C.c_uint64, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "sdfk_trimesh_components": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sdfk_trimesh_components_device": (C.c_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sdfk_trimesh_topology": (C.c_int, [_vp, C.POINTER(_i64), _vp, _i64]),
+    "sdfk_trimesh_topology_device": (C.c_int, [_vp, C.POINTER(_i64), _vp, _i64]),
+    "sdfk_trimesh_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sdfk_trimesh_select_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "sdfk_trimesh_free": (None, [_vp]),
     "sdfk_volume_redistance": (C.c_int, [_vp, _vp, C.c_float, C.c_float, C.POINTER(_i64)]),
     "sdfk_icp_register": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),

@@ -760,6 +760,53 @@ class Mesh:
         from .meshsdf import MeshSdf
         return MeshSdf(self).SamplePoints(n, seed, stratified)
 
+    def Components(self):
+        """The connected components by index, with a row of counts each (MeshSdf.Components) -> MeshComponents."""
+        from .meshsdf import MeshSdf
+        return MeshSdf(self).Components()
+
+    def Topology(self):
+        """The edge census of the mesh: boundary, non-manifold, odd and inconsistent edges, Euler characteristic, IsWatertight
+        (the condition under which ToVoxels' sign is well defined), IsOriented (MeshSdf.Topology) -> MeshTopology."""
+        from .meshsdf import MeshSdf
+        return MeshSdf(self).Topology()
+
+    def _selected(self, sdf, keep):
+        s = sdf.Select(keep)
+        if len(s.VertexIndex) == 0:
+            return Mesh(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros((0,), np.int32))
+        normals = np.ascontiguousarray(np.asarray(self.Normals, np.float32).reshape(-1, 3)[s.VertexIndex])
+        return Mesh(s.Vertices, s.Colors, normals, s.Triangles, s.Vertices.min(axis=0), s.Vertices.max(axis=0))
+
+    def SelectComponents(self, keep):
+        """The mesh of the components whose flag in `keep` is set (one flag per component of Components()): vertices and
+        triangles keep their order, triangles are renumbered, Normals are gathered, Min / Max re-measured.  Index-degenerate
+        triangles and unreferenced vertices belong to no component and disappear.  Keeping nothing gives an empty Mesh."""
+        from .meshsdf import MeshSdf
+        return self._selected(MeshSdf(self), keep)
+
+    def RemoveSmallComponents(self, minTriangles=0, minAreaFraction=0.0):
+        """Keeps the components with at least minTriangles triangles and at least minAreaFraction of the mesh's area weight
+        (a component is kept iff Triangles >= minTriangles and float(AreaWeight) >= float(minAreaFraction) * float(total))."""
+        from .meshsdf import MeshSdf
+        sdf = MeshSdf(self)
+        c = sdf.Components()
+        total = int(c.AreaWeights.sum())
+        keep = [int(t) >= minTriangles and float(int(w)) >= float(minAreaFraction) * float(total) for t, w in zip(c.Triangles, c.AreaWeights)]
+        return self._selected(sdf, keep)
+
+    def LargestComponent(self):
+        """The component of the greatest area weight (ties: more triangles, then the lower number); an empty Mesh when the mesh
+        has no component."""
+        from .meshsdf import MeshSdf
+        sdf = MeshSdf(self)
+        c = sdf.Components()
+        best = -1
+        for k in range(c.Count):
+            if best < 0 or (int(c.AreaWeights[k]), int(c.Triangles[k])) > (int(c.AreaWeights[best]), int(c.Triangles[best])):
+                best = k
+        return self._selected(sdf, [k == best for k in range(c.Count)])
+
     def WriteObj(self, path_or_file):
         """Mesh.WriteObj (Mesh.cs:66-97): `v`, then `vn`, then `f a//a b//b c//c`, 1-based."""
         own = isinstance(path_or_file, str)

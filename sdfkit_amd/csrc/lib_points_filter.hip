@@ -7,7 +7,7 @@
 //
 // Downsample:
 //   k_vf_keys      one lane per point: (packed key, insertion index) as one 16-byte record.
-//   k_rs_hist      a stable LSD radix sort of the records, 8-bit digits, only the digits the three ranges can set (the host knows
+//   k_rs_hist      (device_sort.h, shared with lib_trimesh_topology.hip) a stable LSD radix sort of the records, 8-bit digits, only the digits the three ranges can set (the host knows
 //   k_rs_scatter   them): per pass the digit counts of every tile of kSortTile records (LDS counters; integer adds, order-free),
 //                  digit-major, one exclusive scan over all of them, then the scatter.  A tile is 4 waves x 8 rounds of 64
 //                  consecutive records; wave w owns the w-th quarter of the tile.  In a round the lanes of equal digit find each
@@ -31,6 +31,7 @@
 #include "lib_internal.h"
 #include "device_reduce.h"
 #include "device_scan.h"
+#include "device_sort.h"
 #include "points_color.h"
 #include "points_filter.h"
 #include "points_knn.h"
@@ -42,115 +43,12 @@ namespace {
 using namespace sdfk_walk;
 using namespace sdfk_filter;
 
-// ---- the radix sort ----------------------------------------------------------------------------------------------------------
-constexpr int kSortBlock = 256;
-constexpr int kSortRounds = 8;                                // rounds of 64 records per wave
-constexpr int kSortTile = kSortBlock * kSortRounds;           // 2048 records (tests/test_gpu_points_filter.py TILE repeats it)
-constexpr int kSortWave = 64 * kSortRounds;                   // a wave's contiguous part of the tile
-
-struct alignas(16) Rec {
-    unsigned long long key;
-    uint32_t index, pad;
-};
-
+// ---- the radix sort: device_sort.h ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_vf_keys(const float* __restrict__ xyz, int64_t n, Lattice L, Rec* __restrict__ out)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     out[i] = Rec{voxel_key(L, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]), (uint32_t)i, 0u};
-}
-
-// hist[digit * ntiles + tile] = records of the tile with that digit
-__global__ __launch_bounds__(kSortBlock) void k_rs_hist(const Rec* __restrict__ in, int64_t n, int shift, uint32_t ntiles, uint32_t* __restrict__ hist)
-{
-    __shared__ uint32_t s_cnt[256];
-    s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * kSortTile;
-    for (int j = 0; j < kSortRounds; j++) {
-        const int64_t i = base + j * kSortBlock + threadIdx.x;
-        if (i < n) atomicAdd(&s_cnt[(unsigned)(in[i].key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    hist[(size_t)threadIdx.x * ntiles + blockIdx.x] = s_cnt[threadIdx.x];
-}
-
-// offs: the scanned histogram
-__global__ __launch_bounds__(kSortBlock) void k_rs_scatter(const Rec* __restrict__ in, Rec* __restrict__ out, int64_t n, int shift, uint32_t ntiles,
-                                                           const uint32_t* __restrict__ offs)
-{
-    __shared__ uint32_t s_wave[4][256];   // [wave][digit]: the wave's running count, then its first destination
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int j = 0; j < 4; j++) s_wave[j][threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t wbase = (int64_t)blockIdx.x * kSortTile + (int64_t)w * kSortWave + lane;
-    const unsigned long long lower = (1ull << lane) - 1ull;
-    Rec r[kSortRounds];
-    uint32_t rank[kSortRounds];
-#pragma unroll
-    for (int j = 0; j < kSortRounds; j++) {
-        const int64_t i = wbase + j * 64;
-        const bool valid = i < n;
-        r[j] = valid ? in[i] : Rec{0ull, 0u, 0u};
-        const unsigned digit = (unsigned)(r[j].key >> shift) & 255u;
-        unsigned long long peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const bool bit = (digit >> b) & 1u;
-            const unsigned long long has = __ballot(valid && bit);
-            peers &= bit ? has : ~has;
-        }
-        const uint32_t before = valid ? s_wave[w][digit] : 0u;
-        __builtin_amdgcn_wave_barrier();   // (every peer has read the count before the first of them raises it)
-        const uint32_t below = (uint32_t)__popcll(peers & lower);
-        if (valid && below == 0) s_wave[w][digit] = before + (uint32_t)__popcll(peers);
-        __builtin_amdgcn_wave_barrier();
-        rank[j] = before + below;
-    }
-    __syncthreads();
-    {
-        const unsigned d = threadIdx.x;   // one digit per lane: the waves' counts -> the first destination of each wave's run
-        uint32_t run = offs[(size_t)d * ntiles + blockIdx.x];
-        for (int j = 0; j < 4; j++) {
-            const uint32_t c = s_wave[j][d];
-            s_wave[j][d] = run;
-            run += c;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kSortRounds; j++) {
-        const int64_t i = wbase + j * 64;
-        if (i < n) {
-            const unsigned digit = (unsigned)(r[j].key >> shift) & 255u;
-            const uint32_t dest = s_wave[w][digit] + rank[j];
-            if (dest < n) out[dest] = r[j];   // (always: the histogram counted these same records)
-        }
-    }
-}
-
-// Sorts the n records of a by key, stably, through the passes of `mask`; -> the buffer that holds the result (a or b).
-int radix_sort(Rec* a, Rec* b, int64_t n, unsigned mask, Rec** sorted, const char* who)
-{
-    *sorted = a;
-    if (!mask) return SDFK_OK;
-    const uint32_t ntiles = (uint32_t)((n + kSortTile - 1) / kSortTile);
-    const int64_t nh = (int64_t)ntiles * 256;
-    uint32_t* hist = nullptr;
-    if (int r = dev_alloc((void**)&hist, (size_t)(nh + 1) * sizeof(uint32_t))) return r;
-    int r = SDFK_OK;
-    for (int d = 0; d < 8 && !r; d++) {
-        if (!(mask >> d & 1u)) continue;
-        ProfScope ps("k_rs_pass");
-        hipLaunchKernelGGL(k_rs_hist, dim3(ntiles), dim3(kSortBlock), 0, g.stream, a, n, 8 * d, ntiles, hist);
-        r = sdfk_scan::scan(hist, nh, who);
-        if (r) break;
-        hipLaunchKernelGGL(k_rs_scatter, dim3(ntiles), dim3(kSortBlock), 0, g.stream, a, b, n, 8 * d, ntiles, hist);
-        std::swap(a, b);
-    }
-    dev_free(hist);
-    *sorted = a;
-    return r;
 }
 
 // ---- voxel downsample --------------------------------------------------------------------------------------------------------

@@ -15,9 +15,11 @@
 // Sample (sdfk_trimesh_sample; arithmetic: trimesh_sample.h): the first call makes the integer weights of the triangles (area over
 // the largest area, in units of 2^-32) and their exclusive 64-bit scan W, kept on the handle; every call runs one lane per sample:
 // three stateless draws, a binary search over W, one TriPack gather, the stores.
+// The handle (struct sdfk_trimesh, TriPack) is in trimesh_handle.h, shared with lib_trimesh_topology.hip, which reads W as well.
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "points_grid.h"
+#include "trimesh_handle.h"
 #include "trimesh_sdf.h"
 #include "trimesh_sample.h"
 
@@ -30,14 +32,6 @@ using namespace sdfk_trimesh_sdf;
 namespace smp = sdfk_trimesh_smp;
 
 constexpr int kBlock = 256;
-
-// packed triangle: a, b, c (f32) and the AABB
-struct TriPack {
-    float4 p0;   // ax ay az bx
-    float4 p1;   // by bz cx cy
-    float4 p2;   // cz lox loy loz
-    float4 p3;   // hix hiy hiz -
-};
 
 unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, int64_t(1) << 30)); }
 
@@ -516,22 +510,50 @@ __global__ __launch_bounds__(kBlock) void k_tm_sample(SampleArgs A)
 // ---------------------------------------------------------------------------------------------------------------------------
 // the handle
 // ---------------------------------------------------------------------------------------------------------------------------
-struct sdfk_trimesh {
-    DeviceState* owner = &cur_state();
-    int64_t nv = 0, nt = 0;
-    float* vertices = nullptr;      // nv x 3
-    float* colors = nullptr;        // nv x 3, or null
-    int32_t* idx = nullptr;         // nt x 3
-    TriPack* tri = nullptr;         // nt
-    uint32_t* list = nullptr;       // entries: triangle indices in cell order
-    uint32_t* starts = nullptr;     // cells + 1, x-fastest
-    uint32_t* ystarts = nullptr;    // cells + 1, y-fastest
-    int64_t cells = 0, entries = 0;
-    Grid G{};
-    int64_t last_candidates = 0, last_queries = 0, last_crossings = 0;
-    unsigned long long* sample_W = nullptr;   // nt + 1: the exclusive scan of the sampling weights (made by the first sampling call)
-    int64_t sample_nonzero = 0, sample_total = 0;
-};
+// (struct sdfk_trimesh: trimesh_handle.h)
+// The sampling weights and their scan, once per handle: synchronises to read the total (trimesh_handle.h).
+int trimesh_weights(sdfk_trimesh* t, const char* who)
+{
+    if (t->sample_W) return SDFK_OK;
+    const int64_t nt = t->nt;
+    const unsigned bb = (unsigned)std::min<int64_t>(kAreaParts, (nt + kBlock - 1) / kBlock);
+    unsigned long long* W = nullptr;
+    double* a2 = nullptr;
+    double* part = nullptr;
+    unsigned long long* nonzero = nullptr;
+    int r = dev_alloc((void**)&W, (size_t)(nt + 1) * sizeof(unsigned long long));
+    if (!r) r = dev_alloc((void**)&a2, (size_t)nt * sizeof(double));
+    if (!r) r = dev_alloc((void**)&part, (size_t)(kAreaParts + 1) * sizeof(double));
+    if (!r) r = dev_alloc((void**)&nonzero, sizeof(unsigned long long));
+    hipError_t e = hipSuccess;
+    struct { double a2max; unsigned long long nonzero, total; } host{};
+    if (!r) {
+        e = hipMemsetAsync(nonzero, 0, sizeof(unsigned long long), g.stream);
+        if (e == hipSuccess) {
+            {
+                ProfScope ps("k_tm_area2");
+                hipLaunchKernelGGL(k_tm_area2, dim3(bb), dim3(kBlock), 0, g.stream, t->tri, nt, a2, part, 0);
+                hipLaunchKernelGGL(k_tm_area2, dim3(1), dim3(kBlock), 0, g.stream, t->tri, (int64_t)bb, a2, part, 1);
+            }
+            ProfScope ps("k_tm_sample_weights");
+            hipLaunchKernelGGL(k_tm_sample_weights, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, a2, nt, part + kAreaParts, W, nonzero);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) r = sdfk_scan::scan(W, nt, who);
+        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.a2max, part + kAreaParts, sizeof(double), hipMemcpyDeviceToHost, g.stream);
+        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.nonzero, nonzero, sizeof(unsigned long long), hipMemcpyDeviceToHost, g.stream);
+        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.total, W + nt, sizeof(unsigned long long), hipMemcpyDeviceToHost, g.stream);
+        if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    }
+    dev_free(a2); dev_free(part); dev_free(nonzero);
+    if (!r && e != hipSuccess) r = fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (r) { dev_free(W); return r; }
+    t->sample_W = W;
+    t->sample_no_area = !(host.a2max > 0.0);
+    t->sample_nonzero = (int64_t)host.nonzero;
+    t->sample_total = (int64_t)host.total;
+    return SDFK_OK;
+}
 
 namespace {
 
@@ -539,7 +561,9 @@ void trimesh_release(sdfk_trimesh* t)
 {
     dev_free(t->vertices); dev_free(t->colors); dev_free(t->idx); dev_free(t->tri);
     dev_free(t->list); dev_free(t->starts); dev_free(t->ystarts); dev_free(t->sample_W);
+    dev_free(t->comp_vertex); dev_free(t->comp_triangle);
     t->sample_W = nullptr;
+    t->comp_vertex = t->comp_triangle = nullptr;
     t->vertices = t->colors = nullptr; t->idx = nullptr; t->tri = nullptr; t->list = t->starts = t->ystarts = nullptr;
 }
 
@@ -755,47 +779,11 @@ int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band)
     return SDFK_OK;
 }
 
-// The sampling weights and their scan, once per handle: synchronises to read the total and the refusal.
+// the weights, and the sampler's refusal of a mesh without area
 int sample_prepare(sdfk_trimesh* t, const char* who)
 {
-    if (t->sample_W) return SDFK_OK;
-    const int64_t nt = t->nt;
-    const unsigned bb = (unsigned)std::min<int64_t>(kAreaParts, (nt + kBlock - 1) / kBlock);
-    unsigned long long* W = nullptr;
-    double* a2 = nullptr;
-    double* part = nullptr;
-    unsigned long long* nonzero = nullptr;
-    int r = dev_alloc((void**)&W, (size_t)(nt + 1) * sizeof(unsigned long long));
-    if (!r) r = dev_alloc((void**)&a2, (size_t)nt * sizeof(double));
-    if (!r) r = dev_alloc((void**)&part, (size_t)(kAreaParts + 1) * sizeof(double));
-    if (!r) r = dev_alloc((void**)&nonzero, sizeof(unsigned long long));
-    hipError_t e = hipSuccess;
-    struct { double a2max; unsigned long long nonzero, total; } host{};
-    if (!r) {
-        e = hipMemsetAsync(nonzero, 0, sizeof(unsigned long long), g.stream);
-        if (e == hipSuccess) {
-            {
-                ProfScope ps("k_tm_area2");
-                hipLaunchKernelGGL(k_tm_area2, dim3(bb), dim3(kBlock), 0, g.stream, t->tri, nt, a2, part, 0);
-                hipLaunchKernelGGL(k_tm_area2, dim3(1), dim3(kBlock), 0, g.stream, t->tri, (int64_t)bb, a2, part, 1);
-            }
-            ProfScope ps("k_tm_sample_weights");
-            hipLaunchKernelGGL(k_tm_sample_weights, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, a2, nt, part + kAreaParts, W, nonzero);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) r = sdfk_scan::scan(W, nt, who);
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.a2max, part + kAreaParts, sizeof(double), hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.nonzero, nonzero, sizeof(unsigned long long), hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.total, W + nt, sizeof(unsigned long long), hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    }
-    dev_free(a2); dev_free(part); dev_free(nonzero);
-    if (!r && e != hipSuccess) r = fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    if (!r && !(host.a2max > 0.0)) r = fail(SDFK_ERR_INVALID, "%s: no triangle has an area", who);
-    if (r) { dev_free(W); return r; }
-    t->sample_W = W;
-    t->sample_nonzero = (int64_t)host.nonzero;
-    t->sample_total = (int64_t)host.total;
+    if (int r = trimesh_weights(t, who)) return r;
+    if (t->sample_no_area) return fail(SDFK_ERR_INVALID, "%s: no triangle has an area", who);
     return SDFK_OK;
 }
 

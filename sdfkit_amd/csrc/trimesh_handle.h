@@ -1,0 +1,39 @@
+// trimesh_handle.h -- the handle behind sdfk_trimesh_*: the copied arrays, the packed triangles and their search grid (built by
+// lib_trimesh.hip), the sampling weights' scan (made by the first call that needs it) and the component labels (made by the first
+// topology call, lib_trimesh_topology.hip).  Seen by both translation units.  hipcc only.
+#pragma once
+#include "lib_internal.h"
+#include "points_grid.h"
+
+// packed triangle: a, b, c (f32) and the AABB
+struct TriPack {
+    float4 p0;   // ax ay az bx
+    float4 p1;   // by bz cx cy
+    float4 p2;   // cz lox loy loz
+    float4 p3;   // hix hiy hiz -
+};
+
+struct sdfk_trimesh {
+    DeviceState* owner = &cur_state();
+    int64_t nv = 0, nt = 0;
+    float* vertices = nullptr;      // nv x 3
+    float* colors = nullptr;        // nv x 3, or null
+    int32_t* idx = nullptr;         // nt x 3
+    TriPack* tri = nullptr;         // nt
+    uint32_t* list = nullptr;       // entries: triangle indices in cell order
+    uint32_t* starts = nullptr;     // cells + 1, x-fastest
+    uint32_t* ystarts = nullptr;    // cells + 1, y-fastest
+    int64_t cells = 0, entries = 0;
+    sdfk_points_grid::Grid G{};
+    int64_t last_candidates = 0, last_queries = 0, last_crossings = 0;
+    unsigned long long* sample_W = nullptr;   // nt + 1: the exclusive scan of the sampling weights (made by the first call that needs them)
+    int64_t sample_nonzero = 0, sample_total = 0;
+    bool sample_no_area = false;              // no triangle has an area: W is all zeros, and sampling is refused
+    int32_t* comp_vertex = nullptr;           // nv: the component of every vertex, -1: none (made by the first topology call)
+    int32_t* comp_triangle = nullptr;         // nt
+    int64_t comp_count = 0, comp_rounds = 0, comp_shortcuts = 0;
+};
+
+// The sampling weights and their scan, once per handle (lib_trimesh.hip): synchronises to read the total.  A mesh in which no
+// triangle has an area gets W = 0 everywhere and sample_no_area; refusing it is the sampler's business.
+int trimesh_weights(sdfk_trimesh* t, const char* who);

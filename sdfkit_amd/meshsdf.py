@@ -1,6 +1,7 @@
 """Triangle meshes as signed distance fields over the C ABI entry points sdfk_trimesh_* (include/sdfkit_hip.h,
 csrc/lib_trimesh.hip): the exact closest triangle of arbitrary points, signed distance volumes (Mesh -> Voxels), and points
-sampled on the triangles in proportion to area (Mesh -> points).
+sampled on the triangles in proportion to area (Mesh -> points), and the connectivity of the mesh by index (components, the edge
+census, sub-meshes of components: csrc/lib_trimesh_topology.hip).
 
 The distance is exact (binary64 closest point, ties to the lowest triangle index); the sign is the parity of the mesh's
 crossings along z, meaningful for closed meshes (nested shells included) and deterministic for any mesh.
@@ -19,6 +20,54 @@ SAMPLE_STRATIFIED = 1   # SDFK_TRIMESH_SAMPLE_STRATIFIED
 # MeshSdf.SamplePoints: Points (n, 3) f32, Normals (n, 3) f32 (unit face normals), Colors (n, 3) f32 or None, Triangles (n,) int32,
 # Weights (n, 3) f32 (the barycentric weights of the triangle's three vertices, as the colour blend used them)
 MeshSamples = namedtuple("MeshSamples", "Points Normals Colors Triangles Weights")
+
+
+class _Rows:
+    """The derived quantities of topology rows (one per component, or the census as one row)."""
+
+    @property
+    def EulerCharacteristic(self):
+        return self.Vertices - self.Edges + self.Triangles
+
+    @property
+    def IsWatertight(self):
+        """Every edge is used an even number of times: the condition under which ToVoxels' parity sign is well defined."""
+        return self.OddEdges == 0
+
+    @property
+    def IsOriented(self):
+        return (self.InconsistentEdges == 0) & (self.NonManifoldEdges == 0)
+
+
+class MeshComponents(_Rows):
+    """MeshSdf.Components(): Count; VertexLabels (nv,) / TriangleLabels (nt,) int32 (-1: an unreferenced vertex, an
+    index-degenerate triangle); per component, as int64 arrays of Count: Triangles, Vertices, Edges, BoundaryEdges,
+    NonManifoldEdges, OddEdges, InconsistentEdges, AreaWeights (the sum of the integer sampling weights of the component's
+    triangles); and EulerCharacteristic, IsWatertight, IsOriented per component.  Rounds / ShortcutLaunches: what the labels took."""
+
+    def __init__(self, vlabels, tlabels, rows, stats):
+        self.Count = len(rows)
+        self.VertexLabels, self.TriangleLabels, self.Rows = vlabels, tlabels, rows
+        (self.Triangles, self.Vertices, self.Edges, self.BoundaryEdges, self.NonManifoldEdges, self.OddEdges, self.InconsistentEdges,
+         self.AreaWeights) = (np.ascontiguousarray(rows[:, k]) for k in range(8))
+        self.Rounds, self.ShortcutLaunches = int(stats[0]), int(stats[1])
+
+
+class MeshTopology(_Rows):
+    """MeshSdf.Topology(): the census of the whole mesh as Python ints: Components, Triangles (those that are not
+    index-degenerate), Vertices (referenced), Edges, BoundaryEdges, NonManifoldEdges, OddEdges, InconsistentEdges,
+    DegenerateTriangles; EulerCharacteristic, IsWatertight, IsOriented as for a component."""
+
+    def __init__(self, census, nt):
+        c = [int(x) for x in census]
+        self.Census = c
+        self.Components, self.Vertices, self.Edges, self.BoundaryEdges, self.NonManifoldEdges, self.OddEdges, self.InconsistentEdges, \
+            self.DegenerateTriangles = c
+        self.Triangles = int(nt) - self.DegenerateTriangles
+
+
+# MeshSdf.Select: the kept vertices' old indices, the kept triangles' old indices, the new index array (flat), positions, colours
+MeshSelection = namedtuple("MeshSelection", "VertexIndex TriangleIndex Triangles Vertices Colors")
 
 
 def _ptr(a):
@@ -123,6 +172,41 @@ class MeshSdf:
         s = (C.c_int64 * 2)()
         N.check(N.lib().sdfk_trimesh_sample(self._h, 1, C.c_uint64(0), 0, None, None, None, None, None, s))
         return {"sampled_triangles": int(s[0]), "total_weight": int(s[1])}
+
+    def Components(self):
+        """The connected components by index (sdfk_trimesh_components, sdfk_trimesh_topology) -> MeshComponents.  Two vertices
+        with equal positions and different indices are different vertices."""
+        nv, nt = len(self.Vertices), len(self.Triangles) // 3
+        vl, tl = np.empty(nv, np.int32), np.empty(nt, np.int32)
+        n, st = C.c_int64(), (C.c_int64 * 4)()
+        N.check(N.lib().sdfk_trimesh_components(self._h, _ptr(vl), _ptr(tl), C.byref(n), st))
+        rows = np.zeros((n.value, 8), np.int64)
+        census = (C.c_int64 * 8)()
+        N.check(N.lib().sdfk_trimesh_topology(self._h, census, _ptr(rows), n.value))
+        return MeshComponents(vl, tl, rows, st)
+
+    def Topology(self):
+        """The edge census of the whole mesh (sdfk_trimesh_topology) -> MeshTopology."""
+        census = (C.c_int64 * 8)()
+        N.check(N.lib().sdfk_trimesh_topology(self._h, census, None, 0))
+        return MeshTopology(census[:], len(self.Triangles) // 3)
+
+    def Select(self, keep):
+        """The sub-mesh of the components whose flag in `keep` (one per component) is set (sdfk_trimesh_select) ->
+        MeshSelection; vertices and triangles keep their order and triangles are renumbered."""
+        n = C.c_int64()
+        N.check(N.lib().sdfk_trimesh_components(self._h, None, None, C.byref(n), None))
+        k = np.ascontiguousarray(np.asarray(keep).astype(bool).reshape(-1).astype(np.uint8))
+        if len(k) != n.value:
+            raise ValueError(f"keep has {len(k)} flags, the mesh has {n.value} components")
+        k = np.append(k, np.uint8(0))   # (never empty: a NULL keep array is refused)
+        nv, nt = len(self.Vertices), len(self.Triangles) // 3
+        vi, ti, tr = np.empty(nv, np.int32), np.empty(nt, np.int32), np.empty(3 * nt, np.int32)
+        vs, cs = np.empty((nv, 3), f32), np.empty((nv, 3), f32)
+        kv, kt = C.c_int64(), C.c_int64()
+        N.check(N.lib().sdfk_trimesh_select(self._h, _ptr(k), _ptr(vi), _ptr(ti), _ptr(tr), _ptr(vs), _ptr(cs), C.byref(kv), C.byref(kt)))
+        kv, kt = kv.value, kt.value
+        return MeshSelection(vi[:kv].copy(), ti[:kt].copy(), tr[:3 * kt].copy(), vs[:kv].copy(), cs[:kv].copy())
 
     def stats(self):
         """sdfk_trimesh_stats: grid, triangles, binned pairs, candidates / queries of the last profiled call, crossings."""

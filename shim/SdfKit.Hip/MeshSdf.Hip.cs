@@ -3,6 +3,8 @@
 // point, ties to the lowest triangle index); the sign is the parity of crossings along z, right for closed meshes.
 // SamplePoints (sdfk_trimesh_sample) turns a mesh into a point cloud: points in proportion to area with face normals, colours,
 // triangle indices and barycentric weights, one stated function of the mesh, n, the seed and the mode.
+// Components / Topology / Select (sdfk_trimesh_components, _topology, _select): the connectivity of the mesh by index -- a label per
+// vertex and triangle, a row of integer counts per component, the edge census, and sub-meshes of chosen components.
 // UNCOMPILED HERE (no .NET in the build image); sdfkit_amd/meshsdf.py's MeshSdf is the same layer, tested.
 using System;
 using System.Numerics;
@@ -21,12 +23,55 @@ namespace SdfKit
         public Vector3[] Weights = Array.Empty<Vector3> ();
     }
 
+    /// <summary>MeshSdf.Components: the connected components by index (equal positions with different indices are different
+    /// vertices).  Labels are -1 for an unreferenced vertex and an index-degenerate triangle; the per-component arrays have Count
+    /// entries; AreaWeights sums the integer sampling weights of the component's triangles.</summary>
+    public sealed class MeshComponents
+    {
+        public long Count;
+        public int[] VertexLabels = Array.Empty<int> ();
+        public int[] TriangleLabels = Array.Empty<int> ();
+        public long[] Triangles = Array.Empty<long> ();
+        public long[] Vertices = Array.Empty<long> ();
+        public long[] Edges = Array.Empty<long> ();
+        public long[] BoundaryEdges = Array.Empty<long> ();
+        public long[] NonManifoldEdges = Array.Empty<long> ();
+        public long[] OddEdges = Array.Empty<long> ();
+        public long[] InconsistentEdges = Array.Empty<long> ();
+        public long[] AreaWeights = Array.Empty<long> ();
+        public long Rounds, ShortcutLaunches;
+        public long EulerCharacteristic (int c) => Vertices[c] - Edges[c] + Triangles[c];
+        /// <summary>Every edge is used an even number of times: the condition under which ToVoxels' parity sign is well defined.</summary>
+        public bool IsWatertight (int c) => OddEdges[c] == 0;
+        public bool IsOriented (int c) => InconsistentEdges[c] == 0 && NonManifoldEdges[c] == 0;
+    }
+
+    /// <summary>MeshSdf.Topology: the census of the whole mesh.  Triangles: those that are not index-degenerate; Vertices: referenced.</summary>
+    public sealed class MeshTopology
+    {
+        public long Components, Triangles, Vertices, Edges, BoundaryEdges, NonManifoldEdges, OddEdges, InconsistentEdges, DegenerateTriangles;
+        public long EulerCharacteristic => Vertices - Edges + Triangles;
+        public bool IsWatertight => OddEdges == 0;
+        public bool IsOriented => InconsistentEdges == 0 && NonManifoldEdges == 0;
+    }
+
+    /// <summary>MeshSdf.Select: the kept vertices' and triangles' old indices, the renumbered index array, positions and colours.</summary>
+    public sealed class MeshSelection
+    {
+        public int[] VertexIndex = Array.Empty<int> ();
+        public int[] TriangleIndex = Array.Empty<int> ();
+        public int[] Triangles = Array.Empty<int> ();
+        public Vector3[] Vertices = Array.Empty<Vector3> ();
+        public Vector3[] Colors = Array.Empty<Vector3> ();
+    }
+
     public class MeshSdf : IDisposable
     {
         const int SampleStratified = 1;   // SDFK_TRIMESH_SAMPLE_STRATIFIED
 
         IntPtr handle;   // sdfk_trimesh*
         readonly bool hasColors;
+        readonly long vertexCount, triangleCount;
 
         /// <summary>The triangles of `mesh` (Vertices, Triangles; Colors when any is non-zero).</summary>
         public MeshSdf (Mesh mesh) : this (mesh.Vertices, mesh.Triangles, AnyNonZero (mesh.Colors) ? mesh.Colors : null) { }
@@ -37,6 +82,8 @@ namespace SdfKit
                 throw new ArgumentException ("One colour per vertex", nameof (colors));
             Native.EnsureInit ();
             hasColors = colors != null;
+            vertexCount = vertices.Length;
+            triangleCount = triangles.Length / 3;
             unsafe {
                 fixed (Vector3* v = vertices) fixed (int* t = triangles) fixed (Vector3* c = colors)
                     Native.Check (Native.sdfk_trimesh_create ((float*)v, vertices.Length, t, triangles.Length, (float*)c, out handle));
@@ -90,6 +137,64 @@ namespace SdfKit
             return s;
         }
 
+        /// <summary>The connected components by index, with a row of counts each.</summary>
+        public unsafe MeshComponents Components ()
+        {
+            var c = new MeshComponents { VertexLabels = new int[vertexCount], TriangleLabels = new int[triangleCount] };
+            long count = 0;
+            long* stats = stackalloc long[4];
+            long* census = stackalloc long[8];
+            fixed (int* vl = c.VertexLabels) fixed (int* tl = c.TriangleLabels)
+                Native.Check (Native.sdfk_trimesh_components (handle, vl, tl, &count, stats));
+            var rows = new long[count * 8];
+            fixed (long* r = rows)
+                Native.Check (Native.sdfk_trimesh_topology (handle, census, r, count));
+            var cols = new long[8][];
+            for (int k = 0; k < 8; k++) {
+                cols[k] = new long[count];
+                for (long i = 0; i < count; i++)
+                    cols[k][i] = rows[8 * i + k];
+            }
+            c.Count = count;
+            c.Triangles = cols[0]; c.Vertices = cols[1]; c.Edges = cols[2]; c.BoundaryEdges = cols[3]; c.NonManifoldEdges = cols[4];
+            c.OddEdges = cols[5]; c.InconsistentEdges = cols[6]; c.AreaWeights = cols[7];
+            c.Rounds = stats[0]; c.ShortcutLaunches = stats[1];
+            return c;
+        }
+
+        /// <summary>The edge census of the whole mesh.</summary>
+        public unsafe MeshTopology Topology ()
+        {
+            long* census = stackalloc long[8];
+            Native.Check (Native.sdfk_trimesh_topology (handle, census, null, 0));
+            return new MeshTopology { Components = census[0], Vertices = census[1], Edges = census[2], BoundaryEdges = census[3],
+                                      NonManifoldEdges = census[4], OddEdges = census[5], InconsistentEdges = census[6],
+                                      DegenerateTriangles = census[7], Triangles = triangleCount - census[7] };
+        }
+
+        /// <summary>The sub-mesh of the components whose flag is set (one flag per component): vertices and triangles keep their
+        /// order, triangles are renumbered.</summary>
+        public unsafe MeshSelection Select (ReadOnlySpan<bool> keep)
+        {
+            long count = 0, kv = 0, kt = 0;
+            Native.Check (Native.sdfk_trimesh_components (handle, null, null, &count, null));
+            if (keep.Length != count)
+                throw new ArgumentException ("One flag per component", nameof (keep));
+            var k = new byte[keep.Length + 1];   // (never empty: a NULL keep array is refused)
+            for (int i = 0; i < keep.Length; i++)
+                k[i] = keep[i] ? (byte)1 : (byte)0;
+            var vi = new int[vertexCount];
+            var ti = new int[triangleCount];
+            var tr = new int[triangleCount * 3];
+            var vs = new Vector3[vertexCount];
+            var cs = new Vector3[vertexCount];
+            fixed (byte* kp = k) fixed (int* vip = vi) fixed (int* tip = ti) fixed (int* trp = tr) fixed (Vector3* vsp = vs) fixed (Vector3* csp = cs)
+                Native.Check (Native.sdfk_trimesh_select (handle, kp, vip, tip, trp, (float*)vsp, (float*)csp, &kv, &kt));
+            return new MeshSelection { VertexIndex = vi.AsSpan (0, (int)kv).ToArray (), TriangleIndex = ti.AsSpan (0, (int)kt).ToArray (),
+                                       Triangles = tr.AsSpan (0, (int)kt * 3).ToArray (), Vertices = vs.AsSpan (0, (int)kv).ToArray (),
+                                       Colors = cs.AsSpan (0, (int)kv).ToArray () };
+        }
+
         public void Dispose ()
         {
             if (handle != IntPtr.Zero) {
@@ -127,6 +232,64 @@ namespace SdfKit
         {
             using var m = new MeshSdf (mesh);
             return m.SamplePoints (n, seed, stratified);
+        }
+
+        /// <summary>Mesh.Components: the connected components by index with a row of counts each (MeshSdf.Components).</summary>
+        public static MeshComponents Components (this Mesh mesh)
+        {
+            using var m = new MeshSdf (mesh);
+            return m.Components ();
+        }
+
+        /// <summary>Mesh.Topology: the edge census of the mesh (MeshSdf.Topology).</summary>
+        public static MeshTopology Topology (this Mesh mesh)
+        {
+            using var m = new MeshSdf (mesh);
+            return m.Topology ();
+        }
+
+        static Mesh Selected (Mesh mesh, MeshSdf m, ReadOnlySpan<bool> keep)
+        {
+            var s = m.Select (keep);
+            var normals = new Vector3[s.VertexIndex.Length];
+            for (int i = 0; i < normals.Length; i++)
+                normals[i] = mesh.Normals[s.VertexIndex[i]];
+            return new Mesh (s.Vertices, s.Colors, normals, s.Triangles);   // (the constructor measures Min / Max; empty arrays: an empty Mesh)
+        }
+
+        /// <summary>Mesh.SelectComponents: the mesh of the components whose flag is set; Normals gathered, Min / Max re-measured.</summary>
+        public static Mesh SelectComponents (this Mesh mesh, ReadOnlySpan<bool> keep)
+        {
+            using var m = new MeshSdf (mesh);
+            return Selected (mesh, m, keep);
+        }
+
+        /// <summary>Mesh.RemoveSmallComponents: keeps a component iff Triangles >= minTriangles and
+        /// (double)AreaWeight >= (double)minAreaFraction * (double)total.</summary>
+        public static Mesh RemoveSmallComponents (this Mesh mesh, long minTriangles = 0, float minAreaFraction = 0.0f)
+        {
+            using var m = new MeshSdf (mesh);
+            var c = m.Components ();
+            long total = 0;
+            foreach (var w in c.AreaWeights) total += w;
+            var keep = new bool[c.Count];
+            for (int i = 0; i < keep.Length; i++)
+                keep[i] = c.Triangles[i] >= minTriangles && (double)c.AreaWeights[i] >= (double)minAreaFraction * (double)total;
+            return Selected (mesh, m, keep);
+        }
+
+        /// <summary>Mesh.LargestComponent: the greatest AreaWeight; ties go to more triangles, then to the lower number.</summary>
+        public static Mesh LargestComponent (this Mesh mesh)
+        {
+            using var m = new MeshSdf (mesh);
+            var c = m.Components ();
+            int best = 0;
+            for (int i = 1; i < c.Count; i++)
+                if (c.AreaWeights[i] != c.AreaWeights[best] ? c.AreaWeights[i] > c.AreaWeights[best] : c.Triangles[i] > c.Triangles[best])
+                    best = i;
+            var keep = new bool[c.Count];
+            if (c.Count > 0) keep[best] = true;
+            return Selected (mesh, m, keep);
         }
     }
 }

@@ -161,6 +161,17 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_trimesh_sample_device(IntPtr trimesh, long n, ulong seed, int flags, IntPtr points3Dev,
                                                                              IntPtr normals3Dev, IntPtr colors3Dev, IntPtr triangleDev, IntPtr weights3Dev,
                                                                              long* stats2);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_components(IntPtr trimesh, int* vertexComponent, int* triangleComponent, long* nComponents,
+                                                                          long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_components_device(IntPtr trimesh, IntPtr vertexComponentDev, IntPtr triangleComponentDev,
+                                                                                 long* nComponents, long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_topology(IntPtr trimesh, long* census8, long* componentRows, long capacity);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_topology_device(IntPtr trimesh, long* census8, IntPtr componentRowsDev, long capacity);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_select(IntPtr trimesh, byte* keepComponent, int* vertexIndexOut, int* triangleIndexOut,
+                                                                      int* trianglesOut, float* verticesOut, float* colorsOut, long* nvOut, long* ntOut);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_select_device(IntPtr trimesh, IntPtr keepComponentDev, IntPtr vertexIndexOutDev,
+                                                                             IntPtr triangleIndexOutDev, IntPtr trianglesOutDev, IntPtr verticesOutDev,
+                                                                             IntPtr colorsOutDev, long* nvOut, long* ntOut);
         [DllImport(Lib)] public static extern void sdfk_trimesh_free(IntPtr trimesh);
         [DllImport(Lib)] public static extern int sdfk_volume_redistance(IntPtr src, IntPtr dst, float isoValue, float maxDistance, long* stats4);
         // several GPUs from ONE process (the managed host is one process): include/sdfkit_hip.h, "one process, several GPUs"
