@@ -361,11 +361,28 @@ struct MeshSelection {
     std::vector<Vector3> Vertices, Colors;
 };
 
+// MeshSdf::Adjacency: the neighbours of vertex v are Neighbors[Start[v] .. Start[v + 1]), ascending, each once (by index;
+// index-degenerate triangles connect nothing); Boundary[v] = 1 for the endpoints of an edge with one triangle side.
+struct MeshAdjacency {
+    std::vector<uint32_t> Start, Neighbors;
+    std::vector<uint8_t> Boundary;
+    int64_t Degree(size_t v) const { return (int64_t)Start[v + 1] - (int64_t)Start[v]; }
+};
+
 class Mesh {
 public:
     std::vector<Vector3> Vertices, Colors, Normals;
     std::vector<int32_t> Triangles;
     Vector3 Min, Max;
+    // A new Mesh smoothed by `iterations` iterations of Taubin's lambda | mu (MeshSdf::Smooth; mu = 0: plain Laplacian smoothing,
+    // which shrinks).  Triangles and Colors are copied; Normals are recomputed from the smoothed positions on the side of the
+    // present ones (normals = true) or copied; Min / Max are re-measured.
+    inline Mesh Smooth(int iterations = 10, float lambda = 0.5f, float mu = -0.53f, bool pinBoundary = true, bool normals = true) const;
+    // A new Mesh whose Normals are made from the geometry (MeshSdf::VertexNormals).  Without an argument the side of the present
+    // normals is kept: flipped iff more vertices have a negative dot product with their present normal than a positive one (a
+    // tie, or no usable normals, does not flip; marching-cubes meshes wind with their gradient normals and are not flipped).
+    inline Mesh RecomputeNormals() const;
+    inline Mesh RecomputeNormals(bool flip) const;
     // connectivity by index (MeshSdf(*this).Components / Topology / Select); the Mesh-returning members gather Normals and re-measure
     // Min / Max; a result without components is an empty Mesh
     inline MeshComponents Components() const;
@@ -1210,6 +1227,35 @@ public:
         s.TriangleIndex.resize((size_t)kt); s.Triangles.resize((size_t)kt * 3);
         return s;
     }
+    // The neighbours of every vertex and the boundary bytes (sdfk_trimesh_adjacency); made once per handle and kept on it.
+    MeshAdjacency Adjacency() const
+    {
+        MeshAdjacency a;
+        int64_t n = 0;
+        Check(sdfk_trimesh_adjacency(h_, nullptr, nullptr, nullptr, &n));
+        a.Start.resize((size_t)nv_ + 1); a.Neighbors.resize((size_t)n); a.Boundary.resize((size_t)nv_);
+        Check(sdfk_trimesh_adjacency(h_, a.Start.data(), a.Neighbors.data(), a.Boundary.data(), nullptr));
+        return a;
+    }
+    // The positions after `iterations` iterations of Taubin's lambda | mu smoothing (sdfk_trimesh_smooth: one stated function of
+    // the mesh and the arguments).  An iteration is a step with lambda, then, if mu != 0, a step with mu.  pinBoundary: the
+    // vertices of edges with one triangle side stay.  This handle is not changed: its queries still see the old positions.
+    std::vector<Vector3> Smooth(int iterations, float lambda = 0.5f, float mu = -0.53f, bool pinBoundary = true) const
+    {
+        std::vector<Vector3> out((size_t)nv_);
+        Check(sdfk_trimesh_smooth(h_, iterations, lambda, mu, pinBoundary ? SDFK_TRIMESH_SMOOTH_PIN_BOUNDARY : 0, &out.data()->X));
+        return out;
+    }
+    // Area-weighted unit vertex normals from the geometry (sdfk_trimesh_vertex_normals), zeros at a vertex without a triangle that
+    // has an area.  positions: one per vertex, in place of the handle's own (the output of Smooth, say); empty: the handle's.
+    std::vector<Vector3> VertexNormals(const std::vector<Vector3>& positions = {}, bool flip = false) const
+    {
+        if (!positions.empty() && (int64_t)positions.size() != nv_) throw std::invalid_argument("one position per vertex (positions)");
+        std::vector<Vector3> out((size_t)nv_);
+        Check(sdfk_trimesh_vertex_normals(h_, positions.empty() ? nullptr : &positions.data()->X, flip ? SDFK_TRIMESH_NORMALS_FLIP : 0,
+                                          &out.data()->X));
+        return out;
+    }
     // triangles of non-zero sampling weight and the total weight (the largest triangle has 2^32), as the last SamplePoints read them
     int64_t SampledTriangles() const { return sampleStats_[0]; }
     int64_t SampleTotalWeight() const { return sampleStats_[1]; }
@@ -1249,7 +1295,51 @@ inline Mesh SelectedMesh(const Mesh& from, const MeshSdf& sdf, const std::vector
     }
     return m;
 }
+// The vertex normals of `positions` (empty: the handle's own) on the side of `present`: flipped iff more vertices have a negative
+// dot product ((x x' + y y') + z z' in binary64) with their present normal than a positive one.
+inline std::vector<Vector3> NormalsOnTheSideOf(const MeshSdf& sdf, const std::vector<Vector3>& positions, const std::vector<Vector3>& present)
+{
+    std::vector<Vector3> n = sdf.VertexNormals(positions);
+    if (present.size() != n.size()) return n;
+    int64_t pos = 0, neg = 0;
+    for (size_t i = 0; i < n.size(); i++) {
+        const double d = ((double)n[i].X * (double)present[i].X + (double)n[i].Y * (double)present[i].Y) + (double)n[i].Z * (double)present[i].Z;
+        if (d > 0) pos++;
+        if (d < 0) neg++;
+    }
+    return neg > pos ? sdf.VertexNormals(positions, true) : n;
+}
+inline void Measure(Mesh& m)   // Mesh.cs:30-45
+{
+    m.Min = m.Max = m.Vertices.empty() ? Vector3(0, 0, 0) : m.Vertices[0];
+    for (const Vector3& v : m.Vertices) {
+        m.Min = Vector3(std::min(m.Min.X, v.X), std::min(m.Min.Y, v.Y), std::min(m.Min.Z, v.Z));
+        m.Max = Vector3(std::max(m.Max.X, v.X), std::max(m.Max.Y, v.Y), std::max(m.Max.Z, v.Z));
+    }
+}
 }  // namespace detail
+inline Mesh Mesh::Smooth(int iterations, float lambda, float mu, bool pinBoundary, bool normals) const
+{
+    MeshSdf sdf(*this);
+    Mesh m;
+    m.Vertices = sdf.Smooth(iterations, lambda, mu, pinBoundary);
+    m.Colors = Colors; m.Triangles = Triangles;
+    m.Normals = normals ? detail::NormalsOnTheSideOf(sdf, m.Vertices, Normals) : Normals;
+    detail::Measure(m);
+    return m;
+}
+inline Mesh Mesh::RecomputeNormals() const
+{
+    Mesh m = *this;
+    m.Normals = detail::NormalsOnTheSideOf(MeshSdf(*this), {}, Normals);
+    return m;
+}
+inline Mesh Mesh::RecomputeNormals(bool flip) const
+{
+    Mesh m = *this;
+    m.Normals = MeshSdf(*this).VertexNormals({}, flip);
+    return m;
+}
 inline Mesh Mesh::SelectComponents(const std::vector<bool>& keep) const { return detail::SelectedMesh(*this, MeshSdf(*this), keep); }
 inline Mesh Mesh::RemoveSmallComponents(int64_t minTriangles, float minAreaFraction) const
 {

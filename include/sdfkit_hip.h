@@ -1030,6 +1030,51 @@ int sdfk_trimesh_select(sdfk_trimesh* t, const uint8_t* keep_component, int32_t*
 int sdfk_trimesh_select_device(sdfk_trimesh* t, const void* keep_component_dev, void* vertex_index_out_dev, void* triangle_index_out_dev,
                                void* triangles_out_dev, void* vertices_out_dev, void* colors_out_dev, int64_t* nv_out, int64_t* nt_out);
 
+/* ---- Triangle meshes: adjacency, smoothing, vertex normals (Mesh.Smooth / RecomputeNormals: extensions) -----------------------
+ * Per-vertex gathers over the incidence of a handle's mesh, each ONE function of the input, computed by
+ * csrc/trimesh_adjacency.h (binary64 from the f32 inputs, the operations in the order given here, no contraction, one rounding
+ * to f32 per value; sqrt and the divisions correctly rounded), restated in tests/mesh_smooth_model.py and compared bit for bit.
+ * Incidence is BY INDEX, and index-degenerate triangles (see "Triangle meshes: topology") take no part in it.
+ * Neighbours: every triangle (a, b, c) that is not index-degenerate gives the six directed records (a,b), (b,a), (b,c), (c,b),
+ * (c,a), (a,c), key = from << 32 | to.  They are sorted (csrc/device_sort.h, over only the key bytes nv can set); nbr_start
+ * (nv + 1 x uint32) and nbr (n_entries x uint32) hold the neighbours of every vertex ASCENDING, EACH ONCE: those of v are
+ * nbr[nbr_start[v] .. nbr_start[v + 1]).  The number of records with key (v, w) is the number of triangle sides on the undirected
+ * edge {v, w}; where it is 1 the edge is a boundary edge and boundary[v] = boundary[w] = 1 (nv bytes, 0 elsewhere).
+ * Incident corners (kept on the handle, not handed out): the 3 nt records (vertex, 3 t + k) in (t, k) order, sorted stably by the
+ * vertex: the corners of every vertex in ascending (t, k) order.
+ * Both are made by the first call that needs them (that call synchronises twice to size the arrays) and stay on the handle until
+ * sdfk_trimesh_free: 4 (nv + 1) + 4 n_entries + nv bytes and 4 (nv + 1) + 12 nt bytes.  Temporaries of the making, freed at its
+ * end: two record buffers of 16 x 6 nt bytes and two uint32 arrays of 6 nt + 1.  A handle with 6 nt >= 2^32 is refused.
+ * sdfk_trimesh_adjacency: *n_entries = the length of nbr (may be NULL); nbr_start, nbr, boundary: each may be NULL -- with all
+ * three NULL only the size is returned, so a caller asks twice.  Host arrays, synchronous; _device: caller-owned device buffers,
+ * queued on the library stream.
+ * sdfk_trimesh_smooth: one STEP with factor s maps positions P to P': a vertex without a neighbour, or a pinned one, keeps its
+ * three floats as bits; otherwise per axis acc = (double)P[w0] for the first neighbour, then acc += (double)P[w] over the others
+ * in ascending order, mean = acc / (double)degree, P'[v] = (float)((double)P[v] + (double)s * (mean - (double)P[v])).  Steps are
+ * Jacobi: each reads the result of the one before.  One ITERATION is a step with lambda, then, if mu != 0, a step with mu
+ * (Taubin's lambda | mu: mu < -lambda < 0 does not shrink; mu == 0 is plain Laplacian smoothing).  vertices3_out (nv x 3) = the
+ * handle's positions after `iterations` iterations; 0 copies them.  SDFK_TRIMESH_SMOOTH_PIN_BOUNDARY pins the vertices whose
+ * boundary byte is set (without it an open mesh shrinks from its rim).  THE HANDLE IS NOT CHANGED: its search grid and packed
+ * triangles belong to the old positions; to go on with the smoothed mesh make a new handle (sdfk_trimesh_create_device).  All
+ * steps are queued on the library stream without a host wait between them; the host form synchronises once, at the copy out.
+ * Temporaries: one or two position arrays.
+ * sdfk_trimesh_vertex_normals: positions3 (nv x 3, or NULL: the handle's own) are the positions; triangles are gathered through
+ * the handle's indices.  For vertex v: N = the sum (from +0, in ascending (t, k) order of its incident corners, one rounding
+ * per add) of the triangle's n = (b - a) x (c - a) as "Triangle meshes: sampling" forms it (area weighting); len =
+ * sqrt((N.x N.x + N.y N.y) + N.z N.z); normals3_out[v] = (float)(N_k / len), or with SDFK_TRIMESH_NORMALS_FLIP
+ * (float)(-(N_k / len)).  A vertex with no corner, or whose len is 0 or not finite, gets (+0, +0, +0).  On the meshes
+ * sdfk_march makes, the unflipped normals point the way its gradient normals do.
+ * Refused with SDFK_ERR_INVALID, outputs untouched: a NULL handle, a NULL output, unknown flag bits, a lambda or mu that is not
+ * finite, iterations outside [0, 65536], 6 nt >= 2^32. */
+#define SDFK_TRIMESH_SMOOTH_PIN_BOUNDARY 1
+#define SDFK_TRIMESH_NORMALS_FLIP 1
+int sdfk_trimesh_adjacency(sdfk_trimesh* t, uint32_t* nbr_start, uint32_t* nbr, uint8_t* boundary, int64_t* n_entries);
+int sdfk_trimesh_adjacency_device(sdfk_trimesh* t, void* nbr_start_dev, void* nbr_dev, void* boundary_dev, int64_t* n_entries);
+int sdfk_trimesh_smooth(sdfk_trimesh* t, int32_t iterations, float lambda, float mu, int32_t flags, float* vertices3_out);
+int sdfk_trimesh_smooth_device(sdfk_trimesh* t, int32_t iterations, float lambda, float mu, int32_t flags, void* vertices3_out_dev);
+int sdfk_trimesh_vertex_normals(sdfk_trimesh* t, const float* positions3, int32_t flags, float* normals3_out);
+int sdfk_trimesh_vertex_normals_device(sdfk_trimesh* t, const void* positions3_dev, int32_t flags, void* normals3_out_dev);
+
 /* ---- Redistancing (Voxels.Redistance) ---------------------------------------------------------------------------------------
  * dst gets a signed distance to the iso-surface of src, with src's sign at every voxel: a first-order Eikonal solve (Godunov
  * upwind, Jacobi sweeps to the fixed point -- the fast iterative method family, Jeong & Whitaker 2008).  src is not modified

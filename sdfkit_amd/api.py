@@ -807,6 +807,49 @@ class Mesh:
                 best = k
         return self._selected(sdf, [k == best for k in range(c.Count)])
 
+    def Smooth(self, iterations=10, lam=0.5, mu=-0.53, pinBoundary=True, normals=True):
+        """A new Mesh with the vertices smoothed by `iterations` iterations of Taubin's lambda | mu (MeshSdf.Smooth; mu = 0:
+        plain Laplacian smoothing, which shrinks).  Triangles and Colors are copies; Normals are recomputed from the smoothed
+        positions on the side of the present ones (normals=True, as RecomputeNormals does) or copied; Min / Max are re-measured.
+        Connectivity is by index: vertices with equal positions and different indices do not pull on each other."""
+        from .meshsdf import MeshSdf
+        f32 = np.float32
+        sdf = MeshSdf(self)
+        V = sdf.Smooth(iterations, lam, mu, pinBoundary)
+        old = np.array(self.Normals, f32).reshape(-1, 3)
+        N_ = Mesh._normals_on_the_side_of(sdf, V, old, None) if normals else old
+        m = Mesh(V, np.array(self.Colors, f32).reshape(-1, 3), N_, np.array(self.Triangles, np.int32).reshape(-1))
+        if len(V):
+            m.Min, m.Max = V.min(axis=0), V.max(axis=0)
+        return m
+
+    @staticmethod
+    def _normals_on_the_side_of(sdf, positions, present, flip):
+        """The vertex normals of `positions`; flip=None: flipped iff more vertices have a negative dot product ((x x' + y y') +
+        z z' in binary64) with their present normal than a positive one (integer counts; a tie, or no usable present normals, does
+        not flip)."""
+        n = sdf.VertexNormals(positions)
+        if flip is None:
+            flip = False
+            if present is not None and present.shape == n.shape:
+                a, b = n.astype(np.float64), present.astype(np.float64)
+                with np.errstate(all="ignore"):
+                    d = (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+                flip = int(np.count_nonzero(d < 0)) > int(np.count_nonzero(d > 0))
+        return sdf.VertexNormals(positions, flip=True) if flip else n
+
+    def RecomputeNormals(self, flip=None):
+        """A new Mesh whose Normals are made from the geometry (MeshSdf.VertexNormals: area-weighted, unit length, zeros at a
+        vertex without a triangle that has an area); everything else is copied.  flip=None keeps the side of the present normals
+        (marching-cubes meshes wind with their gradient normals, so they are not flipped); True / False decide it."""
+        from .meshsdf import MeshSdf
+        f32 = np.float32
+        sdf = MeshSdf(self)
+        old = np.array(self.Normals, f32).reshape(-1, 3) if self.Normals is not None else None
+        N_ = Mesh._normals_on_the_side_of(sdf, None, old, flip)
+        return Mesh(np.array(self.Vertices, f32).reshape(-1, 3), np.array(self.Colors, f32).reshape(-1, 3), N_,
+                    np.array(self.Triangles, np.int32).reshape(-1), np.array(self.Min, f32), np.array(self.Max, f32))
+
     def WriteObj(self, path_or_file):
         """Mesh.WriteObj (Mesh.cs:66-97): `v`, then `vn`, then `f a//a b//b c//c`, 1-based."""
         own = isinstance(path_or_file, str)

@@ -562,8 +562,10 @@ void trimesh_release(sdfk_trimesh* t)
     dev_free(t->vertices); dev_free(t->colors); dev_free(t->idx); dev_free(t->tri);
     dev_free(t->list); dev_free(t->starts); dev_free(t->ystarts); dev_free(t->sample_W);
     dev_free(t->comp_vertex); dev_free(t->comp_triangle);
+    dev_free(t->nbr_start); dev_free(t->nbr); dev_free(t->boundary); dev_free(t->inc_start); dev_free(t->inc);
     t->sample_W = nullptr;
     t->comp_vertex = t->comp_triangle = nullptr;
+    t->nbr_start = t->nbr = t->inc_start = t->inc = nullptr; t->boundary = nullptr;
     t->vertices = t->colors = nullptr; t->idx = nullptr; t->tri = nullptr; t->list = t->starts = t->ystarts = nullptr;
 }
 

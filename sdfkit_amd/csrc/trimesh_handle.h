@@ -1,6 +1,7 @@
 // trimesh_handle.h -- the handle behind sdfk_trimesh_*: the copied arrays, the packed triangles and their search grid (built by
 // lib_trimesh.hip), the sampling weights' scan (made by the first call that needs it) and the component labels (made by the first
-// topology call, lib_trimesh_topology.hip).  Seen by both translation units.  hipcc only.
+// topology call, lib_trimesh_topology.hip) and the adjacency (made by the first adjacency, smoothing or vertex-normal call,
+// lib_trimesh_smooth.hip).  Seen by the three translation units.  hipcc only.
 #pragma once
 #include "lib_internal.h"
 #include "points_grid.h"
@@ -32,6 +33,12 @@ struct sdfk_trimesh {
     int32_t* comp_vertex = nullptr;           // nv: the component of every vertex, -1: none (made by the first topology call)
     int32_t* comp_triangle = nullptr;         // nt
     int64_t comp_count = 0, comp_rounds = 0, comp_shortcuts = 0;
+    uint32_t* nbr_start = nullptr;            // nv + 1: the neighbours of v are nbr[nbr_start[v] .. nbr_start[v + 1]), ascending, each once
+    uint32_t* nbr = nullptr;                  // nbr_entries
+    uint8_t* boundary = nullptr;              // nv: 1 for the endpoints of an edge with one triangle side
+    uint32_t* inc_start = nullptr;            // nv + 1: the corners 3 t + k of v are inc[inc_start[v] .. inc_start[v + 1]), ascending
+    uint32_t* inc = nullptr;                  // 3 nt (inc_entries of them used)
+    int64_t nbr_entries = 0, inc_entries = 0;
 };
 
 // The sampling weights and their scan, once per handle (lib_trimesh.hip): synchronises to read the total.  A mesh in which no

@@ -1,7 +1,8 @@
 """Triangle meshes as signed distance fields over the C ABI entry points sdfk_trimesh_* (include/sdfkit_hip.h,
 csrc/lib_trimesh.hip): the exact closest triangle of arbitrary points, signed distance volumes (Mesh -> Voxels), and points
 sampled on the triangles in proportion to area (Mesh -> points), and the connectivity of the mesh by index (components, the edge
-census, sub-meshes of components: csrc/lib_trimesh_topology.hip).
+census, sub-meshes of components: csrc/lib_trimesh_topology.hip), and smoothing and vertex normals over its adjacency
+(csrc/lib_trimesh_smooth.hip).
 
 The distance is exact (binary64 closest point, ties to the lowest triangle index); the sign is the parity of the mesh's
 crossings along z, meaningful for closed meshes (nested shells included) and deterministic for any mesh.
@@ -16,6 +17,8 @@ from . import _native as N
 f32 = np.float32
 
 SAMPLE_STRATIFIED = 1   # SDFK_TRIMESH_SAMPLE_STRATIFIED
+SMOOTH_PIN_BOUNDARY = 1  # SDFK_TRIMESH_SMOOTH_PIN_BOUNDARY
+NORMALS_FLIP = 1         # SDFK_TRIMESH_NORMALS_FLIP
 
 # MeshSdf.SamplePoints: Points (n, 3) f32, Normals (n, 3) f32 (unit face normals), Colors (n, 3) f32 or None, Triangles (n,) int32,
 # Weights (n, 3) f32 (the barycentric weights of the triangle's three vertices, as the colour blend used them)
@@ -68,6 +71,19 @@ class MeshTopology(_Rows):
 
 # MeshSdf.Select: the kept vertices' old indices, the kept triangles' old indices, the new index array (flat), positions, colours
 MeshSelection = namedtuple("MeshSelection", "VertexIndex TriangleIndex Triangles Vertices Colors")
+
+
+class MeshAdjacency:
+    """MeshSdf.Adjacency(): Start (nv + 1,) uint32 and Neighbors uint32 in compressed sparse rows (the neighbours of v are
+    Neighbors[Start[v]:Start[v + 1]], ascending, each once); Boundary (nv,) uint8, 1 for the endpoints of an edge with one
+    triangle side; Degree (nv,) int64."""
+
+    def __init__(self, start, neighbors, boundary):
+        self.Start, self.Neighbors, self.Boundary = start, neighbors, boundary
+        self.Degree = np.diff(start.astype(np.int64))
+
+    def Of(self, v):
+        return self.Neighbors[self.Start[v]:self.Start[v + 1]]
 
 
 def _ptr(a):
@@ -207,6 +223,56 @@ class MeshSdf:
         N.check(N.lib().sdfk_trimesh_select(self._h, _ptr(k), _ptr(vi), _ptr(ti), _ptr(tr), _ptr(vs), _ptr(cs), C.byref(kv), C.byref(kt)))
         kv, kt = kv.value, kt.value
         return MeshSelection(vi[:kv].copy(), ti[:kt].copy(), tr[:3 * kt].copy(), vs[:kv].copy(), cs[:kv].copy())
+
+    def Adjacency(self):
+        """The neighbours of every vertex, ascending and each once, and the boundary bytes (sdfk_trimesh_adjacency) ->
+        MeshAdjacency.  Made once per handle and kept on it."""
+        nv = len(self.Vertices)
+        n = C.c_int64()
+        N.check(N.lib().sdfk_trimesh_adjacency(self._h, None, None, None, C.byref(n)))
+        start, nbr, boundary = np.empty(nv + 1, np.uint32), np.empty(n.value, np.uint32), np.empty(nv, np.uint8)
+        N.check(N.lib().sdfk_trimesh_adjacency(self._h, _ptr(start), _ptr(nbr), _ptr(boundary), None))
+        return MeshAdjacency(start, nbr, boundary)
+
+    @staticmethod
+    def _smooth_flags(pinBoundary):
+        return SMOOTH_PIN_BOUNDARY if pinBoundary else 0
+
+    def Smooth(self, iterations, lam=0.5, mu=-0.53, pinBoundary=True):
+        """The positions after `iterations` iterations of Taubin's lambda | mu smoothing (sdfk_trimesh_smooth: one stated function
+        of the mesh and the arguments) -> (nv, 3) float32.  An iteration is a step with lam, then, if mu != 0, a step with mu; a
+        step moves every vertex by the factor towards the mean of its neighbours (by index, each once).  mu = 0: plain Laplacian
+        smoothing, which shrinks.  pinBoundary: the vertices of edges with one triangle side stay where they are.  This handle is
+        not changed: its distance queries still see the old positions."""
+        out = np.empty((len(self.Vertices), 3), f32)
+        N.check(N.lib().sdfk_trimesh_smooth(self._h, int(iterations), C.c_float(lam), C.c_float(mu), self._smooth_flags(pinBoundary), _ptr(out)))
+        return out
+
+    def SmoothDevice(self, iterations, lam, mu, pinBoundary, vertices_dev):
+        """Smooth into caller-owned device memory (a raw pointer to nv x 3 floats): once the handle has its adjacency this only
+        queues the steps on the library stream."""
+        N.check(N.lib().sdfk_trimesh_smooth_device(self._h, int(iterations), C.c_float(lam), C.c_float(mu), self._smooth_flags(pinBoundary),
+                                                   C.c_void_p(vertices_dev) if vertices_dev else C.c_void_p()))
+
+    def VertexNormals(self, positions=None, flip=False):
+        """Area-weighted unit vertex normals from the geometry (sdfk_trimesh_vertex_normals) -> (nv, 3) float32: the normalised sum
+        of (b - a) x (c - a) over the triangles at each vertex, zeros where there is none.  positions: (nv, 3) to use in place of
+        the handle's own (the output of Smooth, say).  On marching-cubes meshes the unflipped normals point the way the gradient
+        normals do."""
+        nv = len(self.Vertices)
+        p = None
+        if positions is not None:
+            p = np.ascontiguousarray(np.asarray(positions, f32).reshape(-1, 3))
+            if len(p) != nv:
+                raise ValueError(f"positions has {len(p)} rows, the mesh has {nv} vertices")
+        out = np.empty((nv, 3), f32)
+        N.check(N.lib().sdfk_trimesh_vertex_normals(self._h, _ptr(p) if p is not None else C.c_void_p(), NORMALS_FLIP if flip else 0, _ptr(out)))
+        return out
+
+    def VertexNormalsDevice(self, positions_dev, flip, normals_dev):
+        """VertexNormals from and into caller-owned device memory (raw pointers; positions_dev None: the handle's own positions)."""
+        N.check(N.lib().sdfk_trimesh_vertex_normals_device(self._h, C.c_void_p(positions_dev) if positions_dev else C.c_void_p(),
+                                                           NORMALS_FLIP if flip else 0, C.c_void_p(normals_dev) if normals_dev else C.c_void_p()))
 
     def stats(self):
         """sdfk_trimesh_stats: grid, triangles, binned pairs, candidates / queries of the last profiled call, crossings."""

@@ -5,6 +5,8 @@
 // triangle indices and barycentric weights, one stated function of the mesh, n, the seed and the mode.
 // Components / Topology / Select (sdfk_trimesh_components, _topology, _select): the connectivity of the mesh by index -- a label per
 // vertex and triangle, a row of integer counts per component, the edge census, and sub-meshes of chosen components.
+// Adjacency / Smooth / VertexNormals (sdfk_trimesh_adjacency, _smooth, _vertex_normals): the neighbours of every vertex, Taubin
+// smoothing of the positions and area-weighted normals from the geometry; Mesh.Smooth / Mesh.RecomputeNormals on top of them.
 // UNCOMPILED HERE (no .NET in the build image); sdfkit_amd/meshsdf.py's MeshSdf is the same layer, tested.
 using System;
 using System.Numerics;
@@ -53,6 +55,16 @@ namespace SdfKit
         public long EulerCharacteristic => Vertices - Edges + Triangles;
         public bool IsWatertight => OddEdges == 0;
         public bool IsOriented => InconsistentEdges == 0 && NonManifoldEdges == 0;
+    }
+
+    /// <summary>MeshSdf.Adjacency: the neighbours of vertex v are Neighbors[Start[v] .. Start[v + 1]), ascending, each once (by
+    /// index); Boundary[v] = 1 for the endpoints of an edge with one triangle side.</summary>
+    public sealed class MeshAdjacency
+    {
+        public uint[] Start = Array.Empty<uint> ();
+        public uint[] Neighbors = Array.Empty<uint> ();
+        public byte[] Boundary = Array.Empty<byte> ();
+        public long Degree (int v) => (long)Start[v + 1] - Start[v];
     }
 
     /// <summary>MeshSdf.Select: the kept vertices' and triangles' old indices, the renumbered index array, positions and colours.</summary>
@@ -195,6 +207,43 @@ namespace SdfKit
                                        Colors = cs.AsSpan (0, (int)kv).ToArray () };
         }
 
+        const int SmoothPinBoundary = 1;   // SDFK_TRIMESH_SMOOTH_PIN_BOUNDARY
+        const int NormalsFlip = 1;         // SDFK_TRIMESH_NORMALS_FLIP
+
+        /// <summary>The neighbours of every vertex and the boundary bytes; made once per handle and kept on it.</summary>
+        public unsafe MeshAdjacency Adjacency ()
+        {
+            long n = 0;
+            Native.Check (Native.sdfk_trimesh_adjacency (handle, null, null, null, &n));
+            var a = new MeshAdjacency { Start = new uint[vertexCount + 1], Neighbors = new uint[n], Boundary = new byte[vertexCount] };
+            fixed (uint* sp = a.Start) fixed (uint* np = a.Neighbors) fixed (byte* bp = a.Boundary)
+                Native.Check (Native.sdfk_trimesh_adjacency (handle, sp, np, bp, null));
+            return a;
+        }
+
+        /// <summary>The positions after `iterations` iterations of Taubin's lambda | mu smoothing (an iteration is a step with
+        /// lambda, then, if mu != 0, a step with mu; mu = 0: plain Laplacian smoothing).  pinBoundary: the vertices of edges with
+        /// one triangle side stay.  This handle is not changed.</summary>
+        public unsafe Vector3[] Smooth (int iterations, float lambda = 0.5f, float mu = -0.53f, bool pinBoundary = true)
+        {
+            var o = new Vector3[Math.Max (vertexCount, 1)];
+            fixed (Vector3* op = o)
+                Native.Check (Native.sdfk_trimesh_smooth (handle, iterations, lambda, mu, pinBoundary ? SmoothPinBoundary : 0, (float*)op));
+            return o.AsSpan (0, (int)vertexCount).ToArray ();
+        }
+
+        /// <summary>Area-weighted unit vertex normals from the geometry, zeros at a vertex without a triangle that has an area.
+        /// positions: one per vertex in place of the handle's own (the output of Smooth, say); empty: the handle's.</summary>
+        public unsafe Vector3[] VertexNormals (ReadOnlySpan<Vector3> positions = default, bool flip = false)
+        {
+            if (positions.Length != 0 && positions.Length != vertexCount)
+                throw new ArgumentException ("One position per vertex", nameof (positions));
+            var o = new Vector3[Math.Max (vertexCount, 1)];
+            fixed (Vector3* pp = positions) fixed (Vector3* op = o)
+                Native.Check (Native.sdfk_trimesh_vertex_normals (handle, positions.Length != 0 ? (float*)pp : null, flip ? NormalsFlip : 0, (float*)op));
+            return o.AsSpan (0, (int)vertexCount).ToArray ();
+        }
+
         public void Dispose ()
         {
             if (handle != IntPtr.Zero) {
@@ -246,6 +295,42 @@ namespace SdfKit
         {
             using var m = new MeshSdf (mesh);
             return m.Topology ();
+        }
+
+        // the vertex normals of `positions` on the side of `present`: flipped iff more vertices have a negative dot product with
+        // their present normal than a positive one ((x x' + y y') + z z' in binary64; a tie does not flip)
+        static Vector3[] NormalsOnTheSideOf (MeshSdf m, ReadOnlySpan<Vector3> positions, Vector3[] present)
+        {
+            var n = m.VertexNormals (positions);
+            if (present == null || present.Length != n.Length)
+                return n;
+            long pos = 0, neg = 0;
+            for (int i = 0; i < n.Length; i++) {
+                double d = ((double)n[i].X * present[i].X + (double)n[i].Y * present[i].Y) + (double)n[i].Z * present[i].Z;
+                if (d > 0) pos++;
+                if (d < 0) neg++;
+            }
+            return neg > pos ? m.VertexNormals (positions, true) : n;
+        }
+
+        /// <summary>Mesh.Smooth: a new Mesh smoothed by Taubin's lambda | mu (MeshSdf.Smooth); Triangles and Colors copied, Normals
+        /// recomputed from the smoothed positions on the side of the present ones (or copied), Min / Max re-measured.</summary>
+        public static Mesh Smooth (this Mesh mesh, int iterations = 10, float lambda = 0.5f, float mu = -0.53f, bool pinBoundary = true,
+                                   bool normals = true)
+        {
+            using var m = new MeshSdf (mesh);
+            var v = m.Smooth (iterations, lambda, mu, pinBoundary);
+            var n = normals ? NormalsOnTheSideOf (m, v, mesh.Normals) : (Vector3[])mesh.Normals.Clone ();
+            return new Mesh (v, (Vector3[])mesh.Colors.Clone (), n, (int[])mesh.Triangles.Clone ());   // (the constructor measures Min / Max)
+        }
+
+        /// <summary>Mesh.RecomputeNormals: a new Mesh whose Normals are made from the geometry (MeshSdf.VertexNormals).  flip = null
+        /// keeps the side of the present normals (marching-cubes meshes wind with their gradient normals: not flipped).</summary>
+        public static Mesh RecomputeNormals (this Mesh mesh, bool? flip = null)
+        {
+            using var m = new MeshSdf (mesh);
+            var n = flip.HasValue ? m.VertexNormals (default, flip.Value) : NormalsOnTheSideOf (m, default, mesh.Normals);
+            return new Mesh ((Vector3[])mesh.Vertices.Clone (), (Vector3[])mesh.Colors.Clone (), n, (int[])mesh.Triangles.Clone ());
         }
 
         static Mesh Selected (Mesh mesh, MeshSdf m, ReadOnlySpan<bool> keep)

@@ -172,6 +172,14 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_trimesh_select_device(IntPtr trimesh, IntPtr keepComponentDev, IntPtr vertexIndexOutDev,
                                                                              IntPtr triangleIndexOutDev, IntPtr trianglesOutDev, IntPtr verticesOutDev,
                                                                              IntPtr colorsOutDev, long* nvOut, long* ntOut);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_adjacency(IntPtr trimesh, uint* nbrStart, uint* nbr, byte* boundary, long* nEntries);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_adjacency_device(IntPtr trimesh, IntPtr nbrStartDev, IntPtr nbrDev, IntPtr boundaryDev,
+                                                                                long* nEntries);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_smooth(IntPtr trimesh, int iterations, float lambda, float mu, int flags, float* vertices3Out);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_smooth_device(IntPtr trimesh, int iterations, float lambda, float mu, int flags,
+                                                                             IntPtr vertices3OutDev);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_vertex_normals(IntPtr trimesh, float* positions3, int flags, float* normals3Out);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_vertex_normals_device(IntPtr trimesh, IntPtr positions3Dev, int flags, IntPtr normals3OutDev);
         [DllImport(Lib)] public static extern void sdfk_trimesh_free(IntPtr trimesh);
         [DllImport(Lib)] public static extern int sdfk_volume_redistance(IntPtr src, IntPtr dst, float isoValue, float maxDistance, long* stats4);
         // several GPUs from ONE process (the managed host is one process): include/sdfkit_hip.h, "one process, several GPUs"
