@@ -369,11 +369,30 @@ struct MeshAdjacency {
     int64_t Degree(size_t v) const { return (int64_t)Start[v + 1] - (int64_t)Start[v]; }
 };
 
+// MeshSdf::Weld: VertexMap (one per old vertex: the new index of its representative, -1: dropped), the old indices of the new
+// vertices and of the kept triangles, the renumbered index array, the representatives' own positions and colours (zeros when the
+// mesh has none), and what went: vertices merged away, triangles dropped as index-degenerate, representatives nothing names, and
+// the radix passes the sorts ran.
+struct MeshWeld {
+    std::vector<int32_t> VertexMap, VertexIndex, TriangleIndex, Triangles;
+    std::vector<Vector3> Vertices, Colors;
+    int64_t Merged = 0, DegenerateDropped = 0, UnreferencedDropped = 0, Passes = 0;
+};
+
 class Mesh {
 public:
     std::vector<Vector3> Vertices, Colors, Normals;
     std::vector<int32_t> Triangles;
     Vector3 Min, Max;
+    // A new Mesh with the vertices of equal position made one (MeshSdf::Weld): what a triangle soup, or meshes put together by
+    // Concat, need before the members below, which work by index, see their connectivity.  tolerance 0: positions equal as values;
+    // tolerance > 0: the vertices of one cell of the lattice of that size anchored at the origin (a lattice, not a ball query).  A
+    // group becomes its lowest index, which keeps its own position; Colors and Normals are gathered from the representatives;
+    // normals = true recomputes Normals from the welded geometry on the side of the gathered ones.  Min / Max are re-measured;
+    // an empty Mesh results when nothing is left.
+    inline Mesh Weld(float tolerance = 0.0f, bool normals = false) const;
+    // The meshes one after the other, the indices of each offset by the vertices before it (host side; nothing is merged).
+    static inline Mesh Concat(const std::vector<Mesh>& meshes);
     // A new Mesh smoothed by `iterations` iterations of Taubin's lambda | mu (MeshSdf::Smooth; mu = 0: plain Laplacian smoothing,
     // which shrinks).  Triangles and Colors are copied; Normals are recomputed from the smoothed positions on the side of the
     // present ones (normals = true) or copied; Min / Max are re-measured.
@@ -1256,6 +1275,24 @@ public:
                                           &out.data()->X));
         return out;
     }
+    // The mesh with the vertices of equal position made one (sdfk_trimesh_weld: one stated function of the mesh and the
+    // arguments).  tolerance 0: equal as values (-0 equals +0); > 0: the cell of a lattice of that size anchored at the origin --
+    // two vertices closer than the tolerance on opposite sides of a cell face do not weld.  Triangles that become
+    // index-degenerate and representatives no kept triangle names are dropped unless the flags keep them.  This handle is not changed.
+    MeshWeld Weld(float tolerance = 0.0f, bool keepDegenerate = false, bool keepUnreferenced = false) const
+    {
+        MeshWeld w;
+        int64_t kv = 0, kt = 0, stats[4] = {0, 0, 0, 0};
+        w.VertexMap.resize((size_t)nv_); w.VertexIndex.resize((size_t)nv_); w.TriangleIndex.resize((size_t)nt_); w.Triangles.resize((size_t)nt_ * 3);
+        w.Vertices.resize((size_t)nv_); w.Colors.resize((size_t)nv_);
+        Check(sdfk_trimesh_weld(h_, tolerance, (keepDegenerate ? SDFK_WELD_KEEP_DEGENERATE : 0) | (keepUnreferenced ? SDFK_WELD_KEEP_UNREFERENCED : 0),
+                                w.VertexMap.data(), w.VertexIndex.data(), w.TriangleIndex.data(), w.Triangles.data(), &w.Vertices.data()->X,
+                                &w.Colors.data()->X, &kv, &kt, stats));
+        w.VertexIndex.resize((size_t)kv); w.Vertices.resize((size_t)kv); w.Colors.resize((size_t)kv);
+        w.TriangleIndex.resize((size_t)kt); w.Triangles.resize((size_t)kt * 3);
+        w.Merged = stats[0]; w.DegenerateDropped = stats[1]; w.UnreferencedDropped = stats[2]; w.Passes = stats[3];
+        return w;
+    }
     // triangles of non-zero sampling weight and the total weight (the largest triangle has 2^32), as the last SamplePoints read them
     int64_t SampledTriangles() const { return sampleStats_[0]; }
     int64_t SampleTotalWeight() const { return sampleStats_[1]; }
@@ -1338,6 +1375,36 @@ inline Mesh Mesh::RecomputeNormals(bool flip) const
 {
     Mesh m = *this;
     m.Normals = MeshSdf(*this).VertexNormals({}, flip);
+    return m;
+}
+inline Mesh Mesh::Weld(float tolerance, bool normals) const
+{
+    MeshWeld w = MeshSdf(*this).Weld(tolerance);
+    Mesh m;
+    m.Min = m.Max = Vector3(0, 0, 0);
+    if (w.VertexIndex.empty()) return m;
+    m.Normals.resize(w.VertexIndex.size());
+    for (size_t i = 0; i < w.VertexIndex.size(); i++)
+        m.Normals[i] = (size_t)w.VertexIndex[i] < Normals.size() ? Normals[(size_t)w.VertexIndex[i]] : Vector3(0, 0, 0);
+    m.Vertices = std::move(w.Vertices); m.Colors = std::move(w.Colors); m.Triangles = std::move(w.Triangles);
+    if (normals) m.Normals = detail::NormalsOnTheSideOf(MeshSdf(m.Vertices, m.Triangles), {}, m.Normals);
+    detail::Measure(m);
+    return m;
+}
+inline Mesh Mesh::Concat(const std::vector<Mesh>& meshes)
+{
+    Mesh m;
+    for (const Mesh& p : meshes) {
+        const size_t base = m.Vertices.size(), n = p.Vertices.size();
+        if (base + n >= (size_t(1) << 31)) throw std::invalid_argument("2^31 vertices or more (Concat)");
+        m.Vertices.insert(m.Vertices.end(), p.Vertices.begin(), p.Vertices.end());
+        for (size_t i = 0; i < n; i++) {
+            m.Colors.push_back(p.Colors.size() == n ? p.Colors[i] : Vector3(0, 0, 0));
+            m.Normals.push_back(p.Normals.size() == n ? p.Normals[i] : Vector3(0, 0, 0));
+        }
+        for (int32_t t : p.Triangles) m.Triangles.push_back(t + (int32_t)base);
+    }
+    detail::Measure(m);
     return m;
 }
 inline Mesh Mesh::SelectComponents(const std::vector<bool>& keep) const { return detail::SelectedMesh(*this, MeshSdf(*this), keep); }

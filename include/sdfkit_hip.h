@@ -1075,6 +1075,55 @@ int sdfk_trimesh_smooth_device(sdfk_trimesh* t, int32_t iterations, float lambda
 int sdfk_trimesh_vertex_normals(sdfk_trimesh* t, const float* positions3, int32_t flags, float* normals3_out);
 int sdfk_trimesh_vertex_normals_device(sdfk_trimesh* t, const void* positions3_dev, int32_t flags, void* normals3_out_dev);
 
+/* ---- Triangle meshes: welding (Mesh.Weld: an extension) -------------------------------------------------------------------------
+ * The mesh of a handle (nv vertices, nt triangles, optional colours) with the vertices of equal position made one: what a
+ * triangle soup (every STL, many OBJ exports), separately meshed pieces put together, or any mesh given as plain arrays needs
+ * before the functions above, which work BY INDEX, see its connectivity.  ONE function of the input, `tolerance` and `flags`,
+ * computed by the decisions of csrc/trimesh_weld.h, restated in tests/mesh_weld_model.py and compared as bits.  Every decision
+ * is made on integers; no position is ever made: nothing is averaged.
+ * 1. Group key of a vertex.  tolerance == 0 (exact): the 96 bits of (x, y, z) with -0 mapped to +0 per coordinate -- the handle
+ *    holds no NaN and no infinity, so two vertices share a group exactly when their three coordinates are equal as values
+ *    (subnormals are their own values).  tolerance > 0 (lattice): the cell (floor(x / tol), floor(y / tol), floor(z / tol)) of a
+ *    world-anchored lattice with origin (0, 0, 0), as "Point clouds: filters" forms it (binary64 from the f32 inputs; kmin = the
+ *    per-axis least cell over ALL vertices, referenced or not); an axis that spans 2^21 cells or more is refused.  THIS IS A
+ *    LATTICE, NOT A BALL QUERY: two vertices closer than `tolerance` on opposite sides of a cell face do not weld, and two
+ *    vertices of one cell may be up to sqrt(3) tol apart.
+ * 2. Representative.  rep[v] = the lowest vertex index of v's group.
+ * 3. Triangles.  Triangle t becomes (rep[a], rep[b], rep[c]) and is KEPT unless that is index-degenerate (see "Triangle meshes:
+ *    topology"); with SDFK_WELD_KEEP_DEGENERATE every triangle is kept.
+ * 4. Vertices.  v is KEPT iff rep[v] == v and some kept triangle names it; with SDFK_WELD_KEEP_UNREFERENCED every v with
+ *    rep[v] == v is kept.  Kept vertices are numbered in ascending old index, kept triangles likewise.  A kept vertex keeps ITS
+ *    OWN position and colour bits (the representative's: the lowest index wins).
+ * 5. Outputs, any may be NULL; entries beyond the counts are left as they were.  vertex_map (nv): the new index of every old
+ *    vertex's representative, -1 where that representative was dropped.  vertex_index_out (capacity nv) / triangle_index_out
+ *    (nt): the old index of every new vertex / kept triangle.  triangles_out (3 nt): the rewritten, renumbered indices.
+ *    vertices_out / colors_out (3 nv): gathered, colours zeros when the mesh has none.  *nv_out, *nt_out: the counts.
+ *    stats[4] = { vertices merged away (nv less the number of groups), triangles dropped as degenerate, representatives dropped
+ *    as unreferenced, radix passes run }.
+ * 6. What follows.  A mesh with no two equal positions, no index-degenerate triangle and no unreferenced vertex comes back bit
+ *    for bit, vertex_map[v] == v.  Welding a welded mesh changes nothing, in both modes (with the same tolerance).  Duplicate
+ *    triangles are not removed: the census' non-manifold count shows them.
+ * How (csrc/lib_trimesh_weld.hip): one 16-byte record per vertex, sorted stably by key (csrc/device_sort.h) from ascending
+ * indices, so that the first record of a group is its lowest index.  Exact mode has 96 key bits for a 64-bit sort key: it sorts
+ * by x, rewrites the keys to (z, y) and sorts again.  Only the passes whose byte differs between some two keys are run (the OR of
+ * key ^ key[0] over all vertices names them: order-free, and a pass over a byte all keys share moves nothing); lattice mode
+ * runs those among the passes its spans can set.  Head flags, a scan, rep; triangle and vertex keep flags, two scans, the gathers.
+ * Temporaries, freed at the call's end: two record buffers of 16 nv bytes, 17 nv + 8 bytes of flags and numbers, 4 (nt + 1).
+ * THE HANDLE IS NOT CHANGED and keeps nothing of this: the result is another mesh, as after sdfk_trimesh_select.  The plain form
+ * takes host arrays; the _device form caller-owned device buffers and host pointers for the counts and stats, and its outputs
+ * are ready for sdfk_trimesh_create_device.  Both synchronise (the pass masks, the lattice's box and the counts come back to the
+ * host).  Everything welding to nothing (*nt_out == 0) is not an error: it gives 0 and 0 (without
+ * SDFK_WELD_KEEP_UNREFERENCED).
+ * Refused with SDFK_ERR_INVALID, outputs untouched: a NULL handle, a negative, NaN or infinite tolerance, unknown flag bits, a
+ * lattice axis spanning 2^21 cells or more. */
+#define SDFK_WELD_KEEP_DEGENERATE 1
+#define SDFK_WELD_KEEP_UNREFERENCED 2
+int sdfk_trimesh_weld(sdfk_trimesh* t, float tolerance, int32_t flags, int32_t* vertex_map, int32_t* vertex_index_out, int32_t* triangle_index_out,
+                      int32_t* triangles_out, float* vertices_out, float* colors_out, int64_t* nv_out, int64_t* nt_out, int64_t stats[4]);
+int sdfk_trimesh_weld_device(sdfk_trimesh* t, float tolerance, int32_t flags, void* vertex_map_dev, void* vertex_index_out_dev,
+                             void* triangle_index_out_dev, void* triangles_out_dev, void* vertices_out_dev, void* colors_out_dev, int64_t* nv_out,
+                             int64_t* nt_out, int64_t stats[4]);
+
 /* ---- Redistancing (Voxels.Redistance) ---------------------------------------------------------------------------------------
  * dst gets a signed distance to the iso-surface of src, with src's sign at every voxel: a first-order Eikonal solve (Godunov
  * upwind, Jacobi sweeps to the fixed point -- the fast iterative method family, Jeong & Whitaker 2008).  src is not modified

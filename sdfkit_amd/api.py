@@ -850,6 +850,49 @@ class Mesh:
         return Mesh(np.array(self.Vertices, f32).reshape(-1, 3), np.array(self.Colors, f32).reshape(-1, 3), N_,
                     np.array(self.Triangles, np.int32).reshape(-1), np.array(self.Min, f32), np.array(self.Max, f32))
 
+    def Weld(self, tolerance=0.0, normals=False):
+        """A new Mesh with the vertices of equal position made one (MeshSdf.Weld): what a triangle soup, or meshes put together
+        by Concat, need before Components / Topology / Smooth / RecomputeNormals, which work by index, see their connectivity.
+        tolerance 0 welds positions equal as values; tolerance > 0 the vertices of one cell of the lattice of that size anchored
+        at the origin (a lattice, not a ball query: two vertices closer than the tolerance on opposite sides of a cell face do
+        not weld).  A group becomes its lowest index, which keeps its own position; Colors and Normals are gathered from those
+        representatives; triangles that become index-degenerate and vertices nothing names any more disappear.  normals=True:
+        Normals are recomputed from the welded geometry on the side of the gathered ones.  Min / Max are re-measured; an empty
+        Mesh results when nothing is left."""
+        from .meshsdf import MeshSdf
+        f32 = np.float32
+        w = MeshSdf(self).Weld(tolerance)
+        if len(w.VertexIndex) == 0:
+            return Mesh(np.zeros((0, 3), f32), np.zeros((0, 3), f32), np.zeros((0, 3), f32), np.zeros((0,), np.int32))
+        N_ = np.ascontiguousarray(np.asarray(self.Normals, f32).reshape(-1, 3)[w.VertexIndex])
+        if normals:
+            N_ = Mesh._normals_on_the_side_of(MeshSdf((w.Vertices, w.Triangles)), None, N_, None)
+        return Mesh(w.Vertices, w.Colors, N_, w.Triangles, w.Vertices.min(axis=0), w.Vertices.max(axis=0))
+
+    @staticmethod
+    def Concat(meshes):
+        """The meshes put together on the host: the arrays one after the other, the indices of each offset by the vertices before
+        it.  Nothing is merged: Weld() afterwards joins the pieces where their positions agree."""
+        f32 = np.float32
+        meshes = list(meshes)
+        V = [np.asarray(m.Vertices, f32).reshape(-1, 3) for m in meshes]
+        offsets = np.cumsum([0] + [len(v) for v in V])
+
+        def rows(m, v, name):
+            a = getattr(m, name, None)
+            a = None if a is None else np.asarray(a, f32).reshape(-1, 3)
+            return a if a is not None and a.shape == v.shape else np.zeros_like(v)
+
+        if not meshes or offsets[-1] == 0:
+            return Mesh(np.zeros((0, 3), f32), np.zeros((0, 3), f32), np.zeros((0, 3), f32), np.zeros((0,), np.int32))
+        if offsets[-1] >= 2 ** 31:
+            raise ValueError("2^31 vertices or more")
+        T = [np.asarray(m.Triangles, np.int64).reshape(-1) + int(o) for m, o in zip(meshes, offsets)]
+        Vs = np.ascontiguousarray(np.concatenate(V))
+        return Mesh(Vs, np.ascontiguousarray(np.concatenate([rows(m, v, "Colors") for m, v in zip(meshes, V)])),
+                    np.ascontiguousarray(np.concatenate([rows(m, v, "Normals") for m, v in zip(meshes, V)])),
+                    np.concatenate(T).astype(np.int32), Vs.min(axis=0), Vs.max(axis=0))
+
     def WriteObj(self, path_or_file):
         """Mesh.WriteObj (Mesh.cs:66-97): `v`, then `vn`, then `f a//a b//b c//c`, 1-based."""
         own = isinstance(path_or_file, str)

@@ -1,5 +1,6 @@
-// device_sort.h -- the stable LSD radix sort of 16-byte (key, index) records that the voxel filter (lib_points_filter.hip) and the
-// edge census of a triangle mesh (lib_trimesh_topology.hip) share: 8-bit digits, only the passes the caller's mask names.  Per
+// device_sort.h -- the stable LSD radix sort of 16-byte (key, index) records that the voxel filter (lib_points_filter.hip), the
+// edge census and the adjacency of a triangle mesh (lib_trimesh_topology.hip, lib_trimesh_smooth.hip) and its welding
+// (lib_trimesh_weld.hip) share: 8-bit digits, only the passes the caller's mask names.  Per
 // pass the digit counts of every tile of kSortTile records (LDS counters; integer adds, order-free), digit-major, one exclusive
 // scan over all of them (device_scan.h), then the scatter; how the scatter keeps equal digits in order is told at
 // lib_points_filter.hip's head.  Each unit that includes this gets its own copy of the two kernels.  hipcc only.

@@ -1,7 +1,7 @@
 // trimesh_handle.h -- the handle behind sdfk_trimesh_*: the copied arrays, the packed triangles and their search grid (built by
 // lib_trimesh.hip), the sampling weights' scan (made by the first call that needs it) and the component labels (made by the first
 // topology call, lib_trimesh_topology.hip) and the adjacency (made by the first adjacency, smoothing or vertex-normal call,
-// lib_trimesh_smooth.hip).  Seen by the three translation units.  hipcc only.
+// lib_trimesh_smooth.hip).  Seen by those three translation units and by lib_trimesh_weld.hip, which only reads it.  hipcc only.
 #pragma once
 #include "lib_internal.h"
 #include "points_grid.h"

@@ -2,7 +2,7 @@
 csrc/lib_trimesh.hip): the exact closest triangle of arbitrary points, signed distance volumes (Mesh -> Voxels), and points
 sampled on the triangles in proportion to area (Mesh -> points), and the connectivity of the mesh by index (components, the edge
 census, sub-meshes of components: csrc/lib_trimesh_topology.hip), and smoothing and vertex normals over its adjacency
-(csrc/lib_trimesh_smooth.hip).
+(csrc/lib_trimesh_smooth.hip), and welding: the vertices of equal position made one (csrc/lib_trimesh_weld.hip).
 
 The distance is exact (binary64 closest point, ties to the lowest triangle index); the sign is the parity of the mesh's
 crossings along z, meaningful for closed meshes (nested shells included) and deterministic for any mesh.
@@ -19,6 +19,8 @@ f32 = np.float32
 SAMPLE_STRATIFIED = 1   # SDFK_TRIMESH_SAMPLE_STRATIFIED
 SMOOTH_PIN_BOUNDARY = 1  # SDFK_TRIMESH_SMOOTH_PIN_BOUNDARY
 NORMALS_FLIP = 1         # SDFK_TRIMESH_NORMALS_FLIP
+WELD_KEEP_DEGENERATE = 1    # SDFK_WELD_KEEP_DEGENERATE
+WELD_KEEP_UNREFERENCED = 2  # SDFK_WELD_KEEP_UNREFERENCED
 
 # MeshSdf.SamplePoints: Points (n, 3) f32, Normals (n, 3) f32 (unit face normals), Colors (n, 3) f32 or None, Triangles (n,) int32,
 # Weights (n, 3) f32 (the barycentric weights of the triangle's three vertices, as the colour blend used them)
@@ -84,6 +86,17 @@ class MeshAdjacency:
 
     def Of(self, v):
         return self.Neighbors[self.Start[v]:self.Start[v + 1]]
+
+
+class MeshWeld:
+    """MeshSdf.Weld(): VertexMap (nv,) int32 (the new index of every old vertex's representative, -1: dropped); VertexIndex /
+    TriangleIndex int32 (the old index of every new vertex / kept triangle); Vertices, Colors (n, 3) float32 (the representatives'
+    own bits; colours zeros when the mesh has none); Triangles int32 (flat, renumbered); Merged (vertices merged away),
+    DegenerateDropped, UnreferencedDropped, Passes (radix passes run)."""
+
+    def __init__(self, vmap, vi, ti, tr, vs, cs, stats):
+        self.VertexMap, self.VertexIndex, self.TriangleIndex, self.Triangles, self.Vertices, self.Colors = vmap, vi, ti, tr, vs, cs
+        self.Merged, self.DegenerateDropped, self.UnreferencedDropped, self.Passes = (int(x) for x in stats)
 
 
 def _ptr(a):
@@ -273,6 +286,37 @@ class MeshSdf:
         """VertexNormals from and into caller-owned device memory (raw pointers; positions_dev None: the handle's own positions)."""
         N.check(N.lib().sdfk_trimesh_vertex_normals_device(self._h, C.c_void_p(positions_dev) if positions_dev else C.c_void_p(),
                                                            NORMALS_FLIP if flip else 0, C.c_void_p(normals_dev) if normals_dev else C.c_void_p()))
+
+    @staticmethod
+    def _weld_flags(keepDegenerate, keepUnreferenced):
+        return (WELD_KEEP_DEGENERATE if keepDegenerate else 0) | (WELD_KEEP_UNREFERENCED if keepUnreferenced else 0)
+
+    def Weld(self, tolerance=0.0, keepDegenerate=False, keepUnreferenced=False):
+        """The mesh with the vertices of equal position made one (sdfk_trimesh_weld: one stated function of the mesh and the
+        arguments) -> MeshWeld.  tolerance 0: positions equal as values (-0 equals +0); tolerance > 0: the vertices of one cell
+        of the lattice of that size anchored at the origin -- a lattice, not a ball query: two vertices closer than the tolerance
+        on opposite sides of a cell face do not weld.  A group is replaced by its lowest index, which keeps its own position and
+        colour; triangles that become index-degenerate and representatives no kept triangle names are dropped unless the flags
+        keep them.  This handle is not changed."""
+        nv, nt = len(self.Vertices), len(self.Triangles) // 3
+        vm, vi, ti, tr = np.empty(nv, np.int32), np.empty(nv, np.int32), np.empty(nt, np.int32), np.empty(3 * nt, np.int32)
+        vs, cs = np.empty((nv, 3), f32), np.empty((nv, 3), f32)
+        kv, kt, st = C.c_int64(), C.c_int64(), (C.c_int64 * 4)()
+        N.check(N.lib().sdfk_trimesh_weld(self._h, C.c_float(tolerance), self._weld_flags(keepDegenerate, keepUnreferenced), _ptr(vm), _ptr(vi),
+                                          _ptr(ti), _ptr(tr), _ptr(vs), _ptr(cs), C.byref(kv), C.byref(kt), st))
+        kv, kt = kv.value, kt.value
+        return MeshWeld(vm, vi[:kv].copy(), ti[:kt].copy(), tr[:3 * kt].copy(), vs[:kv].copy(), cs[:kv].copy(), st[:])
+
+    def WeldDevice(self, tolerance, keepDegenerate, keepUnreferenced, vertex_map_dev=None, vertex_index_dev=None, triangle_index_dev=None,
+                   triangles_dev=None, vertices_dev=None, colors_dev=None):
+        """Weld into caller-owned device memory (raw pointers; None: that output is not wanted) -> (vertices, triangles, stats):
+        the counts and the four stats.  The outputs are ready for sdfk_trimesh_create_device."""
+        kv, kt, st = C.c_int64(), C.c_int64(), (C.c_int64 * 4)()
+        N.check(N.lib().sdfk_trimesh_weld_device(self._h, C.c_float(tolerance), self._weld_flags(keepDegenerate, keepUnreferenced),
+                                                 *[C.c_void_p(p) if p else C.c_void_p() for p in (vertex_map_dev, vertex_index_dev, triangle_index_dev,
+                                                                                                 triangles_dev, vertices_dev, colors_dev)],
+                                                 C.byref(kv), C.byref(kt), st))
+        return kv.value, kt.value, [int(x) for x in st]
 
     def stats(self):
         """sdfk_trimesh_stats: grid, triangles, binned pairs, candidates / queries of the last profiled call, crossings."""

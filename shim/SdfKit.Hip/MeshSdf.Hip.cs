@@ -7,8 +7,10 @@
 // vertex and triangle, a row of integer counts per component, the edge census, and sub-meshes of chosen components.
 // Adjacency / Smooth / VertexNormals (sdfk_trimesh_adjacency, _smooth, _vertex_normals): the neighbours of every vertex, Taubin
 // smoothing of the positions and area-weighted normals from the geometry; Mesh.Smooth / Mesh.RecomputeNormals on top of them.
+// Weld (sdfk_trimesh_weld): the vertices of equal position made one; Mesh.Weld and Concat (a static of the extensions class) on top.
 // UNCOMPILED HERE (no .NET in the build image); sdfkit_amd/meshsdf.py's MeshSdf is the same layer, tested.
 using System;
+using System.Collections.Generic;
 using System.Numerics;
 using SdfKit.Hip;
 
@@ -68,6 +70,20 @@ namespace SdfKit
     }
 
     /// <summary>MeshSdf.Select: the kept vertices' and triangles' old indices, the renumbered index array, positions and colours.</summary>
+    /// <summary>MeshSdf.Weld: VertexMap (one per old vertex: the new index of its representative, -1: dropped), the old indices of
+    /// the new vertices and of the kept triangles, the renumbered index array, the representatives' own positions and colours
+    /// (zeros when the mesh has none), and what went.</summary>
+    public sealed class MeshWeld
+    {
+        public int[] VertexMap = Array.Empty<int> ();
+        public int[] VertexIndex = Array.Empty<int> ();
+        public int[] TriangleIndex = Array.Empty<int> ();
+        public int[] Triangles = Array.Empty<int> ();
+        public Vector3[] Vertices = Array.Empty<Vector3> ();
+        public Vector3[] Colors = Array.Empty<Vector3> ();
+        public long Merged, DegenerateDropped, UnreferencedDropped, Passes;
+    }
+
     public sealed class MeshSelection
     {
         public int[] VertexIndex = Array.Empty<int> ();
@@ -244,6 +260,33 @@ namespace SdfKit
             return o.AsSpan (0, (int)vertexCount).ToArray ();
         }
 
+        const int WeldKeepDegenerate = 1;     // SDFK_WELD_KEEP_DEGENERATE
+        const int WeldKeepUnreferenced = 2;   // SDFK_WELD_KEEP_UNREFERENCED
+
+        /// <summary>The mesh with the vertices of equal position made one.  tolerance 0: equal as values (-0 equals +0); > 0: one
+        /// cell of the lattice of that size anchored at the origin (not a ball query: two vertices closer than the tolerance on
+        /// opposite sides of a cell face do not weld).  A group becomes its lowest index, which keeps its own position and colour;
+        /// triangles that become index-degenerate and representatives no kept triangle names go unless the flags keep them.
+        /// This handle is not changed.</summary>
+        public unsafe MeshWeld Weld (float tolerance = 0.0f, bool keepDegenerate = false, bool keepUnreferenced = false)
+        {
+            long kv = 0, kt = 0;
+            long* st = stackalloc long[4];
+            var vm = new int[vertexCount];
+            var vi = new int[vertexCount];
+            var ti = new int[triangleCount];
+            var tr = new int[triangleCount * 3];
+            var vs = new Vector3[vertexCount];
+            var cs = new Vector3[vertexCount];
+            int flags = (keepDegenerate ? WeldKeepDegenerate : 0) | (keepUnreferenced ? WeldKeepUnreferenced : 0);
+            fixed (int* vmp = vm) fixed (int* vip = vi) fixed (int* tip = ti) fixed (int* trp = tr) fixed (Vector3* vsp = vs) fixed (Vector3* csp = cs)
+                Native.Check (Native.sdfk_trimesh_weld (handle, tolerance, flags, vmp, vip, tip, trp, (float*)vsp, (float*)csp, &kv, &kt, st));
+            return new MeshWeld { VertexMap = vm, VertexIndex = vi.AsSpan (0, (int)kv).ToArray (), TriangleIndex = ti.AsSpan (0, (int)kt).ToArray (),
+                                  Triangles = tr.AsSpan (0, (int)kt * 3).ToArray (), Vertices = vs.AsSpan (0, (int)kv).ToArray (),
+                                  Colors = cs.AsSpan (0, (int)kv).ToArray (), Merged = st[0], DegenerateDropped = st[1],
+                                  UnreferencedDropped = st[2], Passes = st[3] };
+        }
+
         public void Dispose ()
         {
             if (handle != IntPtr.Zero) {
@@ -331,6 +374,46 @@ namespace SdfKit
             using var m = new MeshSdf (mesh);
             var n = flip.HasValue ? m.VertexNormals (default, flip.Value) : NormalsOnTheSideOf (m, default, mesh.Normals);
             return new Mesh ((Vector3[])mesh.Vertices.Clone (), (Vector3[])mesh.Colors.Clone (), n, (int[])mesh.Triangles.Clone ());
+        }
+
+        /// <summary>Mesh.Weld: a new Mesh with the vertices of equal position made one (MeshSdf.Weld): the first step for a triangle
+        /// soup or for meshes put together by Concat.  Colors and Normals are gathered from the representatives; normals = true
+        /// recomputes Normals from the welded geometry on the side of the gathered ones; Min / Max are re-measured; an empty Mesh
+        /// results when nothing is left.</summary>
+        public static Mesh Weld (this Mesh mesh, float tolerance = 0.0f, bool normals = false)
+        {
+            MeshWeld w;
+            using (var m = new MeshSdf (mesh))
+                w = m.Weld (tolerance);
+            var n = new Vector3[w.VertexIndex.Length];
+            for (int i = 0; i < n.Length; i++)
+                n[i] = mesh.Normals[w.VertexIndex[i]];
+            if (normals && n.Length != 0) {
+                using var welded = new MeshSdf (w.Vertices, w.Triangles);
+                n = NormalsOnTheSideOf (welded, default, n);
+            }
+            return new Mesh (w.Vertices, w.Colors, n, w.Triangles);   // (the constructor measures Min / Max; empty arrays: an empty Mesh)
+        }
+
+        /// <summary>Mesh.Concat: the meshes one after the other, the indices of each offset by the vertices before it (on the host;
+        /// nothing is merged: Weld afterwards joins the pieces where their positions agree).</summary>
+        public static Mesh Concat (IEnumerable<Mesh> meshes)
+        {
+            var v = new List<Vector3> ();
+            var c = new List<Vector3> ();
+            var n = new List<Vector3> ();
+            var t = new List<int> ();
+            foreach (var m in meshes) {
+                int offset = v.Count;
+                if ((long)offset + m.Vertices.Length >= 1L << 31)
+                    throw new ArgumentException ("2^31 vertices or more", nameof (meshes));
+                v.AddRange (m.Vertices);
+                c.AddRange (m.Colors.Length == m.Vertices.Length ? m.Colors : new Vector3[m.Vertices.Length]);
+                n.AddRange (m.Normals.Length == m.Vertices.Length ? m.Normals : new Vector3[m.Vertices.Length]);
+                foreach (int i in m.Triangles)
+                    t.Add (i + offset);
+            }
+            return new Mesh (v.ToArray (), c.ToArray (), n.ToArray (), t.ToArray ());
         }
 
         static Mesh Selected (Mesh mesh, MeshSdf m, ReadOnlySpan<bool> keep)

@@ -180,6 +180,12 @@ namespace SdfKit.Hip
                                                                              IntPtr vertices3OutDev);
         [DllImport(Lib)] public static extern int sdfk_trimesh_vertex_normals(IntPtr trimesh, float* positions3, int flags, float* normals3Out);
         [DllImport(Lib)] public static extern int sdfk_trimesh_vertex_normals_device(IntPtr trimesh, IntPtr positions3Dev, int flags, IntPtr normals3OutDev);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_weld(IntPtr trimesh, float tolerance, int flags, int* vertexMap, int* vertexIndexOut,
+                                                                    int* triangleIndexOut, int* trianglesOut, float* verticesOut, float* colorsOut,
+                                                                    long* nvOut, long* ntOut, long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_weld_device(IntPtr trimesh, float tolerance, int flags, IntPtr vertexMapDev,
+                                                                           IntPtr vertexIndexOutDev, IntPtr triangleIndexOutDev, IntPtr trianglesOutDev,
+                                                                           IntPtr verticesOutDev, IntPtr colorsOutDev, long* nvOut, long* ntOut, long* stats4);
         [DllImport(Lib)] public static extern void sdfk_trimesh_free(IntPtr trimesh);
         [DllImport(Lib)] public static extern int sdfk_volume_redistance(IntPtr src, IntPtr dst, float isoValue, float maxDistance, long* stats4);
         // several GPUs from ONE process (the managed host is one process): include/sdfkit_hip.h, "one process, several GPUs"
