@@ -1134,7 +1134,9 @@ int sdfk_trimesh_weld_device(sdfk_trimesh* t, float tolerance, int32_t flags, vo
  *   h = (DX, DY, DZ), the f32 cell sizes (max - min) / n widened to binary64; s(x) = (double)v(x) - (double)iso_value;
  *   outside(x) = s(x) > 0.0 -- the strict test marching cubes makes, so src and dst mesh to the same sign pattern.
  * 1. Refusal (SDFK_ERR_INVALID, dst untouched): a NaN or infinite value in src (checked on the device; the call synchronises),
- *    a non-finite iso_value, a NaN or negative max_distance, dst of another shape or box than src, volumes without storage.
+ *    a non-finite iso_value, a NaN or negative max_distance, dst of another shape or box than src, volumes without storage, a
+ *    cell size h_a that is not finite or not > 0 (a box with max <= min or a NaN or infinite bound on an axis: sdfk_volume_create
+ *    accepts it; the iteration has no fixed point there).  All but the first are decided on the host, before any launch.
  * 2. Front.  x is on the front if one of its six in-range neighbours n has outside(n) != outside(x).  For each axis a with
  *    such a neighbour, t_a = the least (h_a * |s(x)|) / (|s(x)| + |s(n)|) over them (the linear crossing marching cubes places
  *    on that edge).  T0 = 0 if some t_a == 0, else (float)(1 / sqrt(q)), q = the sum of 1 / (t_a * t_a) over the axes that

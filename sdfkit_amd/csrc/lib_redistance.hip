@@ -183,11 +183,9 @@ bool same_box(const sdfk_volume* a, const sdfk_volume* b)
     return true;
 }
 
-int redistance(const sdfk_volume* src, sdfk_volume* dst, float iso, float band, int64_t stats[4])
+int redistance(const sdfk_volume* src, sdfk_volume* dst, const float d[3], float iso, float band, int64_t stats[4])
 {
     static const char* who = "sdfk_volume_redistance";
-    float d[3], m[3], outside;
-    grid_constants(src, d, m, &outside);
     Geo G{};
     G.nx = src->nx; G.ny = src->ny; G.nz = src->nz; G.pitch = src->pitch();
     G.tx = (G.nx + kTile - 1) / kTile; G.ty = (G.ny + kTile - 1) / kTile; G.tz = (G.nz + kTile - 1) / kTile;
@@ -286,9 +284,16 @@ extern "C" int sdfk_volume_redistance(const sdfk_volume* src, sdfk_volume* dst, 
     if (!src || !dst) return fail(SDFK_ERR_INVALID, "%s: null argument", who);
     if (src->owner != dst->owner) return fail(SDFK_ERR_INVALID, "%s: the volumes belong to different devices", who);
     if (src->elided || !src->values || dst->elided || !dst->values) return fail(SDFK_ERR_INVALID, "%s: a volume has no storage", who);
+    if (src->nx < 1 || src->ny < 1 || src->nz < 1) return fail(SDFK_ERR_INVALID, "%s: empty volume", who);
+    // a box with max <= min or a NaN / infinite bound on an axis (sdfk_volume_create takes any box): the iteration has no fixed
+    // point on a negative cell size, and a negative T would read as frozen.  (Before same_box: a NaN bound equals nothing.)
+    float d[3], m[3], outside;
+    grid_constants(src, d, m, &outside);
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(d[k]) || !(d[k] > 0.0f))
+            return fail(SDFK_ERR_INVALID, "%s: the cell sizes (%g, %g, %g) must be finite and > 0", who, (double)d[0], (double)d[1], (double)d[2]);
     if (!same_box(src, dst)) return fail(SDFK_ERR_INVALID, "%s: dst has another shape or box than src", who);
     if (!std::isfinite(iso_value)) return fail(SDFK_ERR_INVALID, "%s: iso_value must be finite", who);
     if (!(max_distance >= 0.0f)) return fail(SDFK_ERR_INVALID, "%s: max_distance must be >= 0 (+inf: the full field)", who);
-    if (src->nx < 1 || src->ny < 1 || src->nz < 1) return fail(SDFK_ERR_INVALID, "%s: empty volume", who);
-    return redistance(src, dst, iso_value, max_distance, stats);
+    return redistance(src, dst, d, iso_value, max_distance, stats);
 }

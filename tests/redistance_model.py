@@ -114,12 +114,16 @@ def _dilate6(t):
     return out
 
 
-def redistance(values, h, iso=0.0, max_distance=np.inf, max_sweeps=None):
+def redistance(values, h, iso=0.0, max_distance=np.inf, max_sweeps=None, history=None):
     """Steps 2-5 -> (result f32, stats): stats = sweeps (the last, which changes nothing, included; 0 without a front),
-    tile_sweeps (8^3 tiles the block-active schedule sweeps), front voxels, clamped voxels (T > max_distance)."""
+    tile_sweeps (8^3 tiles the block-active schedule sweeps), front voxels, clamped voxels (T > max_distance).
+    history: a list that receives, per sweep, (the mask of tiles the schedule sweeps, the mask of tiles the sweep changed)."""
     values = np.asarray(values, f32)
     if not np.all(np.isfinite(values)) or not np.isfinite(f32(iso)) or not (f32(max_distance) >= 0):
         raise ValueError("refused (step 1)")
+    hf = np.asarray(h, f32)
+    if hf.shape != (3,) or not np.all(np.isfinite(hf)) or not np.all(hf > 0):
+        raise ValueError("refused (step 1): cell sizes %r are not finite and > 0" % (hf.tolist(),))
     band = f32(max_distance)
     out, frozen, T = front(values, h, iso)
     sweeps = tile_sweeps = 0
@@ -128,8 +132,11 @@ def redistance(values, h, iso=0.0, max_distance=np.inf, max_sweeps=None):
         while max_sweeps is None or sweeps < max_sweeps:
             new = sweep(T, frozen, h, band)
             sweeps += 1
-            tile_sweeps += int(_dilate6(changed_tiles).sum())
+            swept = _dilate6(changed_tiles)
+            tile_sweeps += int(swept.sum())
             changed = new != T
+            if history is not None:
+                history.append((swept, _tiles_of(changed)))
             if not changed.any():
                 break
             changed_tiles = _tiles_of(changed)
@@ -138,6 +145,37 @@ def redistance(values, h, iso=0.0, max_distance=np.inf, max_sweeps=None):
     res = np.where(out, m, -m).astype(f32)
     stats = {"sweeps": sweeps, "tile_sweeps": tile_sweeps, "front": int(frozen.sum()), "clamped": int((T > band).sum())}
     return res, stats
+
+
+# ---- the block-active schedule, sweep by sweep (tests/redistance_cases.py) -------------------------------------------------------
+def schedule_history(values, h, iso=0.0, band=np.inf, changes=False):
+    """Per sweep, the boolean mask of the 8^3 tiles the schedule of redistance() sweeps (their sum is stats["tile_sweeps"]).
+    changes=True: (those masks, per sweep the mask of tiles in which the sweep changed a value)."""
+    hist = []
+    redistance(values, h, iso, band, history=hist)
+    swept, changed = [s for s, _ in hist], [c for _, c in hist]
+    return (swept, changed) if changes else swept
+
+
+def idle_runs(history):
+    """[(tile index, first sweep of the gap (0-based), gap length g >= 1)]: the tile is swept in sweep first - 1, not swept in the
+    g sweeps from `first` on, and swept again in sweep first + g."""
+    runs = []
+    if not history:
+        return runs
+    H = np.stack(history)   # (sweeps, tx, ty, tz)
+    for tile in np.argwhere(H.any(axis=0)):
+        col = H[(slice(None),) + tuple(tile)]
+        on = np.flatnonzero(col)
+        for a, b in zip(on[:-1], on[1:]):
+            if b - a > 1:
+                runs.append((tuple(int(t) for t in tile), int(a) + 1, int(b - a - 1)))
+    return runs
+
+
+def idle_gaps(history):
+    """The set of gap lengths g >= 1: runs of g sweeps in which a tile is not swept, between two sweeps in which it is."""
+    return {g for _, _, g in idle_runs(history)}
 
 
 # ---- the cases the tests and tools/gen_redistance_accuracy.py share --------------------------------------------------------------
