@@ -965,7 +965,7 @@ public:
     };
     // The static points whose mean distance to their k nearest (2 <= k <= 64, no farther than maxDistance) is at most
     // mu + stdRatio * sigma over the cloud; a point without a neighbour within maxDistance is isolated and never kept.  The kept
-    // points' colours are colors[Indices[i]].
+    // points' colours are colors[Indices[i]].  stdRatio: finite and not negative.
     Inliers RemoveStatisticalOutliers(int k, float stdRatio, float maxDistance = std::numeric_limits<float>::infinity(),
                                       OutlierStats* stats = nullptr) const
     {

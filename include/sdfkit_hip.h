@@ -735,7 +735,9 @@ int sdfk_points_orient_normals_device(const sdfk_points* s, int32_t k, float max
  *    indices, ascending; points_out the kept points, ready for sdfk_points_create[_device].  *n_kept (may be NULL) receives their
  *    number.  stats (may be NULL): [0] kept, [1] removed (not isolated, above thr), [2] isolated, [3..5] the bits of mu, sigma, thr.
  *    Entries of index_out / points_out from n_kept on are left as they were.
- * 4. SDFK_ERR_INVALID: a NULL set; k outside [2, 64]; a std_ratio that is NaN or negative; a NaN or negative max_distance.
+ * 4. SDFK_ERR_INVALID, outputs and stats untouched: a NULL set; k outside [2, 64]; a std_ratio that is NaN, negative or infinite
+ *    (+inf * sigma is a NaN where sigma = 0, and no mean is <= a NaN); a NaN or negative max_distance.  No accepted argument gives
+ *    a NaN in mu, sigma or thr.
  * Host and device forms as above; both have finished when they return.  Temporaries: 12 n bytes. */
 int sdfk_points_voxel_downsample(const sdfk_points* s, float voxel_size, const float origin[3], float* points_out /* n*3 */,
                                  int32_t* counts /* n */, int32_t* group /* n */, int64_t* m);

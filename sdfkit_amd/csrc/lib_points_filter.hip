@@ -357,7 +357,7 @@ int check_outliers(const sdfk_points* s, int32_t k, float std_ratio, float max_d
     if (int r = require_init()) return r;
     if (!s) return fail(SDFK_ERR_INVALID, "%s: null point set", who);
     if (k < 2 || k > kMaxK) return fail(SDFK_ERR_INVALID, "%s: k = %d is outside [2, %d]", who, (int)k, kMaxK);
-    if (!ratio_is_valid(std_ratio)) return fail(SDFK_ERR_INVALID, "%s: std_ratio is negative or NaN", who);
+    if (!ratio_is_valid(std_ratio)) return fail(SDFK_ERR_INVALID, "%s: std_ratio must be finite and not negative", who);
     if (!radius_is_valid(max_distance)) return fail(SDFK_ERR_INVALID, "%s: max_distance is negative or NaN", who);
     return SDFK_OK;
 }

@@ -88,7 +88,8 @@ SDFK_FILTER_HD int64_t chunks_of(int64_t count) { return (count + kChunk - 1) / 
 SDFK_FILTER_HD double row_mean(double sum_rest, int found) { return found < 2 ? (double)INFINITY : sum_rest / (double)(found - 1); }
 SDFK_FILTER_HD bool is_isolated(double mean) { return !(mean < (double)INFINITY); }
 
-SDFK_FILTER_HD bool ratio_is_valid(float std_ratio) { return std_ratio >= 0.0f; }   // (false for NaN)
+// finite and not negative (false for NaN): +inf times a sigma of 0 would make the threshold a NaN, under which nothing is kept
+SDFK_FILTER_HD bool ratio_is_valid(float std_ratio) { return std_ratio >= 0.0f && std_ratio < INFINITY; }
 
 struct Threshold {
     double mu, sigma, thr;

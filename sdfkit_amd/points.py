@@ -190,7 +190,9 @@ class KdTree:
         distance over the cloud -> (points (kept, 3) float32, indices (kept,) int32 ascending, meanDistance (n,) float32).  A point
         with no neighbour within maxDistance is isolated: its meanDistance is +inf, it takes no part in mu and sigma and is never
         kept.  Per-point data of the kept points, colours for one, is colors[indices].  The tree is not changed: make a new KdTree
-        from the result.  stats: a dict that receives kept, removed, isolated,
+        from the result.  stdRatio must be finite and not negative: 0 keeps what is at most the mean, a large finite one keeps
+        everything that is not isolated; an infinite one is refused like a NaN (infinity times a sigma of 0 is no number).
+        stats: a dict that receives kept, removed, isolated,
         mu, sigma, threshold (include/sdfkit_hip.h, "Point clouds: filters")."""
         n = self.TotalPoints
         pts = np.empty((n, 3), f32)

@@ -207,8 +207,8 @@ namespace SdfKit
         {
             if (k < 2 || k > 64)
                 throw new ArgumentOutOfRangeException (nameof (k), "k must be in 2..64");
-            if (!(stdRatio >= 0))
-                throw new ArgumentOutOfRangeException (nameof (stdRatio), "stdRatio must not be negative");
+            if (!(stdRatio >= 0 && stdRatio < float.PositiveInfinity))
+                throw new ArgumentOutOfRangeException (nameof (stdRatio), "stdRatio must be finite and not negative");
             int n = TotalPoints;
             var points = new Vector3[n];
             var idx = new int[n];

@@ -8,6 +8,8 @@
 //                                   OUT: f32 3 per case: the centroid
 //   points_filter_host thr IN OUT   IN: f64 cases, per case: sum, sqsum, c, std_ratio, sum_rest, found
 //                                   OUT: f64 5 per case: mu, sigma, thr, mean, kept (mu from a first call with sqsum = 0, as the kernels)
+//   points_filter_host ratio IN OUT IN: f32 ratios
+//                                   OUT: i64 per ratio: 1 accepted, 0 refused (ratio_is_valid, what sdfk_points_outliers asks first)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -103,6 +105,11 @@ int main(int argc, char** argv)
             out.insert(out.end(), {T.mu, T.sigma, T.thr, mean, is_kept(mean, T.thr) ? 1.0 : 0.0});
             if (threshold_of(v[0], 0.0, v[2], 0.0f).mu != T.mu && T.mu == T.mu) return 3;   // (the mean does not depend on the second sum)
         }
+        write_all(argv[3], out);
+    } else if (!strcmp(mode, "ratio")) {
+        const auto in = read_all<float>(argv[2]);
+        std::vector<int64_t> out;
+        for (float r : in) out.push_back(ratio_is_valid(r) ? 1 : 0);
         write_all(argv[3], out);
     } else
         return 2;

@@ -149,8 +149,9 @@ def outliers(P, k, std_ratio, max_distance=np.inf, knn=None):
     k = int(k)
     if not 2 <= k <= 64:
         raise Refused("k")
-    if not f32(std_ratio) >= 0:
-        raise Refused("std_ratio")
+    with np.errstate(over="ignore"):                              # (a double beyond FLT_MAX is +inf as the float argument)
+        if not 0 <= f32(std_ratio) < np.inf:                      # finite and not negative (NaN fails both)
+            raise Refused("std_ratio")
     if not f32(max_distance) >= 0:
         raise Refused("max_distance")
     mean = row_means(P, k, max_distance, knn)

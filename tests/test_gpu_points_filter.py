@@ -46,9 +46,11 @@ def downsample_device(tree, size, origin=(0, 0, 0)):
     return pts[:m.value], cnt[:m.value], grp
 
 
-def check_downsample(P, size, origin=(0, 0, 0), device=True):
+def check_downsample(P, size, origin=(0, 0, 0), device=True, tree=None):
+    """tree: a tree that holds P already (one grown with AddPoints, for one); else one is made from P."""
     want = FM.voxel_downsample(P, size, origin)
-    tree = KdTree(P)
+    tree = tree or KdTree(P)
+    assert tree.TotalPoints == len(P)
     forms = [tree.VoxelDownsample(size, origin)] + ([downsample_device(tree, size, origin)] if device else [])
     for got in forms:
         assert len(got[0]) == len(want[0])                                   # m
@@ -170,9 +172,11 @@ def outliers_host(tree, k, ratio, maxd):
     return {"mean_distance": mean, "keep": keep, "index": idx[:kept.value], "points": pts[:kept.value], "stats": np.array(list(st), np.int64)}
 
 
-def check_outliers(P, k, ratio, maxd=INF, knn=None):
+def check_outliers(P, k, ratio, maxd=INF, knn=None, tree=None):
+    """tree: a tree that holds P already; else one is made from P."""
     want = FM.outliers(P, k, ratio, maxd, knn)
-    tree = KdTree(P)
+    tree = tree or KdTree(P)
+    assert tree.TotalPoints == len(P)
     for got in (outliers_host(tree, k, ratio, maxd), outliers_device(tree, k, ratio, maxd)):
         assert np.array_equal(bits(got["mean_distance"]), bits(want["mean_distance"]))
         assert np.array_equal(got["stats"], want["stats"]), (got["stats"], want["stats"])
@@ -252,6 +256,33 @@ def test_outliers_refusals(gpu):
         with pytest.raises(N.SdfKitNativeError) as e:
             tree.RemoveStatisticalOutliers(k, ratio, maxd)
         assert e.value.status == N.ERR_INVALID
+    # an infinite ratio: inf * sigma is a NaN where sigma == 0.  Refused by both entry points and the member, everything left as it was
+    import torch
+    n = tree.TotalPoints
+    with pytest.raises(N.SdfKitNativeError) as e:
+        tree.RemoveStatisticalOutliers(8, INF)
+    assert e.value.status == N.ERR_INVALID
+    mean, keep = np.full(n, -7, f32), np.full(n, 7, np.uint8)
+    idx, pts = np.full(n, -7, np.int32), np.full((n, 3), -7, f32)
+    kept = C.c_int64(-7)
+    st = (C.c_int64 * 6)(*[-7] * 6)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    assert N.lib().sdfk_points_outliers(tree.handle, 8, float(INF), float(INF), p(mean), p(keep), p(idx), p(pts), C.byref(kept), st) == N.ERR_INVALID
+    assert (mean == -7).all() and (keep == 7).all() and (idx == -7).all() and (pts == -7).all() and kept.value == -7 and list(st) == [-7] * 6
+    N.bind_torch_stream()
+    try:
+        dev = torch.device("cuda:0")
+        dm, dk = torch.full((n,), -7.0, dtype=torch.float32, device=dev), torch.full((n,), 7, dtype=torch.uint8, device=dev)
+        di, dp = torch.full((n,), -7, dtype=torch.int32, device=dev), torch.full((n, 3), -7.0, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        d = lambda t: C.c_void_p(t.data_ptr())
+        assert N.lib().sdfk_points_outliers_device(tree.handle, 8, float(INF), float(INF), d(dm), d(dk), d(di), d(dp), C.byref(kept), st) == N.ERR_INVALID
+        N.check(N.lib().sdfk_synchronize())
+        torch.cuda.synchronize()
+        assert (dm == -7).all() and (dk == 7).all() and (di == -7).all() and (dp == -7).all() and kept.value == -7 and list(st) == [-7] * 6
+    finally:
+        N.check(N.lib().sdfk_set_stream(None))
+    assert tree.RemoveStatisticalOutliers(8, 3e38)[1].tolist() == list(range(n))      # the largest ratios are accepted: nothing goes
 
 
 # ---- what the filters are for ----

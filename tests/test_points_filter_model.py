@@ -171,9 +171,23 @@ def test_outlier_model_edge_cases():
     # c = 0
     out = FM.outliers(P[2:], 2, 1.0, 0.5)
     assert list(out["stats"]) == [0, 0, 2, 0, 0, 0] and not out["keep"].any()
-    for bad in ((1, 1.0, np.inf), (65, 1.0, np.inf), (8, -1.0, np.inf), (8, np.nan, np.inf), (8, 1.0, -1.0), (8, 1.0, np.nan)):
+    for bad in ((1, 1.0, np.inf), (65, 1.0, np.inf), (8, -1.0, np.inf), (8, np.nan, np.inf), (8, np.inf, np.inf), (8, 1e39, np.inf),
+                (8, 1.0, -1.0), (8, 1.0, np.nan)):                       # (1e39 rounds to +inf in f32, the type of the argument)
         with pytest.raises(FM.Refused):
             FM.outliers(P, *bad)
+
+
+def test_an_infinite_ratio_would_keep_nothing_where_sigma_is_zero():
+    """Why +inf is refused: with every mean equal, sigma == 0 and thr = mu + inf * 0 is a NaN, under which no point is kept; every
+    finite ratio keeps every point of such a cloud."""
+    P = np.tile(np.array([[0.25, 0.5, 0.75]], f32), (40, 1))
+    mean = FM.row_means(P, 8)
+    with np.errstate(all="ignore"):
+        mu, sigma, thr, c = FM.threshold(mean, np.inf)
+    assert c == 40 and sigma == 0 and np.isnan(thr) and not (mean <= thr).any()
+    for ratio in (0.0, 1.0, 3e38):
+        out = FM.outliers(P, 8, ratio)
+        assert list(out["stats"][:3]) == [40, 0, 0] and not np.isnan(out["thr"])
 
 
 # ---- points_filter.h, built for the host ----
@@ -269,6 +283,21 @@ def test_host_threshold_and_keep_rule_equal_the_model(host):
     out = host("thr", data, f64).reshape(-1, 5)
     assert np.array_equal(out.view(np.uint64), np.array(want, f64).view(np.uint64))
     assert (out[:, 4] == 1).any() and (out[:, 4] == 0).any() and np.isinf(out[:, 3]).any()
+
+
+def test_host_ratio_refusal_equals_the_model(host):
+    """ratio_is_valid: finite and not negative.  Both zeros, the least subnormal and FLT_MAX pass; NaN of either sign, a negative
+    number and both infinities do not -- and the model refuses exactly those."""
+    ratios = np.array([0.0, -0.0, 1e-45, 0.1, 2.0, 3e38, np.finfo(f32).max, np.inf, -np.inf, np.nan, -np.nan, -1e-45, -1.0], f32)
+    want = [1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0]
+    assert list(host("ratio", ratios, np.int64)) == want
+    P = np.array([[0, 0, 0], [1, 0, 0], [0, 2, 0]], f32)
+    for r, ok in zip(ratios, want):
+        if ok:
+            FM.outliers(P, 2, r)
+        else:
+            with pytest.raises(FM.Refused):
+                FM.outliers(P, 2, r)
 
 
 # ---- the C ABI ----
