@@ -2,7 +2,7 @@
 // region growing over the k-nearest graph, confident edges first.  Contract: include/sdfkit_hip.h, "Point clouds: a consistent
 // orientation"; the decisions (validity, dot, the seed's order and sign, one point's choice from its row, the level rule):
 // points_orient.h, checked on the host; the walk, the tiers and the bounded lists: points_walk.h / points_knn.h, shared with every
-// query of the KdTree; the reads of the control block: points_set.h read_back.
+// query of the KdTree; the reads of the control block: device_stage.h read_back.
 //
 //   k_or_rows<CAP>   one lane per static point: its k nearest exactly as k_pts_knn<CAP> finds them (the same tiers), written once
 //                    for the call as SLOT-MAJOR rows (slot * n + point; -1 from the count on): in a round lane i reads slot s of

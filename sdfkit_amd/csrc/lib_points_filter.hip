@@ -415,14 +415,6 @@ int outliers(const sdfk_points* s, int k, float std_ratio, float max_distance, f
     return SDFK_OK;
 }
 
-// the first `count` values of a device array into the caller's (nothing when either is null)
-template <class T>
-hipError_t copy_out(T* host, const T* dev, size_t count)
-{
-    if (!host || !dev || !count) return hipSuccess;
-    return hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, g.stream);
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------------

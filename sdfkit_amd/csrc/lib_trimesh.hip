@@ -15,7 +15,9 @@
 // Sample (sdfk_trimesh_sample; arithmetic: trimesh_sample.h): the first call makes the integer weights of the triangles (area over
 // the largest area, in units of 2^-32) and their exclusive 64-bit scan W, kept on the handle; every call runs one lane per sample:
 // three stateless draws, a binary search over W, one TriPack gather, the stores.
-// The handle (struct sdfk_trimesh, TriPack) is in trimesh_handle.h, shared with lib_trimesh_topology.hip, which reads W as well.
+// The handle (struct sdfk_trimesh, TriPack) is in trimesh_handle.h, shared with lib_trimesh_topology.hip, which reads W as well, with
+// lib_trimesh_smooth.hip and lib_trimesh_weld.hip; trimesh_check, the check of a handle that all four begin with, is defined here.
+// Host side: every work function holds its scratch, and every host form its device copies, in a Staged (device_stage.h).
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "points_grid.h"
@@ -32,8 +34,6 @@ using namespace sdfk_trimesh_sdf;
 namespace smp = sdfk_trimesh_smp;
 
 constexpr int kBlock = 256;
-
-unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, int64_t(1) << 30)); }
 
 // ---- build ------------------------------------------------------------------------------------------------------------------
 // flags[0]: indices out of range, flags[1]: non-finite vertex coordinates
@@ -517,41 +517,40 @@ int trimesh_weights(sdfk_trimesh* t, const char* who)
     if (t->sample_W) return SDFK_OK;
     const int64_t nt = t->nt;
     const unsigned bb = (unsigned)std::min<int64_t>(kAreaParts, (nt + kBlock - 1) / kBlock);
-    unsigned long long* W = nullptr;
-    double* a2 = nullptr;
-    double* part = nullptr;
-    unsigned long long* nonzero = nullptr;
-    int r = dev_alloc((void**)&W, (size_t)(nt + 1) * sizeof(unsigned long long));
-    if (!r) r = dev_alloc((void**)&a2, (size_t)nt * sizeof(double));
-    if (!r) r = dev_alloc((void**)&part, (size_t)(kAreaParts + 1) * sizeof(double));
-    if (!r) r = dev_alloc((void**)&nonzero, sizeof(unsigned long long));
-    hipError_t e = hipSuccess;
+    Staged st;
+    unsigned long long* W = st.kept<unsigned long long>((size_t)nt + 1);
+    double* a2 = st.scratch<double>((size_t)nt);
+    double* part = st.scratch<double>(kAreaParts + 1);
+    unsigned long long* nonzero = st.scratch<unsigned long long>(1);
     struct { double a2max; unsigned long long nonzero, total; } host{};
-    if (!r) {
-        e = hipMemsetAsync(nonzero, 0, sizeof(unsigned long long), g.stream);
-        if (e == hipSuccess) {
-            {
-                ProfScope ps("k_tm_area2");
-                hipLaunchKernelGGL(k_tm_area2, dim3(bb), dim3(kBlock), 0, g.stream, t->tri, nt, a2, part, 0);
-                hipLaunchKernelGGL(k_tm_area2, dim3(1), dim3(kBlock), 0, g.stream, t->tri, (int64_t)bb, a2, part, 1);
-            }
-            ProfScope ps("k_tm_sample_weights");
-            hipLaunchKernelGGL(k_tm_sample_weights, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, a2, nt, part + kAreaParts, W, nonzero);
-            e = hipGetLastError();
+    st.run([&] { return hipMemsetAsync(nonzero, 0, sizeof(unsigned long long), g.stream); });
+    st.run([&] {
+        {
+            ProfScope ps("k_tm_area2");
+            hipLaunchKernelGGL(k_tm_area2, dim3(bb), dim3(kBlock), 0, g.stream, t->tri, nt, a2, part, 0);
+            hipLaunchKernelGGL(k_tm_area2, dim3(1), dim3(kBlock), 0, g.stream, t->tri, (int64_t)bb, a2, part, 1);
         }
-        if (e == hipSuccess) r = sdfk_scan::scan(W, nt, who);
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.a2max, part + kAreaParts, sizeof(double), hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.nonzero, nonzero, sizeof(unsigned long long), hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&host.total, W + nt, sizeof(unsigned long long), hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    }
-    dev_free(a2); dev_free(part); dev_free(nonzero);
-    if (!r && e != hipSuccess) r = fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    if (r) { dev_free(W); return r; }
+        ProfScope ps("k_tm_sample_weights");
+        hipLaunchKernelGGL(k_tm_sample_weights, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, a2, nt, part + kAreaParts, W, nonzero);
+    });
+    st.run([&] { return sdfk_scan::scan(W, nt, who); });
+    st.run([&] { return hipMemcpyAsync(&host.a2max, part + kAreaParts, sizeof(double), hipMemcpyDeviceToHost, g.stream); });
+    st.run([&] { return hipMemcpyAsync(&host.nonzero, nonzero, sizeof(unsigned long long), hipMemcpyDeviceToHost, g.stream); });
+    st.read(&host.total, W + nt, sizeof host.total);
+    if (int r = st.finish(who, false)) return r;
     t->sample_W = W;
     t->sample_no_area = !(host.a2max > 0.0);
     t->sample_nonzero = (int64_t)host.nonzero;
     t->sample_total = (int64_t)host.total;
+    return SDFK_OK;
+}
+
+// What every entry point of the family asks of its handle first (trimesh_handle.h).
+int trimesh_check(const sdfk_trimesh* t, const char* who, int records)
+{
+    if (int r = require_init()) return r;
+    if (!t) return fail(SDFK_ERR_INVALID, "%s: null argument", who);
+    if (records && records * t->nt >= (int64_t(1) << 32)) return fail(SDFK_ERR_INVALID, "%s: 2^32 / %d triangles or more", who, records);
     return SDFK_OK;
 }
 
@@ -575,77 +574,58 @@ int trimesh_build(sdfk_trimesh* t)
 {
     static const char* who = "sdfk_trimesh_create";
     const int64_t nt = t->nt;
-    int r = dev_alloc((void**)&t->tri, (size_t)nt * sizeof(TriPack));
-    unsigned* flags = nullptr;
-    float* part = nullptr;
     const unsigned bb = (unsigned)std::min<int64_t>(1024, (nt + kBlock - 1) / kBlock);
-    if (!r) r = dev_alloc((void**)&flags, 4 * sizeof(unsigned));
-    if (!r) r = dev_alloc((void**)&part, (size_t)(1024 + 1) * 8 * sizeof(float));
-    hipError_t e = hipSuccess;
     struct { unsigned flags[4]; float box[8]; } host{};
-    if (!r) {
+    // (tri, starts, list and ystarts are the handle's from the start: trimesh_make releases them with it when this fails)
+    Staged st;
+    st.run([&] { return dev_alloc((void**)&t->tri, (size_t)nt * sizeof(TriPack)); });
+    unsigned* flags = st.scratch<unsigned>(4);
+    float* part = st.scratch<float>((1024 + 1) * 8);
+    {
         ProfScope ps("k_tm_pack");
-        e = hipMemsetAsync(flags, 0, 4 * sizeof(unsigned), g.stream);
-        if (e == hipSuccess) {
+        st.run([&] { return hipMemsetAsync(flags, 0, 4 * sizeof(unsigned), g.stream); });
+        st.run([&] {
             hipLaunchKernelGGL(k_tm_vcheck, dim3(grid1(std::min<int64_t>(3 * t->nv, int64_t(1) << 20))), dim3(kBlock), 0, g.stream, t->vertices, t->nv, flags);
             hipLaunchKernelGGL(k_tm_pack, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->vertices, t->nv, t->idx, nt, t->tri, flags);
             hipLaunchKernelGGL(k_tm_bounds, dim3(bb), dim3(kBlock), 0, g.stream, t->tri, nt, part, 0);
             hipLaunchKernelGGL(k_tm_bounds, dim3(1), dim3(kBlock), 0, g.stream, t->tri, (int64_t)bb, part, 1);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(host.flags, flags, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, g.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(host.box, part + 8 * 1024, 6 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+        });
+        st.run([&] { return hipMemcpyAsync(host.flags, flags, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, g.stream); });
+        st.read(host.box, part + 8 * 1024, 6 * sizeof(float));
     }
-    dev_free(flags);
-    dev_free(part);
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (int r = st.finish(who, false)) return r;
     if (host.flags[0]) return fail(SDFK_ERR_INVALID, "%s: a triangle index is outside [0, n_vertices)", who);
     if (host.flags[1]) return fail(SDFK_ERR_INVALID, "%s: a vertex has a NaN or infinite coordinate", who);
 
     t->G = grid_for_box(host.box, host.box + 3, nt);
     t->cells = (int64_t)t->G.dim[0] * t->G.dim[1] * t->G.dim[2];
-    unsigned long long* total = nullptr;
-    uint32_t* cursor = nullptr;
-    r = dev_alloc((void**)&t->starts, (size_t)(t->cells + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&total, sizeof(unsigned long long));
     unsigned long long entries = 0;
-    if (!r) {
+    st.run([&] { return dev_alloc((void**)&t->starts, (size_t)(t->cells + 1) * sizeof(uint32_t)); });
+    unsigned long long* total = st.scratch<unsigned long long>(1);
+    {
         ProfScope ps("k_tm_bin");
-        e = hipMemsetAsync(t->starts, 0, (size_t)(t->cells + 1) * sizeof(uint32_t), g.stream);
-        if (e == hipSuccess) e = hipMemsetAsync(total, 0, sizeof(unsigned long long), g.stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_tm_bin_count, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->tri, nt, t->G, t->starts, total);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&entries, total, sizeof entries, hipMemcpyDeviceToHost, g.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+        st.run([&] { return hipMemsetAsync(t->starts, 0, (size_t)(t->cells + 1) * sizeof(uint32_t), g.stream); });
+        st.run([&] { return hipMemsetAsync(total, 0, sizeof(unsigned long long), g.stream); });
+        st.run([&] { hipLaunchKernelGGL(k_tm_bin_count, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->tri, nt, t->G, t->starts, total); });
+        st.read(&entries, total, sizeof entries);
     }
-    dev_free(total);
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (int r = st.finish(who, false)) return r;
     if (entries >= (1ull << 32)) return fail(SDFK_ERR_INVALID, "%s: 2^32 triangle-cell pairs or more", who);
     t->entries = (int64_t)entries;
-    r = sdfk_scan::scan(t->starts, t->cells, who);
-    if (!r) r = dev_alloc((void**)&t->list, (size_t)std::max<int64_t>(t->entries, 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&cursor, (size_t)t->cells * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&t->ystarts, (size_t)(t->cells + 1) * sizeof(uint32_t));
-    if (!r) {
+    st.run([&] { return sdfk_scan::scan(t->starts, t->cells, who); });
+    st.run([&] { return dev_alloc((void**)&t->list, (size_t)std::max<int64_t>(t->entries, 1) * sizeof(uint32_t)); });
+    uint32_t* cursor = st.scratch<uint32_t>((size_t)t->cells);
+    st.run([&] { return dev_alloc((void**)&t->ystarts, (size_t)(t->cells + 1) * sizeof(uint32_t)); });
+    {
         ProfScope ps("k_tm_bin");
-        e = hipMemcpyAsync(cursor, t->starts, (size_t)t->cells * sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream);
-        if (e == hipSuccess) {
+        st.run([&] { return hipMemcpyAsync(cursor, t->starts, (size_t)t->cells * sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream); });
+        st.run([&] {
             hipLaunchKernelGGL(k_tm_bin_scatter, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->tri, nt, t->G, cursor, t->list);
             hipLaunchKernelGGL(k_tm_ycounts, dim3(grid1(t->cells)), dim3(kBlock), 0, g.stream, t->starts, t->G, t->cells, t->ystarts);
-            e = hipGetLastError();
-        }
+        });
     }
-    if (!r && e == hipSuccess) r = sdfk_scan::scan(t->ystarts, t->cells, who);
-    if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);   // (the cursor goes back to the pool; the caller's arrays are not retained)
-    dev_free(cursor);
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return SDFK_OK;
+    st.run([&] { return sdfk_scan::scan(t->ystarts, t->cells, who); });
+    return st.finish(who);   // (synchronises: the caller's arrays are not retained)
 }
 
 int trimesh_make(const void* v, int64_t nv, const void* tris, int64_t ni, const void* colors, bool device, sdfk_trimesh** out)
@@ -662,6 +642,7 @@ int trimesh_make(const void* v, int64_t nv, const void* tris, int64_t ni, const 
     t->nv = nv;
     t->nt = ni / 3;
     const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    // (written out, not Staged: there is no scratch here -- the three arrays are the handle's at once, and trimesh_release frees them)
     int r = dev_alloc((void**)&t->vertices, (size_t)nv * 3 * sizeof(float));
     if (!r) r = dev_alloc((void**)&t->idx, (size_t)ni * sizeof(int32_t));
     if (!r && colors) r = dev_alloc((void**)&t->colors, (size_t)nv * 3 * sizeof(float));
@@ -683,27 +664,22 @@ int trimesh_make(const void* v, int64_t nv, const void* tris, int64_t ni, const 
 
 int closest_launch(const sdfk_trimesh* t, const float* q, int64_t n, QueryOut O)
 {
-    unsigned long long* cand = nullptr;
+    Staged st;
     if (g.prof_on) {
-        if (int r = dev_alloc((void**)&cand, sizeof(unsigned long long))) return r;
-        if (hipMemsetAsync(cand, 0, sizeof(unsigned long long), g.stream) != hipSuccess) { dev_free(cand); return fail(SDFK_ERR_HIP, "sdfk_trimesh_closest: memset"); }
-        O.candidates = cand;
+        O.candidates = st.scratch<unsigned long long>(1);
+        st.run([&] { return hipMemsetAsync(O.candidates, 0, sizeof(unsigned long long), g.stream); });
     }
-    {
+    st.run([&] {
         ProfScope ps("k_tm_closest");
         hipLaunchKernelGGL(k_tm_closest, dim3(grid1(n)), dim3(kBlock), 0, g.stream, search_grid(t), q, n, O);
-    }
-    hipError_t e = hipGetLastError();
-    if (cand) {
+    });
+    if (g.prof_on) {
         unsigned long long c = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&c, cand, sizeof c, hipMemcpyDeviceToHost, g.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+        st.read(&c, O.candidates, sizeof c);
         const_cast<sdfk_trimesh*>(t)->last_candidates = (int64_t)c;
         const_cast<sdfk_trimesh*>(t)->last_queries = n;
-        dev_free(cand);
     }
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_trimesh_closest: %s", hipGetErrorString(e));
-    return SDFK_OK;
+    return st.finish("sdfk_trimesh_closest", false);
 }
 
 int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band)
@@ -716,69 +692,57 @@ int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band)
     grid_constants(v, d, m, &outside);
     const Columns Q{v->nx, v->ny, m[0], m[1], d[0], d[1]};
     const int64_t nt = t->nt, ncol = (int64_t)v->nx * v->ny;
-    int4* box = nullptr;
-    unsigned long long* items = nullptr;
-    uint32_t* col = nullptr;
-    uint32_t* cursor = nullptr;
+    Staged st;
+    int4* box = st.scratch<int4>((size_t)nt);
+    unsigned long long* items = st.scratch<unsigned long long>((size_t)nt + 1);
+    uint32_t* col = st.scratch<uint32_t>((size_t)ncol + 1);
+    uint32_t* cursor = st.scratch<uint32_t>((size_t)ncol);
     double* zrec = nullptr;
     unsigned long long* cand = nullptr;
     unsigned long long n_items = 0;
     uint32_t n_cross = 0;
-    int r = dev_alloc((void**)&box, (size_t)nt * sizeof(int4));
-    if (!r) r = dev_alloc((void**)&items, (size_t)(nt + 1) * sizeof(unsigned long long));
-    if (!r) r = dev_alloc((void**)&col, (size_t)(ncol + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&cursor, (size_t)ncol * sizeof(uint32_t));
-    hipError_t e = hipSuccess;
     auto grid_items = [](unsigned long long n) { return (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>((n + kBlock - 1) / kBlock, 1u << 20)); };
-    if (!r) {
+    {
         ProfScope ps("k_tm_cross");
-        hipLaunchKernelGGL(k_tm_items, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->tri, nt, Q, box, items);
-        e = hipGetLastError();
-        if (e == hipSuccess) r = sdfk_scan::scan(items, nt, who);
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&n_items, items + nt, sizeof n_items, hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipMemsetAsync(col, 0, (size_t)(ncol + 1) * sizeof(uint32_t), g.stream);
-        if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);
-        if (!r && e == hipSuccess && n_items) {
-            hipLaunchKernelGGL(k_tm_cross<0>, dim3(grid_items(n_items)), dim3(kBlock), 0, g.stream, t->tri, nt, Q, box, items, n_items, col, nullptr);
-            e = hipGetLastError();
-        }
-        if (!r && e == hipSuccess) r = sdfk_scan::scan(col, ncol, who);
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&n_cross, col + ncol, sizeof n_cross, hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);
-        if (!r && e == hipSuccess) r = dev_alloc((void**)&zrec, (size_t)std::max<uint32_t>(n_cross, 1) * sizeof(double));
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(cursor, col, (size_t)ncol * sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream);
-        if (!r && e == hipSuccess && n_cross) {
-            hipLaunchKernelGGL(k_tm_cross<1>, dim3(grid_items(n_items)), dim3(kBlock), 0, g.stream, t->tri, nt, Q, box, items, n_items, cursor, zrec);
-            e = hipGetLastError();
-        }
+        st.run([&] { hipLaunchKernelGGL(k_tm_items, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->tri, nt, Q, box, items); });
+        st.run([&] { return sdfk_scan::scan(items, nt, who); });
+        st.run([&] { return hipMemsetAsync(col, 0, (size_t)(ncol + 1) * sizeof(uint32_t), g.stream); });
+        st.read(&n_items, items + nt, sizeof n_items);
+        if (n_items)
+            st.run([&] {
+                hipLaunchKernelGGL(k_tm_cross<0>, dim3(grid_items(n_items)), dim3(kBlock), 0, g.stream, t->tri, nt, Q, box, items, n_items, col, nullptr);
+            });
+        st.run([&] { return sdfk_scan::scan(col, ncol, who); });
+        st.read(&n_cross, col + ncol, sizeof n_cross);
+        zrec = st.scratch<double>(std::max<uint32_t>(n_cross, 1));
+        st.run([&] { return hipMemcpyAsync(cursor, col, (size_t)ncol * sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream); });
+        if (n_cross)
+            st.run([&] {
+                hipLaunchKernelGGL(k_tm_cross<1>, dim3(grid_items(n_items)), dim3(kBlock), 0, g.stream, t->tri, nt, Q, box, items, n_items, cursor, zrec);
+            });
     }
-    if (!r && e == hipSuccess && g.prof_on) {
-        r = dev_alloc((void**)&cand, sizeof(unsigned long long));
-        if (!r) e = hipMemsetAsync(cand, 0, sizeof(unsigned long long), g.stream);
+    if (g.prof_on) {
+        cand = st.scratch<unsigned long long>(1);
+        st.run([&] { return hipMemsetAsync(cand, 0, sizeof(unsigned long long), g.stream); });
     }
     // every d2 whose f32 distance (float)sqrt(d2) is <= band is below next^2 (next: the f32 after band), so the search may stop
     // there: a voxel it leaves unresolved has an f32 distance > band and is clamped, as its exact distance would be
     const double next = (double)nextafterf(band, INFINITY);
     const double stop2 = next * next;
-    if (!r && e == hipSuccess) {
+    st.run([&] {
         VolArgs A{v->values, v->colors, t->colors, t->idx, v->nx, v->ny, v->nz, v->pitch(), v->z0, m[0], m[1], m[2], d[0], d[1], d[2],
                   band, stop2, col, zrec, cand};
         ProfScope ps("k_tm_volume");
         hipLaunchKernelGGL(k_tm_volume, dim3(grid1((int64_t)v->nx * v->ny * v->nz)), dim3(kBlock), 0, g.stream, search_grid(t), A);
-        e = hipGetLastError();
-    }
+    });
     if (cand) {
         unsigned long long c = 0;
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&c, cand, sizeof c, hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);
+        st.read(&c, cand, sizeof c);
         const_cast<sdfk_trimesh*>(t)->last_candidates = (int64_t)c;
         const_cast<sdfk_trimesh*>(t)->last_queries = (int64_t)v->nx * v->ny * v->nz;
     }
     const_cast<sdfk_trimesh*>(t)->last_crossings = n_cross;
-    dev_free(box); dev_free(items); dev_free(col); dev_free(cursor); dev_free(zrec); dev_free(cand);   // (stream-ordered pool)
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return SDFK_OK;
+    return st.finish(who, false);   // (on success the scratch goes back to the stream-ordered pool under the queued volume pass)
 }
 
 // the weights, and the sampler's refusal of a mesh without area
@@ -791,8 +755,7 @@ int sample_prepare(sdfk_trimesh* t, const char* who)
 
 int sample_check(const sdfk_trimesh* t, int64_t n, int32_t flags, const char* who)
 {
-    if (int r = require_init()) return r;
-    if (!t) return fail(SDFK_ERR_INVALID, "%s: null argument", who);
+    if (int r = trimesh_check(t, who, 0)) return r;
     if (n < 0 || n >= (int64_t(1) << 31)) return fail(SDFK_ERR_INVALID, "%s: n must be in [0, 2^31)", who);
     if (flags & ~SDFK_TRIMESH_SAMPLE_STRATIFIED) return fail(SDFK_ERR_INVALID, "%s: unknown flag bits", who);
     return SDFK_OK;
@@ -858,25 +821,11 @@ extern "C" int sdfk_trimesh_closest(const sdfk_trimesh* t, const float* queries3
     if (!t || n < 0 || (n > 0 && !queries3)) return fail(SDFK_ERR_INVALID, "sdfk_trimesh_closest: null / negative argument");
     if (n >= (int64_t(1) << 32)) return fail(SDFK_ERR_INVALID, "sdfk_trimesh_closest: 2^32 queries or more");
     if (n == 0) return SDFK_OK;
-    float* qd = nullptr;
-    int32_t* id = nullptr;
-    float* dd = nullptr;
-    float* cd = nullptr;
-    int r = dev_alloc((void**)&qd, (size_t)n * 3 * sizeof(float));
-    if (!r && triangle) r = dev_alloc((void**)&id, (size_t)n * sizeof(int32_t));
-    if (!r && distance) r = dev_alloc((void**)&dd, (size_t)n * sizeof(float));
-    if (!r && closest3) r = dev_alloc((void**)&cd, (size_t)n * 3 * sizeof(float));
-    hipError_t e = hipSuccess;
-    if (!r) e = hipMemcpyAsync(qd, queries3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) r = closest_launch(t, qd, n, QueryOut{id, dd, cd, nullptr});
-    if (!r && e == hipSuccess && id) e = hipMemcpyAsync(triangle, id, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && dd) e = hipMemcpyAsync(distance, dd, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && cd) e = hipMemcpyAsync(closest3, cd, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(qd); dev_free(id); dev_free(dd); dev_free(cd);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_trimesh_closest: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    Staged st;
+    const float* qd = st.in(queries3, (size_t)n * 3);
+    const QueryOut O{st.out(triangle, (size_t)n), st.out(distance, (size_t)n), st.out(closest3, (size_t)n * 3), nullptr};
+    st.run([&] { return closest_launch(t, qd, n, O); });
+    return st.finish("sdfk_trimesh_closest");
 }
 
 extern "C" int sdfk_trimesh_to_volume(const sdfk_trimesh* t, sdfk_volume* v, float max_distance)
@@ -913,30 +862,15 @@ extern "C" int sdfk_trimesh_sample(sdfk_trimesh* t, int64_t n, uint64_t seed, in
     if (n == 0) return SDFK_OK;
     if (int r = sample_prepare(t, who)) return r;
     sample_stats(t, stats);
-    float* pd = nullptr;
-    float* nd = nullptr;
-    float* cd = nullptr;
-    int32_t* td = nullptr;
-    float* wd = nullptr;
-    const size_t n3 = (size_t)n * 3 * sizeof(float);
-    int r = SDFK_OK;
-    if (points3) r = dev_alloc((void**)&pd, n3);
-    if (!r && normals3) r = dev_alloc((void**)&nd, n3);
-    if (!r && colors3) r = dev_alloc((void**)&cd, n3);
-    if (!r && triangle) r = dev_alloc((void**)&td, (size_t)n * sizeof(int32_t));
-    if (!r && weights3) r = dev_alloc((void**)&wd, n3);
-    hipError_t e = hipSuccess;
-    if (!r) r = sample_launch(t, n, seed, flags, pd, nd, cd, td, wd, who);
-    if (!r && pd) e = hipMemcpyAsync(points3, pd, n3, hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && nd) e = hipMemcpyAsync(normals3, nd, n3, hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && cd) e = hipMemcpyAsync(colors3, cd, n3, hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && td) e = hipMemcpyAsync(triangle, td, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess && wd) e = hipMemcpyAsync(weights3, wd, n3, hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(pd); dev_free(nd); dev_free(cd); dev_free(td); dev_free(wd);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    const size_t n3 = (size_t)n * 3;
+    Staged st;
+    float* pd = st.out(points3, n3);
+    float* nd = st.out(normals3, n3);
+    float* cd = st.out(colors3, n3);
+    int32_t* td = st.out(triangle, (size_t)n);
+    float* wd = st.out(weights3, n3);
+    st.run([&] { return sample_launch(t, n, seed, flags, pd, nd, cd, td, wd, who); });
+    return st.finish(who);
 }
 
 extern "C" int sdfk_trimesh_stats(const sdfk_trimesh* t, int64_t stats[8])

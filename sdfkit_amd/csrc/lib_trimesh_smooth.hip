@@ -19,10 +19,11 @@
 // Smoothing: k_tv_step, one lane per vertex, one launch per step, ping-pong between the output and one temporary so that the
 // last step writes the output; nothing waits on the host between the launches.
 // Normals: k_tv_normals, one lane per vertex over its corners; the triangles' positions are gathered through the index array.
+// Host side: scratch, the adopted structures and the host forms' device copies are held in a Staged (device_stage.h); the handle
+// check (trimesh_check) and the launch size (grid1) are trimesh_handle.h's.
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "device_sort.h"
-#include "points_set.h"   // read_back
 #include "trimesh_adjacency.h"
 #include "trimesh_handle.h"
 
@@ -33,8 +34,6 @@ namespace {
 using namespace sdfk_trimesh_adj;
 
 constexpr int kBlock = 256;
-
-unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock); }
 
 // ---- the records ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_ta_nbr_keys(const int32_t* __restrict__ idx, int64_t nt, int64_t nv, Rec* __restrict__ rec)
@@ -131,72 +130,55 @@ __global__ __launch_bounds__(kBlock) void k_tv_normals(const float* __restrict__
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-int check_handle(const sdfk_trimesh* t, const char* who)
-{
-    if (int r = require_init()) return r;
-    if (!t) return fail(SDFK_ERR_INVALID, "%s: null argument", who);
-    if (too_many_triangles(t->nt)) return fail(SDFK_ERR_INVALID, "%s: 2^32 / 6 triangles or more", who);
-    return SDFK_OK;
-}
-
 // One of the two structures, once per handle: synchronises (the number of entries sizes the list).
 int csr_prepare(sdfk_trimesh* t, bool corners, const char* who)
 {
     if (corners ? t->inc_start != nullptr : t->nbr_start != nullptr) return SDFK_OK;
     const int64_t nv = t->nv, nt = t->nt, n = (corners ? 3 : 6) * nt;
-    Rec* ra = nullptr;
-    Rec* rb = nullptr;
+    Staged st;
+    Rec* ra = st.scratch<Rec>((size_t)n);
+    Rec* rb = st.scratch<Rec>((size_t)n);
     Rec* sorted = nullptr;
-    uint32_t* head = nullptr;      // (neighbours) the head flags, scanned: the place of every entry
-    uint32_t* begin = nullptr;     // the first place of every vertex that has a record
-    uint32_t* start = nullptr;     // kept: degrees, scanned
-    uint32_t* list = nullptr;      // kept
-    uint8_t* boundary = nullptr;   // kept (neighbours)
+    uint32_t* head = corners ? nullptr : st.scratch<uint32_t>((size_t)n + 1);   // (neighbours) the head flags, scanned: the place of every entry
+    uint32_t* begin = st.scratch<uint32_t>((size_t)nv);                        // the first place of every vertex that has a record
+    uint32_t* start = st.kept<uint32_t>((size_t)nv + 1);                       // for the handle: degrees, scanned
+    uint8_t* boundary = corners ? nullptr : st.kept<uint8_t>((size_t)nv);      // for the handle (neighbours)
     uint32_t entries = 0, total = 0;
     int64_t capacity = 3 * nt;
-    int r = dev_alloc((void**)&ra, (size_t)n * sizeof(Rec));
-    if (!r) r = dev_alloc((void**)&rb, (size_t)n * sizeof(Rec));
-    if (!r && !corners) r = dev_alloc((void**)&head, (size_t)(n + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&begin, (size_t)nv * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&start, (size_t)(nv + 1) * sizeof(uint32_t));
-    if (!r && !corners) r = dev_alloc((void**)&boundary, (size_t)nv);
-    hipError_t e = hipSuccess;
-    if (!r) {
+    st.run([&] {
         ProfScope ps(corners ? "k_ta_corner_keys" : "k_ta_nbr_keys");
         if (corners) hipLaunchKernelGGL(k_ta_corner_keys, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->idx, nt, nv, ra);
         else hipLaunchKernelGGL(k_ta_nbr_keys, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->idx, nt, nv, ra);
-        e = hipGetLastError();
-    }
-    if (!r && e == hipSuccess) r = radix_sort(ra, rb, n, corners ? corner_digit_mask(nv) : nbr_digit_mask(nv), &sorted, who);
-    if (!r && e == hipSuccess && !corners) {
+    });
+    st.run([&] { return radix_sort(ra, rb, n, corners ? corner_digit_mask(nv) : nbr_digit_mask(nv), &sorted, who); });
+    if (!corners) {
         ProfScope ps("k_ta_heads");
-        hipLaunchKernelGGL(k_ta_heads, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, nv, head);
-        e = hipGetLastError();
-        if (e == hipSuccess) r = sdfk_scan::scan(head, n, who);
-        if (!r && e == hipSuccess) e = read_back(&entries, head + n, sizeof entries);
+        st.run([&] { hipLaunchKernelGGL(k_ta_heads, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, nv, head); });
+        st.run([&] { return sdfk_scan::scan(head, n, who); });
+        st.read(&entries, head + n, sizeof entries);
         capacity = std::max<int64_t>((int64_t)entries, 1);
     }
-    if (!r && e == hipSuccess) r = dev_alloc((void**)&list, (size_t)capacity * sizeof(uint32_t));
-    if (!r && e == hipSuccess) e = hipMemsetAsync(start, 0, (size_t)(nv + 1) * sizeof(uint32_t), g.stream);
-    if (!r && e == hipSuccess && boundary) e = hipMemsetAsync(boundary, 0, (size_t)nv, g.stream);
-    if (!r && e == hipSuccess) {
+    uint32_t* list = st.kept<uint32_t>((size_t)capacity);   // for the handle
+    st.run([&] { return hipMemsetAsync(start, 0, (size_t)(nv + 1) * sizeof(uint32_t), g.stream); });
+    if (boundary) st.run([&] { return hipMemsetAsync(boundary, 0, (size_t)nv, g.stream); });
+    {
         ProfScope ps("k_ta_entries");
-        if (corners) {
-            hipLaunchKernelGGL(k_ta_entries<0>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, nv, nullptr, begin, list, capacity, nullptr);
-            hipLaunchKernelGGL(k_ta_degree<0>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, nv, nullptr, begin, start);
-        } else {
-            hipLaunchKernelGGL(k_ta_entries<32>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, nv, head, begin, list, capacity, boundary);
-            hipLaunchKernelGGL(k_ta_degree<32>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, nv, head, begin, start);
-        }
-        e = hipGetLastError();
-        if (e == hipSuccess) r = sdfk_scan::scan(start, nv, who);
-        if (!r && e == hipSuccess) e = read_back(&total, start + nv, sizeof total);
+        st.run([&] {
+            if (corners) {
+                hipLaunchKernelGGL(k_ta_entries<0>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, nv, nullptr, begin, list, capacity, nullptr);
+                hipLaunchKernelGGL(k_ta_degree<0>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, nv, nullptr, begin, start);
+            } else {
+                hipLaunchKernelGGL(k_ta_entries<32>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, nv, head, begin, list, capacity, boundary);
+                hipLaunchKernelGGL(k_ta_degree<32>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, nv, head, begin, start);
+            }
+        });
+        st.run([&] { return sdfk_scan::scan(start, nv, who); });
+        st.read(&total, start + nv, sizeof total);
     }
-    if (r || e != hipSuccess) (void)hipStreamSynchronize(g.stream);   // (nothing is freed under a queued kernel's feet)
-    dev_free(ra); dev_free(rb); dev_free(head); dev_free(begin);
-    if (!r && e != hipSuccess) r = fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    if (!r && (int64_t)total > capacity) r = fail(SDFK_ERR_INVALID, "%s: the degrees do not add up to the entries", who);   // (no input reaches this)
-    if (r) { dev_free(start); dev_free(list); dev_free(boundary); return r; }
+    st.run([&] {   // (no input reaches this)
+        return (int64_t)total > capacity ? fail(SDFK_ERR_INVALID, "%s: the degrees do not add up to the entries", who) : (int)SDFK_OK;
+    });
+    if (int r = st.finish(who, false)) return r;   // (the read above has waited; start, list and boundary are the handle's from here)
     if (corners) {
         t->inc_start = start; t->inc = list; t->inc_entries = (int64_t)total;
     } else {
@@ -207,7 +189,7 @@ int csr_prepare(sdfk_trimesh* t, bool corners, const char* who)
 
 int smooth_check(const sdfk_trimesh* t, int32_t iterations, float lambda, float mu, int32_t flags, const void* out, const char* who)
 {
-    if (int r = check_handle(t, who)) return r;
+    if (int r = trimesh_check(t, who, 6)) return r;
     if (!out) return fail(SDFK_ERR_INVALID, "%s: null output", who);
     if (iterations < 0 || iterations > 65536) return fail(SDFK_ERR_INVALID, "%s: iterations must be in [0, 65536]", who);
     if (!std::isfinite(lambda) || !std::isfinite(mu)) return fail(SDFK_ERR_INVALID, "%s: lambda and mu must be finite", who);
@@ -226,11 +208,10 @@ int smooth(sdfk_trimesh* t, int32_t iterations, float lambda, float mu, int32_t 
         return SDFK_OK;
     }
     if (int r = csr_prepare(t, false, who)) return r;
-    float* tmp = nullptr;
-    if (steps >= 2)
-        if (int r = dev_alloc((void**)&tmp, (size_t)nv * 3 * sizeof(float))) return r;
+    Staged st;
+    float* tmp = steps >= 2 ? st.scratch<float>((size_t)nv * 3) : nullptr;
     const uint8_t* pin = (flags & SDFK_TRIMESH_SMOOTH_PIN_BOUNDARY) ? t->boundary : nullptr;
-    {
+    st.run([&] {
         ProfScope ps("k_tv_step");
         const float* src = t->vertices;
         for (int64_t i = 0; i < steps; i++) {
@@ -239,16 +220,13 @@ int smooth(sdfk_trimesh* t, int32_t iterations, float lambda, float mu, int32_t 
                                smooth_factor(i, lambda, mu), dst);
             src = dst;
         }
-        e = hipGetLastError();
-    }
-    dev_free(tmp);   // (stream-ordered pool)
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return SDFK_OK;
+    });
+    return st.finish(who, false);   // (the temporary goes back to the stream-ordered pool under the queued steps)
 }
 
 int normals_check(const sdfk_trimesh* t, int32_t flags, const void* out, const char* who)
 {
-    if (int r = check_handle(t, who)) return r;
+    if (int r = trimesh_check(t, who, 6)) return r;
     if (!out) return fail(SDFK_ERR_INVALID, "%s: null output", who);
     if (flags & ~SDFK_TRIMESH_NORMALS_FLIP) return fail(SDFK_ERR_INVALID, "%s: unknown flag bits", who);
     return SDFK_OK;
@@ -270,15 +248,14 @@ int normals(sdfk_trimesh* t, const float* positions, int32_t flags, float* out, 
 
 int adjacency_out(sdfk_trimesh* t, void* nbr_start, void* nbr, void* boundary, int64_t* n_entries, bool device, const char* who)
 {
-    if (int r = check_handle(t, who)) return r;
+    if (int r = trimesh_check(t, who, 6)) return r;
     if (int r = csr_prepare(t, false, who)) return r;
     const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    hipError_t e = hipSuccess;
-    if (nbr_start) e = hipMemcpyAsync(nbr_start, t->nbr_start, (size_t)(t->nv + 1) * sizeof(uint32_t), kind, g.stream);
-    if (e == hipSuccess && nbr && t->nbr_entries) e = hipMemcpyAsync(nbr, t->nbr, (size_t)t->nbr_entries * sizeof(uint32_t), kind, g.stream);
-    if (e == hipSuccess && boundary) e = hipMemcpyAsync(boundary, t->boundary, (size_t)t->nv, kind, g.stream);
-    const hipError_t es = device ? hipSuccess : hipStreamSynchronize(g.stream);
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
+    Staged st;   // (no device copies: the adjacency is the handle's, and goes straight into the caller's arrays)
+    if (nbr_start) st.run([&] { return hipMemcpyAsync(nbr_start, t->nbr_start, (size_t)(t->nv + 1) * sizeof(uint32_t), kind, g.stream); });
+    if (nbr && t->nbr_entries) st.run([&] { return hipMemcpyAsync(nbr, t->nbr, (size_t)t->nbr_entries * sizeof(uint32_t), kind, g.stream); });
+    if (boundary) st.run([&] { return hipMemcpyAsync(boundary, t->boundary, (size_t)t->nv, kind, g.stream); });
+    if (int r = st.finish(who, !device)) return r;   // (the device form waits for nothing)
     if (n_entries) *n_entries = t->nbr_entries;
     return SDFK_OK;
 }
@@ -317,17 +294,10 @@ extern "C" int sdfk_trimesh_smooth(sdfk_trimesh* t, int32_t iterations, float la
     StateScope in_owner_context(t ? t->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (int r = smooth_check(t, iterations, lambda, mu, flags, vertices3_out, who)) return r;
-    const size_t bytes = (size_t)t->nv * 3 * sizeof(float);
-    float* od = nullptr;
-    int r = dev_alloc((void**)&od, bytes);
-    hipError_t e = hipSuccess;
-    if (!r) r = smooth(t, iterations, lambda, mu, flags, od, who);
-    if (!r) e = hipMemcpyAsync(vertices3_out, od, bytes, hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(od);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    Staged st;
+    float* od = st.out(vertices3_out, (size_t)t->nv * 3);
+    st.run([&] { return smooth(t, iterations, lambda, mu, flags, od, who); });
+    return st.finish(who);
 }
 
 extern "C" int sdfk_trimesh_vertex_normals_device(sdfk_trimesh* t, const void* positions3_dev, int32_t flags, void* normals3_out_dev)
@@ -345,18 +315,9 @@ extern "C" int sdfk_trimesh_vertex_normals(sdfk_trimesh* t, const float* positio
     StateScope in_owner_context(t ? t->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (int r = normals_check(t, flags, normals3_out, who)) return r;
-    const size_t bytes = (size_t)t->nv * 3 * sizeof(float);
-    float* pd = nullptr;
-    float* od = nullptr;
-    int r = dev_alloc((void**)&od, bytes);
-    if (!r && positions3) r = dev_alloc((void**)&pd, bytes);
-    hipError_t e = hipSuccess;
-    if (!r && pd) e = hipMemcpyAsync(pd, positions3, bytes, hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) r = normals(t, pd, flags, od, who);
-    if (!r && e == hipSuccess) e = hipMemcpyAsync(normals3_out, od, bytes, hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(pd); dev_free(od);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    Staged st;
+    float* od = st.out(normals3_out, (size_t)t->nv * 3);
+    const float* pd = st.in(positions3, (size_t)t->nv * 3);   // (null: the handle's own vertices)
+    st.run([&] { return normals(t, pd, flags, od, who); });
+    return st.finish(who);
 }

@@ -25,10 +25,11 @@
 //   name one component (always, on a single-component mesh), one into its row; only a mixed wave adds lane by lane.
 // Select:
 //   k_ts_flags     keep flags per vertex and per triangle; two scans.   k_ts_vertices / k_ts_triangles   the gathers.
+// Host side: scratch, adopted labels and the host forms' device copies are held in a Staged (device_stage.h); the handle check
+// (trimesh_check) and the launch size (grid1) are trimesh_handle.h's.
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "device_sort.h"
-#include "points_set.h"   // read_back
 #include "trimesh_handle.h"
 #include "trimesh_topology.h"
 
@@ -39,8 +40,6 @@ using namespace sdfk_trimesh_topo;
 constexpr int kBlock = 256;
 constexpr int kShortcuts = 8;        // shortcut launches queued per read of the counters
 constexpr int kMaxShortcutBatches = 8;   // per hook round: 64 jumps flatten any tree of fewer than 2^31 vertices (depth halves per jump)
-
-unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock); }
 
 typedef unsigned long long u64;
 
@@ -305,85 +304,68 @@ __global__ __launch_bounds__(kBlock) void k_ts_triangles(const uint32_t* __restr
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-int check_handle(const sdfk_trimesh* t, const char* who)
-{
-    if (int r = require_init()) return r;
-    if (!t) return fail(SDFK_ERR_INVALID, "%s: null argument", who);
-    if (3 * t->nt >= (int64_t(1) << 32)) return fail(SDFK_ERR_INVALID, "%s: 2^32 / 3 triangles or more", who);
-    return SDFK_OK;
-}
-
 // The labels, once per handle: synchronises (the rounds end on a counter the host reads).
 int labels_prepare(sdfk_trimesh* t, const char* who)
 {
     if (t->comp_vertex) return SDFK_OK;
     const int64_t nv = t->nv, nt = t->nt;
-    int32_t* parent = nullptr;
-    uint8_t* referenced = nullptr;
-    uint32_t* flag = nullptr;
-    Ctl* ctl = nullptr;
-    int32_t* vlabel = nullptr;
-    int32_t* tlabel = nullptr;
+    Staged st;
+    int32_t* parent = st.scratch<int32_t>((size_t)nv);
+    uint8_t* referenced = st.scratch<uint8_t>((size_t)nv);
+    uint32_t* flag = st.scratch<uint32_t>((size_t)nv + 1);
+    Ctl* ctl = st.scratch<Ctl>(1);
+    int32_t* vlabel = st.kept<int32_t>((size_t)nv);
+    int32_t* tlabel = st.kept<int32_t>((size_t)nt);
     Ctl host{};
     uint32_t count = 0;
-    int r = dev_alloc((void**)&parent, (size_t)nv * sizeof(int32_t));
-    if (!r) r = dev_alloc((void**)&referenced, (size_t)nv);
-    if (!r) r = dev_alloc((void**)&flag, (size_t)(nv + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&ctl, sizeof(Ctl));
-    if (!r) r = dev_alloc((void**)&vlabel, (size_t)nv * sizeof(int32_t));
-    if (!r) r = dev_alloc((void**)&tlabel, (size_t)nt * sizeof(int32_t));
-    hipError_t e = hipSuccess;
-    if (!r) e = hipMemsetAsync(ctl, 0, sizeof(Ctl), g.stream);
-    if (!r && e == hipSuccess) {
+    st.run([&] { return hipMemsetAsync(ctl, 0, sizeof(Ctl), g.stream); });
+    st.run([&] {
         ProfScope ps("k_tt_init");
         hipLaunchKernelGGL(k_tt_init, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, parent, referenced, nv);
         hipLaunchKernelGGL(k_tt_ref, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->idx, nt, referenced);
-        e = hipGetLastError();
-    }
+    });
     int q = 0;   // launches numbered so far (only q % 3 is used)
     bool flat = true;
     int batches = 0;
     u64 hook_before = 0;
-    while (!r && e == hipSuccess) {
+    while (st.ok()) {
         if (flat) {
-            if ((int64_t)host.rounds >= max_rounds(nv)) { r = fail(SDFK_ERR_INVALID, "%s: the label rounds did not end within n_vertices + 1", who); break; }
+            if ((int64_t)host.rounds >= max_rounds(nv)) {
+                st.run([&] { return fail(SDFK_ERR_INVALID, "%s: the label rounds did not end within n_vertices + 1", who); });
+                break;
+            }
             hook_before = host.hook_changes;
             batches = 0;
             ProfScope ps("k_tt_hook");
             q = (q + 1) % 3;
-            hipLaunchKernelGGL(k_tt_hook, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->idx, nt, parent, ctl, q);
+            hipLaunchKernelGGL(k_tt_hook, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->idx, nt, parent, ctl, q);   // (its error: taken below)
         } else if (++batches > kMaxShortcutBatches) {
-            r = fail(SDFK_ERR_INVALID, "%s: the shortcut launches did not flatten the labels", who);
+            st.run([&] { return fail(SDFK_ERR_INVALID, "%s: the shortcut launches did not flatten the labels", who); });
             break;
         }
-        {
+        st.run([&] {
             ProfScope ps("k_tt_shortcut");
             for (int b = 0; b < kShortcuts; b++) {
                 q = (q + 1) % 3;
                 hipLaunchKernelGGL(k_tt_shortcut, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, parent, nv, ctl, q);
             }
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = read_back(&host, ctl, sizeof host);
-        if (e != hipSuccess) break;
+        });
+        st.read(&host, ctl, sizeof host);
+        if (!st.ok()) break;
         flat = host.count[q] == 0;                                // the last shortcut launch changed nothing
         if (flat && host.hook_changes == hook_before) break;      // and the hook round before them, on a flat forest, neither
     }
-    if (!r && e == hipSuccess) {
+    {
         ProfScope ps("k_tt_labels");
-        hipLaunchKernelGGL(k_tt_roots, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, parent, referenced, nv, flag);
-        e = hipGetLastError();
-        if (e == hipSuccess) r = sdfk_scan::scan(flag, nv, who);
-        if (!r && e == hipSuccess) {
+        st.run([&] { hipLaunchKernelGGL(k_tt_roots, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, parent, referenced, nv, flag); });
+        st.run([&] { return sdfk_scan::scan(flag, nv, who); });
+        st.run([&] {
             hipLaunchKernelGGL(k_tt_vlabel, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, parent, referenced, nv, flag, vlabel);
             hipLaunchKernelGGL(k_tt_tlabel, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->idx, nt, vlabel, tlabel);
-            e = hipGetLastError();
-        }
-        if (!r && e == hipSuccess) e = read_back(&count, flag + nv, sizeof count);
+        });
+        st.read(&count, flag + nv, sizeof count);
     }
-    dev_free(parent); dev_free(referenced); dev_free(flag); dev_free(ctl);   // (stream-ordered pool)
-    if (!r && e != hipSuccess) r = fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    if (r) { dev_free(vlabel); dev_free(tlabel); return r; }
+    if (int r = st.finish(who, false)) return r;   // (the read above has waited; the labels are the handle's from here)
     t->comp_vertex = vlabel;
     t->comp_triangle = tlabel;
     t->comp_count = (int64_t)count;
@@ -398,52 +380,42 @@ int topology(sdfk_trimesh* t, int64_t census8[8], int64_t* rows_out, int64_t cap
     if (int r = labels_prepare(t, who)) return r;
     if (int r = trimesh_weights(t, who)) return r;
     const int64_t nv = t->nv, nt = t->nt, n = 3 * nt, C = t->comp_count;
-    u64* rows = nullptr;     // C x 8, then the census
-    Rec* ra = nullptr;
-    Rec* rb = nullptr;
-    Rec* sorted = nullptr;
-    uint32_t* head = nullptr;
-    uint32_t* fwd = nullptr;
-    uint32_t* start = nullptr;
     const size_t nrow = (size_t)(C + 1) * kRow;
-    int r = dev_alloc((void**)&rows, nrow * sizeof(u64));
-    if (!r) r = dev_alloc((void**)&ra, (size_t)n * sizeof(Rec));
-    if (!r) r = dev_alloc((void**)&rb, (size_t)n * sizeof(Rec));
-    if (!r) r = dev_alloc((void**)&head, (size_t)(n + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&fwd, (size_t)(n + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&start, (size_t)(n + 1) * sizeof(uint32_t));
+    Staged st;
+    u64* rows = st.scratch<u64>(nrow);     // C x 8, then the census
+    Rec* ra = st.scratch<Rec>((size_t)n);
+    Rec* rb = st.scratch<Rec>((size_t)n);
+    Rec* sorted = nullptr;
+    uint32_t* head = st.scratch<uint32_t>((size_t)n + 1);
+    uint32_t* fwd = st.scratch<uint32_t>((size_t)n + 1);
+    uint32_t* start = st.scratch<uint32_t>((size_t)n + 1);
     u64* census = rows ? rows + (size_t)C * kRow : nullptr;
-    hipError_t e = hipSuccess;
-    if (!r) e = hipMemsetAsync(rows, 0, nrow * sizeof(u64), g.stream);
-    if (!r && e == hipSuccess) {
+    st.run([&] { return hipMemsetAsync(rows, 0, nrow * sizeof(u64), g.stream); });
+    st.run([&] {
         ProfScope ps("k_tt_rows");
         hipLaunchKernelGGL(k_tt_tri_rows, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->comp_triangle, t->sample_W, nt, rows);
         hipLaunchKernelGGL(k_tt_vert_rows, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, t->comp_vertex, nv, rows, census);
         hipLaunchKernelGGL(k_tt_keys, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->idx, nt, ra, census);
-        e = hipGetLastError();
-    }
-    if (!r && e == hipSuccess) r = radix_sort(ra, rb, n, key_digit_mask(nv), &sorted, who);
-    if (!r && e == hipSuccess) {
+    });
+    st.run([&] { return radix_sort(ra, rb, n, key_digit_mask(nv), &sorted, who); });
+    {
         ProfScope ps("k_tt_edges");
-        hipLaunchKernelGGL(k_tt_heads, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, head, fwd);
-        e = hipGetLastError();
-        if (e == hipSuccess) r = sdfk_scan::scan(head, n, who);
-        if (!r && e == hipSuccess) r = sdfk_scan::scan(fwd, n, who);
-        if (!r && e == hipSuccess) {
+        st.run([&] { hipLaunchKernelGGL(k_tt_heads, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, head, fwd); });
+        st.run([&] { return sdfk_scan::scan(head, n, who); });
+        st.run([&] { return sdfk_scan::scan(fwd, n, who); });
+        st.run([&] {
             hipLaunchKernelGGL(k_tt_starts, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, head, start);
             hipLaunchKernelGGL(k_tt_edges, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, head, fwd, start, t->comp_vertex, rows, census);
-            e = hipGetLastError();
-        }
+        });
     }
     u64 hc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const int64_t nout = std::min<int64_t>(C, capacity);
-    if (!r && e == hipSuccess && rows_out && nout > 0)
-        e = hipMemcpyAsync(rows_out, rows, (size_t)nout * kRow * sizeof(u64), device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess) e = read_back(hc, census, sizeof hc);
-    else (void)hipStreamSynchronize(g.stream);   // (nothing is freed under a queued kernel's feet)
-    dev_free(rows); dev_free(ra); dev_free(rb); dev_free(head); dev_free(fwd); dev_free(start);
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (rows_out && nout > 0)
+        st.run([&] {
+            return hipMemcpyAsync(rows_out, rows, (size_t)nout * kRow * sizeof(u64), device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, g.stream);
+        });
+    st.read(hc, census, sizeof hc);   // (synchronises: host rows have arrived, too)
+    if (int r = st.finish(who, false)) return r;
     if (census8) {
         for (int k = 0; k < 8; k++) census8[k] = (int64_t)hc[k];
         census8[kCensusComponents] = C;
@@ -463,32 +435,27 @@ struct SelectOut {
 int select_kept(sdfk_trimesh* t, const uint8_t* keep, SelectOut O, int64_t* nv_out, int64_t* nt_out, const char* who)
 {
     const int64_t nv = t->nv, nt = t->nt;
-    uint32_t* vnew = nullptr;
-    uint32_t* tnew = nullptr;
+    Staged st;
+    uint32_t* vnew = st.scratch<uint32_t>((size_t)nv + 1);
+    uint32_t* tnew = st.scratch<uint32_t>((size_t)nt + 1);
     uint32_t counts[2] = {0, 0};
-    int r = dev_alloc((void**)&vnew, (size_t)(nv + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&tnew, (size_t)(nt + 1) * sizeof(uint32_t));
-    hipError_t e = hipSuccess;
-    if (!r) {
+    {
         ProfScope ps("k_ts_select");
-        hipLaunchKernelGGL(k_ts_flags, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, t->comp_vertex, nv, keep, vnew);
-        hipLaunchKernelGGL(k_ts_flags, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->comp_triangle, nt, keep, tnew);
-        e = hipGetLastError();
-        if (e == hipSuccess) r = sdfk_scan::scan(vnew, nv, who);
-        if (!r && e == hipSuccess) r = sdfk_scan::scan(tnew, nt, who);
-        if (!r && e == hipSuccess) {
+        st.run([&] {
+            hipLaunchKernelGGL(k_ts_flags, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, t->comp_vertex, nv, keep, vnew);
+            hipLaunchKernelGGL(k_ts_flags, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->comp_triangle, nt, keep, tnew);
+        });
+        st.run([&] { return sdfk_scan::scan(vnew, nv, who); });
+        st.run([&] { return sdfk_scan::scan(tnew, nt, who); });
+        st.run([&] {
             hipLaunchKernelGGL(k_ts_vertices, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, vnew, nv, t->vertices, t->colors, O.vertex_index, O.vertices,
                                O.colors);
             hipLaunchKernelGGL(k_ts_triangles, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, tnew, nt, vnew, t->idx, O.triangle_index, O.triangles);
-            e = hipGetLastError();
-        }
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&counts[0], vnew + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&counts[1], tnew + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream);
+        });
+        st.run([&] { return hipMemcpyAsync(&counts[0], vnew + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream); });
+        st.run([&] { return hipMemcpyAsync(&counts[1], tnew + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream); });
     }
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(vnew); dev_free(tnew);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
+    if (int r = st.finish(who)) return r;   // (synchronises: the counts are read)
     if (nv_out) *nv_out = counts[0];
     if (nt_out) *nt_out = counts[1];
     return SDFK_OK;
@@ -515,8 +482,9 @@ extern "C" int sdfk_trimesh_components_device(sdfk_trimesh* t, void* vertex_comp
     static const char* who = "sdfk_trimesh_components";
     StateScope in_owner_context(t ? t->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (int r = check_handle(t, who)) return r;
+    if (int r = trimesh_check(t, who, 3)) return r;
     if (int r = labels_prepare(t, who)) return r;
+    // (written out, not Staged: two copies between device arrays that nothing here owns, and nothing to wait for)
     hipError_t e = hipSuccess;
     if (vertex_component_dev) e = hipMemcpyAsync(vertex_component_dev, t->comp_vertex, (size_t)t->nv * sizeof(int32_t), hipMemcpyDeviceToDevice, g.stream);
     if (e == hipSuccess && triangle_component_dev)
@@ -531,14 +499,12 @@ extern "C" int sdfk_trimesh_components(sdfk_trimesh* t, int32_t* vertex_componen
     static const char* who = "sdfk_trimesh_components";
     StateScope in_owner_context(t ? t->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (int r = check_handle(t, who)) return r;
+    if (int r = trimesh_check(t, who, 3)) return r;
     if (int r = labels_prepare(t, who)) return r;
-    hipError_t e = hipSuccess;
-    if (vertex_component) e = hipMemcpyAsync(vertex_component, t->comp_vertex, (size_t)t->nv * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
-    if (e == hipSuccess && triangle_component)
-        e = hipMemcpyAsync(triangle_component, t->comp_triangle, (size_t)t->nt * sizeof(int32_t), hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
+    Staged st;   // (no device copies: the labels are the handle's, and go straight into the caller's arrays)
+    st.run([&] { return copy_out(vertex_component, t->comp_vertex, (size_t)t->nv); });
+    st.run([&] { return copy_out(triangle_component, t->comp_triangle, (size_t)t->nt); });
+    if (int r = st.finish(who)) return r;
     components_stats(t, n_components, stats);
     return SDFK_OK;
 }
@@ -548,7 +514,7 @@ extern "C" int sdfk_trimesh_topology_device(sdfk_trimesh* t, int64_t census[8], 
     static const char* who = "sdfk_trimesh_topology";
     StateScope in_owner_context(t ? t->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (int r = check_handle(t, who)) return r;
+    if (int r = trimesh_check(t, who, 3)) return r;
     if (capacity < 0) return fail(SDFK_ERR_INVALID, "%s: negative capacity", who);
     return topology(t, census, (int64_t*)component_rows_dev, capacity, true, who);
 }
@@ -558,7 +524,7 @@ extern "C" int sdfk_trimesh_topology(sdfk_trimesh* t, int64_t census[8], int64_t
     static const char* who = "sdfk_trimesh_topology";
     StateScope in_owner_context(t ? t->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (int r = check_handle(t, who)) return r;
+    if (int r = trimesh_check(t, who, 3)) return r;
     if (capacity < 0) return fail(SDFK_ERR_INVALID, "%s: negative capacity", who);
     return topology(t, census, component_rows, capacity, false, who);
 }
@@ -569,7 +535,7 @@ extern "C" int sdfk_trimesh_select_device(sdfk_trimesh* t, const void* keep_comp
     static const char* who = "sdfk_trimesh_select";
     StateScope in_owner_context(t ? t->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (int r = check_handle(t, who)) return r;
+    if (int r = trimesh_check(t, who, 3)) return r;
     if (!keep_component_dev) return fail(SDFK_ERR_INVALID, "%s: null keep_component", who);
     if (int r = labels_prepare(t, who)) return r;
     return select_kept(t, (const uint8_t*)keep_component_dev,
@@ -584,34 +550,24 @@ extern "C" int sdfk_trimesh_select(sdfk_trimesh* t, const uint8_t* keep_componen
     static const char* who = "sdfk_trimesh_select";
     StateScope in_owner_context(t ? t->owner : nullptr);
     std::lock_guard<std::recursive_mutex> lk(g_mu);
-    if (int r = check_handle(t, who)) return r;
+    if (int r = trimesh_check(t, who, 3)) return r;
     if (!keep_component) return fail(SDFK_ERR_INVALID, "%s: null keep_component", who);
     if (int r = labels_prepare(t, who)) return r;
     const size_t nv = (size_t)t->nv, nt = (size_t)t->nt, C = (size_t)t->comp_count;
-    uint8_t* keep = nullptr;
-    SelectOut O{nullptr, nullptr, nullptr, nullptr, nullptr};
-    int r = dev_alloc((void**)&keep, std::max<size_t>(C, 1));
-    if (!r && vertex_index_out) r = dev_alloc((void**)&O.vertex_index, nv * sizeof(int32_t));
-    if (!r && triangle_index_out) r = dev_alloc((void**)&O.triangle_index, nt * sizeof(int32_t));
-    if (!r && triangles_out) r = dev_alloc((void**)&O.triangles, 3 * nt * sizeof(int32_t));
-    if (!r && vertices_out) r = dev_alloc((void**)&O.vertices, 3 * nv * sizeof(float));
-    if (!r && colors_out) r = dev_alloc((void**)&O.colors, 3 * nv * sizeof(float));
-    hipError_t e = hipSuccess;
+    Staged st;
+    uint8_t* keep = st.scratch<uint8_t>(std::max<size_t>(C, 1));
+    if (C) st.run([&] { return hipMemcpyAsync(keep, keep_component, C, hipMemcpyHostToDevice, g.stream); });
+    const SelectOut O{vertex_index_out ? st.scratch<int32_t>(nv) : nullptr, triangle_index_out ? st.scratch<int32_t>(nt) : nullptr,
+                      triangles_out ? st.scratch<int32_t>(3 * nt) : nullptr, vertices_out ? st.scratch<float>(3 * nv) : nullptr,
+                      colors_out ? st.scratch<float>(3 * nv) : nullptr};
     int64_t kv = 0, kt = 0;
-    if (!r && C) e = hipMemcpyAsync(keep, keep_component, C, hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) r = select_kept(t, keep, O, &kv, &kt, who);   // (synchronises: the counts size the copies back)
-    auto back = [&](void* host, const void* dev, size_t bytes) {
-        if (!r && e == hipSuccess && dev && bytes) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, g.stream);
-    };
-    back(vertex_index_out, O.vertex_index, (size_t)kv * sizeof(int32_t));
-    back(triangle_index_out, O.triangle_index, (size_t)kt * sizeof(int32_t));
-    back(triangles_out, O.triangles, 3 * (size_t)kt * sizeof(int32_t));
-    back(vertices_out, O.vertices, 3 * (size_t)kv * sizeof(float));
-    back(colors_out, O.colors, 3 * (size_t)kv * sizeof(float));
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(keep); dev_free(O.vertex_index); dev_free(O.triangle_index); dev_free(O.triangles); dev_free(O.vertices); dev_free(O.colors);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
+    st.run([&] { return select_kept(t, keep, O, &kv, &kt, who); });   // (synchronises: the counts size the copies back)
+    st.run([&] { return copy_out(vertex_index_out, O.vertex_index, (size_t)kv); });   // (the kept ones only: the rest of the caller's arrays stays)
+    st.run([&] { return copy_out(triangle_index_out, O.triangle_index, (size_t)kt); });
+    st.run([&] { return copy_out(triangles_out, O.triangles, 3 * (size_t)kt); });
+    st.run([&] { return copy_out(vertices_out, O.vertices, 3 * (size_t)kv); });
+    st.run([&] { return copy_out(colors_out, O.colors, 3 * (size_t)kv); });
+    if (int r = st.finish(who)) return r;
     if (nv_out) *nv_out = kv;
     if (nt_out) *nt_out = kt;
     return SDFK_OK;

@@ -19,10 +19,11 @@
 //                  stable from ascending indices, so the head is the lowest index of its group.
 //   k_tw_tri_flags keep flag of every rewritten triangle; a kept one stores the byte 1 at its three representatives.
 //   k_tw_vert_flags keep flag of every vertex; two scans.   k_tw_vertices / k_tw_triangles   vertex_map and the gathers.
+// Host side: the scratch and the host form's device copies are held in a Staged (device_stage.h); the handle check
+// (trimesh_check) and the launch size (grid1) are trimesh_handle.h's.
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "device_sort.h"
-#include "points_set.h"   // read_back
 #include "trimesh_handle.h"
 #include "trimesh_weld.h"
 
@@ -32,8 +33,6 @@ using namespace sdfk_trimesh_wld;
 
 constexpr int kBlock = 256;
 constexpr unsigned kBoundsBlocks = 1024;   // of k_tw_bounds
-
-unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + kBlock - 1) / kBlock); }
 
 typedef unsigned long long u64;
 
@@ -222,8 +221,7 @@ __global__ __launch_bounds__(kBlock) void k_tw_triangles(const uint32_t* __restr
 // ---- host -------------------------------------------------------------------------------------------------------------------
 int check(const sdfk_trimesh* t, float tolerance, int32_t flags, const char* who)
 {
-    if (int r = require_init()) return r;
-    if (!t) return fail(SDFK_ERR_INVALID, "%s: null argument", who);
+    if (int r = trimesh_check(t, who, 0)) return r;   // (no records per triangle here: the sort is over the vertices)
     if (!tolerance_is_valid(tolerance)) return fail(SDFK_ERR_INVALID, "%s: tolerance must be finite and not negative", who);
     if (!flags_are_valid(flags)) return fail(SDFK_ERR_INVALID, "%s: unknown flag bits", who);
     return SDFK_OK;
@@ -235,108 +233,88 @@ int weld(const sdfk_trimesh* t, float tolerance, int32_t flags, WeldOut O, int64
     const int64_t nv = t->nv, nt = t->nt, n = nv;
     const bool exact = tolerance == 0.0f;
     const uint32_t* P = (const uint32_t*)t->vertices;
-    Ctl* ctl = nullptr;
-    Rec* ra = nullptr;
-    Rec* rb = nullptr;
+    Staged st;
+    Ctl* ctl = st.scratch<Ctl>(1);
+    Rec* ra = st.scratch<Rec>((size_t)n);
+    Rec* rb = st.scratch<Rec>((size_t)n);
     Rec* sorted = nullptr;
-    uint32_t* head = nullptr;
-    int32_t* group_first = nullptr;
-    int32_t* rep = nullptr;
-    uint8_t* used = nullptr;
-    uint32_t* vnew = nullptr;
-    uint32_t* tnew = nullptr;
+    uint32_t* head = st.scratch<uint32_t>((size_t)n + 1);
+    int32_t* group_first = st.scratch<int32_t>((size_t)n);
+    int32_t* rep = st.scratch<int32_t>((size_t)nv);
+    uint8_t* used = st.scratch<uint8_t>((size_t)nv);
+    uint32_t* vnew = st.scratch<uint32_t>((size_t)nv + 1);
+    uint32_t* tnew = st.scratch<uint32_t>((size_t)nt + 1);
     Ctl host{{0xffffffffu, 0xffffffffu, 0xffffffffu}, {0u, 0u, 0u}, {0ull, 0ull}};
     Lattice L{};
     unsigned lattice_mask = 0xffu;
     int passes = 0;
     uint32_t counts[3] = {0, 0, 0};   // groups, kept vertices, kept triangles
-    int r = dev_alloc((void**)&ctl, sizeof(Ctl));
-    if (!r) r = dev_alloc((void**)&ra, (size_t)n * sizeof(Rec));
-    if (!r) r = dev_alloc((void**)&rb, (size_t)n * sizeof(Rec));
-    if (!r) r = dev_alloc((void**)&head, (size_t)(n + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&group_first, (size_t)n * sizeof(int32_t));
-    if (!r) r = dev_alloc((void**)&rep, (size_t)nv * sizeof(int32_t));
-    if (!r) r = dev_alloc((void**)&used, (size_t)nv);
-    if (!r) r = dev_alloc((void**)&vnew, (size_t)(nv + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&tnew, (size_t)(nt + 1) * sizeof(uint32_t));
-    hipError_t e = hipSuccess;
-    if (!r) e = hipMemcpyAsync(ctl, &host, sizeof host, hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) e = hipMemsetAsync(used, 0, (size_t)nv, g.stream);
-    if (!r && e == hipSuccess && !exact) {
-        {
+    st.run([&] { return hipMemcpyAsync(ctl, &host, sizeof host, hipMemcpyHostToDevice, g.stream); });
+    st.run([&] { return hipMemsetAsync(used, 0, (size_t)nv, g.stream); });
+    if (!exact) {
+        st.run([&] {
             ProfScope ps("k_tw_bounds");
             hipLaunchKernelGGL(k_tw_bounds, dim3(std::min(grid1(nv), kBoundsBlocks)), dim3(kBlock), 0, g.stream, P, nv, ctl);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = read_back(&host, ctl, sizeof host);
-        if (e == hipSuccess) {
+        });
+        st.read(&host, ctl, sizeof host);
+        st.run([&] {
             float lo[3], hi[3];
             for (int a = 0; a < 3; a++) {
                 lo[a] = float_of(unordered_bits(host.lo[a]));
                 hi[a] = float_of(unordered_bits(host.hi[a]));
             }
-            if (!lattice_of(tolerance, lo, hi, &L, &lattice_mask))
-                r = fail(SDFK_ERR_INVALID, "%s: an axis spans 2^21 cells of the tolerance or more", who);
-        }
+            if (!lattice_of(tolerance, lo, hi, &L, &lattice_mask)) return fail(SDFK_ERR_INVALID, "%s: an axis spans 2^21 cells of the tolerance or more", who);
+            return (int)SDFK_OK;
+        });
     }
-    if (!r && e == hipSuccess) {
-        {
-            ProfScope ps("k_tw_keys");
-            if (exact) hipLaunchKernelGGL(k_tw_keys<true>, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, P, nv, L, ra, ctl);
-            else hipLaunchKernelGGL(k_tw_keys<false>, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, P, nv, L, ra, ctl);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = read_back(&host, ctl, sizeof host);
-    }
-    if (!r && e == hipSuccess) {
+    st.run([&] {
+        ProfScope ps("k_tw_keys");
+        if (exact) hipLaunchKernelGGL(k_tw_keys<true>, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, P, nv, L, ra, ctl);
+        else hipLaunchKernelGGL(k_tw_keys<false>, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, P, nv, L, ra, ctl);
+    });
+    st.read(&host, ctl, sizeof host);
+    st.run([&] {
         const unsigned mask = pass_mask(host.diff[0]) & lattice_mask;
         passes += passes_of(mask);
-        r = radix_sort(ra, rb, n, mask, &sorted, who);
+        return radix_sort(ra, rb, n, mask, &sorted, who);
+    });
+    if (const unsigned mask = exact ? pass_mask(host.diff[1]) : 0u) {
+        st.run([&] {
+            ProfScope ps("k_tw_rekey");
+            hipLaunchKernelGGL(k_tw_rekey, dim3(grid1(n)), dim3(kBlock), 0, g.stream, P, sorted, n);
+        });
+        passes += passes_of(mask);
+        st.run([&] { return radix_sort(sorted, sorted == ra ? rb : ra, n, mask, &sorted, who); });
     }
-    if (!r && e == hipSuccess && exact) {
-        const unsigned mask = pass_mask(host.diff[1]);
-        if (mask) {
-            {
-                ProfScope ps("k_tw_rekey");
-                hipLaunchKernelGGL(k_tw_rekey, dim3(grid1(n)), dim3(kBlock), 0, g.stream, P, sorted, n);
-                e = hipGetLastError();
-            }
-            passes += passes_of(mask);
-            if (e == hipSuccess) r = radix_sort(sorted, sorted == ra ? rb : ra, n, mask, &sorted, who);
-        }
-    }
-    if (!r && e == hipSuccess) {
+    {
         ProfScope ps("k_tw_groups");
-        if (exact) hipLaunchKernelGGL(k_tw_heads<true>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, P, sorted, n, head);
-        else hipLaunchKernelGGL(k_tw_heads<false>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, P, sorted, n, head);
-        e = hipGetLastError();
-        if (e == hipSuccess) r = sdfk_scan::scan(head, n, who);
-        if (!r && e == hipSuccess) {
+        st.run([&] {
+            if (exact) hipLaunchKernelGGL(k_tw_heads<true>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, P, sorted, n, head);
+            else hipLaunchKernelGGL(k_tw_heads<false>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, P, sorted, n, head);
+        });
+        st.run([&] { return sdfk_scan::scan(head, n, who); });
+        st.run([&] {
             hipLaunchKernelGGL(k_tw_first, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, head, group_first);
             hipLaunchKernelGGL(k_tw_rep, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, head, group_first, rep);
-            e = hipGetLastError();
-        }
+        });
     }
-    if (!r && e == hipSuccess) {
+    {
         ProfScope ps("k_tw_output");
-        hipLaunchKernelGGL(k_tw_tri_flags, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->idx, nt, rep, flags, tnew, used);
-        hipLaunchKernelGGL(k_tw_vert_flags, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, rep, used, nv, flags, vnew);
-        e = hipGetLastError();
-        if (e == hipSuccess) r = sdfk_scan::scan(vnew, nv, who);
-        if (!r && e == hipSuccess) r = sdfk_scan::scan(tnew, nt, who);
-        if (!r && e == hipSuccess) {
+        st.run([&] {
+            hipLaunchKernelGGL(k_tw_tri_flags, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->idx, nt, rep, flags, tnew, used);
+            hipLaunchKernelGGL(k_tw_vert_flags, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, rep, used, nv, flags, vnew);
+        });
+        st.run([&] { return sdfk_scan::scan(vnew, nv, who); });
+        st.run([&] { return sdfk_scan::scan(tnew, nt, who); });
+        st.run([&] {
             hipLaunchKernelGGL(k_tw_vertices, dim3(grid1(nv)), dim3(kBlock), 0, g.stream, vnew, rep, nv, t->vertices, t->colors, O);
             hipLaunchKernelGGL(k_tw_triangles, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, tnew, nt, vnew, rep, t->idx, O);
-            e = hipGetLastError();
-        }
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&counts[0], head + n, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&counts[1], vnew + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream);
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(&counts[2], tnew + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream);
+        });
+        st.run([&] { return hipMemcpyAsync(&counts[0], head + n, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream); });
+        st.run([&] { return hipMemcpyAsync(&counts[1], vnew + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream); });
+        st.run([&] { return hipMemcpyAsync(&counts[2], tnew + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream); });
     }
-    const hipError_t es = hipStreamSynchronize(g.stream);   // (nothing is freed under a queued kernel's feet)
-    dev_free(ctl); dev_free(ra); dev_free(rb); dev_free(head); dev_free(group_first); dev_free(rep); dev_free(used); dev_free(vnew); dev_free(tnew);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
+    if (int r = st.finish(who)) return r;   // (synchronises: the counts are read)
     if (nv_out) *nv_out = counts[1];
     if (nt_out) *nt_out = counts[2];
     if (stats) {
@@ -376,33 +354,21 @@ extern "C" int sdfk_trimesh_weld(sdfk_trimesh* t, float tolerance, int32_t flags
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     if (int r = check(t, tolerance, flags, who)) return r;
     const size_t nv = (size_t)t->nv, nt = (size_t)t->nt;
-    WeldOut O{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int r = SDFK_OK;
-    if (vertex_map) r = dev_alloc((void**)&O.vertex_map, nv * sizeof(int32_t));
-    if (!r && vertex_index_out) r = dev_alloc((void**)&O.vertex_index, nv * sizeof(int32_t));
-    if (!r && triangle_index_out) r = dev_alloc((void**)&O.triangle_index, nt * sizeof(int32_t));
-    if (!r && triangles_out) r = dev_alloc((void**)&O.triangles, 3 * nt * sizeof(int32_t));
-    if (!r && vertices_out) r = dev_alloc((void**)&O.vertices, 3 * nv * sizeof(float));
-    if (!r && colors_out) r = dev_alloc((void**)&O.colors, 3 * nv * sizeof(float));
-    hipError_t e = hipSuccess;
-    int64_t kv = 0, kt = 0, st[4] = {0, 0, 0, 0};
-    if (!r) r = weld(t, tolerance, flags, O, &kv, &kt, st, who);   // (synchronises: the counts size the copies back)
-    auto back = [&](void* host, const void* dev, size_t bytes) {
-        if (!r && e == hipSuccess && dev && bytes) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, g.stream);
-    };
-    back(vertex_map, O.vertex_map, nv * sizeof(int32_t));
-    back(vertex_index_out, O.vertex_index, (size_t)kv * sizeof(int32_t));
-    back(triangle_index_out, O.triangle_index, (size_t)kt * sizeof(int32_t));
-    back(triangles_out, O.triangles, 3 * (size_t)kt * sizeof(int32_t));
-    back(vertices_out, O.vertices, 3 * (size_t)kv * sizeof(float));
-    back(colors_out, O.colors, 3 * (size_t)kv * sizeof(float));
-    const hipError_t es = hipStreamSynchronize(g.stream);
-    dev_free(O.vertex_map); dev_free(O.vertex_index); dev_free(O.triangle_index); dev_free(O.triangles); dev_free(O.vertices); dev_free(O.colors);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
+    Staged st;
+    const WeldOut O{st.out(vertex_map, nv), vertex_index_out ? st.scratch<int32_t>(nv) : nullptr,
+                    triangle_index_out ? st.scratch<int32_t>(nt) : nullptr, triangles_out ? st.scratch<int32_t>(3 * nt) : nullptr,
+                    vertices_out ? st.scratch<float>(3 * nv) : nullptr, colors_out ? st.scratch<float>(3 * nv) : nullptr};
+    int64_t kv = 0, kt = 0, stv[4] = {0, 0, 0, 0};
+    st.run([&] { return weld(t, tolerance, flags, O, &kv, &kt, stv, who); });   // (synchronises: the counts size the copies back)
+    st.run([&] { return copy_out(vertex_index_out, O.vertex_index, (size_t)kv); });   // (the kept ones only: the rest of the caller's arrays stays)
+    st.run([&] { return copy_out(triangle_index_out, O.triangle_index, (size_t)kt); });
+    st.run([&] { return copy_out(triangles_out, O.triangles, 3 * (size_t)kt); });
+    st.run([&] { return copy_out(vertices_out, O.vertices, 3 * (size_t)kv); });
+    st.run([&] { return copy_out(colors_out, O.colors, 3 * (size_t)kv); });
+    if (int r = st.finish(who)) return r;
     if (nv_out) *nv_out = kv;
     if (nt_out) *nt_out = kt;
     if (stats)
-        for (int k = 0; k < 4; k++) stats[k] = st[k];
+        for (int k = 0; k < 4; k++) stats[k] = stv[k];
     return SDFK_OK;
 }

@@ -1,10 +1,15 @@
 // trimesh_handle.h -- the handle behind sdfk_trimesh_*: the copied arrays, the packed triangles and their search grid (built by
 // lib_trimesh.hip), the sampling weights' scan (made by the first call that needs it) and the component labels (made by the first
 // topology call, lib_trimesh_topology.hip) and the adjacency (made by the first adjacency, smoothing or vertex-normal call,
-// lib_trimesh_smooth.hip).  Seen by those three translation units and by lib_trimesh_weld.hip, which only reads it.  hipcc only.
+// lib_trimesh_smooth.hip).  Seen by those three translation units and by lib_trimesh_weld.hip, which only reads it.  With it, what
+// the four share on the host: the staging of device_stage.h, the check of a handle and the size of a one-dimensional launch.
+// hipcc only.
 #pragma once
 #include "lib_internal.h"
+#include "device_stage.h"
 #include "points_grid.h"
+
+#include <algorithm>
 
 // packed triangle: a, b, c (f32) and the AABB
 struct TriPack {
@@ -44,3 +49,10 @@ struct sdfk_trimesh {
 // The sampling weights and their scan, once per handle (lib_trimesh.hip): synchronises to read the total.  A mesh in which no
 // triangle has an area gets W = 0 everywhere and sample_no_area; refusing it is the sampler's business.
 int trimesh_weights(sdfk_trimesh* t, const char* who);
+
+// What every entry point of the family asks of its handle first: the library is initialised, t is not null, and -- for a unit
+// that sorts `records` 32-bit-indexed records per triangle (0: none) -- records * nt < 2^32.  (lib_trimesh.hip)
+int trimesh_check(const sdfk_trimesh* t, const char* who, int records);
+
+// blocks of 256 lanes for n items, one lane each; at least one, at most 2^30 (reached by nothing indexed per vertex or triangle)
+inline unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, int64_t(1) << 30)); }
