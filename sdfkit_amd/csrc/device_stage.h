@@ -1,5 +1,5 @@
-// device_stage.h -- what owns device memory for the length of one call on g.stream, for the point-cloud and the triangle-mesh
-// families alike: Staged, the scratch of a work function and the device copies of a host form's arrays, with the one rule of
+// device_stage.h -- what owns device memory for the length of one call on g.stream, for the point-cloud, the triangle-mesh and
+// the volume units alike: Staged, the scratch of a work function and the device copies of a host form's arrays, with the one rule of
 // when queueing stops, when the stream is waited for and which error is reported; read_back, a device value the host needs on the
 // way; copy_out, the front of a compacted device array into the caller's.  hipcc only.
 #pragma once

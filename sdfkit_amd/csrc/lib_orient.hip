@@ -2,7 +2,7 @@
 // region growing over the k-nearest graph, confident edges first.  Contract: include/sdfkit_hip.h, "Point clouds: a consistent
 // orientation"; the decisions (validity, dot, the seed's order and sign, one point's choice from its row, the level rule):
 // points_orient.h, checked on the host; the walk, the tiers and the bounded lists: points_walk.h / points_knn.h, shared with every
-// query of the KdTree; the reads of the control block: device_stage.h read_back.
+// query of the KdTree; the scratch of a call and the reads of the control block: a Staged (device_stage.h).
 //
 //   k_or_rows<CAP>   one lane per static point: its k nearest exactly as k_pts_knn<CAP> finds them (the same tiers), written once
 //                    for the call as SLOT-MAJOR rows (slot * n + point; -1 from the count on): in a round lane i reads slot s of
@@ -180,71 +180,62 @@ int orient(const sdfk_points* s, int k, float max_distance, int64_t max_seeds, f
 {
     static const char* who = "sdfk_points_orient_normals";
     const int64_t n = s->n;
-    int32_t* rows = nullptr;
-    int32_t* stamp = nullptr;
-    signed char* sgn = nullptr;
-    Ctl* ctl = nullptr;
+    Staged st;
+    int32_t* rows = st.scratch<int32_t>((size_t)n * (size_t)k);
+    int32_t* stamp = st.scratch<int32_t>((size_t)n);
+    signed char* sgn = st.scratch<signed char>((size_t)n);
+    Ctl* ctl = st.scratch<Ctl>(1);
     Ctl host{};
-    int r = dev_alloc((void**)&rows, (size_t)n * (size_t)k * sizeof(int32_t));
-    if (!r) r = dev_alloc((void**)&stamp, (size_t)n * sizeof(int32_t));
-    if (!r) r = dev_alloc((void**)&sgn, (size_t)n);
-    if (!r) r = dev_alloc((void**)&ctl, sizeof(Ctl));
-    hipError_t e = hipSuccess;
-    if (!r) e = hipMemsetAsync(ctl, 0, sizeof(Ctl), g.stream);
-    if (!r && e == hipSuccess) {
+    st.run([&] { return hipMemsetAsync(ctl, 0, sizeof(Ctl), g.stream); });
+    st.run([&] {
         ProfScope ps("k_or_rows");
         const float d2b = radius_d2_bound(max_distance);
         launch_tier(k, n, [&](auto cap, dim3 grid, dim3 block) {
             hipLaunchKernelGGL(k_or_rows<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, normals, rows, stamp, sgn, ctl);
         });
-        e = hipGetLastError();
-    }
+    });
     const unsigned blocks = grid_of(n, kBlock);
     int64_t q = 0;   // launches numbered so far
-    while (!r && e == hipSuccess) {
-        {
+    const auto bounded = [&] { return q > (int64_t(1) << 30) ? fail(SDFK_ERR_INVALID, "%s: 2^30 rounds without an end", who) : (int)SDFK_OK; };
+    while (st.ok()) {
+        st.run([&] {
             ProfScope ps("k_or_seed");
             q++;
             hipLaunchKernelGGL(k_or_seed_find, dim3((unsigned)grid_for((size_t)n, kBlock, 2048)), dim3(kBlock), 0, g.stream, s->xyz, n, stamp, sgn, ctl);
             hipLaunchKernelGGL(k_or_seed_apply, dim3(1), dim3(64), 0, g.stream, (int)q, normals, stamp, sgn, ctl);
-            e = hipGetLastError();
-        }
-        while (e == hipSuccess) {   // this seed's growth, a batch at a time
-            {
+        });
+        while (st.ok()) {   // this seed's growth, a batch at a time
+            st.run([&] {
                 ProfScope ps("k_or_round");
                 for (int b = 0; b < kBatch; b++) {
                     q++;
                     hipLaunchKernelGGL(k_or_round, dim3(blocks), dim3(kBlock), 0, g.stream, rows, n, k, (int)q, normals, stamp, sgn, ctl);
                 }
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = read_back(&host, ctl, sizeof host);
-            if (e != hipSuccess || host.level[q % 3] >= kLevels) break;   // the last queued round found the growth over
-            if (q > (int64_t(1) << 30)) { r = fail(SDFK_ERR_INVALID, "%s: 2^30 rounds without an end", who); break; }
+            });
+            st.read(&host, ctl, sizeof host);
+            if (!st.ok() || host.level[q % 3] >= kLevels) break;   // the last queued round found the growth over
+            st.run(bounded);
         }
-        if (r || e != hipSuccess) break;
+        if (!st.ok()) break;
         unsigned long long oriented = host.seeds;
         for (int l = 0; l < kLevels; l++) oriented += host.per_level[l];
         if (oriented >= host.valid || (int64_t)host.seeds >= max_seeds) break;
-        if (q > (int64_t(1) << 30)) { r = fail(SDFK_ERR_INVALID, "%s: 2^30 rounds without an end", who); break; }
+        st.run(bounded);
     }
-    if (!r && e == hipSuccess) {
+    {
         ProfScope ps("k_or_finish");
-        hipLaunchKernelGGL(k_or_finish, dim3(blocks), dim3(kBlock), 0, g.stream, n, normals, stamp, sgn, ctl);
-        e = hipGetLastError();
-        if (e == hipSuccess && stats) {
-            e = read_back(&host, ctl, sizeof host);
-            stats[0] = (int64_t)host.rounds;
-            stats[1] = (int64_t)host.seeds;
-            stats[2] = (int64_t)host.flipped;
-            stats[3] = (int64_t)host.unreached;
-            stats[4] = n - (int64_t)host.valid;
-            for (int l = 0; l < kLevels; l++) stats[5 + l] = (int64_t)host.per_level[l];
-        }
+        st.run([&] { hipLaunchKernelGGL(k_or_finish, dim3(blocks), dim3(kBlock), 0, g.stream, n, normals, stamp, sgn, ctl); });
+        if (stats) st.read(&host, ctl, sizeof host);
     }
-    dev_free(rows); dev_free(stamp); dev_free(sgn); dev_free(ctl);   // (stream-ordered pool)
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (int r = st.finish(who, false)) return r;   // (no wait of its own: with stats the read above was one)
+    if (stats) {
+        stats[0] = (int64_t)host.rounds;
+        stats[1] = (int64_t)host.seeds;
+        stats[2] = (int64_t)host.flipped;
+        stats[3] = (int64_t)host.unreached;
+        stats[4] = n - (int64_t)host.valid;
+        for (int l = 0; l < kLevels; l++) stats[5 + l] = (int64_t)host.per_level[l];
+    }
     return SDFK_OK;
 }
 

@@ -17,6 +17,7 @@
 //   k_pc_fill<AXIS>     one lane per line of sign bytes along z, then y, then x: unknown voxels take the sign carried along the
 //                       line and the value +-max_distance.  Lines along z are walked by neighbouring lanes nz bytes apart
 //                       (uncoalesced; the array is one byte per voxel and each line stays in cache), the other two coalesce.
+// Host side: the volume's scratch (sign bytes, the known count) and the host forms' device copies are held in a Staged (device_stage.h).
 #include "lib_internal.h"
 #include "points_color.h"
 #include "points_knn.h"
@@ -280,16 +281,13 @@ int to_volume(const sdfk_points* s, const float* normals_dev, const float* color
     float d[3], m[3], outside;
     grid_constants(v, d, m, &outside);
     const int64_t nvox = (int64_t)v->nx * v->ny * v->nz;
-    signed char* sgn = nullptr;
-    unsigned long long* known = nullptr;
-    int r = dev_alloc((void**)&sgn, (size_t)nvox);
-    hipError_t e = hipSuccess;
-    if (!r && stats) {
-        r = dev_alloc((void**)&known, sizeof(unsigned long long));
-        if (!r) e = hipMemsetAsync(known, 0, sizeof(unsigned long long), g.stream);
-    }
-    if (!r && e == hipSuccess)
-        r = walk_launch(s, nvox, "k_pc_volume", who, [&](unsigned long long* counter) {
+    Staged st;
+    signed char* sgn = st.scratch<signed char>((size_t)nvox);
+    unsigned long long* known = stats ? st.scratch<unsigned long long>(1) : nullptr;
+    unsigned long long c = 0;
+    if (stats) st.run([&] { return hipMemsetAsync(known, 0, sizeof(unsigned long long), g.stream); });
+    st.run([&] {
+        return walk_launch(s, nvox, "k_pc_volume", who, [&](unsigned long long* counter) {
             const VolumeArgs A{s->xyz, normals_dev, v->values, sgn, v->nx, v->ny, v->nz, v->pitch(), v->z0, m[0], m[1], m[2], d[0], d[1], d[2],
                                k, radius_d2_bound(max_distance), max_distance, known, counter, colors_dev, colors_dev ? v->colors : nullptr};
             launch_tier(k, nvox, [&](auto cap, dim3 grid, dim3 block) {
@@ -299,26 +297,22 @@ int to_volume(const sdfk_points* s, const float* normals_dev, const float* color
                     hipLaunchKernelGGL((k_pc_volume<decltype(cap)::value, false>), grid, block, 0, g.stream, s->sorted, s->starts, s->G, A);
             });
         });
-    if (!r && e == hipSuccess) {
+    });
+    st.run([&] {
         ProfScope ps("k_pc_fill");
         const int nx = v->nx, ny = v->ny, nz = v->nz, pitch = v->pitch();
         hipLaunchKernelGGL(k_pc_fill<2>, dim3(grid_of((int64_t)nx * ny, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
         hipLaunchKernelGGL(k_pc_fill<1>, dim3(grid_of((int64_t)nx * nz, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
         hipLaunchKernelGGL(k_pc_fill<0>, dim3(grid_of((int64_t)ny * nz, kBlock)), dim3(kBlock), 0, g.stream, sgn, v->values, nx, ny, nz, pitch, max_distance);
-        e = hipGetLastError();
-    }
-    if (!r && e == hipSuccess && stats) {
-        unsigned long long c = 0;
-        e = read_back(&c, known, sizeof c);
+    });
+    if (stats) st.read(&c, known, sizeof c);
+    if (int r = st.finish(who, false)) return r;   // (no wait of its own: with stats the read above was one)
+    if (stats) {
         stats[0] = (int64_t)c;
         stats[1] = nvox - (int64_t)c;
         stats[2] = g.prof_on ? s->last_candidates : 0;
         stats[3] = g.prof_on ? s->last_queries : 0;
     }
-    dev_free(sgn);   // (stream-ordered pool)
-    dev_free(known);
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return SDFK_OK;
 }
 

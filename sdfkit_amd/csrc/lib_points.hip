@@ -18,6 +18,8 @@
 // Everything after the reductions (the distMax rule, the filter, the solve, the Matrix4x4 steps) is icp_solve.h, shared with the host.
 // With a normal per static point the same loop runs the point-to-plane metric: kept count and mean -> the 28 sums of the 6x6 normal
 // equations -> a one-lane eigen-solve and Cayley step ("ICP, point to plane" below).
+// Host side: the scratch of the build and of the ICP, and the arrays a build makes for the handle (kept until it succeeded), are
+// held in a Staged (device_stage.h); points_release alone frees what a handle owns.
 #include "lib_internal.h"
 #include "device_reduce.h"
 #include "device_scan.h"
@@ -452,60 +454,44 @@ void points_release(sdfk_points* s)
     s->starts = nullptr;
 }
 
-// (Re)builds the search structure of s from s->xyz (synchronises: the host reads the bounding box to size the grid).  Refuses
-// non-finite points.
+// Builds the search structure of s, whose sorted and starts are null, from s->xyz (synchronises: the host reads the bounding box
+// to size the grid).  Refuses non-finite points.  s->sorted and s->starts are stored only when everything succeeded.
 int points_build(sdfk_points* s, const char* who)
 {
     const int64_t n = s->n;
     const unsigned bb = (unsigned)std::min<int64_t>(1024, (n + kBlock - 1) / kBlock);
-    float* part = nullptr;
-    float* box_dev = nullptr;
-    int r = dev_alloc((void**)&part, (size_t)bb * 8 * sizeof(float));
-    if (!r) r = dev_alloc((void**)&box_dev, 8 * sizeof(float));
-    if (r) { dev_free(part); return r; }
-    {
+    Staged st;
+    float* part = st.scratch<float>((size_t)bb * 8);
+    float* box_dev = st.scratch<float>(8);
+    float box[8] = {};
+    st.run([&] {
         ProfScope ps("k_pts_bounds");
         hipLaunchKernelGGL(k_pts_bounds, dim3(bb), dim3(kBlock), 0, g.stream, s->xyz, n, part);
         hipLaunchKernelGGL(k_pts_bounds_final, dim3(1), dim3(kBlock), 0, g.stream, part, (int)bb, box_dev);
-    }
-    float box[8] = {};
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(box, box_dev, 7 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->first, s->xyz, 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-    dev_free(part);
-    dev_free(box_dev);
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    });
+    st.run([&] { return hipMemcpyAsync(box, box_dev, 7 * sizeof(float), hipMemcpyDeviceToHost, g.stream); });
+    st.run([&] { return hipMemcpyAsync(s->first, s->xyz, 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream); });
+    if (int r = st.finish(who)) return r;   // (synchronises: the box is read; its scratch goes back before the second phase)
     if (box[6] > 0) return fail(SDFK_ERR_INVALID, "%s: a static point has a NaN or infinite coordinate", who);
 
     s->G = grid_for_box(box, box + 3, n);
     s->cells = (int64_t)s->G.dim[0] * s->G.dim[1] * s->G.dim[2];
-    uint32_t* keys = nullptr;
-    uint32_t* cursor = nullptr;
-    dev_free(s->sorted);
-    dev_free(s->starts);
-    s->sorted = nullptr;
-    s->starts = nullptr;
-    r = dev_alloc((void**)&s->sorted, (size_t)n * sizeof(float4));
-    if (!r) r = dev_alloc((void**)&s->starts, (size_t)(s->cells + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&keys, (size_t)n * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&cursor, (size_t)(s->cells + 1) * sizeof(uint32_t));
-    if (!r) {
+    const size_t cells = (size_t)s->cells;
+    float4* sorted = st.kept<float4>((size_t)n);
+    uint32_t* starts = st.kept<uint32_t>(cells + 1);
+    uint32_t* keys = st.scratch<uint32_t>((size_t)n);
+    uint32_t* cursor = st.scratch<uint32_t>(cells + 1);
+    {
         ProfScope ps("k_pts_build");
-        e = hipMemsetAsync(s->starts, 0, (size_t)(s->cells + 1) * sizeof(uint32_t), g.stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_pts_count, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, s->xyz, n, s->G, keys, s->starts);
-            r = sdfk_scan::scan(s->starts, s->cells, who);
-        }
-        if (!r && e == hipSuccess) e = hipMemcpyAsync(cursor, s->starts, (size_t)s->cells * sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream);
-        if (!r && e == hipSuccess)
-            hipLaunchKernelGGL(k_pts_scatter, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, s->xyz, n, keys, cursor, s->sorted);
-        if (e == hipSuccess) e = hipGetLastError();
+        st.run([&] { return hipMemsetAsync(starts, 0, (cells + 1) * sizeof(uint32_t), g.stream); });
+        st.run([&] { hipLaunchKernelGGL(k_pts_count, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, s->xyz, n, s->G, keys, starts); });
+        st.run([&] { return sdfk_scan::scan(starts, s->cells, who); });
+        st.run([&] { return hipMemcpyAsync(cursor, starts, cells * sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream); });
+        st.run([&] { hipLaunchKernelGGL(k_pts_scatter, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, s->xyz, n, keys, cursor, sorted); });
     }
-    dev_free(keys);
-    dev_free(cursor);
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (int r = st.finish(who, false)) return r;   // (no wait: the queries that follow are queued behind the build)
+    s->sorted = sorted;
+    s->starts = starts;
     return SDFK_OK;
 }
 
@@ -527,18 +513,15 @@ int points_make(const void* pts, int64_t n, bool device, sdfk_points** out)
     if (n < 1) return fail(SDFK_ERR_INVALID, "sdfk_points_create: at least one point must be given");
     if (!pts) return fail(SDFK_ERR_INVALID, "sdfk_points_create: null points");
     if (n >= (int64_t(1) << 31)) return fail(SDFK_ERR_INVALID, "sdfk_points_create: 2^31 points or more");
+    static const char* who = "sdfk_points_create";
     sdfk_points* s = new sdfk_points();
     s->n = n;
-    int r = dev_alloc((void**)&s->xyz, (size_t)n * 3 * sizeof(float));
-    if (!r) {
-        const hipError_t e = hipMemcpyAsync(s->xyz, pts, (size_t)n * 3 * sizeof(float), device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                            g.stream);
-        if (e != hipSuccess) r = fail(SDFK_ERR_HIP, "sdfk_points_create: %s", hipGetErrorString(e));
-    }
-    if (!r) r = points_build(s, "sdfk_points_create");   // (synchronises: the caller's host array is not retained)
-    if (r) {
-        points_release(s);
-        delete s;
+    Staged st;
+    s->xyz = st.kept<float>((size_t)n * 3);
+    st.run([&] { return hipMemcpyAsync(s->xyz, pts, (size_t)n * 3 * sizeof(float), device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, g.stream); });
+    st.run([&] { return points_build(s, who); });   // (synchronises: the caller's host array is not retained)
+    if (int r = st.finish(who, false)) {
+        delete s;   // (nothing to release: finish() freed xyz, and a build that failed stored nothing)
         return r;
     }
     *out = s;
@@ -552,23 +535,19 @@ int points_append(sdfk_points* s, const void* pts, int64_t n, bool device)
     if (s->n + n >= (int64_t(1) << 31)) return fail(SDFK_ERR_INVALID, "sdfk_points_add: 2^31 static points or more");
     if (n == 0) return SDFK_OK;
     // the concatenation, rebuilt; on a refusal the set stays as it was
+    static const char* who = "sdfk_points_add";
     sdfk_points t = *s;
     t.n = s->n + n;
-    t.xyz = nullptr;
     t.sorted = nullptr;
     t.starts = nullptr;
-    int r = dev_alloc((void**)&t.xyz, (size_t)t.n * 3 * sizeof(float));
-    if (!r) {
-        hipError_t e = hipMemcpyAsync(t.xyz, s->xyz, (size_t)s->n * 3 * sizeof(float), hipMemcpyDeviceToDevice, g.stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(t.xyz + s->n * 3, pts, (size_t)n * 3 * sizeof(float), device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, g.stream);
-        if (e != hipSuccess) r = fail(SDFK_ERR_HIP, "sdfk_points_add: %s", hipGetErrorString(e));
-    }
-    if (!r) r = points_build(&t, "sdfk_points_add");
-    if (r) {
-        points_release(&t);
-        return r;
-    }
+    Staged st;
+    t.xyz = st.kept<float>((size_t)t.n * 3);
+    st.run([&] { return hipMemcpyAsync(t.xyz, s->xyz, (size_t)s->n * 3 * sizeof(float), hipMemcpyDeviceToDevice, g.stream); });
+    st.run([&] {
+        return hipMemcpyAsync(t.xyz + s->n * 3, pts, (size_t)n * 3 * sizeof(float), device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, g.stream);
+    });
+    st.run([&] { return points_build(&t, who); });
+    if (int r = st.finish(who, false)) return r;   // (nothing of t to release: finish() freed its xyz, and a build that failed stored nothing)
     points_release(s);
     *s = t;
     return SDFK_OK;
@@ -578,62 +557,50 @@ int points_append(sdfk_points* s, const void* pts, int64_t n, bool device)
 int icp_run(sdfk_points* s, const sdfk_icp_params* prm, const float* normals_dev, float* pts_dev, int64_t n, float total[16], int32_t* iterations,
             int64_t* stats = nullptr)
 {
-    IcpState* S = nullptr;
-    float4* cor = nullptr;
-    IcpPlane* P = nullptr;
-    int32_t* index = nullptr;
     const bool plane = normals_dev != nullptr;
-    int r = dev_alloc((void**)&S, sizeof(IcpState));
-    if (!r) r = dev_alloc((void**)&cor, (size_t)n * sizeof(float4));
-    if (!r && plane) r = dev_alloc((void**)&P, sizeof(IcpPlane));
-    if (!r && plane) r = dev_alloc((void**)&index, (size_t)n * sizeof(int32_t));
+    Staged st;
+    IcpState* S = st.scratch<IcpState>(1);
+    float4* cor = st.scratch<float4>((size_t)n);
+    IcpPlane* P = plane ? st.scratch<IcpPlane>(1) : nullptr;
+    int32_t* index = plane ? st.scratch<int32_t>((size_t)n) : nullptr;
     IcpPlaneArgs B{index, normals_dev, P};
     struct { double count, rsq; int retained; } host_plane{};
     IcpArgs A{pts_dev, cor, n, prm->good_correspondence_distance, prm->converged_max_translation, prm->converged_max_rotation, prm->max_iterations, S};
-    hipError_t e = hipSuccess;
     struct { float total[16]; int iters, stop, converged; } host{};
     for (int q = 0; q < 16; q++) host.total[q] = (q % 5 == 0) ? 1.0f : 0.0f;
-    if (!r && prm->max_iterations > 0) {
-        hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, g.stream, S);
+    if (prm->max_iterations > 0) {
+        st.run([&] { hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, g.stream, S); });
         // Iterations are queued in chunks; the launches of an iteration after the one that stopped the registration exit at once
         // (they read the device flag), and the host looks at the flag between chunks.
         constexpr int kChunk = 4;
-        for (int it0 = 0; !r && e == hipSuccess && it0 < prm->max_iterations; it0 += kChunk) {
-            for (int it = it0; it < std::min(it0 + kChunk, prm->max_iterations) && !r; it++) {
-                SearchOut O{index, nullptr, nullptr, cor, nullptr};
-                r = points_search_launch(s, pts_dev, n, O, S, it);
-                if (r) break;
-                ProfScope ps(plane ? "k_icpp_step" : "k_icp_step");
-                launch_grid_sum(k_icp_dsum, g.stream, A, it);
-                launch_grid_sum(k_icp_dvar, g.stream, A, it);
-                hipLaunchKernelGGL(k_icp_dstats, dim3(1), dim3(kBlock), 0, g.stream, A, it);
-                if (plane) {
-                    launch_grid_sum(k_icpp_centre, g.stream, A, B, it);
-                    hipLaunchKernelGGL(k_icpp_mean, dim3(1), dim3(kBlock), 0, g.stream, A, B, it);
-                    launch_grid_sum(k_icpp_nsum, g.stream, A, B, it);
-                    hipLaunchKernelGGL(k_icpp_solve, dim3(1), dim3(kBlock), 0, g.stream, A, B, it);
-                } else {
-                    launch_grid_sum(k_icp_fsum, g.stream, A, it);
-                    hipLaunchKernelGGL(k_icp_means, dim3(1), dim3(kBlock), 0, g.stream, A, it);
-                    launch_grid_sum(k_icp_csum, g.stream, A, it);
-                    hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(kBlock), 0, g.stream, A, it);
-                }
-                hipLaunchKernelGGL(k_icp_apply, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, A, it);
-                e = hipGetLastError();
+        for (int it0 = 0; st.ok() && it0 < prm->max_iterations; it0 += kChunk) {
+            for (int it = it0; st.ok() && it < std::min(it0 + kChunk, prm->max_iterations); it++) {
+                st.run([&] { return points_search_launch(s, pts_dev, n, SearchOut{index, nullptr, nullptr, cor, nullptr}, S, it); });
+                st.run([&] {
+                    ProfScope ps(plane ? "k_icpp_step" : "k_icp_step");
+                    launch_grid_sum(k_icp_dsum, g.stream, A, it);
+                    launch_grid_sum(k_icp_dvar, g.stream, A, it);
+                    hipLaunchKernelGGL(k_icp_dstats, dim3(1), dim3(kBlock), 0, g.stream, A, it);
+                    if (plane) {
+                        launch_grid_sum(k_icpp_centre, g.stream, A, B, it);
+                        hipLaunchKernelGGL(k_icpp_mean, dim3(1), dim3(kBlock), 0, g.stream, A, B, it);
+                        launch_grid_sum(k_icpp_nsum, g.stream, A, B, it);
+                        hipLaunchKernelGGL(k_icpp_solve, dim3(1), dim3(kBlock), 0, g.stream, A, B, it);
+                    } else {
+                        launch_grid_sum(k_icp_fsum, g.stream, A, it);
+                        hipLaunchKernelGGL(k_icp_means, dim3(1), dim3(kBlock), 0, g.stream, A, it);
+                        launch_grid_sum(k_icp_csum, g.stream, A, it);
+                        hipLaunchKernelGGL(k_icp_solve, dim3(1), dim3(kBlock), 0, g.stream, A, it);
+                    }
+                    hipLaunchKernelGGL(k_icp_apply, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, A, it);
+                });
             }
-            if (r || e != hipSuccess) break;
-            e = hipMemcpyAsync(&host, &S->total, sizeof host, hipMemcpyDeviceToHost, g.stream);
-            if (e == hipSuccess && plane) e = hipMemcpyAsync(&host_plane, &P->count, sizeof host_plane, hipMemcpyDeviceToHost, g.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-            if (e != hipSuccess || host.stop) break;
+            if (plane) st.run([&] { return hipMemcpyAsync(&host_plane, &P->count, sizeof host_plane, hipMemcpyDeviceToHost, g.stream); });
+            st.read(&host, &S->total, sizeof host);
+            if (host.stop) break;
         }
     }
-    dev_free(cor);
-    dev_free(S);
-    dev_free(P);
-    dev_free(index);
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_icp_register: %s", hipGetErrorString(e));
+    if (int r = st.finish("sdfk_icp_register", false)) return r;
     for (int q = 0; q < 16; q++) total[q] = host.total[q];
     *iterations = host.iters;
     if (stats) {   // (of the last iteration run; no iteration: zeros)

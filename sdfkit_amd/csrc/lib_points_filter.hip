@@ -28,6 +28,7 @@
 //   k_of_sum / k_of_var / k_of_thr   the fixed-order reductions of device_reduce.h, as the ICP's: sum and count, squared
 //                  deviations, then mu, sigma and the threshold.
 //   k_of_flags     keep byte, flag and (float)mean; a scan; k_of_scatter writes the kept indices and points.
+// Host side: the scratch and the host forms' device copies are held in a Staged (device_stage.h).
 #include "lib_internal.h"
 #include "device_reduce.h"
 #include "device_scan.h"
@@ -199,37 +200,30 @@ int downsample(const sdfk_points* s, const DownArgs& A, float* points_out, int32
 {
     const char* who = colors3 ? "sdfk_points_voxel_downsample_colors" : "sdfk_points_voxel_downsample";
     const int64_t n = s->n;
-    Rec* ra = nullptr;
-    Rec* rb = nullptr;
+    Staged st;
+    Rec* ra = st.scratch<Rec>((size_t)n);
+    Rec* rb = st.scratch<Rec>((size_t)n);
     Rec* sorted = nullptr;
-    uint32_t* seg = nullptr;
-    uint32_t* first = nullptr;
-    uint32_t* start = nullptr;
-    double* csum = nullptr;
-    double* ccsum = nullptr;
-    hipError_t e = hipSuccess;
+    uint32_t* seg = st.scratch<uint32_t>((size_t)n + 1);
+    uint32_t* first = st.scratch<uint32_t>((size_t)n + 1);
     uint32_t m = 0;
-    int r = dev_alloc((void**)&ra, (size_t)n * sizeof(Rec));
-    if (!r) r = dev_alloc((void**)&rb, (size_t)n * sizeof(Rec));
-    if (!r) r = dev_alloc((void**)&seg, (size_t)(n + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&first, (size_t)(n + 1) * sizeof(uint32_t));
-    if (!r) {
+    st.run([&] {
         ProfScope ps("k_vf_keys");
         hipLaunchKernelGGL(k_vf_keys, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, s->xyz, n, A.L, ra);
-    }
-    if (!r) r = radix_sort(ra, rb, n, A.mask, &sorted, who);
-    if (!r) {
+    });
+    st.run([&] { return radix_sort(ra, rb, n, A.mask, &sorted, who); });
+    {
         ProfScope ps("k_vf_heads");
-        hipLaunchKernelGGL(k_vf_heads, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, sorted, n, seg, first);
-        r = sdfk_scan::scan(seg, n, who);
-        if (!r) r = sdfk_scan::scan(first, n, who);
+        st.run([&] { hipLaunchKernelGGL(k_vf_heads, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, sorted, n, seg, first); });
+        st.run([&] { return sdfk_scan::scan(seg, n, who); });
+        st.run([&] { return sdfk_scan::scan(first, n, who); });
     }
-    if (!r) e = read_back(&m, seg + n, sizeof m);
+    st.read(&m, seg + n, sizeof m);
     const int64_t slots = n / kChunk + (int64_t)m + 2;
-    if (!r && e == hipSuccess) r = dev_alloc((void**)&start, (size_t)(m + 1) * sizeof(uint32_t));
-    if (!r && e == hipSuccess && points_out) r = dev_alloc((void**)&csum, (size_t)slots * 3 * sizeof(double));
-    if (!r && e == hipSuccess && colors_out) r = dev_alloc((void**)&ccsum, (size_t)slots * 3 * sizeof(double));
-    if (!r && e == hipSuccess) {
+    uint32_t* start = st.scratch<uint32_t>((size_t)m + 1);
+    double* csum = points_out ? st.scratch<double>((size_t)slots * 3) : nullptr;
+    double* ccsum = colors_out ? st.scratch<double>((size_t)slots * 3) : nullptr;
+    st.run([&] {
         ProfScope ps("k_vf_centroids");
         hipLaunchKernelGGL(k_vf_starts, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, sorted, n, seg, m, start);
         if (points_out)
@@ -239,12 +233,8 @@ int downsample(const sdfk_points* s, const DownArgs& A, float* points_out, int32
             hipLaunchKernelGGL(k_vc_chunks, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, colors3, ccsum, slots);
             hipLaunchKernelGGL(k_vc_finish, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, sorted, n, seg, start, m, first, ccsum, slots, colors_out);
         }
-        e = hipGetLastError();
-    }
-    if (!r && e == hipSuccess) e = hipStreamSynchronize(g.stream);   // (the call returns when finished)
-    dev_free(ra); dev_free(rb); dev_free(seg); dev_free(first); dev_free(start); dev_free(csum); dev_free(ccsum);
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    });
+    if (int r = st.finish(who)) return r;   // (synchronises: the call returns when finished)
     if (m_out) *m_out = (int64_t)m;
     return SDFK_OK;
 }
@@ -367,50 +357,44 @@ int outliers(const sdfk_points* s, int k, float std_ratio, float max_distance, f
 {
     static const char* who = "sdfk_points_outliers";
     const int64_t n = s->n;
-    double* mean = nullptr;
-    uint32_t* flag = nullptr;
-    OfState* S = nullptr;
-    hipError_t e = hipSuccess;
-    int r = dev_alloc((void**)&mean, (size_t)n * sizeof(double));
-    if (!r) r = dev_alloc((void**)&flag, (size_t)(n + 1) * sizeof(uint32_t));
-    if (!r) r = dev_alloc((void**)&S, sizeof(OfState));
-    if (!r) {
+    Staged st;
+    double* mean = st.scratch<double>((size_t)n);
+    uint32_t* flag = st.scratch<uint32_t>((size_t)n + 1);
+    OfState* S = st.scratch<OfState>(1);
+    st.run([&] {
         ProfScope ps("k_of_mean");
         const float d2b = radius_d2_bound(max_distance);
         launch_tier(k, n, [&](auto cap, dim3 grid, dim3 block) {
             hipLaunchKernelGGL(k_of_mean<decltype(cap)::value>, grid, block, 0, g.stream, s->sorted, s->starts, s->G, s->xyz, n, k, d2b, mean);
         });
-    }
-    if (!r) {
+    });
+    st.run([&] {
         ProfScope ps("k_of_stats");
         launch_grid_sum(k_of_sum, g.stream, mean, n, S);
         launch_grid_sum(k_of_var, g.stream, mean, n, S);
         hipLaunchKernelGGL(k_of_thr, dim3(1), dim3(kBlock), 0, g.stream, S, std_ratio);
-    }
-    if (!r) {
+    });
+    {
         ProfScope ps("k_of_compact");
-        hipLaunchKernelGGL(k_of_flags, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, mean, n, S, mean_distance, keep, flag);
-        r = sdfk_scan::scan(flag, n, who);
-        if (!r && (index_out || points_out))
-            hipLaunchKernelGGL(k_of_scatter, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, mean, n, S, flag, s->xyz, index_out, points_out);
-        if (!r) e = hipGetLastError();
+        st.run([&] { hipLaunchKernelGGL(k_of_flags, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, mean, n, S, mean_distance, keep, flag); });
+        st.run([&] { return sdfk_scan::scan(flag, n, who); });
+        if (index_out || points_out)
+            st.run([&] { hipLaunchKernelGGL(k_of_scatter, dim3(grid_of(n, kBlock)), dim3(kBlock), 0, g.stream, mean, n, S, flag, s->xyz, index_out, points_out); });
     }
     uint32_t kept = 0;
-    double st[4] = {0, 0, 0, 0};   // mu, sigma, thr, c
-    if (!r && e == hipSuccess) e = hipMemcpyAsync(st, &S->mu, sizeof st, hipMemcpyDeviceToHost, g.stream);
-    if (!r && e == hipSuccess) e = read_back(&kept, flag + n, sizeof kept);   // (synchronises: the call returns when finished)
-    dev_free(mean); dev_free(flag); dev_free(S);
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    double sv[4] = {0, 0, 0, 0};   // mu, sigma, thr, c
+    st.run([&] { return hipMemcpyAsync(sv, &S->mu, sizeof sv, hipMemcpyDeviceToHost, g.stream); });
+    st.run([&] { return hipMemcpyAsync(&kept, flag + n, sizeof kept, hipMemcpyDeviceToHost, g.stream); });
+    if (int r = st.finish(who)) return r;   // (synchronises: the count and the statistics are read, and the call returns when finished)
     if (n_kept) *n_kept = (int64_t)kept;
     if (stats) {
-        const int64_t c = (int64_t)st[3];
+        const int64_t c = (int64_t)sv[3];
         stats[0] = (int64_t)kept;
         stats[1] = c - (int64_t)kept;
         stats[2] = n - c;
-        stats[3] = f64_bits(st[0]);
-        stats[4] = f64_bits(st[1]);
-        stats[5] = f64_bits(st[2]);
+        stats[3] = f64_bits(sv[0]);
+        stats[4] = f64_bits(sv[1]);
+        stats[5] = f64_bits(sv[2]);
     }
     return SDFK_OK;
 }

@@ -10,8 +10,10 @@
 // k - 1 (a voxel update reads the 6-neighbourhood only, so any other tile could not change: skipping it IS the full Jacobi
 // sweep).  A swept tile rewrites all of its 512 voxels, so both buffers agree on every tile that did not change last sweep.
 // Fixed point: ctl->last = the last sweep that changed a voxel (atomicMax); a sweep k > last + 1 returns at once, so the host
-// queues sweeps in batches and reads `last` once per batch.
+// queues sweeps in batches and reads `last` once per batch.  Host side: the buffers, the flags and the control block are the
+// scratch of a Staged (device_stage.h), which also makes the reads of the control block.
 #include "lib_internal.h"
+#include "device_stage.h"
 #include "redistance.h"
 
 namespace {
@@ -193,83 +195,67 @@ int redistance(const sdfk_volume* src, sdfk_volume* dst, const float d[3], float
     const int64_t tiles = (int64_t)G.tx * G.ty * G.tz;
     if (tiles >= (int64_t(1) << 31)) return fail(SDFK_ERR_INVALID, "%s: 2^31 tiles of 8^3 voxels or more", who);
     const int64_t nvox = (int64_t)G.nx * G.ny * G.nz;
-    float* t[2] = {nullptr, nullptr};
-    uint32_t* flag[2] = {nullptr, nullptr};
-    Ctl* ctl = nullptr;
+    Staged st;
+    Ctl* ctl = st.scratch<Ctl>(1);
     Ctl host{};
-    int r = dev_alloc((void**)&ctl, sizeof(Ctl));
-    hipError_t e = hipSuccess;
     // 1. refusal: the finite check, before anything of dst is touched
-    if (!r) {
+    {
         ProfScope ps("k_rd_check");
-        e = hipMemsetAsync(ctl, 0, sizeof(Ctl), g.stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_rd_check, dim3((unsigned)grid_for((size_t)nvox, kBlock, 4096)), dim3(kBlock), 0, g.stream, src->values, G, ctl);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&host, ctl, sizeof(Ctl), hipMemcpyDeviceToHost, g.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+        st.run([&] { return hipMemsetAsync(ctl, 0, sizeof(Ctl), g.stream); });
+        st.run([&] { hipLaunchKernelGGL(k_rd_check, dim3((unsigned)grid_for((size_t)nvox, kBlock, 4096)), dim3(kBlock), 0, g.stream, src->values, G, ctl); });
+        st.read(&host, ctl, sizeof(Ctl));
     }
-    if (r || e != hipSuccess || host.nonfinite) {
-        dev_free(ctl);
-        if (r) return r;
-        if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-        return fail(SDFK_ERR_INVALID, "%s: the volume holds a NaN or infinite value", who);
-    }
-    for (int b = 0; b < 2 && !r; b++) {
-        r = dev_alloc((void**)&t[b], (size_t)tiles * kTileVox * sizeof(float));
-        if (!r) r = dev_alloc((void**)&flag[b], (size_t)tiles * sizeof(uint32_t));
+    st.run([&] { return host.nonfinite ? fail(SDFK_ERR_INVALID, "%s: the volume holds a NaN or infinite value", who) : (int)SDFK_OK; });
+    float* t[2];
+    uint32_t* flag[2];
+    for (int b = 0; b < 2; b++) {
+        t[b] = st.scratch<float>((size_t)tiles * kTileVox);
+        flag[b] = st.scratch<uint32_t>((size_t)tiles);
     }
     // 2. front
-    if (!r) {
+    {
         ProfScope ps("k_rd_front");
-        e = hipMemsetAsync(&ctl->last, 0xff, sizeof(int), g.stream);   // -1: no front yet
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_rd_front, dim3((unsigned)tiles), dim3(kBlock), 0, g.stream, src->values, G, iso, t[0], t[1], flag[0], ctl);
-            e = hipGetLastError();
-        }
+        st.run([&] { return hipMemsetAsync(&ctl->last, 0xff, sizeof(int), g.stream); });   // -1: no front yet
+        st.run([&] { hipLaunchKernelGGL(k_rd_front, dim3((unsigned)tiles), dim3(kBlock), 0, g.stream, src->values, G, iso, t[0], t[1], flag[0], ctl); });
     }
     // 3 / 4. sweeps to the fixed point, a batch at a time
     int queued = 0;
-    while (!r && e == hipSuccess) {
-        {
+    while (st.ok()) {
+        st.run([&] {
             ProfScope ps("k_rd_sweep");
             for (int b = 0; b < kBatch; b++) {
                 const int k = ++queued;
                 hipLaunchKernelGGL(k_rd_sweep, dim3((unsigned)tiles), dim3(kBlock), 0, g.stream, G, band, k, t[(k - 1) & 1], t[k & 1], flag[(k - 1) & 1],
                                    flag[k & 1], ctl);
             }
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&host, ctl, sizeof(Ctl), hipMemcpyDeviceToHost, g.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-        if (e != hipSuccess || host.last < queued) break;   // the last queued sweep changed nothing (or never ran)
-        if (queued > (1 << 30)) { r = fail(SDFK_ERR_INVALID, "%s: no fixed point after 2^30 sweeps", who); break; }
+        });
+        st.read(&host, ctl, sizeof(Ctl));
+        if (!st.ok() || host.last < queued) break;   // the last queued sweep changed nothing (or never ran)
+        st.run([&] { return queued > (1 << 30) ? fail(SDFK_ERR_INVALID, "%s: no fixed point after 2^30 sweeps", who) : (int)SDFK_OK; });
     }
     // 5. result (both buffers agree at the fixed point)
-    if (!r && e == hipSuccess) {
+    if (st.ok()) {
         resolve_dependents(dst);   // (a queued mesh may still read the old values)
         volume_values_changed(dst);
         ProfScope ps("k_rd_finish");
-        hipLaunchKernelGGL(k_rd_finish, dim3((unsigned)((nvox + kBlock - 1) / kBlock)), dim3(kBlock), 0, g.stream, src->values, dst->values, G, iso, band,
-                           t[0], ctl);
-        e = hipGetLastError();
-        if (e == hipSuccess && dst->colors && dst != src) {
-            if (src->colors) e = hipMemcpyAsync(dst->colors, src->colors, src->nalloc() * 3 * sizeof(float), hipMemcpyDeviceToDevice, g.stream);
-            else e = hipMemsetAsync(dst->colors, 0, dst->nalloc() * 3 * sizeof(float), g.stream);
-        }
-        if (e == hipSuccess && stats) {
-            e = hipMemcpyAsync(&host, ctl, sizeof(Ctl), hipMemcpyDeviceToHost, g.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
-            stats[0] = host.last + 1;   // the sweeps of a full Jacobi iteration, the one that changes nothing included (0: no front)
-            stats[1] = (int64_t)host.tile_sweeps;
-            stats[2] = (int64_t)host.front;
-            stats[3] = (int64_t)host.clamped;
-        }
+        st.run([&] {
+            hipLaunchKernelGGL(k_rd_finish, dim3((unsigned)((nvox + kBlock - 1) / kBlock)), dim3(kBlock), 0, g.stream, src->values, dst->values, G, iso, band,
+                               t[0], ctl);
+        });
+        if (dst->colors && dst != src)
+            st.run([&] {
+                return src->colors ? hipMemcpyAsync(dst->colors, src->colors, src->nalloc() * 3 * sizeof(float), hipMemcpyDeviceToDevice, g.stream)
+                                   : hipMemsetAsync(dst->colors, 0, dst->nalloc() * 3 * sizeof(float), g.stream);
+            });
+        if (stats) st.read(&host, ctl, sizeof(Ctl));
     }
-    dev_free(t[0]); dev_free(t[1]); dev_free(flag[0]); dev_free(flag[1]); dev_free(ctl);   // (stream-ordered pool)
-    if (r) return r;
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (int r = st.finish(who, false)) return r;   // (no wait of its own: with stats the read above was one)
+    if (stats) {
+        stats[0] = host.last + 1;   // the sweeps of a full Jacobi iteration, the one that changes nothing included (0: no front)
+        stats[1] = (int64_t)host.tile_sweeps;
+        stats[2] = (int64_t)host.front;
+        stats[3] = (int64_t)host.clamped;
+    }
     return SDFK_OK;
 }
 

@@ -1,5 +1,8 @@
 // lib_volume.hip -- volumes (Voxels, Voxels.cs:8-65) and the sampling side of the path: Voxels.SampleSdf, ClipToBounds, SdfEx.Sample, RayMarcher.
+// A volume's own buffers are the handle's for its life; the device copies of a host form's arrays (upload's repitch, eval_points,
+// raymarch) are held in a Staged (device_stage.h).
 #include "lib_internal.h"
+#include "device_stage.h"
 
 // `values` no longer are what a program computed / what the cached sign bits describe
 void volume_values_changed(sdfk_volume* v)
@@ -128,21 +131,15 @@ extern "C" int sdfk_volume_upload(sdfk_volume* v, const float* values, const flo
     }
     // rows of nz % 4 != 0 voxels: the dense host layout goes to a temporary device array, a kernel spreads the rows out
     const size_t rows = (size_t)v->nx * v->ny;
-    float* tmp = nullptr;
-    if (int r = dev_alloc((void**)&tmp, v->nvox() * (colors3 ? 3 : 1) * sizeof(float))) return r;
-    hipError_t e = hipMemcpyAsync(tmp, values, v->nvox() * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_repitch<true>, dim3(grid_for(v->nvox())), dim3(256), 0, g.stream, tmp, v->values, rows, v->nz, v->pitch());
-        if (colors3) {
-            e = hipMemcpyAsync(tmp, colors3, v->nvox() * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(k_repitch<true>, dim3(grid_for(v->nvox() * 3)), dim3(256), 0, g.stream, tmp, v->colors, rows, v->nz * 3, v->pitch() * 3);
-        }
+    Staged st;
+    float* tmp = st.scratch<float>(v->nvox() * (colors3 ? 3 : 1));
+    st.run([&] { return hipMemcpyAsync(tmp, values, v->nvox() * sizeof(float), hipMemcpyHostToDevice, g.stream); });
+    st.run([&] { hipLaunchKernelGGL(k_repitch<true>, dim3(grid_for(v->nvox())), dim3(256), 0, g.stream, tmp, v->values, rows, v->nz, v->pitch()); });
+    if (colors3) {
+        st.run([&] { return hipMemcpyAsync(tmp, colors3, v->nvox() * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream); });
+        st.run([&] { hipLaunchKernelGGL(k_repitch<true>, dim3(grid_for(v->nvox() * 3)), dim3(256), 0, g.stream, tmp, v->colors, rows, v->nz * 3, v->pitch() * 3); });
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);   // the caller's arrays are not retained
-    dev_free(tmp);
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_volume_upload: %s", hipGetErrorString(e));
-    return SDFK_OK;
+    return st.finish("sdfk_volume_upload");   // (synchronises: the caller's arrays are not retained)
 }
 
 extern "C" int sdfk_volume_download(const sdfk_volume* v, float* values, float* colors3)
@@ -151,6 +148,7 @@ extern "C" int sdfk_volume_download(const sdfk_volume* v, float* values, float* 
     if (!v) return fail(SDFK_ERR_INVALID, "sdfk_volume_download: null volume");
     if (int r = require_init()) return r;
     std::vector<CopyPiece> pieces;
+    // (written out, not Staged: the copies go through copy_to_host's pieces and the host pool, not through a stream-ordered copy)
     float* dense_v = nullptr;   // rows of nz % 4 != 0 voxels: packed into dense temporaries first
     float* dense_c = nullptr;
     if (v->pitch() != v->nz) {
@@ -434,22 +432,12 @@ extern "C" int sdfk_eval_points(const sdfk_program* p, const float* points3, int
     if (n >= (int64_t(1) << 31) * 256) return fail(SDFK_ERR_INVALID, "sdfk_eval_points: too many points");
     if (int r = require_init()) return r;
     if (n == 0) return SDFK_OK;
-    float* pd = nullptr;
-    float* od = nullptr;
-    int r = dev_alloc((void**)&pd, (size_t)n * 3 * sizeof(float));
-    if (!r) r = dev_alloc((void**)&od, (size_t)n * 4 * sizeof(float));
-    hipError_t e = hipSuccess;
-    if (!r) e = hipMemcpyAsync(pd, points3, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, g.stream);
+    Staged st;
+    const float* pd = st.in(points3, (size_t)n * 3);
     // (a program that only assigns .W leaves X, Y, Z of the caller's elements alone, as the reference's delegates do: they travel there and back)
-    if (!r && e == hipSuccess && !p->writes_color) e = hipMemcpyAsync(od, rgbw4, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, g.stream);
-    if (!r && e == hipSuccess) r = eval_points_launch(p, pd, n, od);
-    if (!r && e == hipSuccess) e = hipMemcpyAsync(rgbw4, od, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, g.stream);
-    const hipError_t es = hipStreamSynchronize(g.stream);   // (the caller's arrays are not retained; the pool is stream-ordered)
-    dev_free(pd);
-    dev_free(od);
-    if (r) return r;
-    if (e != hipSuccess || es != hipSuccess) return fail(SDFK_ERR_HIP, "sdfk_eval_points: %s", hipGetErrorString(e != hipSuccess ? e : es));
-    return SDFK_OK;
+    float* od = p->writes_color ? st.out(rgbw4, (size_t)n * 4) : st.inout(rgbw4, (size_t)n * 4);
+    st.run([&] { return eval_points_launch(p, pd, n, od); });
+    return st.finish("sdfk_eval_points");   // (synchronises: the caller's arrays are not retained)
 }
 
 // ---------------------------------------------------------------------------
@@ -498,17 +486,10 @@ extern "C" int sdfk_raymarch(const sdfk_program* p, int32_t width, int32_t heigh
     if (int r = require_init()) return r;
     if (!depth && !rgb) return SDFK_OK;
     const size_t n = (size_t)width * height;
-    float* d = nullptr;
-    float* c = nullptr;
-    int r = SDFK_OK;
-    if (depth) r = dev_alloc((void**)&d, n * sizeof(float));
-    if (!r && rgb) r = dev_alloc((void**)&c, n * 3 * sizeof(float));
-    if (!r) r = raymarch_launch(p, width, height, camera_position, view_projection_inverse, near_plane, far_plane, depth_iterations, d, c);
-    if (!r && depth && hipMemcpyAsync(depth, d, n * sizeof(float), hipMemcpyDeviceToHost, g.stream) != hipSuccess) r = fail(SDFK_ERR_HIP, "copy of the depth image failed");
-    if (!r && rgb && hipMemcpyAsync(rgb, c, n * 3 * sizeof(float), hipMemcpyDeviceToHost, g.stream) != hipSuccess) r = fail(SDFK_ERR_HIP, "copy of the colour image failed");
-    if (hipStreamSynchronize(g.stream) != hipSuccess && !r) r = fail(SDFK_ERR_HIP, "hipStreamSynchronize failed");
-    dev_free(d);
-    dev_free(c);
-    return r;
+    Staged st;
+    float* d = st.out(depth, n);
+    float* c = st.out(rgb, n * 3);
+    st.run([&] { return raymarch_launch(p, width, height, camera_position, view_projection_inverse, near_plane, far_plane, depth_iterations, d, c); });
+    return st.finish("sdfk_raymarch");
 }
 

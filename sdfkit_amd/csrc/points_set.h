@@ -1,6 +1,7 @@
 // points_set.h -- the handle behind sdfk_points_* (KdTree): the static points and their search grid, built by lib_points.hip and
 // read by every query of the family (lib_points.hip, lib_points_knn.hip, lib_pointcloud.hip, lib_orient.hip, lib_points_filter.hip) through the walk of
-// points_walk.h.  What owns the copies between host and device (Staged, read_back) is in device_stage.h, included here for them.
+// points_walk.h.  What owns the device memory of one call (Staged: the scratch of a work function, what the handle adopts, the
+// device copies of a host form's arrays) is in device_stage.h, included here for them.
 #pragma once
 #include "lib_internal.h"
 #include "device_stage.h"

@@ -76,7 +76,8 @@ def _device_array(a):
 
 def _call(name, pre, outs, scalars, only=None, device=False):
     """L.<name>(*pre, *outputs, *scalars) or its _device form.  outs: (dtype, shape) per optional output array, each filled with
-    the canary; all are passed, or the one at index `only` and null for the rest.  pre: leading arguments; a numpy array among
+    the canary (or (dtype, array): an array the call updates in place, which starts as a copy of that one); all are passed, or
+    the one at index `only` and null for the rest.  pre: leading arguments; a numpy array among
     them is passed by pointer, from device memory for the device form.  -> ([array or None per output], scalar values)."""
     L = N.lib()
     hold, args, back = [], [], []
@@ -94,7 +95,7 @@ def _call(name, pre, outs, scalars, only=None, device=False):
             args.append(None)
             back.append(None)
             continue
-        a = np.full(shape, CANARY, dt)
+        a = np.array(shape, dt) if isinstance(shape, np.ndarray) else np.full(shape, CANARY, dt)
         hold.append(_device_array(a) if device else a)
         args.append(C.c_void_p(hold[-1].data_ptr()) if device else _vp(a))
         back.append(hold[-1])
