@@ -986,6 +986,72 @@ public:
         }
         return r;
     }
+    struct ClusterStats { int64_t Clusters = 0, Core = 0, Border = 0, Noise = 0, Rounds = 0, Shortcuts = 0; };
+    struct Clustered {
+        std::vector<int32_t> Labels;     // per static point: its cluster, -1: noise
+        std::vector<int32_t> Sizes;      // per cluster: its members, core and border
+        std::vector<uint8_t> Core;       // per static point: 1 iff Counts >= minPoints
+        std::vector<int32_t> Counts;     // per static point: the static points within the radius, itself and its duplicates included
+    };
+    struct Selected {
+        std::vector<Vector3> Points;     // the kept points, in insertion order
+        std::vector<int32_t> Indices;    // their indices, ascending
+        std::vector<int32_t> Labels;     // RemoveSmallClusters only: Clusters' labels of all static points
+    };
+    // Density clustering of the static points (DBSCAN; minPoints = 1: Euclidean cluster extraction): a point is core iff at least
+    // minPoints static points lie within the radius (sqrtf(d2) <= radius, itself included); clusters are the connected components
+    // of the core points, numbered by their lowest core member; any other point takes the cluster of the core point within the radius
+    // that is first in (d2, index) order, or is noise (-1).  The result depends on no order.
+    Clustered Clusters(float radius, int minPoints = 1, ClusterStats* stats = nullptr) const
+    {
+        Clustered r;
+        const size_t n = (size_t)TotalPoints();
+        r.Labels.resize(n);
+        r.Sizes.resize(n);
+        r.Core.resize(n);
+        r.Counts.resize(n);
+        int64_t c = 0, st[6] = {0, 0, 0, 0, 0, 0};
+        Check(sdfk_points_cluster(h_, radius, minPoints, r.Labels.data(), r.Sizes.data(), r.Core.data(), r.Counts.data(), &c, st));
+        r.Sizes.resize((size_t)c);
+        if (stats) *stats = ClusterStats{st[0], st[1], st[2], st[3], st[4], st[5]};
+        return r;
+    }
+    // The static points whose cluster is kept: 0 <= label < keep.size() and keep[label] != 0.  labels: one per static point,
+    // Clusters' or any other.
+    Selected SelectClusters(const std::vector<int32_t>& labels, const std::vector<uint8_t>& keep) const
+    {
+        if ((int64_t)labels.size() != (int64_t)TotalPoints()) throw std::invalid_argument("one label per static point (labels)");
+        Selected r;
+        const size_t n = labels.size();
+        r.Points.resize(n);
+        r.Indices.resize(n);
+        int64_t kept = 0;
+        Check(sdfk_points_select(h_, labels.data(), keep.empty() ? nullptr : keep.data(), (int64_t)keep.size(), r.Indices.data(), &r.Points[0].X, &kept));
+        r.Points.resize((size_t)kept);
+        r.Indices.resize((size_t)kept);
+        return r;
+    }
+    // Clusters, then the points of the clusters of at least minSize members; noise goes.
+    Selected RemoveSmallClusters(float radius, int minPoints = 1, int minSize = 2, ClusterStats* stats = nullptr) const
+    {
+        Clustered c = Clusters(radius, minPoints, stats);
+        std::vector<uint8_t> keep(c.Sizes.size());
+        for (size_t i = 0; i < keep.size(); i++) keep[i] = c.Sizes[i] >= minSize ? 1 : 0;
+        Selected r = SelectClusters(c.Labels, keep);
+        r.Labels = std::move(c.Labels);
+        return r;
+    }
+    // Clusters, then the points of the cluster of greatest size (ties: the lowest number); nothing without a cluster.
+    Selected LargestCluster(float radius, int minPoints = 1) const
+    {
+        const Clustered c = Clusters(radius, minPoints);
+        std::vector<uint8_t> keep(c.Sizes.size(), 0);
+        size_t best = 0;
+        for (size_t i = 1; i < keep.size(); i++)
+            if (c.Sizes[i] > c.Sizes[best]) best = i;
+        if (!keep.empty()) keep[best] = 1;
+        return SelectClusters(c.Labels, keep);
+    }
     struct VolumeStats { int64_t Known = 0, Unknown = 0, Candidates = 0, Queries = 0; };
     // The cloud with one outward normal per static point as a signed distance volume: the blend of the tangent-plane distances of the
     // k nearest points within maxDistance; voxels beyond get +-maxDistance (give a band, then Voxels::Redistance, for a full field).

@@ -43,7 +43,8 @@ extern "C" {
                                    sdfk_points_blend_colors* / sdfk_points_to_volume_colors* / sdfk_points_voxel_downsample_colors* (point
                                    clouds: per-point colours);
                                    sdfk_trimesh_components* / sdfk_trimesh_topology* / sdfk_trimesh_select* (triangle meshes: components,
-                                   edge census, sub-meshes) */
+                                   edge census, sub-meshes);
+                                   sdfk_points_cluster* / sdfk_points_select* (point clouds: clusters) */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -801,6 +802,55 @@ int sdfk_points_voxel_downsample_colors(const sdfk_points* s, float voxel_size, 
 int sdfk_points_voxel_downsample_colors_device(const sdfk_points* s, float voxel_size, const float origin[3] /* host */,
                                                const void* colors3_dev, void* points_out_dev, void* counts_dev, void* group_dev,
                                                void* colors_out_dev, int64_t* m);
+/* ---- Point clouds: clusters (extension) -----------------------------------------------------------------------------------------
+ * "Which points belong together": density clustering of the static points p_i (insertion order, n of them) of a set -- DBSCAN, with
+ * Euclidean cluster extraction as its min_points = 1 case.  sdfk_points_outliers removes lone strays; a floating clump of returns
+ * (a hand, a tripod, a second object) has small neighbour distances and survives it: sdfk_points_cluster finds it and
+ * sdfk_points_select removes it, or splits a scene into objects, before normals, volumes and registration.  Neither changes the
+ * set: the caller makes a new one from the result.  The result is ONE function of the inputs with integer outputs only, its
+ * decisions written once for device and host in csrc/points_cluster.h, restated in tests/points_cluster_model.py and compared as
+ * bits, whatever order the atomics of the label rounds land in.
+ *
+ * within(i, j) holds iff j is in the sdfk_points_radius_* result of the query p_i for `radius`: the same d2 formula, the same
+ * "counts" rule (sqrtf(d2) < FLT_MAX) and the same predicate sqrtf(d2) <= radius on the f32 distance.  d2 is symmetric bit for bit
+ * ((a - b)^2 == (b - a)^2 in binary32), so within is symmetric; within(i, i) holds for every point with finite coordinates.
+ * 1. Count: count_i = the number of j with within(i, j), the point itself and its duplicates included; an int32 that saturates at
+ *    INT32_MAX (unreachable below 2^31 points).
+ * 2. Core: core_i iff count_i >= min_points.
+ * 3. Clusters: the connected components of the graph on the core points with an edge wherever within holds, numbered 0 .. C - 1 in
+ *    ascending order of their lowest core member.
+ * 4. Border: a point that is not core and has at least one core point within the radius gets the cluster of the core point that is
+ *    first in (d2, index) order: equal d2 goes to the lower INDEX, never to the lower cluster number.  (Classical DBSCAN gives such
+ *    a point to whichever cluster reaches it first; this rule depends on no order.)
+ * 5. Noise: every other point gets the label -1.
+ * 6. Sizes: sizes[c] = the members of cluster c, core and border.
+ * 7. Reductions: min_points = 1 is Euclidean clustering -- every point (of finite coordinates) is core and nothing is noise;
+ *    radius = 0 clusters exact duplicates only; radius = +inf makes every counting point a neighbour.
+ * 8. SDFK_ERR_INVALID, outputs and stats untouched: a NULL set; a radius that is NaN or negative; min_points < 1.
+ * Outputs, the caller's, any NULL: labels n x int32; sizes, capacity n x int32, C entries written, entries from C on left as they
+ * were; core n x uint8; counts n x int32; *n_clusters = C.  stats (may be NULL): [0] clusters, [1] core, [2] border, [3] noise
+ * points, [4] hook rounds, [5] shortcut launches that worked -- the last two are diagnostics that may vary from run to run.
+ * How: one lane per point on the shell walk of every KdTree query; labels by min-hooking with atomicMin and pointer jumping, every
+ * hook round repeating the walk -- no edge list is stored.  Temporaries of a call, freed at its end: 8 n bytes (the parents, the
+ * root numbers) and n bytes / 4 n bytes for a core / labels array the caller left NULL.  While sdfk_profile_enable(1) is on,
+ * sdfk_points_stats[3..4] report the candidates of all walks of the call and n.
+ *
+ * sdfk_points_select: the points of the kept clusters.  labels: one int32 per static point -- sdfk_points_cluster's, or any other:
+ * a point is KEPT iff 0 <= label < n_clusters and keep[label] != 0 (keep: n_clusters bytes, as sdfk_trimesh_select's; not read for
+ * any other label).  index_out: the kept indices, ascending; points_out: the kept points, ready for sdfk_points_create[_device];
+ * each of capacity n, either may be NULL, entries from n_kept on left as they were; *n_kept (may be NULL) receives their number.
+ * n_clusters = 0 keeps nothing.  SDFK_ERR_INVALID, outputs untouched: a NULL set, NULL labels, n_clusters < 0, NULL keep with
+ * n_clusters > 0.  Temporaries: 4 n bytes.
+ * Nothing is kept on the handle.  The host forms take host arrays and are synchronous.  The _device forms take caller-owned device
+ * buffers (keep_dev too), run on the library stream and have finished when they return (they read C / n_kept on the way). */
+int sdfk_points_cluster(const sdfk_points* s, float radius, int32_t min_points, int32_t* labels /* n */, int32_t* sizes /* capacity n */,
+                        uint8_t* core /* n */, int32_t* counts /* n */, int64_t* n_clusters, int64_t stats[6]);
+int sdfk_points_cluster_device(const sdfk_points* s, float radius, int32_t min_points, void* labels_dev, void* sizes_dev, void* core_dev,
+                               void* counts_dev, int64_t* n_clusters, int64_t stats[6]);
+int sdfk_points_select(const sdfk_points* s, const int32_t* labels /* n */, const uint8_t* keep /* n_clusters bytes */, int64_t n_clusters,
+                       int32_t* index_out /* n */, float* points_out /* n*3 */, int64_t* n_kept);
+int sdfk_points_select_device(const sdfk_points* s, const void* labels_dev, const void* keep_dev, int64_t n_clusters, void* index_out_dev,
+                              void* points_out_dev, int64_t* n_kept);
 /* IterativeClosestPoint.RegisterPoints (IterativeClosestPoint.cs:53-196): rigidly moves the caller's points (in place) onto the
  * static set and returns the total transform (row-major M11..M44, System.Numerics row-vector convention) and the number of
  * iterations run.  Each iteration is the reference's: nearest static point of every point, the piecewise distMax from the

@@ -145,6 +145,10 @@ SIGNATURES = {
     "sdfk_points_to_volume_colors_device": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f, C.POINTER(_i64)]),
     "sdfk_points_voxel_downsample_colors": (C.c_int, [_vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
     "sdfk_points_voxel_downsample_colors_device": (C.c_int, [_vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "sdfk_points_cluster": (C.c_int, [_vp, _f, _i32, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sdfk_points_cluster_device": (C.c_int, [_vp, _f, _i32, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "sdfk_points_select": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, C.POINTER(_i64)]),
+    "sdfk_points_select_device": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     "sdfk_points_free": (None, [_vp]),
     "sdfk_trimesh_create": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vpp]),
     "sdfk_trimesh_create_device": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vpp]),

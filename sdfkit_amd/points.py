@@ -5,7 +5,8 @@ Vector3 is a float32 numpy array of 3; a span of Vector3 is an (n, 3) float32 ar
 point of least d2, ties to the lowest insertion index; SearchKNearest and
 SearchRadius extend it to the k nearest and to all within a radius, in the same (d2, index) order; EstimateNormals, OrientNormals
 and ToVoxels turn the points into normals, orient them consistently and make a signed distance volume; VoxelDownsample and
-RemoveStatisticalOutliers thin merged scans and drop stray points; SampleColors, ToVoxels(colors=) and VoxelDownsample(colors=)
+RemoveStatisticalOutliers thin merged scans and drop stray points; Clusters, SelectClusters, RemoveSmallClusters and
+LargestCluster tell which points belong together; SampleColors, ToVoxels(colors=) and VoxelDownsample(colors=)
 carry per-point colours along); the structure behind it is a grid of cell lists on the device,
 so the reference's tree internals -- Left, Right, SplitValue, IsLeaf -- are not provided.  SplitAxis is kept as given.
 """
@@ -206,6 +207,60 @@ class KdTree:
             mu, sigma, thr = np.array(st[3:6], np.int64).view(np.float64)
             stats.update(kept=int(st[0]), removed=int(st[1]), isolated=int(st[2]), mu=float(mu), sigma=float(sigma), threshold=float(thr))
         return pts[:kept.value].copy(), idx[:kept.value].copy(), mean
+
+    def Clusters(self, radius, minPoints=1, stats=None):
+        """Extension: density clustering of the static points (DBSCAN; minPoints = 1: Euclidean cluster extraction)
+        -> (labels (n,) int32, sizes (C,) int32, core (n,) bool, counts (n,) int32).  counts: the static points within `radius` of
+        each point (sqrtf(d2) <= radius, as SearchRadius; the point itself and its duplicates included); a point is core iff its
+        count is at least minPoints; clusters are the connected components of the core points under "within radius", numbered by
+        their lowest core member; a point that is not core takes the cluster of the core point within the radius that is first in
+        (d2, index) order -- so the result does not depend on any order -- and is noise, label -1, without one; sizes counts core
+        and border members (include/sdfkit_hip.h, "Point clouds: clusters").  The tree is not changed.  stats: a dict that receives
+        clusters, core, border, noise, rounds, shortcuts."""
+        n = self.TotalPoints
+        labels = np.empty(n, np.int32)
+        sizes = np.empty(n, np.int32)
+        core = np.empty(n, np.uint8)
+        counts = np.empty(n, np.int32)
+        c = C.c_int64()
+        st = (C.c_int64 * 6)()
+        N.check(N.lib().sdfk_points_cluster(self._h, float(f32(radius)), int(minPoints), _ptr(labels), _ptr(sizes), _ptr(core), _ptr(counts),
+                                            C.byref(c), st))
+        if stats is not None:
+            stats.update(clusters=int(st[0]), core=int(st[1]), border=int(st[2]), noise=int(st[3]), rounds=int(st[4]), shortcuts=int(st[5]))
+        return labels, sizes[:c.value].copy(), core.astype(bool), counts
+
+    def SelectClusters(self, labels, keep):
+        """Extension: the static points whose cluster is kept -> (points (kept, 3) float32, indices (kept,) int32 ascending).
+        labels: one int32 per static point, Clusters' or any other; keep: one flag per cluster; a point is kept iff
+        0 <= label < len(keep) and keep[label].  Per-point data of the kept points is data[indices]; make a new KdTree from the
+        points."""
+        n = self.TotalPoints
+        lab = np.ascontiguousarray(np.asarray(labels, dtype=np.int32).reshape(-1))
+        if len(lab) != n:
+            raise ValueError("one label per static point (labels)")
+        kp = np.ascontiguousarray(np.asarray(keep).astype(bool).reshape(-1).astype(np.uint8))
+        pts = np.empty((n, 3), f32)
+        idx = np.empty(n, np.int32)
+        kept = C.c_int64()
+        N.check(N.lib().sdfk_points_select(self._h, _ptr(lab), _ptr(kp), len(kp), _ptr(idx), _ptr(pts), C.byref(kept)))
+        return pts[:kept.value].copy(), idx[:kept.value].copy()
+
+    def RemoveSmallClusters(self, radius, minPoints=1, minSize=2, stats=None):
+        """Extension: Clusters, then the points of the clusters of at least minSize members; noise goes
+        -> (points, indices, labels (n,) int32: Clusters' labels of all static points)."""
+        labels, sizes, _, _ = self.Clusters(radius, minPoints, stats)
+        pts, idx = self.SelectClusters(labels, sizes >= int(minSize))
+        return pts, idx, labels
+
+    def LargestCluster(self, radius, minPoints=1):
+        """Extension: Clusters, then the points of the cluster of greatest size (ties: the lowest number) -> (points, indices);
+        nothing when there is no cluster."""
+        labels, sizes, _, _ = self.Clusters(radius, minPoints)
+        keep = np.zeros(len(sizes), bool)
+        if len(sizes):
+            keep[int(np.argmax(sizes))] = True   # (argmax: the first of the greatest)
+        return self.SelectClusters(labels, keep)
 
     def ToVoxels(self, normals, min, max, nx, ny, nz, k=8, maxDistance=np.inf, clipToBounds=False, stats=None, colors=None):
         """Extension: the point cloud with `normals` (one per static point, pointing outside) as a signed distance volume at the

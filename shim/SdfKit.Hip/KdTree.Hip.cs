@@ -223,6 +223,81 @@ namespace SdfKit
             return points;
         }
 
+        /// <summary>Extension: density clustering of the static points (DBSCAN; minPoints = 1: Euclidean cluster extraction).  A point
+        /// is core iff at least minPoints static points lie within radius (sqrtf(d2) &lt;= radius, itself and its duplicates included:
+        /// counts); clusters are the connected components of the core points, numbered by their lowest core member; any other point
+        /// takes the cluster of the core point within radius that is first in (d2, index) order, or is noise, label -1.  sizes: the
+        /// members per cluster, core and border; stats: clusters, core, border, noise, hook rounds, shortcut launches.  The result
+        /// depends on no order.  The tree is not changed.</summary>
+        public unsafe int[] Clusters (float radius, out int[] sizes, out bool[] core, out int[] counts, out long[] stats, int minPoints = 1)
+        {
+            if (!(radius >= 0))
+                throw new ArgumentOutOfRangeException (nameof (radius), "radius must not be negative or NaN");
+            if (minPoints < 1)
+                throw new ArgumentOutOfRangeException (nameof (minPoints), "minPoints must be at least 1");
+            int n = TotalPoints;
+            var labels = new int[n];
+            var size = new int[n];
+            var coreBytes = new byte[n];
+            counts = new int[n];
+            stats = new long[6];
+            long c = 0;
+            fixed (int* l = labels) fixed (int* s = size) fixed (byte* cb = coreBytes) fixed (int* cn = counts) fixed (long* st = stats)
+                Native.Check (Native.sdfk_points_cluster (handle, radius, minPoints, l, s, cb, cn, &c, st));
+            Array.Resize (ref size, (int)c);
+            sizes = size;
+            core = new bool[n];
+            for (int i = 0; i < n; i++)
+                core[i] = coreBytes[i] != 0;
+            return labels;
+        }
+
+        /// <summary>Extension: the static points whose cluster is kept: 0 &lt;= labels[i] &lt; keep.Length and keep[labels[i]].  labels:
+        /// one per static point, Clusters' or any other.  indices: the kept indices, ascending; per-point data of the kept points is
+        /// data[indices[i]].  Make a new KdTree from the result.</summary>
+        public unsafe Vector3[] SelectClusters (ReadOnlySpan<int> labels, ReadOnlySpan<bool> keep, out int[] indices)
+        {
+            int n = TotalPoints;
+            if (labels.Length != n)
+                throw new ArgumentException ("One label per static point", nameof (labels));
+            var keepBytes = new byte[Math.Max (1, keep.Length)];
+            for (int i = 0; i < keep.Length; i++)
+                keepBytes[i] = keep[i] ? (byte)1 : (byte)0;
+            var points = new Vector3[n];
+            var idx = new int[n];
+            long kept = 0;
+            fixed (int* l = labels) fixed (byte* k = keepBytes) fixed (Vector3* p = points) fixed (int* i = idx)
+                Native.Check (Native.sdfk_points_select (handle, l, k, keep.Length, i, (float*)p, &kept));
+            Array.Resize (ref points, (int)kept);
+            Array.Resize (ref idx, (int)kept);
+            indices = idx;
+            return points;
+        }
+
+        /// <summary>Extension: Clusters, then the points of the clusters of at least minSize members; noise goes.  labels: Clusters'
+        /// labels of all static points.</summary>
+        public Vector3[] RemoveSmallClusters (float radius, out int[] indices, out int[] labels, int minPoints = 1, int minSize = 2)
+        {
+            labels = Clusters (radius, out int[] sizes, out _, out _, out _, minPoints);
+            var keep = new bool[sizes.Length];
+            for (int c = 0; c < keep.Length; c++)
+                keep[c] = sizes[c] >= minSize;
+            return SelectClusters (labels, keep, out indices);
+        }
+
+        /// <summary>Extension: Clusters, then the points of the cluster of greatest size (ties: the lowest number); nothing when there
+        /// is no cluster.</summary>
+        public Vector3[] LargestCluster (float radius, out int[] indices, int minPoints = 1)
+        {
+            int[] labels = Clusters (radius, out int[] sizes, out _, out _, out _, minPoints);
+            var keep = new bool[sizes.Length];
+            int best = 0;
+            for (int c = 1; c < sizes.Length; c++)
+                if (sizes[c] > sizes[best]) best = c;
+            if (keep.Length > 0) keep[best] = true;
+            return SelectClusters (labels, keep, out indices);
+        }
+
         /// <summary>Extension: the static points with one outward normal each as a signed distance volume: the blend of the
         /// tangent-plane distances of the k nearest points (1..64) within maxDistance at every cell centre; voxels farther away
         /// get +-maxDistance, the sign carried over from the known ones.  Give a band, then Voxels.Redistance, for a full field.</summary>

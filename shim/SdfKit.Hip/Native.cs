@@ -125,6 +125,14 @@ namespace SdfKit.Hip
             float* pointsOut, long* nKept, long* stats6);
         [DllImport(Lib)] public static extern int sdfk_points_outliers_device(IntPtr points, int k, float stdRatio, float maxDistance, IntPtr meanDistanceDev, IntPtr keepDev,
             IntPtr indexOutDev, IntPtr pointsOutDev, long* nKept, long* stats6);
+        // point clouds: clusters (KdTree.Hip.cs)
+        [DllImport(Lib)] public static extern int sdfk_points_cluster(IntPtr points, float radius, int minPoints, int* labels, int* sizes, byte* core, int* counts,
+            long* nClusters, long* stats6);
+        [DllImport(Lib)] public static extern int sdfk_points_cluster_device(IntPtr points, float radius, int minPoints, IntPtr labelsDev, IntPtr sizesDev, IntPtr coreDev,
+            IntPtr countsDev, long* nClusters, long* stats6);
+        [DllImport(Lib)] public static extern int sdfk_points_select(IntPtr points, int* labels, byte* keep, long nClusters, int* indexOut, float* pointsOut, long* nKept);
+        [DllImport(Lib)] public static extern int sdfk_points_select_device(IntPtr points, IntPtr labelsDev, IntPtr keepDev, long nClusters, IntPtr indexOutDev,
+            IntPtr pointsOutDev, long* nKept);
         // point clouds: per-point colours (KdTree.Hip.cs)
         [DllImport(Lib)] public static extern int sdfk_points_blend_colors(IntPtr points, float* colors3, float* queries3, long nQueries, int k, float maxDistance,
             float* colorsOut, int* found);
