@@ -1,6 +1,7 @@
 """Mesh.SamplePoints on the MI355X (sdfk_trimesh_sample[_device], csrc/lib_trimesh.hip: k_tm_area2, k_tm_sample_weights, the 64-bit
 scan, k_tm_sample) against the numpy model (tests/mesh_sample_model.py), bit for bit, in both modes, on the smallest meshes at
-which each part can go wrong (tests/mesh_sample_cases.py).  Nothing here has a tolerance of its own: points, normals, colours,
+which each part can go wrong (tests/mesh_sample_cases.py); meshes that are mostly degenerate -- random index soups, 300 of them
+laid over each other -- are in tests/test_gpu_mesh_stress.py.  Nothing here has a tolerance of its own: points, normals, colours,
 triangle indices, weights and stats are compared as bits; the two bounds that appear (2^-23 M for the distance of a sample from
 its triangle; the registration residual) are the model's."""
 import ctypes as C

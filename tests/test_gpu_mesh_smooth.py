@@ -1,9 +1,11 @@
 """Mesh adjacency, smoothing and vertex normals on the MI355X (sdfk_trimesh_adjacency / _smooth / _vertex_normals and their
 _device forms, csrc/lib_trimesh_smooth.hip) against the numpy model (tests/mesh_smooth_model.py).  Every output is one stated
-function of the input, so everything is compared as bits or integers.  The meshes are the smallest at which each part can go
-wrong (tests/mesh_smooth_cases.py): the hand-made shapes, a vertex whose degree crosses a block, sizes on both sides of the
+function of the input, so everything is compared as bits or integers.  The meshes are small, tidy ones
+(tests/mesh_smooth_cases.py): the hand-made shapes, a vertex whose degree crosses a block, sizes on both sides of the
 2048-record sort tile for both sorts, of the third key byte, a permuted grid, a marching-cubes sphere far from the origin and at
-subnormal scale."""
+subnormal scale.  On all of them any order of a vertex's adds rounds to the same float32, and no vertex has more than 301
+neighbours; hubs of 5001 neighbours and 5000 corners (runs longer than a sort tile), random index soups and the mesh on which
+only the stated order of the adds gives the right bits are in tests/test_gpu_mesh_stress.py."""
 import ctypes as C
 import functools
 

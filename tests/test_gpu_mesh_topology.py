@@ -1,8 +1,10 @@
 """Mesh topology on the MI355X (sdfk_trimesh_components / _topology / _select and their _device forms,
 csrc/lib_trimesh_topology.hip) against the numpy model (tests/mesh_topology_model.py).  Every output is an integer (or a gathered
 float) and unique given the input, so everything is compared for equality: labels, component rows, the census, the selection.
-The meshes are the smallest at which each part can go wrong (tests/mesh_topology_cases.py): the hand-made shapes, sizes on both
-sides of a 256-lane block, of the 2048-record sort tile and scan block, of the third key byte, deep label trees, many components."""
+The meshes are small, tidy ones (tests/mesh_topology_cases.py): the hand-made shapes, sizes on both sides of a 256-lane block, of
+the 2048-record sort tile and scan block, of the third key byte, deep label trees, 300 components.  No edge here has more than 3
+triangles; random index soups, an edge of 5000 triangles (a run longer than a sort tile) and 70 000 components are in
+tests/test_gpu_mesh_stress.py."""
 import ctypes as C
 import functools
 

@@ -1,6 +1,7 @@
 """Mesh welding on the MI355X (sdfk_trimesh_weld and its _device form, csrc/lib_trimesh_weld.hip) against the numpy model
 (tests/mesh_weld_model.py).  Every output is one stated function of the input, so everything is compared as bits or integers.
-The meshes are the smallest at which each part can go wrong (tests/mesh_weld_cases.py): soups of hand-made shapes, pairs that
+The meshes are small, tidy ones, no group of more than 6 vertices (a weld group longer than two sort tiles, random index soups
+and the lattice's cell faces at zero and below are in tests/test_gpu_mesh_stress.py): soups of hand-made shapes, pairs that
 differ in one coordinate (the boundary between the two sorts), -0 against +0, one group, duplicates at the first and last index,
 sizes on both sides of the 256-lane block, the 2048-value scan block and the 2048-record sort tile, a permuted soup whose groups
 straddle tiles, every flag, colours, far from the origin and at subnormal scale, the lattice mode at cell centres and across a
