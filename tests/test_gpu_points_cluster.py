@@ -59,6 +59,11 @@ def check(P, radius, min_points, tree=None, rows=None, recorded=None):
     want = CM.cluster(P, radius, min_points, rows)
     if recorded is not None:
         assert want["stats"] == recorded["stats"], (want["stats"], recorded)
+    return check_against(want, P, radius, min_points, tree)
+
+
+def check_against(want, P, radius, min_points, tree=None):
+    """check, against a result of the model that the caller has already."""
     tree = tree or KdTree(P)
     n = len(P)
     for got in (cluster_host(tree, radius, min_points), cluster_host(tree, radius, min_points), cluster_device(tree, radius, min_points)):
