@@ -379,11 +379,30 @@ struct MeshWeld {
     int64_t Merged = 0, DegenerateDropped = 0, UnreferencedDropped = 0, Passes = 0;
 };
 
+// MeshSdf::Simplify: MeshWeld's fields for the clustered mesh -- VertexMap (one per old vertex: the new number of its group, -1:
+// dropped), the representatives' old indices, the kept triangles' old indices, the renumbered index array, the MADE positions and
+// colours -- and the triangles dropped for sharing a vertex set with another, and the kept groups whose quadric placement fell
+// back to the centroid.
+struct MeshSimplify : MeshWeld {
+    int64_t DuplicatesDropped = 0, QuadricFallbacks = 0;
+};
+enum class SimplifyPlacement : int32_t { Representative = SDFK_SIMPLIFY_REPRESENTATIVE, Centroid = SDFK_SIMPLIFY_CENTROID, Quadric = SDFK_SIMPLIFY_QUADRIC };
+enum class SimplifyDuplicates : int32_t { One = 0, Keep = SDFK_SIMPLIFY_KEEP_DUPLICATES, Cancel = SDFK_SIMPLIFY_CANCEL_PAIRS };
+
 class Mesh {
 public:
     std::vector<Vector3> Vertices, Colors, Normals;
     std::vector<int32_t> Triangles;
     Vector3 Min, Max;
+    // A new, smaller Mesh by vertex clustering (MeshSdf::Simplify): the vertices of one cell of the lattice of size cellSize
+    // anchored at the origin become one vertex (Quadric: the point nearest the planes of the cell's triangles, kept inside the
+    // cell; Centroid: their mean; Representative: the lowest index as it is), and the triangles that collapse or come to lie on
+    // top of each other disappear (One: one of each vertex set stays; Keep: all; Cancel: one of an odd number, none of an even
+    // one, which keeps a watertight mesh watertight).  Colors come from the call; Normals are recomputed from the new geometry
+    // on the side of the representatives' gathered ones (normals = true) or gathered; Min / Max are re-measured; an empty Mesh
+    // results when nothing is left.
+    inline Mesh Simplify(float cellSize, SimplifyPlacement placement = SimplifyPlacement::Quadric, SimplifyDuplicates duplicates = SimplifyDuplicates::One,
+                         bool normals = true) const;
     // A new Mesh with the vertices of equal position made one (MeshSdf::Weld): what a triangle soup, or meshes put together by
     // Concat, need before the members below, which work by index, see their connectivity.  tolerance 0: positions equal as values;
     // tolerance > 0: the vertices of one cell of the lattice of that size anchored at the origin (a lattice, not a ball query).  A
@@ -1359,6 +1378,24 @@ public:
         w.Merged = stats[0]; w.DegenerateDropped = stats[1]; w.UnreferencedDropped = stats[2]; w.Passes = stats[3];
         return w;
     }
+    // The mesh made smaller by vertex clustering (sdfk_trimesh_simplify: one stated function of the mesh and the arguments): the
+    // vertices of one cell of the lattice of size cellSize become one made vertex; triangles that become index-degenerate are
+    // dropped, and of those that come to share a vertex set `duplicates` decides.  This handle is not changed.
+    MeshSimplify Simplify(float cellSize, SimplifyPlacement placement = SimplifyPlacement::Quadric,
+                          SimplifyDuplicates duplicates = SimplifyDuplicates::One) const
+    {
+        MeshSimplify w;
+        int64_t kv = 0, kt = 0, stats[6] = {0, 0, 0, 0, 0, 0};
+        w.VertexMap.resize((size_t)nv_); w.VertexIndex.resize((size_t)nv_); w.TriangleIndex.resize((size_t)nt_); w.Triangles.resize((size_t)nt_ * 3);
+        w.Vertices.resize((size_t)nv_); w.Colors.resize((size_t)nv_);
+        Check(sdfk_trimesh_simplify(h_, cellSize, (int32_t)placement, (int32_t)duplicates, w.VertexMap.data(), w.VertexIndex.data(),
+                                    w.TriangleIndex.data(), w.Triangles.data(), &w.Vertices.data()->X, &w.Colors.data()->X, &kv, &kt, stats));
+        w.VertexIndex.resize((size_t)kv); w.Vertices.resize((size_t)kv); w.Colors.resize((size_t)kv);
+        w.TriangleIndex.resize((size_t)kt); w.Triangles.resize((size_t)kt * 3);
+        w.Merged = stats[0]; w.DegenerateDropped = stats[1]; w.DuplicatesDropped = stats[2]; w.UnreferencedDropped = stats[3]; w.Passes = stats[4];
+        w.QuadricFallbacks = stats[5];
+        return w;
+    }
     // triangles of non-zero sampling weight and the total weight (the largest triangle has 2^32), as the last SamplePoints read them
     int64_t SampledTriangles() const { return sampleStats_[0]; }
     int64_t SampleTotalWeight() const { return sampleStats_[1]; }
@@ -1446,6 +1483,20 @@ inline Mesh Mesh::RecomputeNormals(bool flip) const
 inline Mesh Mesh::Weld(float tolerance, bool normals) const
 {
     MeshWeld w = MeshSdf(*this).Weld(tolerance);
+    Mesh m;
+    m.Min = m.Max = Vector3(0, 0, 0);
+    if (w.VertexIndex.empty()) return m;
+    m.Normals.resize(w.VertexIndex.size());
+    for (size_t i = 0; i < w.VertexIndex.size(); i++)
+        m.Normals[i] = (size_t)w.VertexIndex[i] < Normals.size() ? Normals[(size_t)w.VertexIndex[i]] : Vector3(0, 0, 0);
+    m.Vertices = std::move(w.Vertices); m.Colors = std::move(w.Colors); m.Triangles = std::move(w.Triangles);
+    if (normals) m.Normals = detail::NormalsOnTheSideOf(MeshSdf(m.Vertices, m.Triangles), {}, m.Normals);
+    detail::Measure(m);
+    return m;
+}
+inline Mesh Mesh::Simplify(float cellSize, SimplifyPlacement placement, SimplifyDuplicates duplicates, bool normals) const
+{
+    MeshSimplify w = MeshSdf(*this).Simplify(cellSize, placement, duplicates);
     Mesh m;
     m.Min = m.Max = Vector3(0, 0, 0);
     if (w.VertexIndex.empty()) return m;

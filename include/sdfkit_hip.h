@@ -1176,6 +1176,76 @@ int sdfk_trimesh_weld_device(sdfk_trimesh* t, float tolerance, int32_t flags, vo
                              void* triangle_index_out_dev, void* triangles_out_dev, void* vertices_out_dev, void* colors_out_dev, int64_t* nv_out,
                              int64_t* nt_out, int64_t stats[4]);
 
+/* ---- Triangle meshes: simplification (Mesh.Simplify: an extension) ---------------------------------------------------------------
+ * The mesh of a handle made smaller by VERTEX CLUSTERING (Rossignac & Borrel 1993, with Lindstrom's quadric placement, 2000): the
+ * vertices of one cell of a lattice become one vertex, and the triangles that fall on top of each other are cleaned up.  This is
+ * welding by lattice with a position MADE instead of one kept; it is not edge collapse.  ONE function of the input, `cellSize`,
+ * `placement` and `flags`, computed by csrc/trimesh_simplify.h, restated in tests/mesh_simplify_model.py and compared as bits
+ * and integers.  Every decision is made on integers; the arithmetic is binary64 from the f32 inputs, one rounding per written
+ * operation in the written order, no contraction, and each output component is rounded to f32 once.
+ * 1. Groups.  The group of a vertex is its cell of the world-anchored lattice of size cellSize, exactly the lattice mode of
+ *    "Triangle meshes: welding" (the same key, the same refusal of an axis of 2^21 cells or more).  rep[v] = the lowest index of
+ *    v's group; groups are numbered by ascending rep; the MEMBERS of a group are its vertices in ascending index.
+ * 2. Placement of a group's vertex.
+ *    SDFK_SIMPLIFY_REPRESENTATIVE (0): the representative's own position and colour bits; nothing is computed.
+ *    SDFK_SIMPLIFY_CENTROID (1): per axis, the members in ascending index are cut into chunks of 32 (the last may be short); a
+ *      chunk sum takes its members in order (each widened first), the total takes the chunk sums in order, both from +0.0;
+ *      c = total / (double)count, once.  The colour is the same mean of the members' colours (zeros when the mesh has none).
+ *    SDFK_SIMPLIFY_QUADRIC (2): with c the centroid above BEFORE its rounding.  For every member in order, for every corner of
+ *      its incident-corner list in ascending order (the adjacency of the handle: corners 3 t + k, index-degenerate triangles
+ *      listed nowhere), the corner's triangle (p0, p1, p2) in ITS OWN vertex order: q_k = (double)p_k - c per component;
+ *      e1 = q1 - q0, e2 = q2 - q0; n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), NOT normalised (the weight of a
+ *      triangle is its area squared); d = -((n0 q0x + n1 q0y) + n2 q0z); then the nine sums a00 += n0 n0, a01 += n0 n1,
+ *      a02 += n0 n2, a11 += n1 n1, a12 += n1 n2, a22 += n2 n2, b0 += d n0, b1 += d n1, b2 += d n2.  A member's nine sums run
+ *      over its corners from +0.0; a chunk's take its members' in order, the total the chunks' in order (the chunking of the
+ *      centroid).  A TRIANGLE WITH TWO CORNERS IN THE GROUP COUNTS TWICE, one with three three times: it is reached from each
+ *      (a triangle inside the cell has no fixed plane anyway; its weight only pulls toward the planes of its neighbours).
+ *      A is decomposed by the cyclic Jacobi of "Point clouds: normals and volumes" (8 fixed sweeps; eigenvalues l_i = the
+ *      diagonal, eigenvectors v_i = the columns of V).  l_max = l_0, replaced by l_1 when l_1 > l_max, then by l_2 likewise.
+ *      x = (0, 0, 0); for i = 0, 1, 2 in order, when l_i > 1e-3 * l_max:  s = (v_0i (-b0) + v_1i (-b1)) + v_2i (-b2);
+ *      t = s / l_i;  x_k = x_k + v_ki t.  No square root of its own and no order enters.  The position is p = c + x.
+ *      FALLBACK TO THE CENTROID, counted in stats: when l_max > 0 does not hold, or for some axis a, p_a is not finite or not in
+ *      k_a cellSize <= p_a < (k_a + 1) cellSize (binary64; k_a = floor(x_a / cellSize) of the representative, as the lattice
+ *      forms it).  A placed vertex therefore never leaves its cell before the final rounding.  Colours as for the centroid.
+ * 3. Triangles.  Triangle t becomes (rep[a], rep[b], rep[c]); index-degenerate ones are dropped.  The others are grouped by
+ *    VERTEX SET (the sorted triple, whatever the winding).  Default: the lowest triangle index of each set is kept, with its own
+ *    winding.  SDFK_SIMPLIFY_KEEP_DUPLICATES: all are kept.  SDFK_SIMPLIFY_CANCEL_PAIRS: a set with an even number of triangles
+ *    is dropped entirely, one with an odd number keeps its lowest index -- clustering is a simplicial map, and this rule keeps
+ *    the image a cycle mod 2: a mesh whose every edge is used an even number of times (IsWatertight) stays so, which is exactly
+ *    when the parity sign of sdfk_trimesh_to_volume is defined.  The two flags together are refused.
+ * 4. Vertices.  A group is KEPT iff some kept triangle names it.  Kept groups and kept triangles are numbered in ascending old
+ *    (representative / triangle) index.
+ * 5. Outputs, any may be NULL; entries beyond the counts are left as they were.  vertex_map (nv): the new number of every old
+ *    vertex's group, -1 where the group was dropped.  vertex_index_out (capacity nv): the representative's old index of every
+ *    new vertex.  triangle_index_out (nt): the old index of every kept triangle.  triangles_out (3 nt), vertices_out /
+ *    colors_out (3 nv).  stats[6] = { vertices merged away (nv less the groups), triangles dropped as degenerate, triangles
+ *    dropped as duplicates (cancelled ones included), groups dropped as unreferenced, radix passes run (all sorts), quadric
+ *    fallbacks to the centroid (over the KEPT groups: a dropped group is not placed) }.
+ * 6. What follows.  Placement 0 with KEEP_DUPLICATES is sdfk_trimesh_weld(t, cellSize, 0) in every output.  Simplifying twice
+ *    with one cell size and placement 0 changes nothing the second time.
+ * How (csrc/lib_trimesh_simplify.hip): welding's grouping; the group numbers by one scan; per triangle one 16-byte record,
+ * sorted stably twice as welding's exact mode sorts 96 bits (by the least group number, then by (greatest above middle)), only
+ * through the bytes a group number can set (without KEEP_DUPLICATES: 3 * bytes passes, else none); head flags, a scan, run
+ * lengths; keep flags, two scans; one lane per kept group walks group -> members -> corners and places the vertex.
+ * THE HANDLE IS NOT CHANGED and keeps nothing of this but the corner lists of its adjacency, which placement 2 makes when the
+ * handle has none yet.  The plain form takes host arrays; the _device form caller-owned device buffers and host pointers for
+ * the counts and stats, and its outputs are ready for sdfk_trimesh_create_device.  Both synchronise.  A mesh that simplifies to
+ * nothing gives 0 and 0 and is not an error.
+ * Refused with SDFK_ERR_INVALID, outputs untouched: a NULL handle, a cellSize that is not finite and greater than 0, an unknown
+ * placement, unknown flag bits, KEEP_DUPLICATES with CANCEL_PAIRS, a lattice axis spanning 2^21 cells or more, a mesh the
+ * adjacency refuses (2^32 / 6 triangles or more). */
+#define SDFK_SIMPLIFY_REPRESENTATIVE 0
+#define SDFK_SIMPLIFY_CENTROID 1
+#define SDFK_SIMPLIFY_QUADRIC 2
+#define SDFK_SIMPLIFY_KEEP_DUPLICATES 1
+#define SDFK_SIMPLIFY_CANCEL_PAIRS 2
+int sdfk_trimesh_simplify(sdfk_trimesh* t, float cellSize, int32_t placement, int32_t flags, int32_t* vertex_map, int32_t* vertex_index_out,
+                          int32_t* triangle_index_out, int32_t* triangles_out, float* vertices_out, float* colors_out, int64_t* nv_out,
+                          int64_t* nt_out, int64_t stats[6]);
+int sdfk_trimesh_simplify_device(sdfk_trimesh* t, float cellSize, int32_t placement, int32_t flags, void* vertex_map_dev,
+                                 void* vertex_index_out_dev, void* triangle_index_out_dev, void* triangles_out_dev, void* vertices_out_dev,
+                                 void* colors_out_dev, int64_t* nv_out, int64_t* nt_out, int64_t stats[6]);
+
 /* ---- Redistancing (Voxels.Redistance) ---------------------------------------------------------------------------------------
  * dst gets a signed distance to the iso-surface of src, with src's sign at every voxel: a first-order Eikonal solve (Godunov
  * upwind, Jacobi sweeps to the fixed point -- the fast iterative method family, Jeong & Whitaker 2008).  src is not modified

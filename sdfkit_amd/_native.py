@@ -172,6 +172,8 @@ SIGNATURES = {
     "sdfk_trimesh_vertex_normals_device": (C.c_int, [_vp, _vp, _i32, _vp]),
     "sdfk_trimesh_weld": (C.c_int, [_vp, C.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "sdfk_trimesh_weld_device": (C.c_int, [_vp, C.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "sdfk_trimesh_simplify": (C.c_int, [_vp, C.c_float, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "sdfk_trimesh_simplify_device": (C.c_int, [_vp, C.c_float, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "sdfk_trimesh_free": (None, [_vp]),
     "sdfk_volume_redistance": (C.c_int, [_vp, _vp, C.c_float, C.c_float, C.POINTER(_i64)]),
     "sdfk_icp_register": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),

@@ -869,6 +869,26 @@ class Mesh:
             N_ = Mesh._normals_on_the_side_of(MeshSdf((w.Vertices, w.Triangles)), None, N_, None)
         return Mesh(w.Vertices, w.Colors, N_, w.Triangles, w.Vertices.min(axis=0), w.Vertices.max(axis=0))
 
+    def Simplify(self, cellSize, placement="quadric", duplicates="one", normals=True):
+        """A new, smaller Mesh by vertex clustering (MeshSdf.Simplify): the vertices of one cell of the lattice of size cellSize
+        anchored at the origin become one vertex -- placement "quadric": the point nearest the planes of the cell's triangles,
+        kept inside the cell; "centroid": the mean of the cell's vertices; "representative": the lowest index as it is -- and
+        the triangles that collapse or come to lie on top of each other disappear (duplicates "one": one of each vertex set
+        stays; "keep": all; "cancel": one of an odd number, none of an even one, which keeps a watertight mesh watertight for
+        ToVoxels).  A marching-cubes mesh of voxel size h shrinks about 4-, 16-, 64-fold at cellSize 2 h, 4 h, 8 h.  Colors come
+        from the call (the mean of a cell's colours, or the representative's).  Normals are recomputed from the new geometry on
+        the side of the representatives' gathered ones (normals=True) or gathered from the representatives.  Min / Max are
+        re-measured; an empty Mesh results when nothing is left."""
+        from .meshsdf import MeshSdf
+        f32 = np.float32
+        w = MeshSdf(self).Simplify(cellSize, placement, duplicates)
+        if len(w.VertexIndex) == 0:
+            return Mesh(np.zeros((0, 3), f32), np.zeros((0, 3), f32), np.zeros((0, 3), f32), np.zeros((0,), np.int32))
+        N_ = np.ascontiguousarray(np.asarray(self.Normals, f32).reshape(-1, 3)[w.VertexIndex])
+        if normals:
+            N_ = Mesh._normals_on_the_side_of(MeshSdf((w.Vertices, w.Triangles)), None, N_, None)
+        return Mesh(w.Vertices, w.Colors, N_, w.Triangles, w.Vertices.min(axis=0), w.Vertices.max(axis=0))
+
     @staticmethod
     def Concat(meshes):
         """The meshes put together on the host: the arrays one after the other, the indices of each offset by the vertices before

@@ -262,6 +262,8 @@ int adjacency_out(sdfk_trimesh* t, void* nbr_start, void* nbr, void* boundary, i
 
 }  // namespace
 
+int trimesh_corners(sdfk_trimesh* t, const char* who) { return csr_prepare(t, true, who); }   // (trimesh_handle.h)
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // entry points
 // ---------------------------------------------------------------------------------------------------------------------------

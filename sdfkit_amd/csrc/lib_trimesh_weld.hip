@@ -19,6 +19,7 @@
 //                  stable from ascending indices, so the head is the lowest index of its group.
 //   k_tw_tri_flags keep flag of every rewritten triangle; a kept one stores the byte 1 at its three representatives.
 //   k_tw_vert_flags keep flag of every vertex; two scans.   k_tw_vertices / k_tw_triangles   vertex_map and the gathers.
+// The steps up to rep are trimesh_groups (trimesh_handle.h), which lib_trimesh_simplify.hip starts from too.
 // Host side: the scratch and the host form's device copies are held in a Staged (device_stage.h); the handle check
 // (trimesh_check) and the launch size (grid1) are trimesh_handle.h's.
 #include "lib_internal.h"
@@ -149,13 +150,15 @@ __global__ __launch_bounds__(kBlock) void k_tw_first(const Rec* __restrict__ s, 
     if (head[j + 1] != g0 && g0 < n) group_first[g0] = (int32_t)s[j].index;   // (g0 < groups <= n)
 }
 
+// order (or null): the vertex of every sorted position, for a caller that walks the members of a group
 __global__ __launch_bounds__(kBlock) void k_tw_rep(const Rec* __restrict__ s, int64_t n, const uint32_t* __restrict__ head,
-                                                   const int32_t* __restrict__ group_first, int32_t* __restrict__ rep)
+                                                   const int32_t* __restrict__ group_first, int32_t* __restrict__ rep, uint32_t* __restrict__ order)
 {
     const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (j >= n) return;
     const uint32_t g0 = head[j], grp = group_of(g0, head[j + 1] != g0);
     const uint32_t v = s[j].index;
+    if (order) order[j] = v;
     if (grp < n && v < n) rep[v] = group_first[grp];   // (always: sorted position 0 is a head, and the indices are 0 .. n - 1)
 }
 
@@ -227,13 +230,15 @@ int check(const sdfk_trimesh* t, float tolerance, int32_t flags, const char* who
     return SDFK_OK;
 }
 
-// O: device buffers (any may be null); synchronises: the counts and stats are read on the way
-int weld(const sdfk_trimesh* t, float tolerance, int32_t flags, WeldOut O, int64_t* nv_out, int64_t* nt_out, int64_t stats[4], const char* who)
+}  // namespace
+
+// The groups of the handle's vertices (trimesh_handle.h): the steps up to rep, queued on st; the lattice's box and the pass masks
+// come back to the host on the way, so G->passes is final on return.
+void trimesh_groups(const sdfk_trimesh* t, float tolerance, bool want_order, Staged& st, TrimeshGroups* G, const char* who)
 {
-    const int64_t nv = t->nv, nt = t->nt, n = nv;
+    const int64_t nv = t->nv, n = nv;
     const bool exact = tolerance == 0.0f;
     const uint32_t* P = (const uint32_t*)t->vertices;
-    Staged st;
     Ctl* ctl = st.scratch<Ctl>(1);
     Rec* ra = st.scratch<Rec>((size_t)n);
     Rec* rb = st.scratch<Rec>((size_t)n);
@@ -241,16 +246,12 @@ int weld(const sdfk_trimesh* t, float tolerance, int32_t flags, WeldOut O, int64
     uint32_t* head = st.scratch<uint32_t>((size_t)n + 1);
     int32_t* group_first = st.scratch<int32_t>((size_t)n);
     int32_t* rep = st.scratch<int32_t>((size_t)nv);
-    uint8_t* used = st.scratch<uint8_t>((size_t)nv);
-    uint32_t* vnew = st.scratch<uint32_t>((size_t)nv + 1);
-    uint32_t* tnew = st.scratch<uint32_t>((size_t)nt + 1);
+    uint32_t* order = want_order ? st.scratch<uint32_t>((size_t)n) : nullptr;
     Ctl host{{0xffffffffu, 0xffffffffu, 0xffffffffu}, {0u, 0u, 0u}, {0ull, 0ull}};
     Lattice L{};
     unsigned lattice_mask = 0xffu;
     int passes = 0;
-    uint32_t counts[3] = {0, 0, 0};   // groups, kept vertices, kept triangles
     st.run([&] { return hipMemcpyAsync(ctl, &host, sizeof host, hipMemcpyHostToDevice, g.stream); });
-    st.run([&] { return hipMemsetAsync(used, 0, (size_t)nv, g.stream); });
     if (!exact) {
         st.run([&] {
             ProfScope ps("k_tw_bounds");
@@ -295,9 +296,28 @@ int weld(const sdfk_trimesh* t, float tolerance, int32_t flags, WeldOut O, int64
         st.run([&] { return sdfk_scan::scan(head, n, who); });
         st.run([&] {
             hipLaunchKernelGGL(k_tw_first, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, head, group_first);
-            hipLaunchKernelGGL(k_tw_rep, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, head, group_first, rep);
+            hipLaunchKernelGGL(k_tw_rep, dim3(grid1(n)), dim3(kBlock), 0, g.stream, sorted, n, head, group_first, rep, order);
         });
     }
+    *G = TrimeshGroups{order, head, group_first, rep, passes};
+}
+
+namespace {
+
+// O: device buffers (any may be null); synchronises: the counts and stats are read on the way
+int weld(const sdfk_trimesh* t, float tolerance, int32_t flags, WeldOut O, int64_t* nv_out, int64_t* nt_out, int64_t stats[4], const char* who)
+{
+    const int64_t nv = t->nv, nt = t->nt, n = nv;
+    Staged st;
+    TrimeshGroups G{};
+    trimesh_groups(t, tolerance, false, st, &G, who);
+    uint32_t* head = G.head;
+    int32_t* rep = G.rep;
+    uint8_t* used = st.scratch<uint8_t>((size_t)nv);
+    uint32_t* vnew = st.scratch<uint32_t>((size_t)nv + 1);
+    uint32_t* tnew = st.scratch<uint32_t>((size_t)nt + 1);
+    uint32_t counts[3] = {0, 0, 0};   // groups, kept vertices, kept triangles
+    st.run([&] { return hipMemsetAsync(used, 0, (size_t)nv, g.stream); });
     {
         ProfScope ps("k_tw_output");
         st.run([&] {
@@ -321,7 +341,7 @@ int weld(const sdfk_trimesh* t, float tolerance, int32_t flags, WeldOut O, int64
         stats[kStatMerged] = nv - (int64_t)counts[0];
         stats[kStatDegenerate] = nt - (int64_t)counts[2];
         stats[kStatUnreferenced] = (int64_t)counts[0] - (int64_t)counts[1];
-        stats[kStatPasses] = passes;
+        stats[kStatPasses] = G.passes;
     }
     return SDFK_OK;
 }

@@ -1,8 +1,9 @@
 // trimesh_handle.h -- the handle behind sdfk_trimesh_*: the copied arrays, the packed triangles and their search grid (built by
 // lib_trimesh.hip), the sampling weights' scan (made by the first call that needs it) and the component labels (made by the first
 // topology call, lib_trimesh_topology.hip) and the adjacency (made by the first adjacency, smoothing or vertex-normal call,
-// lib_trimesh_smooth.hip).  Seen by those three translation units and by lib_trimesh_weld.hip, which only reads it.  With it, what
-// the four share on the host: the staging of device_stage.h, the check of a handle and the size of a one-dimensional launch.
+// lib_trimesh_smooth.hip).  Seen by those three translation units and by lib_trimesh_weld.hip and lib_trimesh_simplify.hip, which
+// only read it (the latter asks for the corner lists of the adjacency).  With it, what the five share on the host: the staging of
+// device_stage.h, the check of a handle, the size of a one-dimensional launch, and the grouping of the vertices by position.
 // hipcc only.
 #pragma once
 #include "lib_internal.h"
@@ -53,6 +54,23 @@ int trimesh_weights(sdfk_trimesh* t, const char* who);
 // What every entry point of the family asks of its handle first: the library is initialised, t is not null, and -- for a unit
 // that sorts `records` 32-bit-indexed records per triangle (0: none) -- records * nt < 2^32.  (lib_trimesh.hip)
 int trimesh_check(const sdfk_trimesh* t, const char* who, int records);
+
+// The vertices of a handle grouped by position as sdfk_trimesh_weld groups them (lib_trimesh_weld.hip; tolerance 0: equal as
+// values, > 0: the cell of the lattice), for the units that start from the groups (welding itself, lib_trimesh_simplify.hip).  The
+// steps are queued on st, which owns every array below and reports a refusal (an axis of 2^21 cells or more) or a failure at its
+// finish(); nothing is kept on the handle.
+struct TrimeshGroups {
+    uint32_t* order;        // nv (want_order; else null): the vertex at every sorted position -- the members of a group are adjacent, ascending
+    uint32_t* head;         // nv + 1: the scanned head flags of the sorted positions; head[nv] = the number of groups
+    int32_t* group_first;   // nv: the lowest index of every group, the groups in sorted order
+    int32_t* rep;           // nv: the lowest index of every vertex's group
+    int passes;             // radix passes run
+};
+void trimesh_groups(const sdfk_trimesh* t, float tolerance, bool want_order, Staged& st, TrimeshGroups* G, const char* who);
+
+// The corner lists inc_start / inc of the handle, made by the first call that needs them (lib_trimesh_smooth.hip); the caller has
+// checked the handle for 6 records per triangle.
+int trimesh_corners(sdfk_trimesh* t, const char* who);
 
 // blocks of 256 lanes for n items, one lane each; at least one, at most 2^30 (reached by nothing indexed per vertex or triangle)
 inline unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, int64_t(1) << 30)); }

@@ -21,6 +21,8 @@ SMOOTH_PIN_BOUNDARY = 1  # SDFK_TRIMESH_SMOOTH_PIN_BOUNDARY
 NORMALS_FLIP = 1         # SDFK_TRIMESH_NORMALS_FLIP
 WELD_KEEP_DEGENERATE = 1    # SDFK_WELD_KEEP_DEGENERATE
 WELD_KEEP_UNREFERENCED = 2  # SDFK_WELD_KEEP_UNREFERENCED
+SIMPLIFY_PLACEMENTS = {"representative": 0, "centroid": 1, "quadric": 2}   # SDFK_SIMPLIFY_REPRESENTATIVE / _CENTROID / _QUADRIC
+SIMPLIFY_DUPLICATES = {"one": 0, "keep": 1, "cancel": 2}                  # 0, SDFK_SIMPLIFY_KEEP_DUPLICATES, SDFK_SIMPLIFY_CANCEL_PAIRS
 
 # MeshSdf.SamplePoints: Points (n, 3) f32, Normals (n, 3) f32 (unit face normals), Colors (n, 3) f32 or None, Triangles (n,) int32,
 # Weights (n, 3) f32 (the barycentric weights of the triangle's three vertices, as the colour blend used them)
@@ -97,6 +99,19 @@ class MeshWeld:
     def __init__(self, vmap, vi, ti, tr, vs, cs, stats):
         self.VertexMap, self.VertexIndex, self.TriangleIndex, self.Triangles, self.Vertices, self.Colors = vmap, vi, ti, tr, vs, cs
         self.Merged, self.DegenerateDropped, self.UnreferencedDropped, self.Passes = (int(x) for x in stats)
+
+
+class MeshSimplify:
+    """MeshSdf.Simplify(): MeshWeld's fields -- VertexMap (nv,) int32 (the new number of every old vertex's group, -1: dropped);
+    VertexIndex (the representative's old index of every new vertex) / TriangleIndex int32; Vertices, Colors (n, 3) float32 (the
+    MADE vertices); Triangles int32 (flat, renumbered); Merged, DegenerateDropped, UnreferencedDropped, Passes -- and
+    DuplicatesDropped (triangles dropped for sharing a vertex set with another), QuadricFallbacks (kept groups placed at their
+    centroid because the quadric's minimiser did not exist or left the cell)."""
+
+    def __init__(self, vmap, vi, ti, tr, vs, cs, stats):
+        self.VertexMap, self.VertexIndex, self.TriangleIndex, self.Triangles, self.Vertices, self.Colors = vmap, vi, ti, tr, vs, cs
+        (self.Merged, self.DegenerateDropped, self.DuplicatesDropped, self.UnreferencedDropped, self.Passes,
+         self.QuadricFallbacks) = (int(x) for x in stats)
 
 
 def _ptr(a):
@@ -316,6 +331,45 @@ class MeshSdf:
                                                  *[C.c_void_p(p) if p else C.c_void_p() for p in (vertex_map_dev, vertex_index_dev, triangle_index_dev,
                                                                                                  triangles_dev, vertices_dev, colors_dev)],
                                                  C.byref(kv), C.byref(kt), st))
+        return kv.value, kt.value, [int(x) for x in st]
+
+    @staticmethod
+    def _simplify_codes(placement, duplicates):
+        if placement not in SIMPLIFY_PLACEMENTS:
+            raise ValueError(f"placement must be one of {sorted(SIMPLIFY_PLACEMENTS)}")
+        if duplicates not in SIMPLIFY_DUPLICATES:
+            raise ValueError(f"duplicates must be one of {sorted(SIMPLIFY_DUPLICATES)}")
+        return SIMPLIFY_PLACEMENTS[placement], SIMPLIFY_DUPLICATES[duplicates]
+
+    def Simplify(self, cellSize, placement="quadric", duplicates="one"):
+        """The mesh made smaller by vertex clustering (sdfk_trimesh_simplify: one stated function of the mesh and the arguments)
+        -> MeshSimplify.  The vertices of one cell of the lattice of size cellSize anchored at the origin become one vertex:
+        placement "representative" (the lowest index, as it is), "centroid" (the mean of the cell's vertices) or "quadric" (the
+        point nearest the planes of the cell's triangles, kept inside the cell; the centroid where that fails).  Triangles that
+        become index-degenerate are dropped; of those that come to share a vertex set, duplicates "one" keeps the lowest index,
+        "keep" all, "cancel" the lowest index of an odd number and none of an even one -- which keeps a watertight mesh
+        watertight.  This handle is not changed."""
+        code, flags = self._simplify_codes(placement, duplicates)
+        nv, nt = len(self.Vertices), len(self.Triangles) // 3
+        vm, vi, ti, tr = np.empty(nv, np.int32), np.empty(nv, np.int32), np.empty(nt, np.int32), np.empty(3 * nt, np.int32)
+        vs, cs = np.empty((nv, 3), f32), np.empty((nv, 3), f32)
+        kv, kt, st = C.c_int64(), C.c_int64(), (C.c_int64 * 6)()
+        N.check(N.lib().sdfk_trimesh_simplify(self._h, C.c_float(cellSize), code, flags, _ptr(vm), _ptr(vi), _ptr(ti), _ptr(tr), _ptr(vs),
+                                              _ptr(cs), C.byref(kv), C.byref(kt), st))
+        kv, kt = kv.value, kt.value
+        return MeshSimplify(vm, vi[:kv].copy(), ti[:kt].copy(), tr[:3 * kt].copy(), vs[:kv].copy(), cs[:kv].copy(), st[:])
+
+    def SimplifyDevice(self, cellSize, placement, duplicates, vertex_map_dev=None, vertex_index_dev=None, triangle_index_dev=None,
+                       triangles_dev=None, vertices_dev=None, colors_dev=None):
+        """Simplify into caller-owned device memory (raw pointers; None: that output is not wanted) -> (vertices, triangles, stats):
+        the counts and the six stats.  The outputs are ready for sdfk_trimesh_create_device."""
+        code, flags = self._simplify_codes(placement, duplicates)
+        kv, kt, st = C.c_int64(), C.c_int64(), (C.c_int64 * 6)()
+        N.check(N.lib().sdfk_trimesh_simplify_device(self._h, C.c_float(cellSize), code, flags,
+                                                     *[C.c_void_p(p) if p else C.c_void_p() for p in (vertex_map_dev, vertex_index_dev,
+                                                                                                     triangle_index_dev, triangles_dev, vertices_dev,
+                                                                                                     colors_dev)],
+                                                     C.byref(kv), C.byref(kt), st))
         return kv.value, kt.value, [int(x) for x in st]
 
     def stats(self):

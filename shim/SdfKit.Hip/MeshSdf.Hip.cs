@@ -8,6 +8,7 @@
 // Adjacency / Smooth / VertexNormals (sdfk_trimesh_adjacency, _smooth, _vertex_normals): the neighbours of every vertex, Taubin
 // smoothing of the positions and area-weighted normals from the geometry; Mesh.Smooth / Mesh.RecomputeNormals on top of them.
 // Weld (sdfk_trimesh_weld): the vertices of equal position made one; Mesh.Weld and Concat (a static of the extensions class) on top.
+// Simplify (sdfk_trimesh_simplify): vertex clustering, the vertices of one lattice cell made one made vertex; Mesh.Simplify on top.
 // UNCOMPILED HERE (no .NET in the build image); sdfkit_amd/meshsdf.py's MeshSdf is the same layer, tested.
 using System;
 using System.Collections.Generic;
@@ -83,6 +84,23 @@ namespace SdfKit
         public Vector3[] Colors = Array.Empty<Vector3> ();
         public long Merged, DegenerateDropped, UnreferencedDropped, Passes;
     }
+
+    /// <summary>MeshSdf.Simplify: MeshWeld's fields for the clustered mesh (VertexMap: the new number of every old vertex's group;
+    /// Vertices and Colors: the made ones), the triangles dropped for sharing a vertex set with another, and the kept groups
+    /// whose quadric placement fell back to the centroid.</summary>
+    public sealed class MeshSimplify
+    {
+        public int[] VertexMap = Array.Empty<int> ();
+        public int[] VertexIndex = Array.Empty<int> ();
+        public int[] TriangleIndex = Array.Empty<int> ();
+        public int[] Triangles = Array.Empty<int> ();
+        public Vector3[] Vertices = Array.Empty<Vector3> ();
+        public Vector3[] Colors = Array.Empty<Vector3> ();
+        public long Merged, DegenerateDropped, DuplicatesDropped, UnreferencedDropped, Passes, QuadricFallbacks;
+    }
+
+    public enum SimplifyPlacement { Representative = 0, Centroid = 1, Quadric = 2 }   // SDFK_SIMPLIFY_REPRESENTATIVE, _CENTROID, _QUADRIC
+    public enum SimplifyDuplicates { One = 0, Keep = 1, Cancel = 2 }                    // 0, SDFK_SIMPLIFY_KEEP_DUPLICATES, SDFK_SIMPLIFY_CANCEL_PAIRS
 
     public sealed class MeshSelection
     {
@@ -287,6 +305,31 @@ namespace SdfKit
                                   UnreferencedDropped = st[2], Passes = st[3] };
         }
 
+        /// <summary>The mesh made smaller by vertex clustering: the vertices of one cell of the lattice of size cellSize anchored at
+        /// the origin become one vertex (Quadric: the point nearest the planes of the cell's triangles, kept inside the cell, the
+        /// centroid where that fails; Centroid: their mean; Representative: the lowest index as it is).  Triangles that become
+        /// index-degenerate go; of those that come to share a vertex set, One keeps the lowest index, Keep all, Cancel the lowest
+        /// index of an odd number and none of an even one (a watertight mesh stays watertight).  This handle is not changed.</summary>
+        public unsafe MeshSimplify Simplify (float cellSize, SimplifyPlacement placement = SimplifyPlacement.Quadric,
+                                             SimplifyDuplicates duplicates = SimplifyDuplicates.One)
+        {
+            long kv = 0, kt = 0;
+            long* st = stackalloc long[6];
+            var vm = new int[vertexCount];
+            var vi = new int[vertexCount];
+            var ti = new int[triangleCount];
+            var tr = new int[triangleCount * 3];
+            var vs = new Vector3[vertexCount];
+            var cs = new Vector3[vertexCount];
+            fixed (int* vmp = vm) fixed (int* vip = vi) fixed (int* tip = ti) fixed (int* trp = tr) fixed (Vector3* vsp = vs) fixed (Vector3* csp = cs)
+                Native.Check (Native.sdfk_trimesh_simplify (handle, cellSize, (int)placement, (int)duplicates, vmp, vip, tip, trp, (float*)vsp, (float*)csp,
+                                                            &kv, &kt, st));
+            return new MeshSimplify { VertexMap = vm, VertexIndex = vi.AsSpan (0, (int)kv).ToArray (), TriangleIndex = ti.AsSpan (0, (int)kt).ToArray (),
+                                      Triangles = tr.AsSpan (0, (int)kt * 3).ToArray (), Vertices = vs.AsSpan (0, (int)kv).ToArray (),
+                                      Colors = cs.AsSpan (0, (int)kv).ToArray (), Merged = st[0], DegenerateDropped = st[1], DuplicatesDropped = st[2],
+                                      UnreferencedDropped = st[3], Passes = st[4], QuadricFallbacks = st[5] };
+        }
+
         public void Dispose ()
         {
             if (handle != IntPtr.Zero) {
@@ -391,6 +434,25 @@ namespace SdfKit
             if (normals && n.Length != 0) {
                 using var welded = new MeshSdf (w.Vertices, w.Triangles);
                 n = NormalsOnTheSideOf (welded, default, n);
+            }
+            return new Mesh (w.Vertices, w.Colors, n, w.Triangles);   // (the constructor measures Min / Max; empty arrays: an empty Mesh)
+        }
+
+        /// <summary>Mesh.Simplify: a new, smaller Mesh by vertex clustering (MeshSdf.Simplify).  Colors come from the call; Normals are
+        /// recomputed from the new geometry on the side of the representatives' gathered ones (normals = true) or gathered; Min /
+        /// Max are re-measured; an empty Mesh results when nothing is left.</summary>
+        public static Mesh Simplify (this Mesh mesh, float cellSize, SimplifyPlacement placement = SimplifyPlacement.Quadric,
+                                     SimplifyDuplicates duplicates = SimplifyDuplicates.One, bool normals = true)
+        {
+            MeshSimplify w;
+            using (var m = new MeshSdf (mesh))
+                w = m.Simplify (cellSize, placement, duplicates);
+            var n = new Vector3[w.VertexIndex.Length];
+            for (int i = 0; i < n.Length; i++)
+                n[i] = mesh.Normals[w.VertexIndex[i]];
+            if (normals && n.Length != 0) {
+                using var made = new MeshSdf (w.Vertices, w.Triangles);
+                n = NormalsOnTheSideOf (made, default, n);
             }
             return new Mesh (w.Vertices, w.Colors, n, w.Triangles);   // (the constructor measures Min / Max; empty arrays: an empty Mesh)
         }

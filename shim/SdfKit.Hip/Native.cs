@@ -194,6 +194,12 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_trimesh_weld_device(IntPtr trimesh, float tolerance, int flags, IntPtr vertexMapDev,
                                                                            IntPtr vertexIndexOutDev, IntPtr triangleIndexOutDev, IntPtr trianglesOutDev,
                                                                            IntPtr verticesOutDev, IntPtr colorsOutDev, long* nvOut, long* ntOut, long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_simplify(IntPtr trimesh, float cellSize, int placement, int flags, int* vertexMap,
+                                                                        int* vertexIndexOut, int* triangleIndexOut, int* trianglesOut, float* verticesOut,
+                                                                        float* colorsOut, long* nvOut, long* ntOut, long* stats6);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_simplify_device(IntPtr trimesh, float cellSize, int placement, int flags, IntPtr vertexMapDev,
+                                                                               IntPtr vertexIndexOutDev, IntPtr triangleIndexOutDev, IntPtr trianglesOutDev,
+                                                                               IntPtr verticesOutDev, IntPtr colorsOutDev, long* nvOut, long* ntOut, long* stats6);
         [DllImport(Lib)] public static extern void sdfk_trimesh_free(IntPtr trimesh);
         [DllImport(Lib)] public static extern int sdfk_volume_redistance(IntPtr src, IntPtr dst, float isoValue, float maxDistance, long* stats4);
         // several GPUs from ONE process (the managed host is one process): include/sdfkit_hip.h, "one process, several GPUs"
