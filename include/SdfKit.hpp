@@ -191,6 +191,9 @@ using SdfIndexedOutputModifierFunc = std::function<Vec3(Vec3 /*index*/, Vec3 /*p
 class Mesh;
 class Voxels;
 class MeshSdf;
+struct FloatData;
+struct Vec3Data;
+struct Matrix4x4;
 
 // The reference's `Sdf` delegate (Sdf.cs:8), restricted to SDFs that have a GPU program.
 class Sdf {
@@ -333,6 +336,26 @@ struct MeshSamples {
     std::vector<Vector3> Weights;
 };
 
+// MeshSdf::RayCast / Mesh::RayCast (not in the reference): per ray the first triangle hit (-1: none), the distance in units of
+// |direction| (+inf: none) and the barycentric weights of the triangle's three vertices (NaN: none), in MeshSamples' layout.
+struct MeshRayHits {
+    std::vector<Vector3> Origins, Directions;
+    std::vector<int32_t> Triangles;
+    std::vector<float> Distances;
+    std::vector<Vector3> Weights;
+    bool Hit(size_t i) const { return Triangles[i] >= 0; }
+    // origin + direction * distance of the hits, in ray order (made on the host)
+    std::vector<Vector3> Points() const
+    {
+        std::vector<Vector3> p;
+        for (size_t i = 0; i < Triangles.size(); i++)
+            if (Triangles[i] >= 0)
+                p.push_back(Vector3(Origins[i].X + Directions[i].X * Distances[i], Origins[i].Y + Directions[i].Y * Distances[i],
+                                    Origins[i].Z + Directions[i].Z * Distances[i]));
+        return p;
+    }
+};
+
 // MeshSdf::Components / Mesh::Components (not in the reference): the connected components by index (two vertices with equal
 // positions and different indices are different vertices).  Labels are -1 for an unreferenced vertex and an index-degenerate
 // triangle; the per-component arrays have Count entries; AreaWeights sums the integer sampling weights of the component's triangles.
@@ -432,6 +455,15 @@ public:
     inline Mesh LargestComponent() const;
     // n points on the triangles in proportion to area (MeshSdf(*this).SamplePoints)
     inline MeshSamples SamplePoints(int64_t n, uint64_t seed = 0, bool stratified = true) const;
+    // the first hit of every ray, and whether each ray hits anything within the range (MeshSdf(*this).RayCast / Occluded)
+    inline MeshRayHits RayCast(const std::vector<Vector3>& origins, const std::vector<Vector3>& directions, float tMin = 0.0f, float tMax = INFINITY) const;
+    inline std::vector<bool> Occluded(const std::vector<Vector3>& origins, const std::vector<Vector3>& directions, float tMin = 0.0f,
+                                      float tMax = INFINITY) const;
+    // the mesh rendered as SdfEx.ToImage renders an SDF: the same camera, light, sky and lens (MeshSdf(*this).Render)
+    inline Vec3Data ToImage(int width, int height, const Matrix4x4& viewTransform, float verticalFieldOfViewDegrees = 60.0f,
+                            float nearPlaneDistance = 1.0f, float farPlaneDistance = 100.0f) const;
+    inline Vec3Data ToImage(int width, int height, Vector3 cameraPosition, Vector3 cameraTarget, Vector3 cameraUp, float verticalFieldOfViewDegrees = 60.0f,
+                            float nearPlaneDistance = 1.0f, float farPlaneDistance = 100.0f) const;
     Vector3 Center() const { return (Min + Max) * 0.5f; }
     Vector3 Size() const { return Max - Min; }
     float Radius() const { return (Max - Min).Length() * 0.5f; }
@@ -1396,6 +1428,40 @@ public:
         w.QuadricFallbacks = stats[5];
         return w;
     }
+    // The first hit of every ray origin + t direction, tMin <= t <= tMax (sdfk_trimesh_raycast: one stated function of the mesh, the
+    // rays and the range; the watertight ray-triangle test in binary64, ties to the lowest triangle index).  Directions need not be
+    // unit vectors; one origin may be given for all directions.  A ray with a NaN or infinite component or a zero direction is a miss.
+    MeshRayHits RayCast(const std::vector<Vector3>& origins, const std::vector<Vector3>& directions, float tMin = 0.0f, float tMax = INFINITY) const
+    {
+        MeshRayHits r;
+        Rays(origins, directions, r.Origins, r.Directions);
+        const size_t n = r.Directions.size();
+        r.Triangles.resize(n); r.Distances.resize(n); r.Weights.resize(n);
+        Check(sdfk_trimesh_raycast(h_, n ? &r.Origins.data()->X : nullptr, n ? &r.Directions.data()->X : nullptr, (int64_t)n, tMin, tMax, 0,
+                                   r.Triangles.data(), r.Distances.data(), n ? &r.Weights.data()->X : nullptr));
+        return r;
+    }
+    // Whether anything is hit within the range, per ray (SDFK_RAY_ANY_HIT: the search stops at the first hit it meets).
+    std::vector<bool> Occluded(const std::vector<Vector3>& origins, const std::vector<Vector3>& directions, float tMin = 0.0f, float tMax = INFINITY) const
+    {
+        std::vector<Vector3> o, d;
+        Rays(origins, directions, o, d);
+        std::vector<int32_t> tri(d.size());
+        Check(sdfk_trimesh_raycast(h_, d.empty() ? nullptr : &o.data()->X, d.empty() ? nullptr : &d.data()->X, (int64_t)d.size(), tMin, tMax,
+                                   SDFK_RAY_ANY_HIT, tri.data(), nullptr, nullptr));
+        std::vector<bool> out(d.size());
+        for (size_t i = 0; i < d.size(); i++) out[i] = tri[i] >= 0;
+        return out;
+    }
+    // The mesh as one camera sees it (sdfk_trimesh_render), with RayMarcher's own camera, lens defaults, light and sky: Render is
+    // Lambert-shaded (vertex colours blended; a mesh without is white), RenderDepth the distance along every pixel's ray (+inf: the
+    // sky), RenderTriangles the triangle every pixel sees (-1: the sky).  Defined after RayMarcher, whose camera they use.
+    inline Vec3Data Render(int width, int height, const Matrix4x4& viewTransform, float verticalFieldOfViewDegrees = 60.0f, float nearPlaneDistance = 1.0f,
+                           float farPlaneDistance = 100.0f) const;
+    inline FloatData RenderDepth(int width, int height, const Matrix4x4& viewTransform, float verticalFieldOfViewDegrees = 60.0f,
+                                 float nearPlaneDistance = 1.0f, float farPlaneDistance = 100.0f) const;
+    inline std::vector<int32_t> RenderTriangles(int width, int height, const Matrix4x4& viewTransform, float verticalFieldOfViewDegrees = 60.0f,
+                                                float nearPlaneDistance = 1.0f, float farPlaneDistance = 100.0f) const;
     // triangles of non-zero sampling weight and the total weight (the largest triangle has 2^32), as the last SamplePoints read them
     int64_t SampledTriangles() const { return sampleStats_[0]; }
     int64_t SampleTotalWeight() const { return sampleStats_[1]; }
@@ -1408,6 +1474,15 @@ private:
         return false;
     }
     void Counts(int64_t* nv, int64_t* nt) const { *nv = nv_; *nt = nt_; }
+    static void Rays(const std::vector<Vector3>& origins, const std::vector<Vector3>& directions, std::vector<Vector3>& o, std::vector<Vector3>& d)
+    {
+        if (origins.size() != directions.size() && origins.size() != 1) throw std::invalid_argument("one origin per direction, or one for all");
+        d = directions;
+        if (origins.size() == directions.size()) o = origins;
+        else o.assign(directions.size(), origins[0]);
+    }
+    inline void RenderImages(int width, int height, const Matrix4x4& view, float fov, float nearp, float farp, float* depth, float* rgb,
+                             int32_t* triangle) const;
     sdfk_trimesh* h_ = nullptr;
     bool hasColors_ = false;
     int64_t nv_ = 0, nt_ = 0;
@@ -1415,6 +1490,14 @@ private:
 };
 
 inline MeshSamples Mesh::SamplePoints(int64_t n, uint64_t seed, bool stratified) const { return MeshSdf(*this).SamplePoints(n, seed, stratified); }
+inline MeshRayHits Mesh::RayCast(const std::vector<Vector3>& origins, const std::vector<Vector3>& directions, float tMin, float tMax) const
+{
+    return MeshSdf(*this).RayCast(origins, directions, tMin, tMax);
+}
+inline std::vector<bool> Mesh::Occluded(const std::vector<Vector3>& origins, const std::vector<Vector3>& directions, float tMin, float tMax) const
+{
+    return MeshSdf(*this).Occluded(origins, directions, tMin, tMax);
+}
 inline MeshComponents Mesh::Components() const { return MeshSdf(*this).Components(); }
 inline MeshTopology Mesh::Topology() const { return MeshSdf(*this).Topology(); }
 namespace detail {
@@ -1591,16 +1674,19 @@ public:
     FloatData RenderDepth() const { FloatData d; d.Width = w_; d.Height = h_; d.Values.resize((size_t)w_ * h_); Run(d.Values.data(), nullptr); return d; }
 
     // host part of GetCameraRays (RayMarcher.cs:97-112): the camera position and the inverse view-projection sdfk_raymarch takes
-    void Camera(float pos[3], Matrix4x4& vpi) const
+    void Camera(float pos[3], Matrix4x4& vpi) const { CameraOf(ViewTransform, w_, h_, VerticalFieldOfViewDegrees, NearPlaneDistance, FarPlaneDistance, pos, vpi); }
+    // (static: MeshSdf's renders use the same camera and have no Sdf to construct a RayMarcher with)
+    static void CameraOf(const Matrix4x4& view, int width, int height, float verticalFieldOfViewDegrees, float nearPlane, float farPlane, float pos[3],
+                         Matrix4x4& vpi)
     {
         Matrix4x4 cam;
-        Matrix4x4::Invert(ViewTransform, cam);
+        Matrix4x4::Invert(view, cam);
         pos[0] = ((0.0f * cam.M[0][0] + 0.0f * cam.M[1][0]) + 0.0f * cam.M[2][0]) + cam.M[3][0];
         pos[1] = ((0.0f * cam.M[0][1] + 0.0f * cam.M[1][1]) + 0.0f * cam.M[2][1]) + cam.M[3][1];
         pos[2] = ((0.0f * cam.M[0][2] + 0.0f * cam.M[1][2]) + 0.0f * cam.M[2][2]) + cam.M[3][2];
-        const Matrix4x4 proj = Matrix4x4::CreatePerspectiveFieldOfView(VerticalFieldOfViewDegrees * 3.14159274f / 180.0f, (float)w_ / (float)h_,
-                                                                       NearPlaneDistance, FarPlaneDistance);
-        Matrix4x4::Invert(ViewTransform * proj, vpi);
+        const Matrix4x4 proj = Matrix4x4::CreatePerspectiveFieldOfView(verticalFieldOfViewDegrees * 3.14159274f / 180.0f, (float)width / (float)height,
+                                                                       nearPlane, farPlane);
+        Matrix4x4::Invert(view * proj, vpi);
     }
 
 private:
@@ -1615,5 +1701,51 @@ private:
     int w_, h_;
     Sdf sdf_;
 };
+
+// ---- MeshSdf's and Mesh's renders: RayMarcher's camera, sdfk_trimesh_render's images ---------------------------------------
+inline void MeshSdf::RenderImages(int width, int height, const Matrix4x4& view, float fov, float nearp, float farp, float* depth, float* rgb,
+                                  int32_t* triangle) const
+{
+    float pos[3];
+    Matrix4x4 vpi;
+    RayMarcher::CameraOf(view, width, height, fov, nearp, farp, pos, vpi);
+    Check(sdfk_trimesh_render(h_, width, height, pos, &vpi.M[0][0], nearp, farp, depth, rgb, triangle));
+}
+inline Vec3Data MeshSdf::Render(int width, int height, const Matrix4x4& viewTransform, float verticalFieldOfViewDegrees, float nearPlaneDistance,
+                                float farPlaneDistance) const
+{
+    Vec3Data d;
+    d.Width = width; d.Height = height;
+    d.Values.resize((size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0) * 3);
+    RenderImages(width, height, viewTransform, verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance, nullptr, d.Values.data(), nullptr);
+    return d;
+}
+inline FloatData MeshSdf::RenderDepth(int width, int height, const Matrix4x4& viewTransform, float verticalFieldOfViewDegrees, float nearPlaneDistance,
+                                      float farPlaneDistance) const
+{
+    FloatData d;
+    d.Width = width; d.Height = height;
+    d.Values.resize((size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0));
+    RenderImages(width, height, viewTransform, verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance, d.Values.data(), nullptr, nullptr);
+    return d;
+}
+inline std::vector<int32_t> MeshSdf::RenderTriangles(int width, int height, const Matrix4x4& viewTransform, float verticalFieldOfViewDegrees,
+                                                     float nearPlaneDistance, float farPlaneDistance) const
+{
+    std::vector<int32_t> t((size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0));
+    RenderImages(width, height, viewTransform, verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance, nullptr, nullptr, t.data());
+    return t;
+}
+inline Vec3Data Mesh::ToImage(int width, int height, const Matrix4x4& viewTransform, float verticalFieldOfViewDegrees, float nearPlaneDistance,
+                              float farPlaneDistance) const
+{
+    return MeshSdf(*this).Render(width, height, viewTransform, verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance);
+}
+inline Vec3Data Mesh::ToImage(int width, int height, Vector3 cameraPosition, Vector3 cameraTarget, Vector3 cameraUp, float verticalFieldOfViewDegrees,
+                              float nearPlaneDistance, float farPlaneDistance) const
+{
+    return ToImage(width, height, Matrix4x4::CreateLookAt(cameraPosition, cameraTarget, cameraUp), verticalFieldOfViewDegrees, nearPlaneDistance,
+                   farPlaneDistance);
+}
 
 }  // namespace SdfKit

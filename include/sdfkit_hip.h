@@ -44,7 +44,8 @@ extern "C" {
                                    clouds: per-point colours);
                                    sdfk_trimesh_components* / sdfk_trimesh_topology* / sdfk_trimesh_select* (triangle meshes: components,
                                    edge census, sub-meshes);
-                                   sdfk_points_cluster* / sdfk_points_select* (point clouds: clusters) */
+                                   sdfk_points_cluster* / sdfk_points_select* (point clouds: clusters);
+                                   sdfk_trimesh_raycast* / sdfk_trimesh_render* (triangle meshes: ray casting) */
 
 typedef enum sdfk_status {
     SDFK_OK = 0,
@@ -1245,6 +1246,65 @@ int sdfk_trimesh_simplify(sdfk_trimesh* t, float cellSize, int32_t placement, in
 int sdfk_trimesh_simplify_device(sdfk_trimesh* t, float cellSize, int32_t placement, int32_t flags, void* vertex_map_dev,
                                  void* vertex_index_out_dev, void* triangle_index_out_dev, void* triangles_out_dev, void* vertices_out_dev,
                                  void* colors_out_dev, int64_t* nv_out, int64_t* nt_out, int64_t stats[6]);
+
+/* ---- Triangle meshes: ray casting (MeshSdf.RayCast / Occluded / Render, Mesh.ToImage) ----------------------------------------
+ * What does this ray hit: the other spatial query of a handle next to the closest triangle.  ONE function of the mesh, the rays and
+ * the range, computed by csrc/trimesh_ray.h (no contraction), restated in tests/mesh_ray_model.py as brute force over all triangles
+ * and compared bit for bit.  The handle is only read, and nothing about its construction is different.
+ *
+ * The ray-triangle test is the watertight test of Woop, Benthin and Wald (2013), carried out entirely in binary64 from the f32
+ * inputs.  Per ray (origin o, direction d, which need not be a unit vector): kz = the axis of greatest |d|, ties to the lowest
+ * axis; kx = (kz + 1) % 3, ky = (kx + 1) % 3, the two swapped when d[kz] < 0; Sx = d[kx] / d[kz], Sy = d[ky] / d[kz],
+ * Sz = 1 / d[kz].  Per triangle (a, b, c): A = a - o, B = b - o, C = c - o; Ax = A[kx] - Sx A[kz], Ay = A[ky] - Sy A[kz], likewise
+ * Bx, By, Cx, Cy; U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax.  A miss if some of U, V, W is < 0 and some is > 0 (a
+ * zero counts as inside); det = (U + V) + W, a miss if det == 0; T = (U (Sz A[kz]) + V (Sz B[kz])) + W (Sz C[kz]); t = T / det.  A
+ * hit iff t_min <= t <= t_max and t is finite (compared in binary64; a NaN is a miss).  The two triangles of a shared edge form
+ * that edge's function from the same products, so no ray passes between them.
+ *
+ * The answer for a ray is the hit of least (t, triangle index) over ALL triangles of the mesh: triangle = its index,
+ * distance = (float)t in units of |d|, weights3 = (float)(U / det), (float)(V / det), (float)(W / det) -- the weights of a, b, c,
+ * in the layout of sdfk_trimesh_sample.  A miss gives triangle = -1, distance = +inf and NaN weights.  A ray with a NaN or
+ * infinite origin or direction component, or with a zero direction, is a miss.  Any output may be NULL.
+ * flags: SDFK_RAY_ANY_HIT (occlusion queries): triangle = 0 when any triangle is hit within the range and -1 otherwise, the search
+ * stops at the first hit it meets, and distance and weights3 must be NULL.  Any other bit is refused.
+ * Refused (SDFK_ERR_INVALID, nothing written): a null handle, n < 0 or n >= 2^32, a NaN t_min or t_max, t_min > t_max, an unknown
+ * flag, null origins or directions with n > 0.  n == 0 succeeds and touches nothing.
+ *
+ * How (csrc/lib_trimesh_ray.hip): one lane per ray walks the grid the triangles were binned into, slab by slab along the ray's
+ * dominant axis, visiting in each slab the few cells that the ray's box over that slab -- widened by the grid's stated slack --
+ * covers, and stops when every unvisited slab begins beyond the best t.  The walk is conservative (csrc/trimesh_ray.h gives the
+ * argument), so the answer equals brute force; a host program runs the same walk against brute force without a GPU.  One caveat
+ * is stated there: a ray lying in a triangle's plane to within binary64 rounding may be reported by brute force at a t unrelated
+ * to the geometry (an exactly coplanar ray has det == 0 and misses).
+ *
+ * sdfk_trimesh_render: one ray per pixel (i, j) of a width x height image, row-major, generated exactly as sdfk_raymarch's kernel
+ * generates it (the same f32 arithmetic, copied op for op into csrc/trimesh_ray.h camera_ray): x = -1 + 2 i / (width - 1),
+ * y = 1 - 2 j / (height - 1), v = ((x m[q] + y m[4 + q]) + 0 m[8 + q]) + 1 m[12 + q], v.xyz / v.w - camera, divided by its length.
+ * t_min = near_plane, t_max = far_plane (refused like t_min and t_max).  depth[j width + i] = distance (+inf for a miss, which the
+ * ray marcher's "depth > far" rule reads as sky); triangle as above; rgb: a miss is the sky (0.5, 0.75, 1.0), a hit is
+ * dv c + 0.1 with the ray marcher's constants: the hit point s = camera + r distance (f32, mul then add); the normal is the
+ * triangle's binary64 (b - a) x (c - a) divided by its binary64 length ((n0 n0 + n1 n1) + n2 n2 under the root), rounded to f32,
+ * negated when (nx rx + ny ry) + nz rz > 0 in f32, the zero vector for a zero cross product; the light vector (5, 5, 10) - s
+ * normalised as the ray marcher normalises (v (1 / length) when the length is > 0); dv = max(n . l, 0); c = the f32 blend
+ * (ca wa + cb wb) + cc wc of the vertex colours with the f32 weights, or (1, 1, 1) when the mesh has none.  Widths and heights of 1
+ * give non-finite rays, as in the ray marcher: those pixels are misses.  Any image may be NULL, but at least one must be given;
+ * width, height >= 1 and fewer than 2^31 pixels.
+ *
+ * The _device forms take device buffers (camera and matrix stay host pointers) and only queue work on the library stream; the
+ * plain forms take host arrays and synchronise.  While sdfk_profile_enable(1) is on, a ray cast or render counts as the last
+ * query of sdfk_trimesh_stats: stats[5] = the binary64 ray-triangle tests it ran, stats[6] = its rays (that call synchronises).
+ * No float atomics: results are bitwise reproducible. */
+#define SDFK_RAY_ANY_HIT 1
+int sdfk_trimesh_raycast(const sdfk_trimesh* t, const float* origins3, const float* directions3, int64_t n, float t_min, float t_max,
+                         int32_t flags, int32_t* triangle, float* distance, float* weights3);
+int sdfk_trimesh_raycast_device(const sdfk_trimesh* t, const void* origins3_dev, const void* directions3_dev, int64_t n, float t_min,
+                                float t_max, int32_t flags, void* triangle_dev, void* distance_dev, void* weights3_dev);
+int sdfk_trimesh_render(const sdfk_trimesh* t, int32_t width, int32_t height, const float camera_position[3],
+                        const float view_projection_inverse[16], float near_plane, float far_plane, float* depth, float* rgb,
+                        int32_t* triangle);
+int sdfk_trimesh_render_device(const sdfk_trimesh* t, int32_t width, int32_t height, const float camera_position[3],
+                               const float view_projection_inverse[16], float near_plane, float far_plane, void* depth_dev, void* rgb_dev,
+                               void* triangle_dev);
 
 /* ---- Redistancing (Voxels.Redistance) ---------------------------------------------------------------------------------------
  * dst gets a signed distance to the iso-surface of src, with src's sign at every voxel: a first-order Eikonal solve (Godunov

@@ -174,6 +174,10 @@ SIGNATURES = {
     "sdfk_trimesh_weld_device": (C.c_int, [_vp, C.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "sdfk_trimesh_simplify": (C.c_int, [_vp, C.c_float, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "sdfk_trimesh_simplify_device": (C.c_int, [_vp, C.c_float, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "sdfk_trimesh_raycast": (C.c_int, [_vp, _vp, _vp, _i64, C.c_float, C.c_float, _i32, _vp, _vp, _vp]),
+    "sdfk_trimesh_raycast_device": (C.c_int, [_vp, _vp, _vp, _i64, C.c_float, C.c_float, _i32, _vp, _vp, _vp]),
+    "sdfk_trimesh_render": (C.c_int, [_vp, _i32, _i32, _fp, _fp, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "sdfk_trimesh_render_device": (C.c_int, [_vp, _i32, _i32, _fp, _fp, C.c_float, C.c_float, _vp, _vp, _vp]),
     "sdfk_trimesh_free": (None, [_vp]),
     "sdfk_volume_redistance": (C.c_int, [_vp, _vp, C.c_float, C.c_float, C.POINTER(_i64)]),
     "sdfk_icp_register": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),

@@ -760,6 +760,26 @@ class Mesh:
         from .meshsdf import MeshSdf
         return MeshSdf(self).SamplePoints(n, seed, stratified)
 
+    def RayCast(self, origins, directions, tMin=0.0, tMax=float("inf")):
+        """The first hit of every ray with the mesh: triangle, distance, barycentric weights (sdfkit_amd.meshsdf.MeshSdf.RayCast)
+        -> MeshRayHits.  To cast many batches against one mesh, keep a MeshSdf and call its RayCast."""
+        from .meshsdf import MeshSdf
+        return MeshSdf(self).RayCast(origins, directions, tMin, tMax)
+
+    def Occluded(self, origins, directions, tMin=0.0, tMax=float("inf")):
+        """Whether each ray hits anything within the range (MeshSdf.Occluded) -> bool array."""
+        from .meshsdf import MeshSdf
+        return MeshSdf(self).Occluded(origins, directions, tMin, tMax)
+
+    def ToImage(self, width, height, *camera, verticalFieldOfViewDegrees=60.0, nearPlaneDistance=1.0, farPlaneDistance=100.0,
+                depthIterations=40, batchSize=2048, maxDegreeOfParallelism=-1):
+        """The mesh rendered as SdfEx.ToImage renders an SDF: camera = viewTransform, or position, target, up; the same light,
+        sky and lens (MeshSdf.Render) -> Vec3Data.  depthIterations, batchSize and maxDegreeOfParallelism are accepted for the
+        signature's sake: a ray cast has no iterations."""
+        from .meshsdf import MeshSdf
+        return MeshSdf(self).Render(width, height, *camera, verticalFieldOfViewDegrees=verticalFieldOfViewDegrees,
+                                    nearPlaneDistance=nearPlaneDistance, farPlaneDistance=farPlaneDistance)
+
     def Components(self):
         """The connected components by index, with a row of counts each (MeshSdf.Components) -> MeshComponents."""
         from .meshsdf import MeshSdf

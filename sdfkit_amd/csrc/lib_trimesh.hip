@@ -16,7 +16,8 @@
 // the largest area, in units of 2^-32) and their exclusive 64-bit scan W, kept on the handle; every call runs one lane per sample:
 // three stateless draws, a binary search over W, one TriPack gather, the stores.
 // The handle (struct sdfk_trimesh, TriPack) is in trimesh_handle.h, shared with lib_trimesh_topology.hip, which reads W as well, with
-// lib_trimesh_smooth.hip and lib_trimesh_weld.hip; trimesh_check, the check of a handle that all four begin with, is defined here.
+// lib_trimesh_smooth.hip, lib_trimesh_weld.hip, lib_trimesh_simplify.hip and lib_trimesh_ray.hip (which walks the grid along
+// rays); trimesh_check, the check of a handle that all of them begin with, is defined here.
 // Host side: every work function holds its scratch, and every host form its device copies, in a Staged (device_stage.h).
 #include "lib_internal.h"
 #include "device_scan.h"

@@ -1,8 +1,9 @@
 // trimesh_handle.h -- the handle behind sdfk_trimesh_*: the copied arrays, the packed triangles and their search grid (built by
 // lib_trimesh.hip), the sampling weights' scan (made by the first call that needs it) and the component labels (made by the first
 // topology call, lib_trimesh_topology.hip) and the adjacency (made by the first adjacency, smoothing or vertex-normal call,
-// lib_trimesh_smooth.hip).  Seen by those three translation units and by lib_trimesh_weld.hip and lib_trimesh_simplify.hip, which
-// only read it (the latter asks for the corner lists of the adjacency).  With it, what the five share on the host: the staging of
+// lib_trimesh_smooth.hip).  Seen by those three translation units and by lib_trimesh_weld.hip, lib_trimesh_simplify.hip and
+// lib_trimesh_ray.hip, which only read it (simplification asks for the corner lists of the adjacency; the ray caster walks the
+// search grid).  With it, what the six share on the host: the staging of
 // device_stage.h, the check of a handle, the size of a one-dimensional launch, and the grouping of the vertices by position.
 // hipcc only.
 #pragma once

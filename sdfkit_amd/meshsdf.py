@@ -2,7 +2,8 @@
 csrc/lib_trimesh.hip): the exact closest triangle of arbitrary points, signed distance volumes (Mesh -> Voxels), and points
 sampled on the triangles in proportion to area (Mesh -> points), and the connectivity of the mesh by index (components, the edge
 census, sub-meshes of components: csrc/lib_trimesh_topology.hip), and smoothing and vertex normals over its adjacency
-(csrc/lib_trimesh_smooth.hip), and welding: the vertices of equal position made one (csrc/lib_trimesh_weld.hip).
+(csrc/lib_trimesh_smooth.hip), and welding: the vertices of equal position made one (csrc/lib_trimesh_weld.hip), and ray casting:
+the first hit or any hit of arbitrary rays, and camera renders of the mesh (csrc/lib_trimesh_ray.hip).
 
 The distance is exact (binary64 closest point, ties to the lowest triangle index); the sign is the parity of the mesh's
 crossings along z, meaningful for closed meshes (nested shells included) and deterministic for any mesh.
@@ -23,6 +24,7 @@ WELD_KEEP_DEGENERATE = 1    # SDFK_WELD_KEEP_DEGENERATE
 WELD_KEEP_UNREFERENCED = 2  # SDFK_WELD_KEEP_UNREFERENCED
 SIMPLIFY_PLACEMENTS = {"representative": 0, "centroid": 1, "quadric": 2}   # SDFK_SIMPLIFY_REPRESENTATIVE / _CENTROID / _QUADRIC
 SIMPLIFY_DUPLICATES = {"one": 0, "keep": 1, "cancel": 2}                  # 0, SDFK_SIMPLIFY_KEEP_DUPLICATES, SDFK_SIMPLIFY_CANCEL_PAIRS
+RAY_ANY_HIT = 1          # SDFK_RAY_ANY_HIT
 
 # MeshSdf.SamplePoints: Points (n, 3) f32, Normals (n, 3) f32 (unit face normals), Colors (n, 3) f32 or None, Triangles (n,) int32,
 # Weights (n, 3) f32 (the barycentric weights of the triangle's three vertices, as the colour blend used them)
@@ -112,6 +114,21 @@ class MeshSimplify:
         self.VertexMap, self.VertexIndex, self.TriangleIndex, self.Triangles, self.Vertices, self.Colors = vmap, vi, ti, tr, vs, cs
         (self.Merged, self.DegenerateDropped, self.DuplicatesDropped, self.UnreferencedDropped, self.Passes,
          self.QuadricFallbacks) = (int(x) for x in stats)
+
+
+class MeshRayHits:
+    """MeshSdf.RayCast(): Triangles (n,) int32 (-1: a miss), Distances (n,) float32 in units of |direction| (+inf: a miss),
+    Weights (n, 3) float32 (the barycentric weights of the triangle's three vertices, in SamplePoints' layout; NaN: a miss), Hit
+    (n,) bool; Points() -> the hit points origin + direction * distance of the hits, (Hit.sum(), 3) float32, made on the host."""
+
+    def __init__(self, origins, directions, triangles, distances, weights):
+        self.Origins, self.Directions = origins, directions
+        self.Triangles, self.Distances, self.Weights = triangles, distances, weights
+        self.Hit = triangles >= 0
+
+    def Points(self):
+        h = self.Hit
+        return (self.Origins[h] + self.Directions[h] * self.Distances[h, None]).astype(f32)
 
 
 def _ptr(a):
@@ -371,6 +388,103 @@ class MeshSdf:
                                                                                                      colors_dev)],
                                                      C.byref(kv), C.byref(kt), st))
         return kv.value, kt.value, [int(x) for x in st]
+
+    @staticmethod
+    def _rays(origins, directions):
+        o = np.ascontiguousarray(np.asarray(origins, f32).reshape(-1, 3))
+        d = np.ascontiguousarray(np.asarray(directions, f32).reshape(-1, 3))
+        if len(d) != len(o):
+            if len(o) != 1:
+                raise ValueError(f"{len(o)} origins for {len(d)} directions")
+            o = np.ascontiguousarray(np.broadcast_to(o, d.shape))   # (one origin for every direction)
+        return o, d
+
+    def RayCast(self, origins, directions, tMin=0.0, tMax=float("inf")):
+        """The first hit of every ray origin + t direction, tMin <= t <= tMax (sdfk_trimesh_raycast: one stated function of the
+        mesh, the rays and the range; the watertight ray-triangle test in binary64, ties to the lowest triangle index) ->
+        MeshRayHits.  Directions need not be unit vectors: t, and so Distances, is in units of |direction|.  One origin may be
+        given for all directions.  A ray with a NaN or infinite component or a zero direction is a miss."""
+        o, d = self._rays(origins, directions)
+        n = len(o)
+        tri, dist, w = np.empty(n, np.int32), np.empty(n, f32), np.empty((n, 3), f32)
+        N.check(N.lib().sdfk_trimesh_raycast(self._h, _ptr(o), _ptr(d), n, C.c_float(tMin), C.c_float(tMax), 0, _ptr(tri), _ptr(dist), _ptr(w)))
+        return MeshRayHits(o, d, tri, dist, w)
+
+    def RayCastDevice(self, origins_dev, directions_dev, n, tMin=0.0, tMax=float("inf"), triangles_dev=None, distances_dev=None, weights_dev=None,
+                      anyHit=False):
+        """RayCast from and into caller-owned device memory (raw pointers; None: that output is not wanted): only queues work on
+        the library stream.  anyHit: the occlusion query of Occluded (triangles 0 / -1; no distances, no weights)."""
+        N.check(N.lib().sdfk_trimesh_raycast_device(self._h, *[C.c_void_p(p) if p else C.c_void_p() for p in (origins_dev, directions_dev)], int(n),
+                                                    C.c_float(tMin), C.c_float(tMax), RAY_ANY_HIT if anyHit else 0,
+                                                    *[C.c_void_p(p) if p else C.c_void_p() for p in (triangles_dev, distances_dev, weights_dev)]))
+
+    def Occluded(self, origins, directions, tMin=0.0, tMax=float("inf")):
+        """Whether anything is hit within the range, per ray (sdfk_trimesh_raycast with SDFK_RAY_ANY_HIT: the search stops at the
+        first hit it meets) -> (n,) bool, equal to RayCast(...).Hit.  For the line of sight between a sensor s and a point p:
+        Occluded(s, p - s, tMin, 1 - margin)."""
+        o, d = self._rays(origins, directions)
+        n = len(o)
+        tri = np.empty(n, np.int32)
+        N.check(N.lib().sdfk_trimesh_raycast(self._h, _ptr(o), _ptr(d), n, C.c_float(tMin), C.c_float(tMax), RAY_ANY_HIT, _ptr(tri), None, None))
+        return tri >= 0
+
+    @staticmethod
+    def _camera(width, height, camera, verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance):
+        """RayMarcher's own camera: the position and the inverse view-projection of (viewTransform,) or (position, target, up)"""
+        from .raymarch import Matrix4x4, RayMarcher
+        rm = RayMarcher(width, height, None)
+        if camera:
+            rm.ViewTransform = np.asarray(camera[0], f32) if len(camera) == 1 else Matrix4x4.CreateLookAt(*camera)
+        if verticalFieldOfViewDegrees is not None:
+            rm.VerticalFieldOfViewDegrees = verticalFieldOfViewDegrees
+        if nearPlaneDistance is not None:
+            rm.NearPlaneDistance = nearPlaneDistance
+        if farPlaneDistance is not None:
+            rm.FarPlaneDistance = farPlaneDistance
+        return rm.camera() + (rm.NearPlaneDistance, rm.FarPlaneDistance)
+
+    def _render(self, width, height, camera, lens, want_depth, want_rgb, want_triangles):
+        width, height = int(width), int(height)
+        unknown = set(lens) - {"verticalFieldOfViewDegrees", "nearPlaneDistance", "farPlaneDistance"}
+        if unknown:
+            raise TypeError(f"unknown arguments {sorted(unknown)}")
+        if width < 1 or height < 1:   # (the library refuses it; there is no camera of such an image to derive first)
+            N.check(N.lib().sdfk_trimesh_render(self._h, width, height, N.f3((0, 0, 0)), (C.c_float * 16)(), C.c_float(0), C.c_float(1), None, None, None))
+        pos, vpi, near, far = self._camera(width, height, camera, lens.get("verticalFieldOfViewDegrees"), lens.get("nearPlaneDistance"),
+                                           lens.get("farPlaneDistance"))
+        shape = (max(height, 0), max(width, 0))
+        depth = np.empty(shape, f32) if want_depth else None
+        rgb = np.empty(shape + (3,), f32) if want_rgb else None
+        tri = np.empty(shape, np.int32) if want_triangles else None
+        N.check(N.lib().sdfk_trimesh_render(self._h, width, height, N.f3(pos), (C.c_float * 16)(*[float(x) for x in vpi.ravel()]), C.c_float(near),
+                                            C.c_float(far), *[a.ctypes.data if a is not None else None for a in (depth, rgb, tri)]))
+        return depth, rgb, tri
+
+    def Render(self, width, height, *camera, **lens):
+        """The mesh as one camera sees it, Lambert-shaded with RayMarcher's light and sky (sdfk_trimesh_render) -> Vec3Data.
+        camera: nothing (RayMarcher's default view), a view transform, or position, target, up; lens: verticalFieldOfViewDegrees,
+        nearPlaneDistance, farPlaneDistance -- RayMarcher's, with its defaults.  Vertex colours are blended; a mesh without is white."""
+        from .raymarch import Vec3Data
+        return Vec3Data(self._render(width, height, camera, lens, False, True, False)[1])
+
+    def RenderDepth(self, width, height, *camera, **lens):
+        """The distance along every pixel's ray to the first surface between the near and the far plane, +inf where there is none
+        -> FloatData: a depth image as RayMarcher.RenderDepth makes of an SDF."""
+        from .raymarch import FloatData
+        return FloatData(self._render(width, height, camera, lens, True, False, False)[0])
+
+    def RenderTriangles(self, width, height, *camera, **lens):
+        """The index of the triangle every pixel sees, -1 for the sky -> (height, width) int32."""
+        return self._render(width, height, camera, lens, False, False, True)[2]
+
+    def RenderDevice(self, width, height, camera_position, view_projection_inverse, nearPlaneDistance, farPlaneDistance, depth_dev=None, rgb_dev=None,
+                     triangles_dev=None):
+        """sdfk_trimesh_render_device: the images into caller-owned device memory (raw pointers; None: not wanted), queued on the
+        library stream.  camera_position (3) and view_projection_inverse (4 x 4) as RayMarcher.camera() returns them."""
+        N.check(N.lib().sdfk_trimesh_render_device(self._h, int(width), int(height), N.f3(camera_position),
+                                                   (C.c_float * 16)(*[float(x) for x in np.asarray(view_projection_inverse, f32).ravel()]),
+                                                   C.c_float(nearPlaneDistance), C.c_float(farPlaneDistance),
+                                                   *[C.c_void_p(p) if p else C.c_void_p() for p in (depth_dev, rgb_dev, triangles_dev)]))
 
     def stats(self):
         """sdfk_trimesh_stats: grid, triangles, binned pairs, candidates / queries of the last profiled call, crossings."""

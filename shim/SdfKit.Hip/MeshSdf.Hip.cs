@@ -9,6 +9,8 @@
 // smoothing of the positions and area-weighted normals from the geometry; Mesh.Smooth / Mesh.RecomputeNormals on top of them.
 // Weld (sdfk_trimesh_weld): the vertices of equal position made one; Mesh.Weld and Concat (a static of the extensions class) on top.
 // Simplify (sdfk_trimesh_simplify): vertex clustering, the vertices of one lattice cell made one made vertex; Mesh.Simplify on top.
+// RayCast / Occluded / Render / RenderDepth / RenderTriangles (sdfk_trimesh_raycast, _render): the first hit or any hit of arbitrary
+// rays, and the mesh as a camera sees it (the ray marcher's camera, light and sky); Mesh.RayCast / Occluded / ToImage on top.
 // UNCOMPILED HERE (no .NET in the build image); sdfkit_amd/meshsdf.py's MeshSdf is the same layer, tested.
 using System;
 using System.Collections.Generic;
@@ -83,6 +85,27 @@ namespace SdfKit
         public Vector3[] Vertices = Array.Empty<Vector3> ();
         public Vector3[] Colors = Array.Empty<Vector3> ();
         public long Merged, DegenerateDropped, UnreferencedDropped, Passes;
+    }
+
+    /// <summary>MeshSdf.RayCast: per ray the first triangle hit (-1: none), the distance in units of |direction| (+inf: none) and the
+    /// barycentric weights of the triangle's three vertices (NaN: none), in MeshSamples' layout.</summary>
+    public sealed class MeshRayHits
+    {
+        public Vector3[] Origins = Array.Empty<Vector3> ();
+        public Vector3[] Directions = Array.Empty<Vector3> ();
+        public int[] Triangles = Array.Empty<int> ();
+        public float[] Distances = Array.Empty<float> ();
+        public Vector3[] Weights = Array.Empty<Vector3> ();
+        public bool Hit (int i) => Triangles[i] >= 0;
+        /// <summary>origin + direction * distance of the hits, in ray order (made on the host).</summary>
+        public Vector3[] Points ()
+        {
+            var p = new List<Vector3> ();
+            for (int i = 0; i < Triangles.Length; i++)
+                if (Triangles[i] >= 0)
+                    p.Add (Origins[i] + Directions[i] * Distances[i]);
+            return p.ToArray ();
+        }
     }
 
     /// <summary>MeshSdf.Simplify: MeshWeld's fields for the clustered mesh (VertexMap: the new number of every old vertex's group;
@@ -330,6 +353,82 @@ namespace SdfKit
                                       UnreferencedDropped = st[3], Passes = st[4], QuadricFallbacks = st[5] };
         }
 
+        const int RayAnyHit = 1;   // SDFK_RAY_ANY_HIT
+
+        /// <summary>The first hit of every ray origin + t direction, tMin &lt;= t &lt;= tMax: the watertight ray-triangle test in binary64,
+        /// ties to the lowest triangle index.  Directions need not be unit vectors.  A ray with a NaN or infinite component or a zero
+        /// direction is a miss.</summary>
+        public unsafe MeshRayHits RayCast (ReadOnlySpan<Vector3> origins, ReadOnlySpan<Vector3> directions, float tMin = 0, float tMax = float.PositiveInfinity)
+        {
+            if (origins.Length != directions.Length)
+                throw new ArgumentException ("one origin per direction");
+            int n = directions.Length;
+            var r = new MeshRayHits { Origins = origins.ToArray (), Directions = directions.ToArray (), Triangles = new int[n], Distances = new float[n],
+                                      Weights = new Vector3[n] };
+            fixed (Vector3* o = r.Origins) fixed (Vector3* d = r.Directions) fixed (int* t = r.Triangles) fixed (float* dist = r.Distances)
+            fixed (Vector3* w = r.Weights)
+                Native.Check (Native.sdfk_trimesh_raycast (handle, (float*)o, (float*)d, n, tMin, tMax, 0, t, dist, (float*)w));
+            return r;
+        }
+
+        /// <summary>Whether anything is hit within the range, per ray (the search stops at the first hit it meets).</summary>
+        public unsafe bool[] Occluded (ReadOnlySpan<Vector3> origins, ReadOnlySpan<Vector3> directions, float tMin = 0, float tMax = float.PositiveInfinity)
+        {
+            if (origins.Length != directions.Length)
+                throw new ArgumentException ("one origin per direction");
+            int n = directions.Length;
+            var tri = new int[n];
+            fixed (Vector3* o = origins) fixed (Vector3* d = directions) fixed (int* t = tri)
+                Native.Check (Native.sdfk_trimesh_raycast (handle, (float*)o, (float*)d, n, tMin, tMax, RayAnyHit, t, null, null));
+            var occluded = new bool[n];
+            for (int i = 0; i < n; i++)
+                occluded[i] = tri[i] >= 0;
+            return occluded;
+        }
+
+        // The camera of RayMarcher.GetCameraRays: the position is the translation of the inverted view transform, the matrix the
+        // inverse of view * perspective (System.Numerics, as the reference computes them).
+        unsafe void RenderImages (int width, int height, Matrix4x4 viewTransform, float verticalFieldOfViewDegrees, float near, float far,
+                                  float* depth, float* rgb, int* triangle)
+        {
+            Matrix4x4.Invert (viewTransform, out var cam);
+            var pos = Vector3.Transform (Vector3.Zero, cam);
+            var proj = Matrix4x4.CreatePerspectiveFieldOfView (verticalFieldOfViewDegrees * MathF.PI / 180.0f, (float)width / height, near, far);
+            Matrix4x4.Invert (viewTransform * proj, out var vpi);
+            Native.Check (Native.sdfk_trimesh_render (handle, width, height, (float*)&pos, (float*)&vpi, near, far, depth, rgb, triangle));
+        }
+
+        /// <summary>The mesh as one camera sees it, Lambert-shaded with the ray marcher's light and sky: width * height RGB triples,
+        /// row-major.  Vertex colours are blended; a mesh without is white.</summary>
+        public unsafe Vector3[] Render (int width, int height, Matrix4x4 viewTransform, float verticalFieldOfViewDegrees = 60, float nearPlaneDistance = 1,
+                                        float farPlaneDistance = 100)
+        {
+            var rgb = new Vector3[width * height];
+            fixed (Vector3* p = rgb)
+                RenderImages (width, height, viewTransform, verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance, null, (float*)p, null);
+            return rgb;
+        }
+
+        /// <summary>The distance along every pixel's ray to the first surface between the planes, +inf where there is none.</summary>
+        public unsafe float[] RenderDepth (int width, int height, Matrix4x4 viewTransform, float verticalFieldOfViewDegrees = 60, float nearPlaneDistance = 1,
+                                           float farPlaneDistance = 100)
+        {
+            var depth = new float[width * height];
+            fixed (float* p = depth)
+                RenderImages (width, height, viewTransform, verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance, p, null, null);
+            return depth;
+        }
+
+        /// <summary>The triangle every pixel sees, -1 for the sky.</summary>
+        public unsafe int[] RenderTriangles (int width, int height, Matrix4x4 viewTransform, float verticalFieldOfViewDegrees = 60, float nearPlaneDistance = 1,
+                                             float farPlaneDistance = 100)
+        {
+            var tri = new int[width * height];
+            fixed (int* p = tri)
+                RenderImages (width, height, viewTransform, verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance, null, null, p);
+            return tri;
+        }
+
         public void Dispose ()
         {
             if (handle != IntPtr.Zero) {
@@ -456,6 +555,42 @@ namespace SdfKit
             }
             return new Mesh (w.Vertices, w.Colors, n, w.Triangles);   // (the constructor measures Min / Max; empty arrays: an empty Mesh)
         }
+
+        /// <summary>Mesh.RayCast: the first hit of every ray with the mesh (MeshSdf.RayCast).  To cast many batches against one
+        /// mesh, keep a MeshSdf.</summary>
+        public static MeshRayHits RayCast (this Mesh mesh, ReadOnlySpan<Vector3> origins, ReadOnlySpan<Vector3> directions, float tMin = 0,
+                                           float tMax = float.PositiveInfinity)
+        {
+            using var m = new MeshSdf (mesh);
+            return m.RayCast (origins, directions, tMin, tMax);
+        }
+
+        /// <summary>Mesh.Occluded: whether each ray hits anything within the range (MeshSdf.Occluded).</summary>
+        public static bool[] Occluded (this Mesh mesh, ReadOnlySpan<Vector3> origins, ReadOnlySpan<Vector3> directions, float tMin = 0,
+                                       float tMax = float.PositiveInfinity)
+        {
+            using var m = new MeshSdf (mesh);
+            return m.Occluded (origins, directions, tMin, tMax);
+        }
+
+        /// <summary>Mesh.ToImage: the mesh rendered as SdfEx.ToImage renders an SDF -- the same camera, light, sky and lens --
+        /// as a Vec3Data (MeshSdf.Render).</summary>
+        public static Vec3Data ToImage (this Mesh mesh, int width, int height, Matrix4x4 viewTransform, float verticalFieldOfViewDegrees = 60,
+                                        float nearPlaneDistance = 1, float farPlaneDistance = 100)
+        {
+            using var m = new MeshSdf (mesh);
+            var rgb = m.Render (width, height, viewTransform, verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance);
+            var image = new Vec3Data (width, height);
+            for (int y = 0; y < height; y++)
+                for (int x = 0; x < width; x++)
+                    image[x, y] = rgb[y * width + x];
+            return image;
+        }
+
+        public static Vec3Data ToImage (this Mesh mesh, int width, int height, Vector3 cameraPosition, Vector3 cameraTarget, Vector3 cameraUp,
+                                        float verticalFieldOfViewDegrees = 60, float nearPlaneDistance = 1, float farPlaneDistance = 100)
+            => mesh.ToImage (width, height, Matrix4x4.CreateLookAt (cameraPosition, cameraTarget, cameraUp), verticalFieldOfViewDegrees, nearPlaneDistance,
+                             farPlaneDistance);
 
         /// <summary>Mesh.Concat: the meshes one after the other, the indices of each offset by the vertices before it (on the host;
         /// nothing is merged: Weld afterwards joins the pieces where their positions agree).</summary>

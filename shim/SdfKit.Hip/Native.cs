@@ -200,6 +200,15 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_trimesh_simplify_device(IntPtr trimesh, float cellSize, int placement, int flags, IntPtr vertexMapDev,
                                                                                IntPtr vertexIndexOutDev, IntPtr triangleIndexOutDev, IntPtr trianglesOutDev,
                                                                                IntPtr verticesOutDev, IntPtr colorsOutDev, long* nvOut, long* ntOut, long* stats6);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_raycast(IntPtr trimesh, float* origins3, float* directions3, long n, float tMin, float tMax,
+                                                                       int flags, int* triangle, float* distance, float* weights3);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_raycast_device(IntPtr trimesh, IntPtr origins3Dev, IntPtr directions3Dev, long n, float tMin,
+                                                                              float tMax, int flags, IntPtr triangleDev, IntPtr distanceDev, IntPtr weights3Dev);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_render(IntPtr trimesh, int width, int height, float* cameraPosition, float* viewProjectionInverse,
+                                                                      float near, float far, float* depth, float* rgb, int* triangle);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_render_device(IntPtr trimesh, int width, int height, float* cameraPosition,
+                                                                             float* viewProjectionInverse, float near, float far, IntPtr depthDev, IntPtr rgbDev,
+                                                                             IntPtr triangleDev);
         [DllImport(Lib)] public static extern void sdfk_trimesh_free(IntPtr trimesh);
         [DllImport(Lib)] public static extern int sdfk_volume_redistance(IntPtr src, IntPtr dst, float isoValue, float maxDistance, long* stats4);
         // several GPUs from ONE process (the managed host is one process): include/sdfkit_hip.h, "one process, several GPUs"
