@@ -236,7 +236,12 @@ typedef enum sdfk_option {
                                  * -- when the program is cheap enough to be evaluated a second time, one voxel per lane.  0 (default): two
                                  * passes for programs of at most 24 operations (one primitive with a constant colour) on grids of at least
                                  * 2^21 voxels, one pass otherwise; 1: always one pass; 2: always two.  Bit-identical results either way. */
-    SDFK_OPT_COUNT_ = 18
+    SDFK_OPT_COUNT_BYTES = 18,  /* 1 (default): a sdfk_sample_march job whose fused sampler has just written the sign bytes of its own, stored volume
+                                   (step 1, a byte pitch that is a multiple of 8, at most 8192 compaction blocks) counts its active cells straight
+                                   from those bytes (k_count_bytes): no sign-word array, no transposer launch.  0: every job regroups the bytes into
+                                   words first (k_bits_transpose, k_compact), as all other jobs always do.  Meshes are bit-identical
+                                   (an option added since ABI 6; existing keys unchanged) */
+    SDFK_OPT_COUNT_ = 19
 } sdfk_option;
 int sdfk_set_option(int32_t key, int64_t value);
 int sdfk_get_option(int32_t key, int64_t* value);

@@ -207,6 +207,7 @@ OPT_DIST_EXCHANGE, OPT_DIST_LANES, OPT_HW_QUEUES, OPT_CODE_CACHE, OPT_PREFAULT_H
 OPT_IDLE_PROGRAMS = 15
 OPT_ELIDE_VOLUME = 16
 OPT_COLOR_PASSES = 17
+OPT_COUNT_BYTES = 18
 
 
 def library_path():

@@ -551,6 +551,7 @@ void config_from_env_once()
     g_cfg.prefault_huge = geti("SDFK_PREFAULT_HUGE", 0) ? 1 : 0;
     g_cfg.place_streams = geti("SDFK_STREAM_PLACEMENT", 1) ? 1 : 0;
     g_cfg.idle_lane = geti("SDFK_IDLE_LANE", 1) ? 1 : 0;
+    g_cfg.count_bytes = geti("SDFK_COUNT_BYTES", 1) ? 1 : 0;
     g_cfg.sample_mode = geti("SDFK_SAMPLE_MODE", -1);
     g_cfg.hw_queues = geti("GPU_MAX_HW_QUEUES", 0);
     g_cfg.env_cache_dir = gets("SDFK_CACHE_DIR");
@@ -679,6 +680,7 @@ extern "C" void sdfk_shutdown(void)
         for (auto& kv : lane.free_blocks) (void)hipFree(kv.second);
         lane.free_blocks.clear();
         lane.clean_cull_headers.clear();   // (still among the live blocks: freed with them)
+        lane.clean_counts.clear();
     }
     for (auto& kv : g.live_blocks) (void)hipFree(kv.first);
     g.live_blocks.clear();
@@ -812,6 +814,7 @@ extern "C" int sdfk_set_option(int32_t key, int64_t value)
     case SDFK_OPT_DIST_INDEX16: if (!in(0, 1)) break; g_cfg.dist_index16 = (int)value; return SDFK_OK;
     case SDFK_OPT_STREAM_PLACEMENT: if (!in(0, 1)) break; g_cfg.place_streams = (int)value; return SDFK_OK;
     case SDFK_OPT_IDLE_LANE: if (!in(0, 1)) break; g_cfg.idle_lane = (int)value; return SDFK_OK;
+    case SDFK_OPT_COUNT_BYTES: if (!in(0, 1)) break; g_cfg.count_bytes = (int)value; return SDFK_OK;
     case SDFK_OPT_CODE_CACHE: if (!in(0, 1)) break; g_cfg.code_cache = (int)value; return SDFK_OK;
     case SDFK_OPT_IDLE_PROGRAMS: if (!in(0, 1024)) break; g_cfg.idle_programs = (int)value; codes_trim(); return SDFK_OK;
     case SDFK_OPT_ELIDE_VOLUME: if (!in(0, 2)) break; g_cfg.elide_volume = (int)value; return SDFK_OK;
@@ -840,6 +843,7 @@ extern "C" int sdfk_get_option(int32_t key, int64_t* value)
     case SDFK_OPT_DIST_INDEX16: *value = g_cfg.dist_index16; break;
     case SDFK_OPT_STREAM_PLACEMENT: *value = g_cfg.place_streams; break;
     case SDFK_OPT_IDLE_LANE: *value = g_cfg.idle_lane; break;
+    case SDFK_OPT_COUNT_BYTES: *value = g_cfg.count_bytes; break;
     case SDFK_OPT_CODE_CACHE: *value = g_cfg.code_cache; break;
     case SDFK_OPT_IDLE_PROGRAMS: *value = g_cfg.idle_programs; break;
     case SDFK_OPT_ELIDE_VOLUME: *value = g_cfg.elide_volume; break;

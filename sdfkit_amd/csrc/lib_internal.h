@@ -76,6 +76,7 @@ struct Config {
     int prefault_huge = 0;    // SDFK_OPT_PREFAULT_HUGE
     int place_streams = 1;    // SDFK_OPT_STREAM_PLACEMENT
     int idle_lane = 1;        // SDFK_OPT_IDLE_LANE
+    int count_bytes = 1;      // SDFK_OPT_COUNT_BYTES
     int copy_threads = 0;     // SDFK_COPY_THREADS (0: min(16, cores / 2)); fixed once the pool has started
     int sample_mode = -1;     // SDFK_SAMPLE_MODE (debugging: force the row-tiled (0) / plane-chunk (1) sampler)
     int hw_queues = 0;        // GPU_MAX_HW_QUEUES as the process had it when the library initialised (0: unset)
@@ -120,7 +121,10 @@ struct Context {
     static constexpr int NSIDE = 4;
     // (clean_cull_headers: counter blocks of the culling kernel that are known to be all zero IN THIS LANE'S STREAM ORDER -- the count pass
     // of the job that used one last cleared it --, so that a volume-less job needs no memset in front of its first kernel)
-    struct Lane { hipStream_t stream = nullptr; std::multimap<size_t, void*> free_blocks; std::vector<uint32_t*> clean_cull_headers; };
+    // (clean_counts: the same for the count arrays of jobs that count from the sign bytes -- k_count_bytes ADDS into blockcnt / wavecnt, k_resolve
+    // of the job that used a block last zeroed it --, by size in bytes)
+    struct Lane { hipStream_t stream = nullptr; std::multimap<size_t, void*> free_blocks; std::vector<uint32_t*> clean_cull_headers;
+                  std::multimap<size_t, void*> clean_counts; };
     Lane lanes[1 + NSIDE];
     // stream placement (place_streams): the streams the library made for its lanes and the exchange, the class -- set of
     // streams that must not be busy together -- each was measured to be in, and who uses which
@@ -450,6 +454,9 @@ struct sdfk_volume {
     uint8_t* bits8 = nullptr;         // the sampling kernel's byte form of the same bits ([y][x/8][z])
     float bits_iso = 0.0f;
     bool bits_valid = false;
+    // the private volume of a sdfk_sample_march job that counts from the bytes (SDFK_OPT_COUNT_BYTES): `bits` is never allocated, the
+    // sampler's transposer launch is left out, bits_valid speaks of bits8.  Nobody but that job's marching cubes reads such a volume.
+    bool bytes_only = false;
     // the program whose output `values` still is, with the arguments it ran with (nullptr once
     // the values may have changed): marching cubes then re-evaluates cell corners instead of
     // gathering them
@@ -513,6 +520,13 @@ struct sdfk_march_job {
     bool finished = false;
     bool empty = false;
     bool have_bits = false;
+    // SDFK_OPT_COUNT_BYTES: the count pass reads the volume's sign bytes (P.bits8; P.bits is null).  blockcnt and wavecnt are then ONE
+    // block that is zero whenever no classification is in flight (`counts`: from the lane's clean blocks or cleared once; back there
+    // at release if counts_clean -- the last launch_classify got as far as queueing k_resolve, which zeroes it)
+    bool count_bytes = false;
+    void* counts = nullptr;
+    size_t counts_bytes = 0;
+    bool counts_clean = false;
     uint8_t* bits8 = nullptr;            // byte form of the sign bits (k_signbits8 -> k_bits_transpose), job-owned
     sdfk_program* eval_prog = nullptr;   // corners by re-evaluation (holds a reference)
     SampleArgs eval_args;

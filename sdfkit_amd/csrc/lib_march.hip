@@ -60,6 +60,11 @@ void job_release(sdfk_march_job* j, bool kernels_may_be_queued)
     }
     for (void* p : j->owned) dev_free(p);
     j->owned.clear();
+    if (j->counts) {   // (zero again, in its lane's order: the next job of that lane with as many blocks takes it as it is)
+        if (j->counts_clean && g.lanes[j->lane].clean_counts.size() < 16) g.lanes[j->lane].clean_counts.emplace(j->counts_bytes, j->counts);
+        else dev_free(j->counts);
+        j->counts = nullptr;
+    }
     if (j->eval_prog) program_release(j->eval_prog);
     j->eval_prog = nullptr;
     if (j->sub) {
@@ -128,7 +133,12 @@ int launch_classify(sdfk_march_job* j, bool publish)
         ProfScope ps("k_compact");
         // (a workgroup takes the same 1024 segments of K2_LPB consecutive layers: mc_kernels.hip)
         const int nwg = ((P.lay_list_end - P.lay_count_begin + K2_LPB - 1) / K2_LPB) * P.bpl;
-        hipLaunchKernelGGL(k_compact<false>, dim3(nwg), dim3(256), 0, g.stream, P);
+        if (j->count_bytes) {
+            // from the sign bytes (SDFK_OPT_COUNT_BYTES): four cell rows of one word column per workgroup, 512 layers per grid step in z
+            j->counts_clean = false;   // (until k_resolve, which zeroes the counts again, is queued behind this)
+            hipLaunchKernelGGL(k_count_bytes, dim3((unsigned)(P.ncy + 3) / 4, (unsigned)P.nxw, (unsigned)(P.ncz + 511) / 512), dim3(256), 0, g.stream, P);
+        } else
+            hipLaunchKernelGGL(k_compact<false>, dim3(nwg), dim3(256), 0, g.stream, P);
         // (the count pass clears the culling kernel's counters: host bookkeeping of a device-side effect, so only once the launch is
         // known to be queued and to have workgroups -- a counter block recorded as clean that is not would make the next volume-less
         // job walk stale work lists)
@@ -136,8 +146,9 @@ int launch_classify(sdfk_march_job* j, bool publish)
         if (P.zero_cull && j->cull_clean && nwg > 0) *j->cull_clean = true;
         if (P.blockpre) hipLaunchKernelGGL(k_blockscan, dim3(1), dim3(1024), 0, g.stream, P);   // (many blocks: their prefix in one pass)
         if (SDFK_COMPACT_STRIDED && K2_LPB == 1)   // (the write pass with interleaved segments: mc_kernels.hip)
-            if (P.segmask) hipLaunchKernelGGL(k_compact_write<true>, dim3((P.lay_list_end - P.lay_count_begin) * P.bpl), dim3(256), 0, g.stream, P);
-            else hipLaunchKernelGGL(k_compact_write<false>, dim3((P.lay_list_end - P.lay_count_begin) * P.bpl), dim3(256), 0, g.stream, P);
+            if (j->count_bytes) hipLaunchKernelGGL((k_compact_write<true, true>), dim3((P.lay_list_end - P.lay_count_begin) * P.bpl), dim3(256), 0, g.stream, P);
+            else if (P.segmask) hipLaunchKernelGGL((k_compact_write<true, false>), dim3((P.lay_list_end - P.lay_count_begin) * P.bpl), dim3(256), 0, g.stream, P);
+            else hipLaunchKernelGGL((k_compact_write<false, false>), dim3((P.lay_list_end - P.lay_count_begin) * P.bpl), dim3(256), 0, g.stream, P);
         else
             hipLaunchKernelGGL(k_compact<true>, dim3(nwg), dim3(256), 0, g.stream, P);
         HIPCHK(hipGetLastError());
@@ -165,6 +176,7 @@ int launch_classify(sdfk_march_job* j, bool publish)
         // needs the counts before (or without) emitting
         if (publish) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, g.stream, P);
         HIPCHK(hipGetLastError());
+        j->counts_clean = true;   // (k_resolve cleared blockcnt / wavecnt behind their last reader)
     }
     return SDFK_OK;
 }
@@ -264,16 +276,41 @@ int setup_job(const sdfk_volume* v, float iso, int step, int layer_begin, int la
         j->eval_prog->refs++;
         j->eval_args = v->sampled_args;
     }
-    j->have_bits = (step == 1 && v->bits && v->bits_valid && v->bits_iso == iso);
-    if (j->have_bits) P.bits = v->bits;   // written by the fused sampling kernel; owned by the volume
+    const int nlog = (P.lay_list_end - P.lay_count_begin) * P.bpl;
+    // SDFK_OPT_COUNT_BYTES: the volume holds the sampler's sign bytes and nothing made words of them (count_bytes_applies, below)
+    j->count_bytes = step == 1 && v->bytes_only && v->bits8 && v->bits_valid && v->bits_iso == iso && !slab && P.lay_count_begin == 0 &&
+                     P.lay_list_end == P.ncz && nlog <= MC_SCAN_BLOCKS && SDFK_COMPACT_STRIDED && K2_LPB == 1 && SDFK_COMPACT_MASKS;
+    j->have_bits = j->count_bytes || (step == 1 && v->bits && v->bits_valid && v->bits_iso == iso);
+    if (j->count_bytes) {
+        P.bits = nullptr;
+        P.bits8 = v->bits8; P.nx8 = v->nx8(); P.pitch8 = v->pitch8();
+        P.nsegp = (P.ncy * P.nxw + 7) & ~7;
+        r = r ? r : job_alloc(j, &P.segvalid, (size_t)((P.ncz + 511) / 512) * 8 * P.nsegp);
+    } else if (j->have_bits) P.bits = v->bits;   // written by the fused sampling kernel; owned by the volume
     else {
         uint64_t* bits = nullptr;
         r = r ? r : job_alloc(j, &bits, (size_t)P.nz * P.ny * P.nxw + 8);   // k_compact reads 4 words past a row pair
         P.bits = bits;
         r = r ? r : job_alloc(j, &j->bits8, (size_t)P.ny * ((P.nx + 7) / 8) * ((P.nz + 3) & ~3) + 64);
     }
-    r = r ? r : job_alloc(j, &P.blockcnt, (size_t)(P.lay_list_end - P.lay_count_begin) * P.bpl + 1);
-    r = r ? r : job_alloc(j, &P.wavecnt, (size_t)(P.lay_list_end - P.lay_count_begin) * P.bpl * 4 + 4);
+    if (j->count_bytes && !r) {
+        // k_count_bytes ADDS into the counts: one block for both, zero in this lane's stream order -- a block k_resolve of an earlier job
+        // of the lane left that way, or a new one, cleared once
+        j->counts_bytes = ((size_t)nlog + 1) * sizeof(uint64_t) + ((size_t)nlog * 4 + 4) * sizeof(uint32_t);
+        auto& clean = g.lanes[g.cur_lane].clean_counts;
+        auto it = clean.find(j->counts_bytes);
+        if (it != clean.end()) { j->counts = it->second; clean.erase(it); }
+        else {
+            r = dev_alloc(&j->counts, j->counts_bytes);
+            if (!r && hipMemsetAsync(j->counts, 0, j->counts_bytes, g.stream) != hipSuccess) r = fail(SDFK_ERR_HIP, "hipMemsetAsync failed");
+        }
+        j->counts_clean = !r;
+        P.blockcnt = (uint64_t*)j->counts;
+        P.wavecnt = (uint32_t*)((char*)j->counts + ((size_t)nlog + 1) * sizeof(uint64_t));
+    } else {
+        r = r ? r : job_alloc(j, &P.blockcnt, (size_t)nlog + 1);
+        r = r ? r : job_alloc(j, &P.wavecnt, (size_t)nlog * 4 + 4);
+    }
     P.segmask = nullptr;
     if (SDFK_COMPACT_STRIDED && K2_LPB == 1 && SDFK_COMPACT_MASKS)   // (the write pass reads the count pass's masks: mc_kernels.hip)
         r = r ? r : job_alloc(j, &P.segmask, (size_t)(P.lay_list_end - P.lay_count_begin) * P.bpl * 1024 + 4);
@@ -1211,6 +1248,19 @@ extern "C" int sdfk_march_host(const float* values, const float* colors3, int32_
     return r;
 }
 
+// SDFK_OPT_COUNT_BYTES: may the private volume of a sdfk_sample_march job keep its sign bits as the sampler's BYTES only, for a count pass
+// that reads those (k_count_bytes)?  The kernel's shape decides: 8-byte loads along z need rows of a multiple of 8 bytes; a block's counts
+// are sums over many workgroups, which the write pass sums again itself only up to MC_SCAN_BLOCKS blocks (beyond, k_blockscan would need
+// them too); whole volumes, step 1.  (setup_job asks the same of the job and falls back to the voxels if anything else is off.)
+static bool count_bytes_applies(const sdfk_volume* v, int step)
+{
+    if (!g_cfg.count_bytes || step != 1 || v->z0 != 0 || v->nz != v->nz_global || v->nx < 2 || v->ny < 2 || v->nz < 2) return false;
+    if (v->elided && g_cfg.elide_volume >= 2) return false;   // (block culling writes words, there are no bytes)
+    if ((v->pitch8() & 7) != 0 || v->nxw() > 65535) return false;
+    const size_t bpl = ((size_t)(v->ny - 1) * v->nxw() + 1023) / 1024;
+    return bpl * (size_t)(v->nz - 1) <= (size_t)MC_SCAN_BLOCKS && SDFK_COMPACT_STRIDED && K2_LPB == 1 && SDFK_COMPACT_MASKS;
+}
+
 extern "C" int sdfk_sample_march(const sdfk_program* p, const float min[3], const float max[3],
                                  int32_t nx, int32_t ny, int32_t nz, int32_t clip_to_bounds,
                                  float iso_value, int32_t step, sdfk_mesh** out)
@@ -1270,6 +1320,7 @@ extern "C" int sdfk_sample_march(const sdfk_program* p, const float min[3], cons
         const int dflt = (int64_t)nx * ny * nz >= (int64_t(1) << 27) ? 1 : 0;
         g.token_mask = (lane > 0 && g.side_lanes > 1) ? (g_cfg.tokens >= 0 ? g_cfg.tokens : dflt) : 0;
     }
+    if (!r) v->bytes_only = count_bytes_applies(v, step);   // (nobody but this job's marching cubes ever reads v)
     if (!r) r = sample_impl(p, v, clip_to_bounds, step == 1 ? iso_value : 0.0f);
     if (!r) r = sdfk_march(v, iso_value, step, out);
     g.token_mask = 0;

@@ -244,7 +244,7 @@ int sample_impl(const sdfk_program* p, sdfk_volume* v, int32_t clip_to_bounds, f
     {
         // fused sampling + sign bits (iso known or guessed 0): marching cubes then skips its
         // dense pass over the volume
-        if (!v->bits) {
+        if (!v->bits && !v->bytes_only) {   // (bytes_only, SDFK_OPT_COUNT_BYTES: the job's count pass reads the bytes themselves)
             if (int r = dev_alloc((void**)&v->bits, v->nbitwords() * sizeof(uint64_t))) return r;
         }
         if (!v->bits8 && !(v->elided && g_cfg.elide_volume >= 2)) {   // (block culling writes the words directly: no byte form)
@@ -356,7 +356,7 @@ int sample_impl(const sdfk_program* p, sdfk_volume* v, int32_t clip_to_bounds, f
             v->bits_valid = false;
             return SDFK_OK;
         }
-        if (!(v->elided && g_cfg.elide_volume >= 2)) {   // (the block-culling kernels write the words themselves)
+        if (!(v->elided && g_cfg.elide_volume >= 2) && !v->bytes_only) {   // (the block-culling kernels write the words themselves)
             ProfScope ps("k_bits_transpose");
             hipLaunchKernelGGL(k_bits_transpose, transpose_grid(v->nz, v->ny, v->nxw()), dim3(256), 0, g.stream,
                                v->bits8, v->bits, v->nx8(), v->ny, v->nz, v->nxw(), v->pitch8());

@@ -59,9 +59,11 @@ __global__ void k_bits_transpose(const uint8_t* __restrict__ bits8, uint64_t* __
 template <bool WRITE> __global__ void k_compact(McParams P);
 extern template __global__ void k_compact<true>(McParams P);
 extern template __global__ void k_compact<false>(McParams P);
-template <bool MASKS> __global__ void k_compact_write(McParams P);
-extern template __global__ void k_compact_write<true>(McParams P);
-extern template __global__ void k_compact_write<false>(McParams P);
+__global__ void k_count_bytes(McParams P);
+template <bool MASKS, bool VALID> __global__ void k_compact_write(McParams P);
+extern template __global__ void k_compact_write<true, false>(McParams P);
+extern template __global__ void k_compact_write<false, false>(McParams P);
+extern template __global__ void k_compact_write<true, true>(McParams P);
 __global__ void k_blockscan(McParams P);
 __global__ void k_publish(McParams P);
 __global__ void k_chunkscan(McParams P);

@@ -35,6 +35,7 @@
 #include <stdint.h>
 #include "mc_device.h"
 #include "mc_kernels.h"
+#include "mc_signbytes.h"
 
 namespace sdfk {
 
@@ -290,7 +291,7 @@ __device__ __forceinline__ int compact_block_of_workgroup(int nlay, int bpl)
 // ---------------------------------------------------------------------------
 // K2: ordered compaction of active cells
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t shr1_in(uint64_t w, uint64_t next) { return (w >> 1) | (next << 63); }
+// (shr1_in and segment_mask, the activity of a 64-cell segment from its sign words: mc_signbytes.h)
 
 typedef unsigned long long u64x2u __attribute__((ext_vector_type(2), aligned(8)));
 
@@ -300,24 +301,6 @@ __device__ __forceinline__ void load_words5(const uint64_t* p, uint64_t* w)
     const u64x2u lo = *reinterpret_cast<const u64x2u*>(p);
     const u64x2u hi = *reinterpret_cast<const u64x2u*>(p + 2);
     w[0] = lo.x; w[1] = lo.y; w[2] = hi.x; w[3] = hi.y; w[4] = p[4];
-}
-
-// activity of the 64 cells x = 64*xw .. 64*xw+63 of one cell row: a/b/c/d = sign words of the
-// voxel rows (y,z) (y+1,z) (y,z+1) (y+1,z+1), *n = the following word of the same row.
-// `rem` = number of cells of this word that exist (x < ncx); the word after the last one of a
-// row may hold anything: it only reaches bit 63, a cell that never exists.
-// Corners: v0=a v1=as v2=bs v3=b v4=c v5=cs v6=ds v7=d.  A cell is active when some corner
-// differs from v0; its sign word is 0xA5 or 0x5A (case 13) when v1,v3,v4,v6 differ from v0 and
-// v2,v5,v7 equal it.
-__device__ __forceinline__ uint64_t segment_mask(uint64_t a, uint64_t an, uint64_t b, uint64_t bn, uint64_t c, uint64_t cn,
-                                                 uint64_t d, uint64_t dn, int rem, uint64_t& m13)
-{
-    const uint64_t as = shr1_in(a, an), bs = shr1_in(b, bn), cs = shr1_in(c, cn), ds = shr1_in(d, dn);
-    const uint64_t valid = rem >= 64 ? ~0ull : (rem <= 0 ? 0ull : ((1ull << rem) - 1ull));
-    const uint64_t x1 = a ^ as, x3 = a ^ b, x4 = a ^ c, x6 = a ^ ds;
-    const uint64_t eq = (a ^ bs) | (a ^ cs) | (a ^ d);
-    m13 = (x1 & x3 & x4 & x6) & ~eq & valid;
-    return (x1 | x3 | x4 | x6 | eq) & valid;
 }
 
 // A sign plane is a flat array of ny*nxw words and cell row y uses voxel rows y and y+1, so
@@ -534,6 +517,97 @@ __global__ __launch_bounds__(256) void k_compact(McParams P)
     }
 }
 
+// The count pass straight from the sampler's sign BYTES bits8[y][x/8][z]: no k_bits_transpose in front, no `bits` array.  The bytes of
+// one byte row run along z, so here the LANES run along z: a wavefront owns one segment column (y, xw) for a chunk of 512
+// consecutive layers (blockIdx.z), lane L its planes 8 L .. 8 L + 7.  Per voxel row (y and y + 1) a lane issues nine 8-byte loads -- the
+// eight byte rows of word xw and the row that follows, 512 contiguous bytes per wavefront instruction, all eighteen before the first
+// is used -- and transposes the 8 x 8 bytes in registers (mc_signbytes.h): eight X words, the very words the transposer would have
+// stored.  Plane 8 L + 8 of the lane's last layer is the next lane's plane 0; lane 63 takes it from memory (the chunk's edge: lanes
+// 0 .. 8 load a byte each).  segment_mask then gives, bit for bit, what k_compact<false> computes from the words.
+// A workgroup is four consecutive y of one xw: of the five voxel rows it reads, three come out of the CU's cache.
+// Results, in the layouts the write pass knows ([block = (layer, part)][...]):
+//   segmask   the non-zero masks only; segvalid says which those are, a ballot per layer (a bit per lane = per layer 8 L + j), stored
+//             for EVERY segment and layer -- what is stale in segmask is never read;
+//   wavecnt / blockcnt  a block's segments are spread over many workgroups here, so its counts are SUMS: 64-bit atomicAdd into arrays
+//             that are zero when the kernel starts (k_resolve clears them for the next time, after their last reader), the
+//             workgroup's four rows added up in LDS first, zeros skipped -- a few dozen adds per address at most.
+__global__ __launch_bounds__(256) void k_count_bytes(McParams P)
+{
+    __shared__ uint32_t s_cnt[512], s_n13[512];
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+    const int y = (int)blockIdx.x * 4 + wave, xw = (int)blockIdx.y, zc = (int)blockIdx.z * 512;
+    const int nlay = P.lay_list_end;   // (lay_count_begin == 0: whole volumes only)
+    const bool row_ok = y < P.ncy;     // (uniform over the wavefront)
+    const int z = zc + 8 * lane;
+    s_cnt[threadIdx.x] = s_cnt[threadIdx.x + 256] = 0;
+    s_n13[threadIdx.x] = s_n13[threadIdx.x + 256] = 0;
+    uint64_t rows[2][9];
+    uint32_t edge[2] = {0, 0};
+#pragma unroll
+    for (int v = 0; v < 2; v++) {
+#pragma unroll
+        for (int t = 0; t < 9; t++) {
+            const int x8 = 8 * xw + t;
+            rows[v][t] = 0;   // (byte rows beyond nx, planes beyond the row: no sign bits)
+            if (row_ok && x8 < P.nx8 && z < P.pitch8)   // pitch8 % 8 == 0: the eight bytes are all inside the row, or none is
+                rows[v][t] = *reinterpret_cast<const uint64_t*>(P.bits8 + ((size_t)(y + v) * P.nx8 + x8) * P.pitch8 + z);
+        }
+        if (row_ok && lane < 9 && 8 * xw + lane < P.nx8 && zc + 512 < P.nz)
+            edge[v] = P.bits8[((size_t)(y + v) * P.nx8 + 8 * xw + lane) * P.pitch8 + zc + 512];
+    }
+    if (P.zero_cull && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 64) P.zero_cull[32 * threadIdx.x] = 0u;
+    __syncthreads();   // (s_cnt / s_n13 are zero)
+    // plane z + 8: the next lane's first byte of every row, i.e. its plane-0 word before any transposition
+    uint64_t w8[2], n8[2];
+#pragma unroll
+    for (int v = 0; v < 2; v++) {
+        uint64_t mine = 0, ew = 0;
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            mine |= (rows[v][t] & 0xffull) << (8 * t);
+            ew |= (uint64_t)(__builtin_amdgcn_readlane((int)edge[v], t) & 0xff) << (8 * t);
+        }
+        const uint32_t en = (uint32_t)__builtin_amdgcn_readlane((int)edge[v], 8) & 1u;
+        w8[v] = __shfl_down(mine, 1);
+        n8[v] = (uint64_t)__shfl_down((uint32_t)(rows[v][8] & 1ull), 1);
+        if (lane == 63) { w8[v] = ew; n8[v] = en; }
+    }
+    uint64_t m[8], m13[8];
+    signbytes_lane_masks(rows, w8, n8, P.ncx - xw * 64, row_ok ? nlay - z : 0, m, m13);
+    const int i = y * P.nxw + xw;            // the segment: block part i / 1024, the write pass's quarter (i / 256) % 4
+    const int q = i >> 8, q0 = ((int)blockIdx.x * 4 * P.nxw + xw) >> 8;   // quarter of this wavefront and of the workgroup's first
+    uint64_t ballots = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint64_t bal = __builtin_amdgcn_ballot_w64(m[j] != 0ull);
+        if (lane == j) ballots = bal;
+        if (m[j] != 0ull) {   // (implies row_ok and z + j < nlay)
+            const int lay = z + j;
+            P.segmask[((size_t)lay * P.bpl + (i >> 10)) * 1024u + (unsigned)(i & 1023)] = m[j];
+            const uint32_t c = (uint32_t)__popcll(m[j]), c13 = (uint32_t)__popcll(m13[j]);
+            if (q == q0) {
+                atomicAdd(&s_cnt[8 * lane + j], c);
+                if (c13) atomicAdd(&s_n13[8 * lane + j], c13);
+            } else {   // (a workgroup whose rows straddle two quarters: the later rows add for themselves)
+                atomicAdd(&P.wavecnt[(size_t)lay * P.bpl * 4 + q], c);
+                atomicAdd(reinterpret_cast<unsigned long long*>(&P.blockcnt[(size_t)lay * P.bpl + (q >> 2)]), (unsigned long long)c | ((unsigned long long)c13 << 32));
+            }
+        }
+    }
+    if (row_ok && lane < 8) P.segvalid[((size_t)blockIdx.z * 8 + lane) * P.nsegp + i] = ballots;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int l = (int)threadIdx.x + 256 * k;
+        const uint32_t c = s_cnt[l], c13 = s_n13[l];
+        if (c) {
+            const int lay = zc + l;
+            atomicAdd(&P.wavecnt[(size_t)lay * P.bpl * 4 + q0], c);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&P.blockcnt[(size_t)lay * P.bpl + (q0 >> 2)]), (unsigned long long)c | ((unsigned long long)c13 << 32));
+        }
+    }
+}
+
 // The write pass with the lanes' segments INTERLEAVED (SDFK_COMPACT_STRIDED): lane L of a block takes segments L, L + 256, L + 512 and
 // L + 768 of the block's 1024 instead of four consecutive ones.  A run of busy segments -- a row near a tangent of the surface
 // holds up to 64 records per segment -- then spreads over neighbouring lanes instead of piling up to 256 records on one lane, whose
@@ -544,7 +618,7 @@ __global__ __launch_bounds__(256) void k_compact(McParams P)
 #ifndef SDFK_KW_MINWAVES
 #define SDFK_KW_MINWAVES 1
 #endif
-template <bool MASKS>   // MASKS: P.segmask holds the count pass's activity masks
+template <bool MASKS, bool VALID>   // MASKS: P.segmask holds the count pass's activity masks; VALID: ... of k_count_bytes, those P.segvalid names
 __global__ __launch_bounds__(256, MASKS ? SDFK_KW_MINWAVES : 1) void k_compact_write(McParams P)
 {
     const int nlay = P.lay_list_end - P.lay_count_begin, nlog = nlay * P.bpl;
@@ -578,7 +652,16 @@ __global__ __launch_bounds__(256, MASKS ? SDFK_KW_MINWAVES : 1) void k_compact_w
         const uint64_t* q = P.segmask + (size_t)b * 1024u + threadIdx.x;
 #pragma unroll
         for (int k = 0; k < 4; k++)
-            if (look[k] && s0 + 256 * k < nseg) m[k] = q[256 * k];
+            if (look[k] && s0 + 256 * k < nseg) {
+                if (VALID) {
+                    // k_count_bytes stored the non-zero masks only: one bit per segment and layer says which, everything else in segmask
+                    // is stale and is not read.  (Loading both words side by side and masking -- no second dependent round trip, but
+                    // every stale line fetched -- was measured slower: 15.1 against 14.3 us at 512^3.)
+                    const uint64_t vb = P.segvalid[((size_t)(lay >> 9) * 8 + (lay & 7)) * P.nsegp + s0 + 256 * k];
+                    if ((vb >> ((lay & 511) >> 3)) & 1ull) m[k] = q[256 * k];
+                } else
+                    m[k] = q[256 * k];
+            }
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int s = s0 + 256 * k;
@@ -956,6 +1039,14 @@ __global__ __launch_bounds__(256, 5) void k_resolve(McParams P)
         if (t < MCLUT_NROWS) s_ord[t] = a0;
         if (t + 256 < MCLUT_NROWS) s_ord[t + 256] = a1;
         if (t + 512 < MCLUT_NROWS) s_ord[t + 512] = a2;
+    }
+    {   // the compaction's counts have had their last reader (the write pass, the kernel before the corners): zero again, for a count
+        // pass that ADDS into them (k_count_bytes) -- the job's next classification, or the next job that takes this block over
+        const int nclr = (P.lay_list_end - P.lay_count_begin) * P.bpl * 4 + 4;
+        for (int i = (int)(blockIdx.x * 256u + threadIdx.x); i < nclr; i += (int)(gridDim.x * 256u)) {
+            P.wavecnt[i] = 0u;
+            if (4 * i < nclr) P.blockcnt[i] = 0ull;
+        }
     }
     __syncthreads();
     const uint32_t n = min(P.counters->n_active, P.cap_active);
@@ -1955,8 +2046,9 @@ template __global__ void k_signbits8<true>(const float* __restrict__ values, uin
 template __global__ void k_signbits8<false>(const float* __restrict__ values, uint8_t* __restrict__ bits8, int nx, int ny, int nz, int nx8, int pitch, float iso);
 template __global__ void k_compact<true>(McParams P);
 template __global__ void k_compact<false>(McParams P);
-template __global__ void k_compact_write<true>(McParams P);
-template __global__ void k_compact_write<false>(McParams P);
+template __global__ void k_compact_write<true, false>(McParams P);
+template __global__ void k_compact_write<false, false>(McParams P);
+template __global__ void k_compact_write<true, true>(McParams P);
 template __global__ void k_vertices<true>(McParams P, McMeshOut M);
 template __global__ void k_vertices<false>(McParams P, McMeshOut M);
 template __global__ void k_repitch<true>(const float* __restrict__ src, float* __restrict__ dst, size_t rows, int w, int pw);

@@ -67,6 +67,12 @@ struct McParams {
     uint32_t* wavecnt;     // active cells per wavefront of the count pass ([block][4])
     uint64_t* segmask;     // non-null: the count pass leaves the activity masks of the wavefronts that found something ([block][1024 segments],
                            // a bit per cell); the write pass loads ONE word per segment instead of sixteen sign words and recomputes nothing
+    // count pass from the sign BYTES (k_count_bytes, mc_kernels.hip): `bits` is null then, nothing made the words
+    const uint8_t* bits8;  // non-null: the sampler's byte form [y][x/8][z] (a byte = the sign bits of 8 consecutive x), rows of pitch8 bytes
+    int nx8, pitch8;       // byte rows per y: ceil(nx / 8); pitch8 % 8 == 0
+    uint64_t* segvalid;    // [z / 512][z % 8][segment (rows of nsegp words)], bit (z % 512) / 8: segmask holds this segment's mask in layer z
+                           // (written for every segment and layer, unlike segmask: never stale)
+    int nsegp;             // ncy * nxw rounded up to a multiple of 8
     uint32_t* blockpre;    // non-null (grids of more than MC_SCAN_BLOCKS logical blocks): exclusive prefix of blockcnt's cell counts, by
                            // k_blockscan between the two passes -- a write-pass workgroup that sums its predecessors itself reads
                            // O(blocks) words, O(blocks^2) per launch: 16 K blocks at 1024^3
