@@ -531,7 +531,7 @@ struct sdfk_march_job {
     sdfk_program* eval_prog = nullptr;   // corners by re-evaluation (holds a reference)
     SampleArgs eval_args;
     bool colors_elided = false;        // the volume has no colour storage although its program writes colours (SDFK_OPT_ELIDE_VOLUME)
-    int slot = -1;                 // index of the pinned result slot (owned until job_release)
+    int slot = -1;                 // index of the pinned result slot (owned until job_destroy)
     int lane = 0;                  // lane the job's kernels are queued on
     bool* cull_clean = nullptr;        // the source volume's "its culling counters are zero again": set when the count pass is queued
     float* bounds_partial = nullptr;   // per-workgroup AABB partials of k_vertices (allocated once per job: launch_emit is allocation-free after)
@@ -552,7 +552,7 @@ bool dist_active();
 void resolve_dependents(const sdfk_volume* v);
 void free_mesh_buffers(sdfk_mesh* m);
 void drop_source(sdfk_mesh* m);
-void job_release(sdfk_march_job* j, bool kernels_may_be_queued = false);
+void job_destroy(sdfk_march_job* j, bool kernels_may_be_queued = false);
 void program_release(sdfk_program* p);
 void volume_values_changed(sdfk_volume* v);
 void codes_drop_idle();

@@ -43,8 +43,10 @@ int acquire_slot()
     return -1;
 }
 
-void job_release(sdfk_march_job* j, bool kernels_may_be_queued)
+// Gives back everything a job owns and deletes it.
+void job_destroy(sdfk_march_job* j, bool kernels_may_be_queued)
 {
+    if (!j) return;
     if (j->slot >= 0) {
         Context::SlotState& st = g.slot_state[j->slot];
         st.busy = false;
@@ -56,31 +58,20 @@ void job_release(sdfk_march_job* j, bool kernels_may_be_queued)
             if (e == hipSuccess) st.drop_pending = true;
             else (void)hipStreamSynchronize(lane_stream(j->lane));   // no event: wait here instead
         }
-        j->slot = -1;
     }
     for (void* p : j->owned) dev_free(p);
-    j->owned.clear();
     if (j->counts) {   // (zero again, in its lane's order: the next job of that lane with as many blocks takes it as it is)
         if (j->counts_clean && g.lanes[j->lane].clean_counts.size() < 16) g.lanes[j->lane].clean_counts.emplace(j->counts_bytes, j->counts);
         else dev_free(j->counts);
-        j->counts = nullptr;
     }
     if (j->eval_prog) program_release(j->eval_prog);
-    j->eval_prog = nullptr;
     if (j->sub) {
         dev_free(j->sub->values);
         dev_free(j->sub->colors);
         delete j->sub;
-        j->sub = nullptr;
     }
+    delete j;
 }
-
-#ifndef SDFK_COMPACT_MASKS
-#define SDFK_COMPACT_MASKS 1   // the count pass leaves its activity masks for the write pass (McParams::segmask)
-#endif
-#ifndef SDFK_COMPACT_STRIDED
-#define SDFK_COMPACT_STRIDED 1   // the write pass with interleaved segments (k_compact_write, mc_kernels.hip)
-#endif
 
 int alloc_records(sdfk_march_job* j, size_t c)
 {
@@ -131,26 +122,21 @@ int launch_classify(sdfk_march_job* j, bool publish)
     }
     {
         ProfScope ps("k_compact");
-        // (a workgroup takes the same 1024 segments of K2_LPB consecutive layers: mc_kernels.hip)
-        const int nwg = ((P.lay_list_end - P.lay_count_begin + K2_LPB - 1) / K2_LPB) * P.bpl;
+        const int nlog = (P.lay_list_end - P.lay_count_begin) * P.bpl;   // logical blocks (layer, part): a workgroup each
         if (j->count_bytes) {
             // from the sign bytes (SDFK_OPT_COUNT_BYTES): four cell rows of one word column per workgroup, 512 layers per grid step in z
             j->counts_clean = false;   // (until k_resolve, which zeroes the counts again, is queued behind this)
             hipLaunchKernelGGL(k_count_bytes, dim3((unsigned)(P.ncy + 3) / 4, (unsigned)P.nxw, (unsigned)(P.ncz + 511) / 512), dim3(256), 0, g.stream, P);
         } else
-            hipLaunchKernelGGL(k_compact<false>, dim3(nwg), dim3(256), 0, g.stream, P);
+            hipLaunchKernelGGL(k_compact, dim3(nlog), dim3(256), 0, g.stream, P);
         // (the count pass clears the culling kernel's counters: host bookkeeping of a device-side effect, so only once the launch is
         // known to be queued and to have workgroups -- a counter block recorded as clean that is not would make the next volume-less
         // job walk stale work lists)
         HIPCHK(hipGetLastError());
-        if (P.zero_cull && j->cull_clean && nwg > 0) *j->cull_clean = true;
+        if (P.zero_cull && j->cull_clean && nlog > 0) *j->cull_clean = true;
         if (P.blockpre) hipLaunchKernelGGL(k_blockscan, dim3(1), dim3(1024), 0, g.stream, P);   // (many blocks: their prefix in one pass)
-        if (SDFK_COMPACT_STRIDED && K2_LPB == 1)   // (the write pass with interleaved segments: mc_kernels.hip)
-            if (j->count_bytes) hipLaunchKernelGGL((k_compact_write<true, true>), dim3((P.lay_list_end - P.lay_count_begin) * P.bpl), dim3(256), 0, g.stream, P);
-            else if (P.segmask) hipLaunchKernelGGL((k_compact_write<true, false>), dim3((P.lay_list_end - P.lay_count_begin) * P.bpl), dim3(256), 0, g.stream, P);
-            else hipLaunchKernelGGL((k_compact_write<false, false>), dim3((P.lay_list_end - P.lay_count_begin) * P.bpl), dim3(256), 0, g.stream, P);
-        else
-            hipLaunchKernelGGL(k_compact<true>, dim3(nwg), dim3(256), 0, g.stream, P);
+        if (j->count_bytes) hipLaunchKernelGGL(k_compact_write<true>, dim3(nlog), dim3(256), 0, g.stream, P);   // (only the masks segvalid names)
+        else hipLaunchKernelGGL(k_compact_write<false>, dim3(nlog), dim3(256), 0, g.stream, P);
         HIPCHK(hipGetLastError());
     }
     const int nchunks = (int)((P.cap_active + MC_CHUNK - 1u) / MC_CHUNK);
@@ -199,12 +185,13 @@ int setup_job(const sdfk_volume* v, float iso, int step, int layer_begin, int la
     const bool slab = (v->z0 != 0 || v->nz != v->nz_global);
     if (step != 1 && (slab || layer_begin != 0)) return fail(SDFK_ERR_UNSUPPORTED, "slab meshing supports step == 1 only");
     sdfk_march_job* j = new sdfk_march_job();
+    struct Guard { sdfk_march_job* j; ~Guard() { job_destroy(j); } } on_failure{j};   // (every error return below; disarmed on success)
     j->gnx = v->nx; j->gny = v->ny; j->gnz = v->nz_global;
     memcpy(j->gmin, v->gmin, sizeof j->gmin);
     memcpy(j->gmax, v->gmax, sizeof j->gmax);
     j->lane = g.cur_lane;
     j->slot = acquire_slot();
-    if (j->slot < 0) { delete j; return fail(SDFK_ERR_NOMEM, "more than %d marching-cubes jobs are alive", Context::NSLOTS); }
+    if (j->slot < 0) return fail(SDFK_ERR_NOMEM, "more than %d marching-cubes jobs are alive", Context::NSLOTS);
     const sdfk_volume* w = v;
     if (step > 1) {
         // MarchingCubes.cs:49-80 touches only voxels at multiples of step
@@ -215,7 +202,7 @@ int setup_job(const sdfk_volume* v, float iso, int step, int layer_begin, int la
         j->sub = s;
         int r = dev_alloc((void**)&s->values, s->nalloc() * sizeof(float));
         if (!r && v->colors) r = dev_alloc((void**)&s->colors, s->nalloc() * 3 * sizeof(float));
-        if (r) { job_release(j); delete j; return r; }
+        if (r) return r;
         ProfScope ps("k_subsample");
         hipLaunchKernelGGL(k_subsample, dim3(grid_for(s->nvox())), dim3(256), 0, g.stream, v->values, v->colors,
                            s->values, s->colors, v->nx, v->ny, v->pitch(), s->nx, s->ny, s->nz, s->pitch(), step);
@@ -228,10 +215,8 @@ int setup_job(const sdfk_volume* v, float iso, int step, int layer_begin, int la
     j->colors_elided = w->elided && w->elided_colors;
     // (the counters of the culling kernel that made this volume's sign bits: the count pass clears them for the lane's next job)
     if (w->elided && w->cull_header && w->cull_header_lane == g.cur_lane) { P.zero_cull = w->cull_header; j->cull_clean = &w->cull_header_clean; }
-    if (w->elided && (step != 1 || !w->sampled_by || !g_cfg.corner_eval || (w->elided_colors && !g_cfg.vcolor_eval) || !w->bits_valid || w->bits_iso != iso)) {
-        job_release(j); delete j;
+    if (w->elided && (step != 1 || !w->sampled_by || !g_cfg.corner_eval || (w->elided_colors && !g_cfg.vcolor_eval) || !w->bits_valid || w->bits_iso != iso))
         return fail(SDFK_ERR_INVALID, "internal: a volume without storage can only be meshed by the program that sampled it (step 1, same iso)");
-    }
     P.nx = w->nx; P.ny = w->ny; P.nz = w->nz;
     P.nzp = w->pitch();
     {   // bit split of the packed cell coordinates: 16 + 16 unless one of nx, ny needs more (the other then needs fewer)
@@ -246,24 +231,20 @@ int setup_job(const sdfk_volume* v, float iso, int step, int layer_begin, int la
     P.iso = iso;
     P.step = step;
     const int ncz_global = w->nz_global - 1;
-    if (layer_begin < 0 || layer_end > std::max(ncz_global, 0) || layer_begin > layer_end) {
-        job_release(j); delete j;
+    if (layer_begin < 0 || layer_end > std::max(ncz_global, 0) || layer_begin > layer_end)
         return fail(SDFK_ERR_INVALID, "layer range [%d,%d) outside [0,%d)", layer_begin, layer_end, ncz_global);
-    }
     P.lay_emit_begin = layer_begin - w->z0;
     P.lay_emit_end = layer_end - w->z0;
     P.lay_count_begin = layer_begin > 0 ? P.lay_emit_begin - 1 : P.lay_emit_begin;
     P.lay_list_end = std::min(P.lay_emit_end + 1, P.ncz);   // the layer above feeds seam normals
     j->empty = (P.ncx <= 0 || P.ncy <= 0 || P.ncz <= 0 || layer_begin == layer_end);
     memset(&j->c, 0, sizeof j->c);
-    if (j->empty) { *out = j; return SDFK_OK; }
+    if (j->empty) { on_failure.j = nullptr; *out = j; return SDFK_OK; }
     {   // context planes the slab must hold (see sdfkit_hip.h)
         const int need_lo = std::max(layer_begin - 2, 0), need_hi = std::min(layer_end + 2, w->nz_global);
-        if (w->z0 > need_lo || w->z0 + w->nz < need_hi) {
-            job_release(j); delete j;
+        if (w->z0 > need_lo || w->z0 + w->nz < need_hi)
             return fail(SDFK_ERR_INVALID, "slab planes [%d,%d) do not cover the context [%d,%d) of layers [%d,%d)",
                         w->z0, w->z0 + w->nz, need_lo, need_hi, layer_begin, layer_end);
-        }
     }
     // logical blocks of k_compact: 1024 consecutive 64-cell segments of one layer
     P.bpl = (int)(((size_t)P.ncy * P.nxw + 1023) / 1024);
@@ -276,10 +257,10 @@ int setup_job(const sdfk_volume* v, float iso, int step, int layer_begin, int la
         j->eval_prog->refs++;
         j->eval_args = v->sampled_args;
     }
-    const int nlog = (P.lay_list_end - P.lay_count_begin) * P.bpl;
+    const int nlay = P.lay_list_end - P.lay_count_begin, nlog = nlay * P.bpl;
     // SDFK_OPT_COUNT_BYTES: the volume holds the sampler's sign bytes and nothing made words of them (count_bytes_applies, below)
     j->count_bytes = step == 1 && v->bytes_only && v->bits8 && v->bits_valid && v->bits_iso == iso && !slab && P.lay_count_begin == 0 &&
-                     P.lay_list_end == P.ncz && nlog <= MC_SCAN_BLOCKS && SDFK_COMPACT_STRIDED && K2_LPB == 1 && SDFK_COMPACT_MASKS;
+                     P.lay_list_end == P.ncz && nlog <= MC_SCAN_BLOCKS;
     j->have_bits = j->count_bytes || (step == 1 && v->bits && v->bits_valid && v->bits_iso == iso);
     if (j->count_bytes) {
         P.bits = nullptr;
@@ -311,19 +292,37 @@ int setup_job(const sdfk_volume* v, float iso, int step, int layer_begin, int la
         r = r ? r : job_alloc(j, &P.blockcnt, (size_t)nlog + 1);
         r = r ? r : job_alloc(j, &P.wavecnt, (size_t)nlog * 4 + 4);
     }
-    P.segmask = nullptr;
-    if (SDFK_COMPACT_STRIDED && K2_LPB == 1 && SDFK_COMPACT_MASKS)   // (the write pass reads the count pass's masks: mc_kernels.hip)
-        r = r ? r : job_alloc(j, &P.segmask, (size_t)(P.lay_list_end - P.lay_count_begin) * P.bpl * 1024 + 4);
+    r = r ? r : job_alloc(j, &P.segmask, (size_t)nlog * 1024 + 4);   // (the write pass reads the count pass's masks: mc_kernels.hip)
     P.blockpre = nullptr;
-    if ((P.lay_list_end - P.lay_count_begin) * P.bpl > MC_SCAN_BLOCKS && SDFK_COMPACT_STRIDED && K2_LPB == 1)   // (k_blockscan: mc_kernels.hip)
-        r = r ? r : job_alloc(j, &P.blockpre, (size_t)(P.lay_list_end - P.lay_count_begin) * P.bpl + 1);
-    r = r ? r : job_alloc(j, &P.rowstart, (size_t)(P.lay_list_end - P.lay_count_begin) * P.ncy + 2);
+    if (nlog > MC_SCAN_BLOCKS) r = r ? r : job_alloc(j, &P.blockpre, (size_t)nlog + 1);   // (k_blockscan: mc_kernels.hip)
+    r = r ? r : job_alloc(j, &P.rowstart, (size_t)nlay * P.ncy + 2);
     r = r ? r : job_alloc(j, &P.counters, 1);
     P.host_counters = &g.slots_dev[j->slot].c;
     j->rec_first = j->owned.size();
     r = r ? r : alloc_records(j, cap_records);
-    if (r) { job_release(j); delete j; return r; }
+    if (r) return r;
+    on_failure.j = nullptr;
     *out = j;
+    return SDFK_OK;
+}
+
+// Classify and wait for the counters; a record list that was too small is reallocated at its exact size and the job classified again.
+// (Case-13 sign words in a volume without storage: left to march_exact after the first pass, which starts over with storage.)
+static int classify_exact(sdfk_march_job* j, const sdfk_volume* v)
+{
+    int r = launch_classify(j, true);
+    r = r ? r : wait_counters(j);
+    if (r || (v->elided && j->c.n_case13 != 0) || j->c.n_active <= j->P.cap_active) return r;
+    r = alloc_records(j, j->c.n_active);
+    r = r ? r : launch_classify(j, true);
+    return r ? r : wait_counters(j);
+}
+
+// Mesh.Triangles is int[]: the last vertex index of a mesh whose indices start at vertex_base
+static int check_vertex_index(int64_t vertex_base, const McCounters& c)
+{
+    if (vertex_base + ((int64_t)c.total_v - (int64_t)c.nghost) >= (int64_t(1) << 31))
+        return fail(SDFK_ERR_UNSUPPORTED, "vertex index exceeds int32 (Mesh.Triangles is int[])");
     return SDFK_OK;
 }
 
@@ -342,6 +341,10 @@ int alloc_mesh(sdfk_mesh** out, size_t cap_v, size_t cap_i)
     *out = m;
     return SDFK_OK;
 }
+
+// Speculative capacities: the sizes of the previous mesh of this shape, +25 % and a floor.
+static size_t hint_records(const Context::Hint& h) { return (size_t)h.n_active + h.n_active / 4 + 4096; }
+static int alloc_mesh_hinted(sdfk_mesh** out, const Context::Hint& h) { return alloc_mesh(out, (size_t)h.nv + h.nv / 4 + 4096, (size_t)h.ni + h.ni / 4 + 12288); }
 
 // emit: vertices (+ AABB partials) then triangles (+ AABB reduction).  Launches only.
 int launch_emit(sdfk_march_job* j, sdfk_mesh* m, int64_t vertex_base)
@@ -464,24 +467,16 @@ int march_exact(const sdfk_volume* v, float iso, int step, int layer_begin, int 
         r = alloc_mesh(&m, 0, 0);
         if (!r) m->bounds_valid = true;
     } else {
-        r = launch_classify(j, true);
-        r = r ? r : wait_counters(j);
+        r = classify_exact(j, v);
         if (!r && v->elided && j->c.n_case13 != 0) {
             // case-13 sign words: k_resolve's dead-cell test reads neighbouring VOXELS, and this volume has none
             // (SDFK_OPT_ELIDE_VOLUME): give it its storage, sample again with stores, start over
-            job_release(j);
-            delete j;
+            job_destroy(j);
             if (int r2 = volume_materialize(const_cast<sdfk_volume*>(v))) return r2;
             return march_exact(v, iso, step, layer_begin, layer_end, vertex_base, key, out);
         }
-        if (!r && j->c.n_active > j->P.cap_active) {   // record list too small: exact size, redo
-            r = alloc_records(j, j->c.n_active);
-            r = r ? r : launch_classify(j, true);
-            r = r ? r : wait_counters(j);
-        }
         r = r ? r : alloc_mesh(&m, (size_t)(j->c.total_v - j->c.nghost), (size_t)j->c.total_t * 3);
-        if (!r && vertex_base + (int64_t)(j->c.total_v - j->c.nghost) >= (int64_t(1) << 31))
-            r = fail(SDFK_ERR_UNSUPPORTED, "vertex index exceeds int32 (Mesh.Triangles is int[])");
+        r = r ? r : check_vertex_index(vertex_base, j->c);
         if (!r && j->c.n_active > 0) {
             r = launch_emit(j, m, vertex_base);
             r = r ? r : wait_counters(j);
@@ -492,21 +487,23 @@ int march_exact(const sdfk_volume* v, float iso, int step, int layer_begin, int 
             g.hints[key] = Context::Hint{j->c.n_active, (uint32_t)m->nv, (uint32_t)m->ni};
         }
     }
-    job_release(j);
-    delete j;
+    job_destroy(j);
     if (r) { if (m) sdfk_mesh_free(m); return r; }
     *out = m;
     return SDFK_OK;
 }
 
+// the handle's five arrays are not its own (or not any more): forget them
+static void mesh_forget_arrays(sdfk_mesh* m)
+{
+    m->borrowed = false;
+    m->vertices = m->colors = m->normals = m->bounds = nullptr;
+    m->triangles = nullptr;
+}
+
 void free_mesh_buffers(sdfk_mesh* m)
 {
-    if (m->borrowed) {   // the buffers belong to a GraphJob
-        m->borrowed = false;
-        m->vertices = m->colors = m->normals = m->bounds = nullptr;
-        m->triangles = nullptr;
-        return;
-    }
+    if (m->borrowed) return mesh_forget_arrays(m);   // the buffers belong to a GraphJob
     if (!m->external) {
         dev_free(m->vertices);   // stream-ordered pool: no sync needed
         dev_free(m->colors);
@@ -515,8 +512,7 @@ void free_mesh_buffers(sdfk_mesh* m)
     }
     m->external = false;
     dev_free(m->bounds);
-    m->vertices = m->colors = m->normals = m->bounds = nullptr;
-    m->triangles = nullptr;
+    mesh_forget_arrays(m);
 }
 
 void drop_source(sdfk_mesh* m)
@@ -548,17 +544,13 @@ int mesh_resolve(sdfk_mesh* m)
     const bool fits = !needs_voxels && j->c.n_active <= j->P.cap_active && j->c.overflow == 0 &&
                       (size_t)(j->c.total_v - j->c.nghost) <= m->cap_v && (size_t)j->c.total_t * 3 <= m->cap_i;
     if (!r && fits) {
-        if (m->vertex_base + (int64_t)(j->c.total_v - j->c.nghost) >= (int64_t(1) << 31))
-            r = fail(SDFK_ERR_UNSUPPORTED, "vertex index exceeds int32 (Mesh.Triangles is int[])");
-        else {
+        r = check_vertex_index(m->vertex_base, j->c);
+        if (!r) {
             finalize_mesh(j, m, true);
             g.hints[m->key] = Context::Hint{j->c.n_active, (uint32_t)m->nv, (uint32_t)m->ni};
         }
     }
-    if (!m->graph_job) {   // (a job of a captured launch graph belongs to its GraphJob and is replayed)
-        job_release(j);
-        delete j;
-    }
+    if (!m->graph_job) job_destroy(j);   // (a job of a captured launch graph belongs to its GraphJob and is replayed)
     if (!r && !fits) {   // the guess was too small: the exact two-phase path, into the same handle
         sdfk_mesh* x = nullptr;
         r = march_exact(m->src, m->iso, m->step, m->layer_begin, m->layer_end, m->vertex_base, m->key, &x);
@@ -641,12 +633,12 @@ int march_range(const sdfk_volume* v, float iso, int step, int layer_begin, int 
         // is returned without waiting: the host meets the GPU only when a result is read.
         const Context::Hint h = it->second;
         sdfk_march_job* j = nullptr;
-        int r = setup_job(v, iso, step, layer_begin, layer_end, (size_t)h.n_active + h.n_active / 4 + 4096, &j);
+        int r = setup_job(v, iso, step, layer_begin, layer_end, hint_records(h), &j);
         if (r) return r;
         if (!j->empty) {
             sdfk_mesh* m = nullptr;
             if (!(emit_dst && external_mesh(emit_dst, emit_capacity, v->colors != nullptr, h.nv, h.ni, &m)))
-                r = alloc_mesh(&m, (size_t)h.nv + h.nv / 4 + 4096, (size_t)h.ni + h.ni / 4 + 12288);
+                r = alloc_mesh_hinted(&m, h);
             r = r ? r : launch_classify(j, false);
             r = r ? r : launch_emit(j, m, vertex_base);
             if (!r) {
@@ -657,8 +649,7 @@ int march_range(const sdfk_volume* v, float iso, int step, int layer_begin, int 
             if (r) {
                 (void)hipStreamSynchronize(g.stream);
                 if (m) { if (m->done) (void)hipEventDestroy(m->done); m->done = nullptr; sdfk_mesh_free(m); }
-                job_release(j);
-                delete j;
+                job_destroy(j);
                 return r;
             }
             m->pending = j;
@@ -670,8 +661,7 @@ int march_range(const sdfk_volume* v, float iso, int step, int layer_begin, int 
             *out = m;
             return SDFK_OK;
         }
-        job_release(j);
-        delete j;
+        job_destroy(j);
     }
     return march_exact(v, iso, step, layer_begin, layer_end, vertex_base, key, out);
 }
@@ -723,13 +713,13 @@ void graph_job_destroy(GraphJob* q)
     if (q->graph) (void)hipGraphDestroy(q->graph);
     if (q->ran) (void)hipEventDestroy(q->ran);
     if (sdfk_mesh* b = q->borrower) {   // (only at shutdown: a handle that outlives the library reads as failed)
-        b->graph_job = nullptr; b->borrowed = false;
-        b->vertices = b->colors = b->normals = b->bounds = nullptr; b->triangles = nullptr;
+        b->graph_job = nullptr;
+        mesh_forget_arrays(b);
         b->nv = b->ni = 0; b->pending = nullptr; b->src = nullptr;
         if (!b->status) { b->status = SDFK_ERR_INVALID; b->error = "the library was shut down"; }
     }
     LaneScope on_lane(q->lane);
-    if (q->job) { job_release(q->job); delete q->job; }
+    job_destroy(q->job);
     if (q->proto) { q->proto->graph_job = nullptr; q->proto->borrowed = false; sdfk_mesh_free(q->proto); }
     if (q->vol) sdfk_volume_free(q->vol);
     if (q->prog) program_release(const_cast<sdfk_program*>(q->prog));
@@ -774,6 +764,15 @@ void graph_jobs_forget_volume(const sdfk_volume* v)
         if (g.graph_jobs[i]->slab && g.graph_jobs[i]->ext_vol == v) graph_job_destroy(g.graph_jobs[i]);   // (erases the entry)
         else i++;
     }
+}
+
+// the least recently used GraphJob that no live handle borrows from (null: none)
+static GraphJob* graph_job_lru_free()
+{
+    GraphJob* lru = nullptr;
+    for (GraphJob* c : g.graph_jobs)
+        if (!c->busy && (!lru || c->last_use < lru->last_use)) lru = c;
+    return lru;
 }
 
 bool graphs_enabled(int64_t nvox)
@@ -826,9 +825,7 @@ int graph_sample_march(const sdfk_program* p, const float mn[3], const float mx[
             if (g.graph_sightings[fk]++ == 0) return SDFK_OK;
         }
         if (alive >= 3 || g.graph_jobs.size() >= 24 || g.graph_bytes > (size_t(4) << 30)) {
-            GraphJob* lru = nullptr;   // make room: the least recently used free one, if any
-            for (GraphJob* c : g.graph_jobs)
-                if (!c->busy && (!lru || c->last_use < lru->last_use)) lru = c;
+            GraphJob* lru = graph_job_lru_free();   // make room, if any is free
             if (!lru || alive >= 3) return SDFK_OK;
             graph_job_destroy(lru);
         }
@@ -840,20 +837,26 @@ int graph_sample_march(const sdfk_program* p, const float mn[3], const float mx[
         g.graph_jobs.push_back(q);
         const size_t before = [] { size_t b = 0; for (auto& kv : g.live_blocks) b += kv.second.size; return b; }();
         int r = sdfk_volume_create(nx, ny, nz, mn, mx, p->writes_color ? 1 : 0, &q->vol);
-        // (first run outside the capture: compiles / loads the kernels, allocates the sign-bit arrays, marks the volume as this program's output)
-        if (!r) r = sample_impl(p, q->vol, clip, iso);
-        if (!r) r = setup_job(q->vol, iso, 1, 0, std::max(nz - 1, 0), (size_t)h.n_active + h.n_active / 4 + 4096, &q->job);
-        if (!r && (q->job->empty || !q->job->have_bits)) r = -1;   // (an iso value that never compares equal, NaN, leaves the sign-bit pass to the job)
-        if (!r) r = alloc_mesh(&q->proto, (size_t)h.nv + h.nv / 4 + 4096, (size_t)h.ni + h.ni / 4 + 12288);
-        if (!r) r = launch_classify(q->job, false);
-        if (!r) r = launch_emit(q->job, q->proto, 0);   // (allocates the AABB partials: the captured run below does not allocate)
+        // The chain the graph holds.  Its first run, outside the capture, compiles / loads the kernels, allocates the sign-bit arrays and
+        // marks the volume as this program's output; the job and the mesh buffers are built behind its sampling (the job takes the
+        // volume's sign bits), and launch_emit allocates the AABB partials: the captured run does not allocate.
+        auto chain = [&](bool first) {
+            int rc = sample_impl(p, q->vol, clip, iso);
+            if (!rc && first) {
+                rc = setup_job(q->vol, iso, 1, 0, std::max(nz - 1, 0), hint_records(h), &q->job);
+                if (!rc && (q->job->empty || !q->job->have_bits)) rc = -1;   // (an iso value that never compares equal, NaN, leaves the sign-bit pass to the job)
+                if (!rc) rc = alloc_mesh_hinted(&q->proto, h);
+            }
+            if (!rc) rc = launch_classify(q->job, false);
+            if (!rc) rc = launch_emit(q->job, q->proto, 0);
+            return rc;
+        };
+        if (!r) r = chain(true);
         if (!r) {
             hipStream_t st = lane_stream(lane);
             hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
             if (e == hipSuccess) {
-                int rc = sample_impl(p, q->vol, clip, iso);
-                if (!rc) rc = launch_classify(q->job, false);
-                if (!rc) rc = launch_emit(q->job, q->proto, 0);
+                const int rc = chain(false);
                 e = hipStreamEndCapture(st, &q->graph);
                 if (e == hipSuccess && rc) e = hipErrorUnknown;
             }
@@ -892,7 +895,7 @@ int graph_sample_march(const sdfk_program* p, const float mn[3], const float mx[
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(lane_stream(lane));
         if (m->done) (void)hipEventDestroy(m->done);
-        m->borrowed = false; m->vertices = m->colors = m->normals = m->bounds = nullptr; m->triangles = nullptr;
+        mesh_forget_arrays(m);
         q->busy = false;
         q->borrower = nullptr;
         delete m;
@@ -964,9 +967,7 @@ int graph_slab_enqueue(const sdfk_program* p, sdfk_volume* slab, int clip, float
     sdfk_mesh* proto = nullptr;
     if (!external_mesh((char*)dst, capacity, slab->colors != nullptr, h.nv, h.ni, &proto)) return SDFK_OK;
     if (g.graph_jobs.size() >= 24) {
-        GraphJob* lru = nullptr;
-        for (GraphJob* c : g.graph_jobs)
-            if (!c->busy && (!lru || c->last_use < lru->last_use)) lru = c;
+        GraphJob* lru = graph_job_lru_free();
         if (!lru) { sdfk_mesh_free(proto); return SDFK_OK; }
         graph_job_destroy(lru);
     }
@@ -978,21 +979,26 @@ int graph_slab_enqueue(const sdfk_program* p, sdfk_volume* slab, int clip, float
     q->key = key; q->hint = h; q->proto = proto;
     q->post_out = pc ? (void*)pc->out : nullptr;
     g.graph_jobs.push_back(q);
-    int r = sample_impl(p, slab, clip, iso);   // (outside the capture: loads the kernels, allocates the sign-bit arrays; this call's run)
-    if (!r) r = setup_job(slab, iso, 1, lb, le, (size_t)h.n_active + h.n_active / 4 + 4096, &q->job);
-    if (!r && (q->job->empty || !q->job->have_bits)) r = -1;
-    if (!r) r = launch_classify(q->job, false);
-    if (!r) r = launch_emit(q->job, q->proto, 0);
-    if (!r) r = launch_post_compact(pc, dst, capacity);
+    // The chain the graph holds.  Its first run, outside the capture, is this call's: it loads the kernels and allocates the sign-bit
+    // arrays, and the job is built behind its sampling (it takes the slab's sign bits).
+    auto chain = [&](bool first) {
+        int rc = sample_impl(p, slab, clip, iso);
+        if (!rc && first) {
+            rc = setup_job(slab, iso, 1, lb, le, hint_records(h), &q->job);
+            if (!rc && (q->job->empty || !q->job->have_bits)) rc = -1;
+        }
+        if (!rc) rc = launch_classify(q->job, false);
+        if (!rc) rc = launch_emit(q->job, q->proto, 0);
+        if (!rc) rc = launch_post_compact(pc, dst, capacity);
+        return rc;
+    };
+    int r = chain(true);
     if (!r) {
         q->args = slab->sampled_args;
         hipStream_t st = lane_stream(lane);
         hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
         if (e == hipSuccess) {
-            int rc = sample_impl(p, slab, clip, iso);
-            if (!rc) rc = launch_classify(q->job, false);
-            if (!rc) rc = launch_emit(q->job, q->proto, 0);
-            if (!rc) rc = launch_post_compact(pc, dst, capacity);
+            const int rc = chain(false);
             e = hipStreamEndCapture(st, &q->graph);
             if (e == hipSuccess && rc) e = hipErrorUnknown;
         }
@@ -1031,14 +1037,8 @@ extern "C" int sdfk_march_begin(const sdfk_volume* v, float iso_value, int32_t l
     int r = setup_job(v, iso_value, 1, layer_begin, layer_end, 0, &j);
     if (r) return r;
     if (!j->empty) {
-        r = launch_classify(j, true);
-        r = r ? r : wait_counters(j);
-        if (!r && j->c.n_active > j->P.cap_active) {
-            r = alloc_records(j, j->c.n_active);
-            r = r ? r : launch_classify(j, true);
-            r = r ? r : wait_counters(j);
-        }
-        if (r) { job_release(j); delete j; return r; }
+        r = classify_exact(j, v);
+        if (r) { job_destroy(j); return r; }
     }
     if (n_vertices) *n_vertices = (int64_t)j->c.total_v - (int64_t)j->c.nghost;
     if (n_indices) *n_indices = (int64_t)j->c.total_t * 3;
@@ -1054,7 +1054,7 @@ extern "C" int sdfk_march_finish(sdfk_march_job* j, int64_t vertex_base, sdfk_me
     if (int r = require_init()) return r;
     if (j->finished) return fail(SDFK_ERR_INVALID, "march job already finished");
     const int64_t nv = (int64_t)j->c.total_v - (int64_t)j->c.nghost;
-    if (vertex_base + nv >= (int64_t(1) << 31)) return fail(SDFK_ERR_UNSUPPORTED, "vertex index exceeds int32 (Mesh.Triangles is int[])");
+    if (int r = check_vertex_index(vertex_base, j->c)) return r;
     sdfk_mesh* m = nullptr;
     int r = alloc_mesh(&m, (size_t)nv, (size_t)j->c.total_t * 3);
     if (r) return r;
@@ -1076,8 +1076,7 @@ extern "C" void sdfk_march_job_free(sdfk_march_job* job)
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     bind_thread();
     if (!job) return;
-    job_release(job);   // stream-ordered pool: no sync needed
-    delete job;
+    job_destroy(job);   // stream-ordered pool: no sync needed
 }
 
 extern "C" int sdfk_march(const sdfk_volume* v, float iso_value, int32_t step, sdfk_mesh** out)
@@ -1258,7 +1257,7 @@ static bool count_bytes_applies(const sdfk_volume* v, int step)
     if (v->elided && g_cfg.elide_volume >= 2) return false;   // (block culling writes words, there are no bytes)
     if ((v->pitch8() & 7) != 0 || v->nxw() > 65535) return false;
     const size_t bpl = ((size_t)(v->ny - 1) * v->nxw() + 1023) / 1024;
-    return bpl * (size_t)(v->nz - 1) <= (size_t)MC_SCAN_BLOCKS && SDFK_COMPACT_STRIDED && K2_LPB == 1 && SDFK_COMPACT_MASKS;
+    return bpl * (size_t)(v->nz - 1) <= (size_t)MC_SCAN_BLOCKS;
 }
 
 extern "C" int sdfk_sample_march(const sdfk_program* p, const float min[3], const float max[3],

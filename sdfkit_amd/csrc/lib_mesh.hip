@@ -177,10 +177,7 @@ extern "C" void sdfk_mesh_free(sdfk_mesh* m)
     if (m->pending) {   // never read: drop the queued job's workspace (stream-ordered, no wait)
         for (auto it = g.pending.begin(); it != g.pending.end(); ++it)
             if (*it == m) { g.pending.erase(it); break; }
-        if (!m->graph_job) {
-            job_release(m->pending, true);   // its kernels may still be queued (and will still write the result slot)
-            delete m->pending;
-        }
+        if (!m->graph_job) job_destroy(m->pending, true);   // its kernels may still be queued (and will still write the result slot)
         m->pending = nullptr;
         if (m->done) (void)hipEventDestroy(m->done);
     }

@@ -9,13 +9,6 @@
 
 namespace sdfk {
 
-// layers of sign planes a k_compact workgroup walks (mc_kernels.hip, "K2": 1 is the product, measured)
-#ifndef SDFK_COMPACT_LPB
-#define SDFK_COMPACT_LPB 1
-#endif
-constexpr int K2_LPB = SDFK_COMPACT_LPB;
-static_assert(K2_LPB >= 1 && K2_LPB <= 8, "sign planes per workgroup are held in registers");
-
 // ---- Z-slab payload header (sdfkit_amd/dist.py; SDFK_SLAB_HEADER_BYTES) -------------------------------------
 // cap_v: vertex slots each of the V / (C) / N sections is laid out for -- the sections start at 64, 64 + 12 cap_v, ...,
 // the indices at 64 + vbytes * cap_v.  0 (or nv) = dense.  A step that emits straight into the send buffer lays the
@@ -56,14 +49,11 @@ template <bool FLAT> __global__ void k_signbits8(const float* __restrict__ value
 extern template __global__ void k_signbits8<true>(const float* __restrict__ values, uint8_t* __restrict__ bits8, int nx, int ny, int nz, int nx8, int pitch, float iso);
 extern template __global__ void k_signbits8<false>(const float* __restrict__ values, uint8_t* __restrict__ bits8, int nx, int ny, int nz, int nx8, int pitch, float iso);
 __global__ void k_bits_transpose(const uint8_t* __restrict__ bits8, uint64_t* __restrict__ bits, int nx8, int ny, int nz, int nxw, int pitch8);
-template <bool WRITE> __global__ void k_compact(McParams P);
-extern template __global__ void k_compact<true>(McParams P);
-extern template __global__ void k_compact<false>(McParams P);
+__global__ void k_compact(McParams P);
 __global__ void k_count_bytes(McParams P);
-template <bool MASKS, bool VALID> __global__ void k_compact_write(McParams P);
-extern template __global__ void k_compact_write<true, false>(McParams P);
-extern template __global__ void k_compact_write<false, false>(McParams P);
-extern template __global__ void k_compact_write<true, true>(McParams P);
+template <bool VALID> __global__ void k_compact_write(McParams P);
+extern template __global__ void k_compact_write<false>(McParams P);
+extern template __global__ void k_compact_write<true>(McParams P);
 __global__ void k_blockscan(McParams P);
 __global__ void k_publish(McParams P);
 __global__ void k_chunkscan(McParams P);

@@ -205,29 +205,6 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
     return v;
 }
 
-// exclusive prefix of v over the 256 lanes of the workgroup, *total = workgroup sum; `red` is
-// summed over the workgroup on the side (same barriers) and returned through the reference
-__device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t& red, uint32_t* total)
-{
-    __shared__ uint32_t s_incl[4], s_red[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t n = __shfl_up(incl, o);
-        if (lane >= o) incl += n;
-    }
-    const uint32_t r = wave_sum_u32(red);
-    __syncthreads();
-    if (lane == 63) { s_incl[wave] = incl; s_red[wave] = r; }
-    __syncthreads();
-    uint32_t pre = incl - v;
-    for (int w = 0; w < wave; w++) pre += s_incl[w];
-    *total = s_incl[0] + s_incl[1] + s_incl[2] + s_incl[3];
-    red = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-    return pre;
-}
-
 // exclusive prefix of v over the 256 lanes of the workgroup; *total = workgroup sum
 __device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t v, uint64_t* s_wave /*[4]*/, uint64_t* total)
 {
@@ -303,21 +280,6 @@ __device__ __forceinline__ void load_words5(const uint64_t* p, uint64_t* w)
     w[0] = lo.x; w[1] = lo.y; w[2] = hi.x; w[3] = hi.y; w[4] = p[4];
 }
 
-// A sign plane is a flat array of ny*nxw words and cell row y uses voxel rows y and y+1, so
-// segment i = y*nxw + xw (64 cells) reads words i, i+1, i+nxw, i+nxw+1 of planes z and z+1:
-// sweep order == i order.  Logical block b = (layer, 1024 consecutive segments); each lane owns
-// 4 consecutive segments and keeps their words in registers (20 words, five 16/8-byte loads per
-// voxel row).  WRITE = false: count the active cells of the block; WRITE = true: write them at
-// (sum of the earlier blocks) + in-block prefix.
-// A WORKGROUP takes the same 1024 segments of K2_LPB consecutive layers -- K2_LPB logical blocks -- and keeps all K2_LPB + 1
-// sign planes it needs in registers: plane z + 1 of one layer is plane z of the next, so a plane is fetched (K2_LPB + 1) / K2_LPB
-// times per pass instead of twice (with one workgroup per logical block the second fetch comes from another XCD's workgroup
-// and misses its L2: 34 MB through the fabric for a 16.8 MB array).  All loads of a lane are issued up front.
-// K2_LPB = 1 is the product: measured at 512^3 (round 5, profiles/r05_ab_compact_layers.txt), both passes together take 25.9 us
-// with 1, 30.1 with 2 and 41.3 with 4 layers per workgroup -- a quarter of the workgroups, each lane four layers in a row with a
-// workgroup scan per layer -- and the pipelined step does not move (0.1399 / 0.1391 / 0.1449 ms): the fabric serves the second
-// fetch at no visible cost, the longer workgroups cost what they cost.
-
 // Totals of the compaction and the layer marks, from the count pass's blockcnt[] (one workgroup: the write pass's first block, or
 // k_blockscan).
 // (out of line, the few fields it needs by value: inlined into the write pass its registers cost every workgroup of that kernel a
@@ -365,156 +327,63 @@ __device__ __forceinline__ void publish_compaction(const McParams& P, int nlay, 
                             (P.lay_emit_end - P.lay_count_begin) * P.bpl, nlog);
 }
 
-template <bool WRITE>
+// The count pass from the sign WORDS.  A sign plane is a flat array of ny*nxw words and cell row y uses voxel rows y and y+1, so
+// segment i = y*nxw + xw (64 cells) reads words i, i+1, i+nxw, i+nxw+1 of planes z and z+1: sweep order == i order.  Logical block
+// b = (layer, 1024 consecutive segments), one workgroup per block; each lane owns 4 consecutive segments and keeps their words in
+// registers (20 words per plane, five 16/8-byte loads per voxel row), all loads issued up front.
+// (Several layers per workgroup, their shared planes kept in registers, were measured slower at 512^3: profiles/r05_ab_compact_layers.txt,
+// docs/history.md.)
 __global__ __launch_bounds__(256) void k_compact(McParams P)
 {
     const int nlay = P.lay_list_end - P.lay_count_begin;
-    const int nlog = nlay * P.bpl;                           // logical blocks: [layer][part]
-    const int wg = K2_LPB == 1 ? compact_block_of_workgroup(nlay, P.bpl) : (int)blockIdx.x;   // (the workgroup's place in (layer group, part) order)
-    const int part = wg % P.bpl, lay0 = (wg / P.bpl) * K2_LPB;
-    const int nl = min(K2_LPB, nlay - lay0);                 // layers of this workgroup
-    const int b0 = lay0 * P.bpl + part;                      // logical block of its first layer; layer l: b0 + l * bpl
+    const int b = compact_block_of_workgroup(nlay, P.bpl);   // logical block = (layer, part)
+    const int lay = b / P.bpl, part = b - lay * P.bpl;
     const int nseg = P.ncy * P.nxw;
     const int i0 = part * 1024 + 4 * (int)threadIdx.x;
     const int wave = (int)(threadIdx.x >> 6);
-    // the count pass recorded which wavefronts found nothing in which layer: those skip the sign words here
-    bool look[K2_LPB];
-#pragma unroll
-    for (int l = 0; l < K2_LPB; l++) look[l] = l < nl && (!WRITE || P.wavecnt[(b0 + l * P.bpl) * 4 + wave] != 0);
-    // write pass: this lane's share of the counts of all blocks before b0, loaded HERE (four independent loads per trip, in
-    // flight together with the sign words below) -- a plain "load; add" loop after the words cost up to eight dependent L2
-    // round trips for the last blocks of a 512^3 grid --, and of the bpl blocks between two consecutive layers of this workgroup
-    uint32_t before[K2_LPB];
-#pragma unroll
-    for (int l = 0; l < K2_LPB; l++) before[l] = 0;
-    if (WRITE) {
-        for (int i = threadIdx.x; i < b0; i += 1024) {
-            const uint32_t c0 = (uint32_t)P.blockcnt[i];
-            const uint32_t c1 = i + 256 < b0 ? (uint32_t)P.blockcnt[i + 256] : 0u;
-            const uint32_t c2 = i + 512 < b0 ? (uint32_t)P.blockcnt[i + 512] : 0u;
-            const uint32_t c3 = i + 768 < b0 ? (uint32_t)P.blockcnt[i + 768] : 0u;
-            before[0] += (c0 + c1) + (c2 + c3);
-        }
-#pragma unroll
-        for (int l = 1; l < K2_LPB; l++)
-            if (l < nl)
-                for (int i = threadIdx.x; i < P.bpl; i += 256) before[l] += (uint32_t)P.blockcnt[b0 + (l - 1) * P.bpl + i];
-    }
-    int y0 = 0, xw0 = 0;
+    uint64_t m[4] = {0, 0, 0, 0};
+    uint32_t cnt = 0, n13 = 0;
     if (i0 < nseg) {
-        y0 = i0 / P.nxw;
-        xw0 = i0 - y0 * P.nxw;
-    }
-    // sign planes lay0 .. lay0 + nl of this lane's two voxel rows: plane p serves layers p - 1 and p
-    uint64_t w[K2_LPB + 1][2][5];
-    {
+        // sign planes z and z + 1 of this lane's two voxel rows
+        uint64_t w[2][2][5];
         const size_t plane = (size_t)P.ny * P.nxw;
-        const uint64_t* f0 = P.bits + (size_t)(P.lay_count_begin + lay0) * plane + i0;
+        const uint64_t* f0 = P.bits + (size_t)(P.lay_count_begin + lay) * plane + i0;
 #pragma unroll
-        for (int p = 0; p <= K2_LPB; p++) {
-            const bool need = i0 < nseg && ((p > 0 && look[p - 1]) || (p < K2_LPB && look[p]));
-            if (need) {
-                load_words5(f0 + (size_t)p * plane, w[p][0]);
-                load_words5(f0 + (size_t)p * plane + P.nxw, w[p][1]);
-            } else {
+        for (int p = 0; p < 2; p++) {
+            load_words5(f0 + (size_t)p * plane, w[p][0]);
+            load_words5(f0 + (size_t)p * plane + P.nxw, w[p][1]);
+        }
+        int xk = i0 % P.nxw;
 #pragma unroll
-                for (int k = 0; k < 5; k++) w[p][0][k] = w[p][1][k] = 0;
-            }
+        for (int k = 0; k < 4; k++) {
+            const int rem = (i0 + k < nseg) ? P.ncx - xk * 64 : 0;
+            uint64_t m13;
+            m[k] = segment_mask(w[0][0][k], w[0][0][k + 1], w[0][1][k], w[0][1][k + 1], w[1][0][k], w[1][0][k + 1], w[1][1][k], w[1][1][k + 1],
+                                rem, m13);
+            cnt += (uint32_t)__popcll(m[k]);
+            n13 += (uint32_t)__popcll(m13);
+            if (++xk == P.nxw) xk = 0;
         }
     }
-    uint32_t cnts[K2_LPB], n13s[K2_LPB];
-    uint32_t base_acc = 0;   // (write pass) records before the current layer's block
-#pragma unroll
-    for (int l = 0; l < K2_LPB; l++) {
-        cnts[l] = n13s[l] = 0;
-        if (l >= nl) continue;   // (uniform over the workgroup)
-        uint64_t m[4] = {0, 0, 0, 0};
-        uint32_t cnt = 0, n13 = 0;
-        if (look[l] && i0 < nseg) {
-            int xk = xw0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int rem = (i0 + k < nseg) ? P.ncx - xk * 64 : 0;
-                uint64_t m13;
-                m[k] = segment_mask(w[l][0][k], w[l][0][k + 1], w[l][1][k], w[l][1][k + 1], w[l + 1][0][k], w[l + 1][0][k + 1],
-                                    w[l + 1][1][k], w[l + 1][1][k + 1], rem, m13);
-                cnt += (uint32_t)__popcll(m[k]);
-                n13 += (uint32_t)__popcll(m13);
-                if (++xk == P.nxw) xk = 0;
-            }
-        }
-        if (!WRITE) {
-            cnts[l] = cnt; n13s[l] = n13;
-            // (the masks of a wavefront that found something, for the write pass: its lane t holds segments 4 t .. 4 t + 3 of the block)
-            if (P.segmask && __builtin_amdgcn_ballot_w64(cnt != 0u) != 0ull) {
-                uint64_t* q = P.segmask + ((size_t)(b0 + l * P.bpl) * 1024u + 4u * threadIdx.x);
-                *reinterpret_cast<u64x2u*>(q) = u64x2u{m[0], m[1]};
-                *reinterpret_cast<u64x2u*>(q + 2) = u64x2u{m[2], m[3]};
-            }
-            continue;
-        }
-        // exclusive prefix of this block = sum of the counts of all earlier blocks (a few thousand
-        // words, read cooperatively: cheaper than a separate scan launch)
-        uint32_t total, red = before[l];
-        const uint32_t pre = block_excl_scan_u32(cnt, red, &total);   // also reduces `red` over the workgroup
-        base_acc += red;
-        const int lay = lay0 + l, z = P.lay_count_begin + lay;
-        if (b0 == 0 && l == 0) {
-            // The FIRST block publishes the totals and the layer marks: everything here follows from the count pass's blockcnt[], the
-            // first block starts first and its extra work hides behind the rest of the launch (the last block, which did this in
-            // rounds 1-3, starts last and was the launch's tail)
-            publish_compaction(P, nlay, nlog);
-        }
-        if (i0 < nseg) {
-            uint32_t pos = base_acc + pre;
-            uint32_t* rowstart = P.rowstart + (size_t)lay * P.ncy;
-            int y = y0, xw = xw0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if (i0 + k < nseg) {
-                    if (xw == 0) rowstart[y] = pos;   // first record of cell row (z, y)
-                    const uint32_t yz = (uint32_t)y << P.xbits;
-                    uint64_t mk = m[k];
-                    while (mk) {
-                        const int bit = __builtin_ctzll(mk);
-                        mk &= mk - 1;
-                        if (pos < P.cap_active) {
-                            P.rec_xy[pos] = (uint32_t)(xw * 64 + bit) | yz;
-                            P.rec_z[pos] = (uint32_t)z;
-                        }
-                        pos++;
-                    }
-                    if (++xw == P.nxw) { xw = 0; y++; }
-                }
-            }
-        }
+    // (the masks of a wavefront that found something, for the write pass: its lane t holds segments 4 t .. 4 t + 3 of the block)
+    if (__builtin_amdgcn_ballot_w64(cnt != 0u) != 0ull) {
+        uint64_t* q = P.segmask + ((size_t)b * 1024u + 4u * threadIdx.x);
+        *reinterpret_cast<u64x2u*>(q) = u64x2u{m[0], m[1]};
+        *reinterpret_cast<u64x2u*>(q + 2) = u64x2u{m[2], m[3]};
     }
-    if (!WRITE) {
-        if (P.zero_cull && blockIdx.x == 0 && threadIdx.x < 64) P.zero_cull[32 * threadIdx.x] = 0u;   // (read for the last time by the kernel before this one)
-        // low 32 bits: active cells of the block; high 32 bits: its case-13 sign words (rare)
-        __shared__ uint32_t s_cnt[K2_LPB][4], s_n13[K2_LPB];
-        if (threadIdx.x < K2_LPB) s_n13[threadIdx.x] = 0;
-        uint32_t wsum[K2_LPB];
-#pragma unroll
-        for (int l = 0; l < K2_LPB; l++) wsum[l] = wave_sum_u32(cnts[l]);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int l = 0; l < K2_LPB; l++)
-                if (l < nl) {
-                    s_cnt[l][wave] = wsum[l];
-                    P.wavecnt[(b0 + l * P.bpl) * 4 + wave] = wsum[l];   // lets the write pass skip empty wavefronts
-                }
-        }
-#pragma unroll
-        for (int l = 0; l < K2_LPB; l++)
-            if (n13s[l]) atomicAdd(&s_n13[l], n13s[l]);
-        __syncthreads();
-        if ((int)threadIdx.x < nl) {
-            const int l = (int)threadIdx.x;
-            P.blockcnt[b0 + l * P.bpl] = (uint64_t)(s_cnt[l][0] + s_cnt[l][1] + s_cnt[l][2] + s_cnt[l][3]) | ((uint64_t)s_n13[l] << 32);
-        }
+    if (P.zero_cull && blockIdx.x == 0 && threadIdx.x < 64) P.zero_cull[32 * threadIdx.x] = 0u;   // (read for the last time by the kernel before this one)
+    // low 32 bits: active cells of the block; high 32 bits: its case-13 sign words (rare)
+    __shared__ uint32_t s_cnt[4], s_n13;
+    if (threadIdx.x == 0) s_n13 = 0;
+    const uint32_t wsum = wave_sum_u32(cnt);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        s_cnt[wave] = wsum;
+        P.wavecnt[b * 4 + wave] = wsum;   // lets the write pass skip empty wavefronts
     }
+    if (n13) atomicAdd(&s_n13, n13);
+    __syncthreads();
+    if (threadIdx.x == 0) P.blockcnt[b] = (uint64_t)(s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]) | ((uint64_t)s_n13 << 32);
 }
 
 // The count pass straight from the sampler's sign BYTES bits8[y][x/8][z]: no k_bits_transpose in front, no `bits` array.  The bytes of
@@ -523,7 +392,7 @@ __global__ __launch_bounds__(256) void k_compact(McParams P)
 // eight byte rows of word xw and the row that follows, 512 contiguous bytes per wavefront instruction, all eighteen before the first
 // is used -- and transposes the 8 x 8 bytes in registers (mc_signbytes.h): eight X words, the very words the transposer would have
 // stored.  Plane 8 L + 8 of the lane's last layer is the next lane's plane 0; lane 63 takes it from memory (the chunk's edge: lanes
-// 0 .. 8 load a byte each).  segment_mask then gives, bit for bit, what k_compact<false> computes from the words.
+// 0 .. 8 load a byte each).  segment_mask then gives, bit for bit, what k_compact computes from the words.
 // A workgroup is four consecutive y of one xw: of the five voxel rows it reads, three come out of the CU's cache.
 // Results, in the layouts the write pass knows ([block = (layer, part)][...]):
 //   segmask   the non-zero masks only; segvalid says which those are, a ballot per layer (a bit per lane = per layer 8 L + j), stored
@@ -608,7 +477,7 @@ __global__ __launch_bounds__(256) void k_count_bytes(McParams P)
     }
 }
 
-// The write pass with the lanes' segments INTERLEAVED (SDFK_COMPACT_STRIDED): lane L of a block takes segments L, L + 256, L + 512 and
+// The write pass, with the lanes' segments INTERLEAVED: lane L of a block takes segments L, L + 256, L + 512 and
 // L + 768 of the block's 1024 instead of four consecutive ones.  A run of busy segments -- a row near a tangent of the surface
 // holds up to 64 records per segment -- then spreads over neighbouring lanes instead of piling up to 256 records on one lane, whose
 // serial walk over its set bits was the tail of the launch (round 4's timeline: writing 1.0 us for the first wavefront, up to 5 us of
@@ -618,8 +487,8 @@ __global__ __launch_bounds__(256) void k_count_bytes(McParams P)
 #ifndef SDFK_KW_MINWAVES
 #define SDFK_KW_MINWAVES 1
 #endif
-template <bool MASKS, bool VALID>   // MASKS: P.segmask holds the count pass's activity masks; VALID: ... of k_count_bytes, those P.segvalid names
-__global__ __launch_bounds__(256, MASKS ? SDFK_KW_MINWAVES : 1) void k_compact_write(McParams P)
+template <bool VALID>   // VALID: P.segmask holds the masks of k_count_bytes, those P.segvalid names
+__global__ __launch_bounds__(256, SDFK_KW_MINWAVES) void k_compact_write(McParams P)
 {
     const int nlay = P.lay_list_end - P.lay_count_begin, nlog = nlay * P.bpl;
     const int b = compact_block_of_workgroup(nlay, P.bpl);   // logical block = (layer, part)
@@ -627,7 +496,8 @@ __global__ __launch_bounds__(256, MASKS ? SDFK_KW_MINWAVES : 1) void k_compact_w
     const int z = P.lay_count_begin + lay;
     const int nseg = P.ncy * P.nxw;
     const int s0 = part * 1024 + (int)threadIdx.x;
-    // this lane's share of the counts of all blocks before b (in flight together with the sign words below)
+    // this lane's share of the counts of all blocks before b, loaded HERE (four independent loads per trip, in flight together with the
+    // masks below) -- a plain "load; add" loop behind them cost up to eight dependent L2 round trips for the last blocks of a 512^3 grid
     // (grids of many blocks: ONE word, left by k_blockscan -- summing 16 K predecessors per workgroup is 16 dependent round trips)
     uint32_t before = 0;
     if (P.blockpre) {
@@ -646,55 +516,25 @@ __global__ __launch_bounds__(256, MASKS ? SDFK_KW_MINWAVES : 1) void k_compact_w
     for (int k = 0; k < 4; k++) look[k] = P.wavecnt[b * 4 + k] != 0;   // (uniform over the workgroup)
     uint64_t m[4] = {0, 0, 0, 0};
     int ys[4] = {0, 0, 0, 0}, xws[4] = {0, 0, 0, 0};
-    if (MASKS) {
-        // the count pass left the masks of the quarters that hold something: one 8-byte load per segment (512 contiguous bytes per
-        // wavefront instruction) instead of four 16-byte loads and the activity logic again -- 40 instead of 96 VGPRs
-        const uint64_t* q = P.segmask + (size_t)b * 1024u + threadIdx.x;
+    // the count pass left the masks of the quarters that hold something: one 8-byte load per segment (512 contiguous bytes per
+    // wavefront instruction) instead of four 16-byte loads of sign words and the activity logic again -- 40 instead of 96 VGPRs
+    const uint64_t* q = P.segmask + (size_t)b * 1024u + threadIdx.x;
 #pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (look[k] && s0 + 256 * k < nseg) {
-                if (VALID) {
-                    // k_count_bytes stored the non-zero masks only: one bit per segment and layer says which, everything else in segmask
-                    // is stale and is not read.  (Loading both words side by side and masking -- no second dependent round trip, but
-                    // every stale line fetched -- was measured slower: 15.1 against 14.3 us at 512^3.)
-                    const uint64_t vb = P.segvalid[((size_t)(lay >> 9) * 8 + (lay & 7)) * P.nsegp + s0 + 256 * k];
-                    if ((vb >> ((lay & 511) >> 3)) & 1ull) m[k] = q[256 * k];
-                } else
-                    m[k] = q[256 * k];
-            }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int s = s0 + 256 * k;
-            if (s < nseg) { ys[k] = s / P.nxw; xws[k] = s - ys[k] * P.nxw; }
-        }
-    } else {
-        const size_t plane = (size_t)P.ny * P.nxw;
-        const uint64_t* f0 = P.bits + (size_t)z * plane;
-        u64x2u wa[4], wb[4], wc[4], wd[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {      // all loads first
-            const int s = s0 + 256 * k;
-            wa[k] = wb[k] = wc[k] = wd[k] = u64x2u{0, 0};
-            if (look[k] && s < nseg) {
-                const uint64_t* q = f0 + s;
-                wa[k] = *reinterpret_cast<const u64x2u*>(q);
-                wb[k] = *reinterpret_cast<const u64x2u*>(q + P.nxw);
-                wc[k] = *reinterpret_cast<const u64x2u*>(q + plane);
-                wd[k] = *reinterpret_cast<const u64x2u*>(q + plane + P.nxw);
-            }
+    for (int k = 0; k < 4; k++)
+        if (look[k] && s0 + 256 * k < nseg) {
+            if (VALID) {
+                // k_count_bytes stored the non-zero masks only: one bit per segment and layer says which, everything else in segmask
+                // is stale and is not read.  (Loading both words side by side and masking -- no second dependent round trip, but
+                // every stale line fetched -- was measured slower: 15.1 against 14.3 us at 512^3.)
+                const uint64_t vb = P.segvalid[((size_t)(lay >> 9) * 8 + (lay & 7)) * P.nsegp + s0 + 256 * k];
+                if ((vb >> ((lay & 511) >> 3)) & 1ull) m[k] = q[256 * k];
+            } else
+                m[k] = q[256 * k];
         }
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int s = s0 + 256 * k;
-            if (s < nseg) {
-                ys[k] = s / P.nxw;
-                xws[k] = s - ys[k] * P.nxw;
-                if (look[k]) {
-                    uint64_t m13;
-                    m[k] = segment_mask(wa[k].x, wa[k].y, wb[k].x, wb[k].y, wc[k].x, wc[k].y, wd[k].x, wd[k].y, P.ncx - xws[k] * 64, m13);
-                }
-            }
-        }
+    for (int k = 0; k < 4; k++) {
+        const int s = s0 + 256 * k;
+        if (s < nseg) { ys[k] = s / P.nxw; xws[k] = s - ys[k] * P.nxw; }
     }
     // segment order within the block = (quarter k, lane): exclusive prefix of the packed per-quarter counts over the lanes, then the
     // totals of the quarters before
@@ -710,7 +550,9 @@ __global__ __launch_bounds__(256, MASKS ? SDFK_KW_MINWAVES : 1) void k_compact_w
     __syncthreads();
     const uint32_t base = s_before[0] + s_before[1] + s_before[2] + s_before[3];
     if (b == 0 && !P.blockpre) {
-        // the first block publishes the totals and the layer marks (everything follows from the count pass's blockcnt[])
+        // The FIRST block publishes the totals and the layer marks: everything here follows from the count pass's blockcnt[], the
+        // first block starts first and its extra work hides behind the rest of the launch (the last block, which did this in
+        // rounds 1-3, starts last and was the launch's tail)
         publish_compaction(P, nlay, nlog);
     }
     uint32_t* rowstart = P.rowstart + (size_t)lay * P.ncy;
@@ -2044,11 +1886,8 @@ __global__ __launch_bounds__(256) void k_repitch(const float* __restrict__ src, 
 // ---- explicit instantiations of the template kernels (declared in mc_kernels.h; launched from lib_*.hip) ---------------------------
 template __global__ void k_signbits8<true>(const float* __restrict__ values, uint8_t* __restrict__ bits8, int nx, int ny, int nz, int nx8, int pitch, float iso);
 template __global__ void k_signbits8<false>(const float* __restrict__ values, uint8_t* __restrict__ bits8, int nx, int ny, int nz, int nx8, int pitch, float iso);
-template __global__ void k_compact<true>(McParams P);
-template __global__ void k_compact<false>(McParams P);
-template __global__ void k_compact_write<true, false>(McParams P);
-template __global__ void k_compact_write<false, false>(McParams P);
-template __global__ void k_compact_write<true, true>(McParams P);
+template __global__ void k_compact_write<false>(McParams P);
+template __global__ void k_compact_write<true>(McParams P);
 template __global__ void k_vertices<true>(McParams P, McMeshOut M);
 template __global__ void k_vertices<false>(McParams P, McMeshOut M);
 template __global__ void k_repitch<true>(const float* __restrict__ src, float* __restrict__ dst, size_t rows, int w, int pw);

@@ -15,7 +15,6 @@ namespace sdfk {
 #endif
 constexpr uint32_t MC_CHUNK = MC_CHUNK_RECORDS;
 static_assert(MC_CHUNK >= 64 && MC_CHUNK <= 256, "one 256-thread workgroup per chunk");
-// vertex-id slots per chunk (rec_vid): a record references at most 13 distinct vertex ids (12 edges + the centre vertex)
 // logical compaction blocks / chunks of records above which ONE workgroup computes their prefix between two kernels of the chain
 // (k_blockscan, k_chunkscan) instead of every consumer workgroup summing its predecessors itself
 // (8192: a one-workgroup launch costs a serial chain ~6 us; what it saves grows with the square of the count -- ~2 us at 5 000 chunks,
@@ -28,6 +27,7 @@ static_assert(MC_CHUNK >= 64 && MC_CHUNK <= 256, "one 256-thread workgroup per c
 #endif
 constexpr int MC_SCAN_BLOCKS = SDFK_SCAN_BLOCKS;
 constexpr uint32_t MC_SCAN_CHUNKS = SDFK_SCAN_CHUNKS;
+// vertex-id slots per chunk (rec_vid): a record references at most 13 distinct vertex ids (12 edges + the centre vertex)
 constexpr uint32_t MC_VSTRIDE = MC_CHUNK * 13u;
 static_assert(MC_VSTRIDE <= 4096, "the in-chunk slot prefix has 12 bits in rec_info");
 
@@ -65,8 +65,8 @@ struct McParams {
     int bpl;               // logical blocks of k_compact per layer: ceil(ncy * nxw / 1024)
     uint64_t* blockcnt;    // per logical block of k_compact: active cells | case-13 sign words << 32
     uint32_t* wavecnt;     // active cells per wavefront of the count pass ([block][4])
-    uint64_t* segmask;     // non-null: the count pass leaves the activity masks of the wavefronts that found something ([block][1024 segments],
-                           // a bit per cell); the write pass loads ONE word per segment instead of sixteen sign words and recomputes nothing
+    uint64_t* segmask;     // always present: the count pass leaves the activity masks of the wavefronts that found something ([block][1024
+                           // segments], a bit per cell); the write pass loads ONE word per segment instead of sixteen sign words
     // count pass from the sign BYTES (k_count_bytes, mc_kernels.hip): `bits` is null then, nothing made the words
     const uint8_t* bits8;  // non-null: the sampler's byte form [y][x/8][z] (a byte = the sign bits of 8 consecutive x), rows of pitch8 bytes
     int nx8, pitch8;       // byte rows per y: ceil(nx / 8); pitch8 % 8 == 0

@@ -1,6 +1,6 @@
 // signbytes_host.cpp -- stand-alone test program (g++, also with -fsanitize=address,undefined): the bit logic of k_count_bytes,
 // csrc/mc_signbytes.h, compiled for the host from the very header the kernel includes, against the two kernels it replaces on its path:
-// the sign words as k_bits_transpose regroups them from bits8[y][x/8][z], and segment_mask on those words the way k_compact<false>
+// the sign words as k_bits_transpose regroups them from bits8[y][x/8][z], and segment_mask on those words the way k_compact
 // walks them (a flat plane of ny * nxw words, the word after a segment = the next word of the plane).  A "wavefront" here is a loop
 // over 64 lanes that loads what the kernel's lanes load (same offsets, same guards); its masks, the per-block and per-quarter counts,
 // the case-13 counts and the validity bits must equal the reference's, bit for bit.  tests/test_signbytes_host.py builds and runs it.
@@ -46,7 +46,7 @@ struct Result {
     }
 };
 
-// k_bits_transpose + k_compact<false>
+// k_bits_transpose + k_compact
 static void reference(const Grid& g, const std::vector<uint8_t>& b8, std::vector<uint64_t>& words, Result& R)
 {
     words.assign((size_t)g.nz * g.ny * g.nxw + 8, 0x5a5a5a5a5a5a5a5aull);   // (the padding k_compact may read holds anything)

@@ -1,6 +1,6 @@
 """SDFK_OPT_COUNT_BYTES: a sdfk_sample_march job (SdfEx.ToMesh) whose sampler has just written the sign bytes of its own volume counts
 its active cells straight from those bytes (k_count_bytes: lanes along z, the 8 x 8 byte transposition in registers) instead of
-regrouping them into words first (k_bits_transpose) and counting from the words (k_compact<false>).  The old kernels are the
+regrouping them into words first (k_bits_transpose) and counting from the words (k_compact).  The old kernels are the
 reference here: with the option off the very same call takes them, and the four mesh arrays, the bounds and both cell counts must
 come out byte for byte the same.  Shapes: one lane (nz = 8), the hand-over between lanes (16), a full 512-layer chunk and the chunk
 boundary (520), one, two and three words per row with a partial last word (nx = 64, 72, 130), enough segments for a second quarter

@@ -347,6 +347,21 @@ def test_sparse_rows_volume(gpu):
     ov, oc = O.sample(scene, mn, mx, *n)
     om = O.march(ov, oc, mn, mx)
     assert_mesh_equal(sdf.ToMesh(mn, mx, *n, clipToBounds=False), om)
+    # and two compaction blocks per layer under both placements of k_compact's workgroups: 342 cell rows of 3 words are 1026 segments,
+    # so the second block of a layer holds two segments (one lane, half full); of the 67 x 2 workgroups 128 are dealt in runs of 16
+    # layers per XCD and the last 6 (layers 64 .. 66) in plain order.  The count pass's block index and the masks it hands to the write
+    # pass must agree in both -- seen only where the second block has active cells (y = 341, x >= 64), in both groups of layers
+    shape = (130, 343, 68)
+    X, Y, Z = np.meshgrid(*[np.arange(n, dtype=np.float32) for n in shape], indexing="ij")
+    v = (np.sin(0.9 * X) * np.cos(0.8 * Y) + 0.6 * np.sin(0.11 * Z) - 0.1).astype(np.float32)
+    c = np.random.default_rng(13).uniform(0, 1, shape + (3,)).astype(np.float32)
+    om = O.march(v, c, [-1] * 3, [1] * 3)
+    idx = om.cells[:, 0].astype(np.int64)
+    cx, cy, cz = idx % shape[0], idx // shape[0] % shape[1], idx // (shape[0] * shape[1])
+    tail = (cy == 341) & (cx >= 64)
+    assert (len(idx), int((tail & (cz < 64)).sum()), int((tail & (cz >= 64)).sum())) == (1250514, 1341, 57)
+    for rep in range(2):   # (first call: the exact path; second: speculative sizes)
+        assert_mesh_equal(MarchingCubes.CreateMesh(Voxels(v, c, [-1] * 3, [1] * 3)), om)
 
 
 def test_many_layers_many_chunks(gpu):

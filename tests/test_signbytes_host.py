@@ -1,6 +1,6 @@
 """The bit logic of the count pass that reads the sampler's sign BYTES (k_count_bytes, csrc/mc_signbytes.h), on the host: the 8 x 8 byte
 transposition in registers, the next-word bits, and a lane-by-lane walk of a wavefront's column against what the two kernels it
-replaces compute -- the words as k_bits_transpose regroups them, segment_mask on those words as k_compact<false> walks them: transposed
+replaces compute -- the words as k_bits_transpose regroups them, segment_mask on those words as k_compact walks them: transposed
 words, masks, counts, case-13 counts and validity bits, bit for bit.  tests/cpp/signbytes_host.cpp is a stand-alone program (its own
 main) that includes the very header the kernel includes; all-zero, all-one, checkerboards, random fills, a single set / clear bit at
 every byte and bit position, nx = 64, 65, 72, 128, ny = 2, 3, rows with padding, a 512-layer chunk boundary.  It is built and run twice:
