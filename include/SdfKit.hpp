@@ -459,6 +459,10 @@ public:
     inline MeshRayHits RayCast(const std::vector<Vector3>& origins, const std::vector<Vector3>& directions, float tMin = 0.0f, float tMax = INFINITY) const;
     inline std::vector<bool> Occluded(const std::vector<Vector3>& origins, const std::vector<Vector3>& directions, float tMin = 0.0f,
                                       float tMax = INFINITY) const;
+    // the generalized winding number of every point, and whether it is inside (MeshSdf(*this).WindingNumber / Contains; beta < 0:
+    // the default)
+    inline std::vector<float> WindingNumber(const std::vector<Vector3>& points, float beta = -1.0f) const;
+    inline std::vector<bool> Contains(const std::vector<Vector3>& points, float beta = -1.0f) const;
     // the mesh rendered as SdfEx.ToImage renders an SDF: the same camera, light, sky and lens (MeshSdf(*this).Render)
     inline Vec3Data ToImage(int width, int height, const Matrix4x4& viewTransform, float verticalFieldOfViewDegrees = 60.0f,
                             float nearPlaneDistance = 1.0f, float farPlaneDistance = 100.0f) const;
@@ -1257,6 +1261,10 @@ inline void WriteTgaHeader(std::ostream& w, int imageType, int width, int height
 // ---------------------------------------------------------------------------------------
 // Triangle meshes as signed distance fields (not in the reference: Mesh -> Voxels), sdfk_trimesh_* (include/sdfkit_hip.h)
 // ---------------------------------------------------------------------------------------
+enum class MeshSign : int32_t { Parity = SDFK_TRIMESH_SIGN_PARITY, Winding = SDFK_TRIMESH_SIGN_WINDING };
+// the smallest beta of the recorded list at which every case of tests/golden/mesh_winding_accuracy.json keeps every sign
+constexpr float DefaultWindingBeta = 2.5f;
+
 class MeshSdf {
 public:
     // The triangles of `vertices` / `triangles` (three indices each); `colors` (one per vertex) may be empty.
@@ -1283,17 +1291,22 @@ public:
     }
     // The signed distance at the cell centres of Voxels(min, max, nx, ny, nz); distances above maxDistance become
     // +-maxDistance.  Without a band, large volumes far from a fine mesh are slow.
-    Voxels ToVoxels(Vector3 min, Vector3 max, int nx, int ny, int nz, float maxDistance = INFINITY, bool clipToBounds = false) const
+    // sign: MeshSign::Parity (crossings along z: exact on watertight meshes, streaks on others) or MeshSign::Winding
+    // (|WindingNumber| > 1/2 with the acceptance parameter beta: holes are capped by the 1/2 level set and overlapping pieces are
+    // united; the values next to a cap are distances to the mesh's triangles, not to the cap, until Voxels::Redistance has run).
+    Voxels ToVoxels(Vector3 min, Vector3 max, int nx, int ny, int nz, float maxDistance = INFINITY, bool clipToBounds = false,
+                    MeshSign sign = MeshSign::Parity, float beta = DefaultWindingBeta) const
     {
         Voxels v(min, max, nx, ny, nz);
-        SampleInto(v, maxDistance);
+        SampleInto(v, maxDistance, sign, beta);
         if (clipToBounds) v.ClipToBounds();
         return v;
     }
-    void SampleInto(Voxels& v, float maxDistance = INFINITY) const
+    void SampleInto(Voxels& v, float maxDistance = INFINITY, MeshSign sign = MeshSign::Parity, float beta = DefaultWindingBeta) const
     {
         v.Ensure(hasColors_ || v.hasColors_);
-        Check(sdfk_trimesh_to_volume(h_, v.h_, maxDistance));
+        if (sign == MeshSign::Parity) Check(sdfk_trimesh_to_volume(h_, v.h_, maxDistance));
+        else Check(sdfk_trimesh_to_volume_signed(h_, v.h_, maxDistance, (int32_t)sign, beta));
         v.values_.clear();
         v.hostNewer_ = false;
         v.version_++;
@@ -1453,6 +1466,25 @@ public:
         for (size_t i = 0; i < d.size(); i++) out[i] = tri[i] >= 0;
         return out;
     }
+    // The generalized winding number of every point (sdfk_trimesh_winding: one stated function of the mesh, the point and beta): on
+    // a closed, consistently oriented mesh 0 outside and +1 or -1 inside, 2 where closed pieces overlap, 0 in a cavity; smooth where
+    // the mesh is open; NaN for a point with a NaN or infinite coordinate.  Clusters of triangles farther than beta times their
+    // radius are replaced by their first-order term; beta = INFINITY sums every triangle.  The hierarchy is made by the handle's
+    // first call and kept.
+    std::vector<float> WindingNumber(const std::vector<Vector3>& points, float beta = DefaultWindingBeta) const
+    {
+        std::vector<float> w(points.size());
+        Check(sdfk_trimesh_winding(h_, points.empty() ? nullptr : &points.data()->X, (int64_t)points.size(), beta, w.data(), nullptr));
+        return w;
+    }
+    // Whether each point is inside: |winding number| > 1/2, decided in binary64 before the rounding to float.  Independent of which
+    // way the normals point; the union of overlapping closed pieces; holes are capped by the 1/2 level set.
+    std::vector<bool> Contains(const std::vector<Vector3>& points, float beta = DefaultWindingBeta) const
+    {
+        std::vector<uint8_t> in(points.size());
+        Check(sdfk_trimesh_winding(h_, points.empty() ? nullptr : &points.data()->X, (int64_t)points.size(), beta, nullptr, in.data()));
+        return std::vector<bool>(in.begin(), in.end());
+    }
     // The mesh as one camera sees it (sdfk_trimesh_render), with RayMarcher's own camera, lens defaults, light and sky: Render is
     // Lambert-shaded (vertex colours blended; a mesh without is white), RenderDepth the distance along every pixel's ray (+inf: the
     // sky), RenderTriangles the triangle every pixel sees (-1: the sky).  Defined after RayMarcher, whose camera they use.
@@ -1497,6 +1529,14 @@ inline MeshRayHits Mesh::RayCast(const std::vector<Vector3>& origins, const std:
 inline std::vector<bool> Mesh::Occluded(const std::vector<Vector3>& origins, const std::vector<Vector3>& directions, float tMin, float tMax) const
 {
     return MeshSdf(*this).Occluded(origins, directions, tMin, tMax);
+}
+inline std::vector<float> Mesh::WindingNumber(const std::vector<Vector3>& points, float beta) const
+{
+    return MeshSdf(*this).WindingNumber(points, beta < 0 ? DefaultWindingBeta : beta);
+}
+inline std::vector<bool> Mesh::Contains(const std::vector<Vector3>& points, float beta) const
+{
+    return MeshSdf(*this).Contains(points, beta < 0 ? DefaultWindingBeta : beta);
 }
 inline MeshComponents Mesh::Components() const { return MeshSdf(*this).Components(); }
 inline MeshTopology Mesh::Topology() const { return MeshSdf(*this).Topology(); }

@@ -1311,7 +1311,69 @@ int sdfk_trimesh_render_device(const sdfk_trimesh* t, int32_t width, int32_t hei
                                const float view_projection_inverse[16], float near_plane, float far_plane, void* depth_dev, void* rgb_dev,
                                void* triangle_dev);
 
-/* ---- Redistancing (Voxels.Redistance) ---------------------------------------------------------------------------------------
+/* ---- Triangle meshes: generalized winding number (MeshSdf.WindingNumber / Contains, Mesh.ToVoxels(sign = "winding")) ---------
+ * A sign for meshes that are not watertight.  The winding number of a query q is the sum over the triangles of their signed solid
+ * angles seen from q, over 4 pi (Jacobson et al. 2013): on a closed, consistently oriented mesh an integer (0 outside, +1 inside
+ * outward-facing triangles, -1 inside inward-facing ones, 2 where two closed pieces overlap, 0 in a cavity whose shell faces the
+ * other way), and a smooth function where the mesh is open.  INSIDE means |w| > 1/2, decided on the binary64 sum before it is
+ * rounded: the absolute value makes the rule independent of which way the normals point, and an overlap counts as inside (the
+ * union; parity gives the XOR).  Far clusters of triangles are replaced by their first-order term (Barill et al. 2018).
+ * ONE function of (mesh, query, beta), computed by csrc/trimesh_winding.h (no contraction, no library transcendental), restated
+ * in tests/mesh_winding_model.py and compared bit for bit.  All arithmetic is binary64 on the widened f32 inputs, one rounding per
+ * written operation; every dot product and squared length is (x0 y0 + x1 y1) + x2 y2.
+ *
+ * Triangle term.  A = a - q, B = b - q, C = c - q; det = A . (B x C) with B x C = (B1 C2 - B2 C1, B2 C0 - B0 C2, B0 C1 - B1 C0);
+ * den = (((|A| |B|) |C| + (A . B) |C|) + (B . C) |A|) + (C . A) |B|; term = atan2(det, den) / (2 pi), which is Omega / (4 pi) of
+ * Van Oosterom and Strackee.  atan2 is the routine of csrc/mathops.h kept in binary64 (atan2_64: t = min / max of the absolute
+ * values, j = rint(8 t), u = (8 t - j) / (8 + t j), atan(j / 8) from a table + (u + (u u^2) P(u^2)), pi / 2 - . when |y| > |x|,
+ * pi - . when x < 0, negated when y < 0; zeros, infinities and NaN as C99 Annex F), never a library's.  Edge cases: q equal to a
+ * vertex gives det = +-0, den = +0 and the term +-0.  q in the triangle's plane: outside the triangle the term is det's rounding
+ * noise over a positive den, about 0; inside it or on an edge den <= 0 and the term is +1/2 or -1/2 by the sign of det, which
+ * there is a zero or rounding noise.  A triangle with two equal vertices has det = +-0 exactly and adds +-0 wherever den > 0,
+ * which is everywhere off its segment; on the segment den is zero up to rounding, and the term is +-0 or +-1/2 by that rounding.
+ * Three distinct collinear vertices behave like a triangle seen in its plane.  A query with a NaN or infinite
+ * coordinate visits nothing: its w is NaN, and it is not inside.
+ *
+ * Hierarchy (built on the device by the first call that needs it, kept on the handle until sdfk_trimesh_free).  L = the least
+ * L >= 0 with 16 * 4^L >= triangles, at most 6.  A lattice of 2^L cells per axis covers the cube whose low corner is the low corner of
+ * the mesh's f32 box and whose edge e is the box's greatest extent; a triangle belongs to the cell of its centroid
+ * ((a + b) + c) / 3: per axis (int)((centroid - lo) (2^L / e)) clamped to [0, 2^L - 1] (cell 0 when e = 0).  The three cell indices are
+ * interleaved (x lowest) into a code; the triangles are sorted by (code, index).  The nodes of level l = 0 .. L are the 8^l
+ * prefixes of the codes, the eight children of a node in the order dx + 2 dy + 4 dz; a node's triangles are one run of the sorted
+ * order.  Per triangle n = (b - a) x (c - a) and weight = |n|.  The sums of n, of weight * centroid and of weight start from 0 and
+ * add, for a cell of level L, its triangles in sorted order, and for a node above, its eight children's sums in child order.
+ * N = sum n / 2; P = sum(weight centroid) / sum weight (the centroid of the node's first triangle when that is 0); r2 = the greatest
+ * |v - P|^2 over the vertices of the node's triangles.
+ *
+ * The sum.  w starts at 0 at the root; the walk is depth first, children in child order.  At a node that has triangles, with
+ * D = P - q and d2 = |D|^2: if d2 > (beta beta) r2 the node adds (D . N) / (4 pi (d2 sqrt(d2))); otherwise, at level L or with at
+ * most 4 triangles, it adds its triangles' terms in sorted order; otherwise its children are visited.  w is added up in exactly this
+ * order in binary64 -- one lane owns one query, so no order of lanes or atomics exists to depend on, and no term is rounded on the
+ * way.  beta = +inf never takes a cluster term: brute force through the same code.  beta = 0 takes the root's.
+ *
+ * sdfk_trimesh_winding: per query winding = (float)w and inside = 1 when |w| > 1/2 (w in binary64), else 0; either output may be
+ * NULL.  Host arrays, synchronous; _device: device buffers, asynchronous on the library stream once the handle has its hierarchy.
+ * Refused (SDFK_ERR_INVALID, nothing written): a null handle, n < 0 or n >= 2^32, beta < 0 or NaN, null queries with n > 0.
+ * n == 0 succeeds and touches nothing.
+ * sdfk_trimesh_to_volume_signed: sdfk_trimesh_to_volume with the sign chosen.  SDFK_TRIMESH_SIGN_PARITY is sdfk_trimesh_to_volume
+ * itself (the same code: beta is ignored).  SDFK_TRIMESH_SIGN_WINDING: distances, colours, the band and slabs are the same; voxel
+ * (i, j, k) is negative iff the query at its f32 cell centre is inside as above; no crossing records are made (stats[7] of
+ * sdfk_trimesh_stats becomes 0).  On a watertight mesh the two agree wherever no rounding decides (everywhere off the surface).
+ * Any other sign_mode, beta < 0 or NaN are refused.  Limits: the cluster term is first order (its error falls as (r / d)^2 per
+ * cluster: see DESIGN.md for measured errors per beta); a hole is capped by the |w| = 1/2 level set, not by a minimal surface;
+ * values next to such a cap are distances to the mesh's triangles, not to the cap, until sdfk_redistance has run.
+ * sdfk_trimesh_winding_stats (diagnostics; never builds anything): stats[0] = L (-1: no hierarchy yet), stats[1] = nodes that
+ * have triangles, stats[2] = triangles in the fullest cell of level L, stats[3] = times the hierarchy was built (0 or 1);
+ * of the last winding call or winding volume made while sdfk_profile_enable(1) was on (that call synchronises):
+ * stats[4] = cluster terms, stats[5] = triangle terms, stats[6] = queries; stats[7] = nodes in all. */
+#define SDFK_TRIMESH_SIGN_PARITY 0
+#define SDFK_TRIMESH_SIGN_WINDING 1
+int sdfk_trimesh_winding(sdfk_trimesh* t, const float* queries3, int64_t n, float beta, float* winding, uint8_t* inside);
+int sdfk_trimesh_winding_device(sdfk_trimesh* t, const void* queries3_dev, int64_t n, float beta, void* winding_dev, void* inside_dev);
+int sdfk_trimesh_to_volume_signed(sdfk_trimesh* t, sdfk_volume* v, float max_distance, int32_t sign_mode, float beta);
+int sdfk_trimesh_winding_stats(const sdfk_trimesh* t, int64_t stats[8]);
+
+/* ---- Redistancing (Voxels.Redistance)---------------------------------------------------------------------------------------
  * dst gets a signed distance to the iso-surface of src, with src's sign at every voxel: a first-order Eikonal solve (Godunov
  * upwind, Jacobi sweeps to the fixed point -- the fast iterative method family, Jeong & Whitaker 2008).  src is not modified
  * (dst may be src: in place).  Colours: copied from src when both volumes have them, zeroed when only dst has.  Cached sign

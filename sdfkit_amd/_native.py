@@ -178,6 +178,10 @@ SIGNATURES = {
     "sdfk_trimesh_raycast_device": (C.c_int, [_vp, _vp, _vp, _i64, C.c_float, C.c_float, _i32, _vp, _vp, _vp]),
     "sdfk_trimesh_render": (C.c_int, [_vp, _i32, _i32, _fp, _fp, C.c_float, C.c_float, _vp, _vp, _vp]),
     "sdfk_trimesh_render_device": (C.c_int, [_vp, _i32, _i32, _fp, _fp, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "sdfk_trimesh_winding": (C.c_int, [_vp, _vp, _i64, C.c_float, _vp, _vp]),
+    "sdfk_trimesh_winding_device": (C.c_int, [_vp, _vp, _i64, C.c_float, _vp, _vp]),
+    "sdfk_trimesh_to_volume_signed": (C.c_int, [_vp, _vp, C.c_float, _i32, C.c_float]),
+    "sdfk_trimesh_winding_stats": (C.c_int, [_vp, C.POINTER(_i64)]),
     "sdfk_trimesh_free": (None, [_vp]),
     "sdfk_volume_redistance": (C.c_int, [_vp, _vp, C.c_float, C.c_float, C.POINTER(_i64)]),
     "sdfk_icp_register": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),

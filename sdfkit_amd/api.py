@@ -746,13 +746,27 @@ class Mesh:
         s = self.Size
         return np.float32(np.sqrt((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]) * np.float32(0.5))
 
-    def ToVoxels(self, min, max, nx, ny, nz, maxDistance=float("inf"), clipToBounds=False):
+    def ToVoxels(self, min, max, nx, ny, nz, maxDistance=float("inf"), clipToBounds=False, sign="parity", beta=None):
         """The mesh as a signed distance volume (sdfkit_amd.meshsdf.MeshSdf.ToVoxels): exact distances at the cell centres
         Voxels.SampleSdf evaluates, signed by crossing parity along z (closed meshes), colours blended from the vertex
         colours.  Not in the reference, which converts SDF -> Voxels -> Mesh only.  Give maxDistance for large volumes: the
-        unbanded search is slow far from a fine mesh (MeshSdf.ToVoxels)."""
-        from .meshsdf import MeshSdf
-        return MeshSdf(self).ToVoxels(min, max, nx, ny, nz, maxDistance, clipToBounds)
+        unbanded search is slow far from a fine mesh (MeshSdf.ToVoxels).  sign="winding": the sign of the generalized winding
+        number instead (beta: its acceptance parameter) -- for meshes with holes or overlapping pieces; with a band, then
+        Voxels.Redistance() and ToMesh(), it repairs such a mesh into a watertight one."""
+        from .meshsdf import DEFAULT_WINDING_BETA, MeshSdf
+        return MeshSdf(self).ToVoxels(min, max, nx, ny, nz, maxDistance, clipToBounds, sign, DEFAULT_WINDING_BETA if beta is None else beta)
+
+    def WindingNumber(self, points, beta=None):
+        """The generalized winding number of every point (sdfkit_amd.meshsdf.MeshSdf.WindingNumber) -> (n,) float32.  To query
+        many batches against one mesh, keep a MeshSdf and call its WindingNumber: the hierarchy is made once per handle."""
+        from .meshsdf import DEFAULT_WINDING_BETA, MeshSdf
+        return MeshSdf(self).WindingNumber(points, DEFAULT_WINDING_BETA if beta is None else beta)
+
+    def Contains(self, points, beta=None):
+        """Whether each point is inside the mesh, |winding number| > 1/2 (MeshSdf.Contains) -> bool array: also for meshes with
+        holes, inside-out meshes and overlapping closed pieces (their union)."""
+        from .meshsdf import DEFAULT_WINDING_BETA, MeshSdf
+        return MeshSdf(self).Contains(points, DEFAULT_WINDING_BETA if beta is None else beta)
 
     def SamplePoints(self, n, seed=0, stratified=True):
         """n points on the mesh in proportion to area, with face normals, blended colours, triangle indices and barycentric

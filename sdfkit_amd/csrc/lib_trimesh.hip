@@ -371,6 +371,7 @@ struct VolArgs {
     double stop2;             // (the band's f32 successor)^2: every d2 whose f32 distance is <= band lies below it
     const uint32_t* cstart;   // nx * ny + 1
     const double* zrec;
+    const uint8_t* sign;      // null: parity of the crossings; else a byte per voxel (unpadded, z fastest), non-zero: inside
     unsigned long long* candidates;
 };
 
@@ -394,10 +395,13 @@ __global__ __launch_bounds__(kBlock) void k_tm_volume(SearchGrid S, VolArgs A)
         if ((threadIdx.x & 63) == 0 && s) atomicAdd(A.candidates, s);
     }
     if (!active) return;
-    // parity of the crossings of this column below the voxel centre
-    const double zk = (double)q[2];
     unsigned cnt = 0;
-    for (uint32_t r = A.cstart[row], r1 = A.cstart[row + 1]; r < r1; r++) cnt += A.zrec[r] < zk ? 1u : 0u;
+    if (A.sign) cnt = A.sign[g0] ? 1u : 0u;   // (the caller's sign: lib_trimesh_winding.hip)
+    else {
+        // parity of the crossings of this column below the voxel centre
+        const double zk = (double)q[2];
+        for (uint32_t r = A.cstart[row], r1 = A.cstart[row + 1]; r < r1; r++) cnt += A.zrec[r] < zk ? 1u : 0u;
+    }
     float d = B.bi >= 0 ? (float)__builtin_sqrt(B.d2) : INFINITY;
     const bool clamped = d > A.band;   // (decided on the f32 distance: the same voxels as the +inf run's values say)
     if (clamped) d = A.band;
@@ -563,6 +567,8 @@ void trimesh_release(sdfk_trimesh* t)
     dev_free(t->list); dev_free(t->starts); dev_free(t->ystarts); dev_free(t->sample_W);
     dev_free(t->comp_vertex); dev_free(t->comp_triangle);
     dev_free(t->nbr_start); dev_free(t->nbr); dev_free(t->boundary); dev_free(t->inc_start); dev_free(t->inc);
+    dev_free(t->wn_nodes); dev_free(t->wn_order);
+    t->wn_nodes = nullptr; t->wn_order = nullptr;
     t->sample_W = nullptr;
     t->comp_vertex = t->comp_triangle = nullptr;
     t->nbr_start = t->nbr = t->inc_start = t->inc = nullptr; t->boundary = nullptr;
@@ -683,7 +689,7 @@ int closest_launch(const sdfk_trimesh* t, const float* q, int64_t n, QueryOut O)
     return st.finish("sdfk_trimesh_closest", false);
 }
 
-int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band)
+int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band, const uint8_t* sign)
 {
     static const char* who = "sdfk_trimesh_to_volume";
     if (v->elided || !v->values) return fail(SDFK_ERR_INVALID, "%s: the volume has no storage", who);
@@ -694,16 +700,17 @@ int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band)
     const Columns Q{v->nx, v->ny, m[0], m[1], d[0], d[1]};
     const int64_t nt = t->nt, ncol = (int64_t)v->nx * v->ny;
     Staged st;
-    int4* box = st.scratch<int4>((size_t)nt);
-    unsigned long long* items = st.scratch<unsigned long long>((size_t)nt + 1);
-    uint32_t* col = st.scratch<uint32_t>((size_t)ncol + 1);
-    uint32_t* cursor = st.scratch<uint32_t>((size_t)ncol);
+    uint32_t* col = nullptr;
     double* zrec = nullptr;
     unsigned long long* cand = nullptr;
     unsigned long long n_items = 0;
     uint32_t n_cross = 0;
     auto grid_items = [](unsigned long long n) { return (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>((n + kBlock - 1) / kBlock, 1u << 20)); };
-    {
+    if (!sign) {
+        int4* box = st.scratch<int4>((size_t)nt);
+        unsigned long long* items = st.scratch<unsigned long long>((size_t)nt + 1);
+        col = st.scratch<uint32_t>((size_t)ncol + 1);
+        uint32_t* cursor = st.scratch<uint32_t>((size_t)ncol);
         ProfScope ps("k_tm_cross");
         st.run([&] { hipLaunchKernelGGL(k_tm_items, dim3(grid1(nt)), dim3(kBlock), 0, g.stream, t->tri, nt, Q, box, items); });
         st.run([&] { return sdfk_scan::scan(items, nt, who); });
@@ -732,7 +739,7 @@ int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band)
     const double stop2 = next * next;
     st.run([&] {
         VolArgs A{v->values, v->colors, t->colors, t->idx, v->nx, v->ny, v->nz, v->pitch(), v->z0, m[0], m[1], m[2], d[0], d[1], d[2],
-                  band, stop2, col, zrec, cand};
+                  band, stop2, col, zrec, sign, cand};
         ProfScope ps("k_tm_volume");
         hipLaunchKernelGGL(k_tm_volume, dim3(grid1((int64_t)v->nx * v->ny * v->nz)), dim3(kBlock), 0, g.stream, search_grid(t), A);
     });
@@ -785,6 +792,8 @@ void sample_stats(const sdfk_trimesh* t, int64_t stats[2])
 
 }  // namespace
 
+int trimesh_to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band, const uint8_t* sign_dev) { return to_volume(t, v, band, sign_dev); }
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // entry points
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -836,7 +845,7 @@ extern "C" int sdfk_trimesh_to_volume(const sdfk_trimesh* t, sdfk_volume* v, flo
     if (int r = require_init()) return r;
     if (!t || !v) return fail(SDFK_ERR_INVALID, "sdfk_trimesh_to_volume: null argument");
     if (!(max_distance >= 0.0f)) return fail(SDFK_ERR_INVALID, "sdfk_trimesh_to_volume: max_distance must be >= 0 (+inf: exact everywhere)");
-    return to_volume(t, v, max_distance);
+    return to_volume(t, v, max_distance, nullptr);
 }
 
 extern "C" int sdfk_trimesh_sample_device(sdfk_trimesh* t, int64_t n, uint64_t seed, int32_t flags, void* points3_dev, void* normals3_dev,

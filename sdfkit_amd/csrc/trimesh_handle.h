@@ -3,7 +3,7 @@
 // topology call, lib_trimesh_topology.hip) and the adjacency (made by the first adjacency, smoothing or vertex-normal call,
 // lib_trimesh_smooth.hip).  Seen by those three translation units and by lib_trimesh_weld.hip, lib_trimesh_simplify.hip and
 // lib_trimesh_ray.hip, which only read it (simplification asks for the corner lists of the adjacency; the ray caster walks the
-// search grid).  With it, what the six share on the host: the staging of
+// search grid), and by lib_trimesh_winding.hip, which keeps its hierarchy here.  With it, what the six share on the host: the staging of
 // device_stage.h, the check of a handle, the size of a one-dimensional launch, and the grouping of the vertices by position.
 // hipcc only.
 #pragma once
@@ -46,6 +46,11 @@ struct sdfk_trimesh {
     uint32_t* inc_start = nullptr;            // nv + 1: the corners 3 t + k of v are inc[inc_start[v] .. inc_start[v + 1]), ascending
     uint32_t* inc = nullptr;                  // 3 nt (inc_entries of them used)
     int64_t nbr_entries = 0, inc_entries = 0;
+    void* wn_nodes = nullptr;                 // the nodes of the winding-number hierarchy (sdfk_trimesh_wn::Node; made by the first winding call)
+    uint32_t* wn_order = nullptr;             // nt: the triangles sorted by (cell code, index)
+    int wn_levels = -1;                       // L; -1: no hierarchy yet
+    int64_t wn_occupied = 0, wn_max_leaf = 0, wn_builds = 0;
+    int64_t last_wn_clusters = 0, last_wn_triangles = 0, last_wn_queries = 0;
 };
 
 // The sampling weights and their scan, once per handle (lib_trimesh.hip): synchronises to read the total.  A mesh in which no
@@ -55,6 +60,11 @@ int trimesh_weights(sdfk_trimesh* t, const char* who);
 // What every entry point of the family asks of its handle first: the library is initialised, t is not null, and -- for a unit
 // that sorts `records` 32-bit-indexed records per triangle (0: none) -- records * nt < 2^32.  (lib_trimesh.hip)
 int trimesh_check(const sdfk_trimesh* t, const char* who, int records);
+
+// sdfk_trimesh_to_volume's work (lib_trimesh.hip; the arguments are checked).  sign_dev null: the parity of the crossings along z.
+// Otherwise one byte per voxel in the order of the volume pass ((i * ny + j) * nz + k, unpadded), non-zero: inside -- the sign of
+// lib_trimesh_winding.hip -- and no crossing records are made.
+int trimesh_to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band, const uint8_t* sign_dev);
 
 // The vertices of a handle grouped by position as sdfk_trimesh_weld groups them (lib_trimesh_weld.hip; tolerance 0: equal as
 // values, > 0: the cell of the lattice), for the units that start from the groups (welding itself, lib_trimesh_simplify.hip).  The

@@ -3,10 +3,12 @@ csrc/lib_trimesh.hip): the exact closest triangle of arbitrary points, signed di
 sampled on the triangles in proportion to area (Mesh -> points), and the connectivity of the mesh by index (components, the edge
 census, sub-meshes of components: csrc/lib_trimesh_topology.hip), and smoothing and vertex normals over its adjacency
 (csrc/lib_trimesh_smooth.hip), and welding: the vertices of equal position made one (csrc/lib_trimesh_weld.hip), and ray casting:
-the first hit or any hit of arbitrary rays, and camera renders of the mesh (csrc/lib_trimesh_ray.hip).
+the first hit or any hit of arbitrary rays, and camera renders of the mesh (csrc/lib_trimesh_ray.hip), and the generalized winding
+number: is this point inside, for meshes that are open or overlap themselves as well (csrc/lib_trimesh_winding.hip).
 
 The distance is exact (binary64 closest point, ties to the lowest triangle index); the sign is the parity of the mesh's
-crossings along z, meaningful for closed meshes (nested shells included) and deterministic for any mesh.
+crossings along z, meaningful for closed meshes (nested shells included) and deterministic for any mesh -- or, with
+sign="winding", |winding number| > 1/2, which degrades gracefully on holes and takes the union of overlapping pieces.
 """
 import ctypes as C
 from collections import namedtuple
@@ -25,6 +27,11 @@ WELD_KEEP_UNREFERENCED = 2  # SDFK_WELD_KEEP_UNREFERENCED
 SIMPLIFY_PLACEMENTS = {"representative": 0, "centroid": 1, "quadric": 2}   # SDFK_SIMPLIFY_REPRESENTATIVE / _CENTROID / _QUADRIC
 SIMPLIFY_DUPLICATES = {"one": 0, "keep": 1, "cancel": 2}                  # 0, SDFK_SIMPLIFY_KEEP_DUPLICATES, SDFK_SIMPLIFY_CANCEL_PAIRS
 RAY_ANY_HIT = 1          # SDFK_RAY_ANY_HIT
+SIGN_MODES = {"parity": 0, "winding": 1}   # SDFK_TRIMESH_SIGN_PARITY / _WINDING
+# The acceptance parameter of the winding number's cluster terms: the smallest beta of the recorded list at which every case of
+# tests/golden/mesh_winding_accuracy.json keeps every sign (at 2.0 eight voxels beside the cap of the capped-off sphere flip; at
+# 2.5 the worst error of w over the recorded volumes is 2.0e-2, against the threshold's 0.5).
+DEFAULT_WINDING_BETA = 2.5
 
 # MeshSdf.SamplePoints: Points (n, 3) f32, Normals (n, 3) f32 (unit face normals), Colors (n, 3) f32 or None, Triangles (n,) int32,
 # Weights (n, 3) f32 (the barycentric weights of the triangle's three vertices, as the colour blend used them)
@@ -181,23 +188,31 @@ class MeshSdf:
             N.check(N.lib().sdfk_trimesh_closest(self._h, _ptr(q), n, _ptr(tri), _ptr(dist), _ptr(cp)))
         return tri, dist, cp
 
-    def ToVoxels(self, min, max, nx, ny, nz, maxDistance=float("inf"), clipToBounds=False):
+    def ToVoxels(self, min, max, nx, ny, nz, maxDistance=float("inf"), clipToBounds=False, sign="parity", beta=DEFAULT_WINDING_BETA):
         """The signed distance at the cell centres of Voxels(min, max, nx, ny, nz) (the centres Voxels.SampleSdf evaluates);
         distances beyond maxDistance become +-maxDistance.  clipToBounds: Voxels.ClipToBounds afterwards.
+        sign: "parity" (crossings along z: exact on watertight meshes, streaks on others) or "winding" (|WindingNumber| > 1/2 with
+        the acceptance parameter beta: holes are capped by the 1/2 level set and overlapping pieces are united; the values next to
+        a cap are distances to the mesh's triangles, not to the cap, until Voxels.Redistance() has run).
         Slow without a band on large volumes far from a fine mesh (every voxel searches until its nearest triangle: the 1.6 M
         triangle sphere into 256^3 takes tens of seconds unbanded, a fraction of a second with a band of a few voxels).  For the far
         field of a large volume, give a band and call Voxels.Redistance() on the result."""
         from .api import Voxels
         vox = Voxels(min, max, nx, ny, nz)
-        self.SampleInto(vox, maxDistance)
+        self.SampleInto(vox, maxDistance, sign, beta)
         if clipToBounds:
             vox.ClipToBounds()
         return vox
 
-    def SampleInto(self, voxels, maxDistance=float("inf")):
+    def SampleInto(self, voxels, maxDistance=float("inf"), sign="parity", beta=DEFAULT_WINDING_BETA):
         """Writes the signed distance (and, when the mesh has colours, the blended colours) into an existing Voxels."""
+        if sign not in SIGN_MODES:
+            raise ValueError(f"sign must be one of {sorted(SIGN_MODES)}")
         h = voxels._ensure_device(self.Colors is not None or voxels._has_colors)
-        N.check(N.lib().sdfk_trimesh_to_volume(self._h, h, C.c_float(maxDistance)))
+        if sign == "parity":
+            N.check(N.lib().sdfk_trimesh_to_volume(self._h, h, C.c_float(maxDistance)))
+        else:
+            N.check(N.lib().sdfk_trimesh_to_volume_signed(self._h, h, C.c_float(maxDistance), SIGN_MODES[sign], C.c_float(beta)))
         voxels._host_values = voxels._host_colors = None   # the device copy is now the truth
         voxels._version += 1
         return voxels
@@ -485,6 +500,42 @@ class MeshSdf:
                                                    (C.c_float * 16)(*[float(x) for x in np.asarray(view_projection_inverse, f32).ravel()]),
                                                    C.c_float(nearPlaneDistance), C.c_float(farPlaneDistance),
                                                    *[C.c_void_p(p) if p else C.c_void_p() for p in (depth_dev, rgb_dev, triangles_dev)]))
+
+    def _winding(self, points, beta, want_winding, want_inside):
+        q = np.ascontiguousarray(np.asarray(points, f32).reshape(-1, 3))
+        n = len(q)
+        w = np.empty(n, f32) if want_winding else None
+        inside = np.empty(n, np.uint8) if want_inside else None
+        N.check(N.lib().sdfk_trimesh_winding(self._h, _ptr(q), n, C.c_float(beta), _ptr(w), _ptr(inside)))
+        return w, inside
+
+    def WindingNumber(self, points, beta=DEFAULT_WINDING_BETA):
+        """The generalized winding number of every point (sdfk_trimesh_winding: one stated function of the mesh, the point and
+        beta) -> (n,) float32: on a closed, consistently oriented mesh 0 outside and +1 (outward-facing triangles) or -1 inside, 2
+        where closed pieces overlap, 0 in a cavity; a smooth function where the mesh is open; NaN for a point with a NaN or
+        infinite coordinate.  Clusters of triangles farther than beta times their radius are replaced by their first-order term;
+        beta = inf sums every triangle.  The hierarchy is made by the handle's first call and kept."""
+        return self._winding(points, beta, True, False)[0]
+
+    def Contains(self, points, beta=DEFAULT_WINDING_BETA):
+        """Whether each point is inside the mesh: |winding number| > 1/2, decided in binary64 before the rounding to float32 ->
+        (n,) bool.  Independent of which way the normals point; the union of overlapping closed pieces; holes are capped by the
+        1/2 level set."""
+        return self._winding(points, beta, False, True)[1].astype(bool)
+
+    def WindingNumberDevice(self, points_dev, n, beta=DEFAULT_WINDING_BETA, winding_dev=None, inside_dev=None):
+        """WindingNumber / Contains from and into caller-owned device memory (raw pointers; None: that output is not wanted;
+        inside is one byte per point): once the handle has its hierarchy this only queues work on the library stream."""
+        N.check(N.lib().sdfk_trimesh_winding_device(self._h, C.c_void_p(points_dev) if points_dev else C.c_void_p(), int(n), C.c_float(beta),
+                                                    *[C.c_void_p(p) if p else C.c_void_p() for p in (winding_dev, inside_dev)]))
+
+    def winding_stats(self):
+        """sdfk_trimesh_winding_stats: the hierarchy (levels -1 before the first winding call) and the term counts of the last
+        profiled call."""
+        s = (C.c_int64 * 8)()
+        N.check(N.lib().sdfk_trimesh_winding_stats(self._h, s))
+        return {"levels": int(s[0]), "occupied_nodes": int(s[1]), "largest_leaf": int(s[2]), "builds": int(s[3]), "cluster_terms": int(s[4]),
+                "triangle_terms": int(s[5]), "queries": int(s[6]), "nodes": int(s[7])}
 
     def stats(self):
         """sdfk_trimesh_stats: grid, triangles, binned pairs, candidates / queries of the last profiled call, crossings."""

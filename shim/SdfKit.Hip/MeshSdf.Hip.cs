@@ -11,6 +11,8 @@
 // Simplify (sdfk_trimesh_simplify): vertex clustering, the vertices of one lattice cell made one made vertex; Mesh.Simplify on top.
 // RayCast / Occluded / Render / RenderDepth / RenderTriangles (sdfk_trimesh_raycast, _render): the first hit or any hit of arbitrary
 // rays, and the mesh as a camera sees it (the ray marcher's camera, light and sky); Mesh.RayCast / Occluded / ToImage on top.
+// WindingNumber / Contains / ToVoxels (sign: MeshSign.Winding) (sdfk_trimesh_winding, _to_volume_signed): the generalized winding
+// number -- is this point inside, also for meshes with holes or overlapping pieces; Mesh.WindingNumber / Contains on top.
 // UNCOMPILED HERE (no .NET in the build image); sdfkit_amd/meshsdf.py's MeshSdf is the same layer, tested.
 using System;
 using System.Collections.Generic;
@@ -180,10 +182,14 @@ namespace SdfKit
 
         /// <summary>The signed distance at the cell centres of Voxels(min, max, nx, ny, nz) (the centres SampleSdf evaluates);
         /// distances above maxDistance become +-maxDistance.  Without a band, large volumes far from a fine mesh are slow.</summary>
-        public Voxels ToVoxels (Vector3 min, Vector3 max, int nx, int ny, int nz, float maxDistance = float.PositiveInfinity, bool clipToBounds = false)
+        /// <summary>sign: MeshSign.Parity (crossings along z: exact on watertight meshes, streaks on others) or MeshSign.Winding
+        /// (|WindingNumber| &gt; 1/2 with the acceptance parameter beta: holes are capped by the 1/2 level set and overlapping pieces
+        /// are united; the values next to a cap are distances to the mesh's triangles until Voxels.Redistance has run).</summary>
+        public Voxels ToVoxels (Vector3 min, Vector3 max, int nx, int ny, int nz, float maxDistance = float.PositiveInfinity, bool clipToBounds = false,
+                                MeshSign sign = MeshSign.Parity, float beta = DefaultWindingBeta)
         {
             var v = new Voxels (min, max, nx, ny, nz);
-            v.SampleMesh (this, maxDistance);
+            v.SampleMesh (this, maxDistance, sign, beta);
             if (clipToBounds)
                 v.ClipToBounds ();
             return v;
@@ -372,6 +378,43 @@ namespace SdfKit
         }
 
         /// <summary>Whether anything is hit within the range, per ray (the search stops at the first hit it meets).</summary>
+        /// <summary>The smallest beta of the recorded list at which every case of tests/golden/mesh_winding_accuracy.json keeps
+        /// every sign.</summary>
+        public const float DefaultWindingBeta = 2.5f;
+
+        /// <summary>The generalized winding number of every point (sdfk_trimesh_winding: one stated function of the mesh, the point
+        /// and beta): on a closed, consistently oriented mesh 0 outside and +1 or -1 inside, 2 where closed pieces overlap, 0 in a
+        /// cavity; smooth where the mesh is open; NaN for a point with a NaN or infinite coordinate.  beta = +inf sums every
+        /// triangle.  The hierarchy is made by the handle's first call and kept.</summary>
+        public unsafe float[] WindingNumber (ReadOnlySpan<Vector3> points, float beta = DefaultWindingBeta)
+        {
+            var w = new float[points.Length];
+            fixed (Vector3* q = points) fixed (float* o = w)
+                Native.Check (Native.sdfk_trimesh_winding (handle, (float*)q, points.Length, beta, o, null));
+            return w;
+        }
+
+        /// <summary>Whether each point is inside: |winding number| &gt; 1/2, decided in binary64 before the rounding to float.
+        /// Independent of which way the normals point; the union of overlapping closed pieces; holes are capped by the 1/2 level
+        /// set.</summary>
+        public unsafe bool[] Contains (ReadOnlySpan<Vector3> points, float beta = DefaultWindingBeta)
+        {
+            var b = new byte[points.Length];
+            fixed (Vector3* q = points) fixed (byte* o = b)
+                Native.Check (Native.sdfk_trimesh_winding (handle, (float*)q, points.Length, beta, null, o));
+            var inside = new bool[b.Length];
+            for (int i = 0; i < b.Length; i++)
+                inside[i] = b[i] != 0;
+            return inside;
+        }
+
+        /// <summary>WindingNumber / Contains from and into caller-owned device memory (inside: one byte per point; IntPtr.Zero: that
+        /// output is not wanted): once the handle has its hierarchy this only queues work on the library stream.</summary>
+        public void WindingNumberDevice (IntPtr pointsDev, long n, float beta, IntPtr windingDev, IntPtr insideDev)
+        {
+            Native.Check (Native.sdfk_trimesh_winding_device (handle, pointsDev, n, beta, windingDev, insideDev));
+        }
+
         public unsafe bool[] Occluded (ReadOnlySpan<Vector3> origins, ReadOnlySpan<Vector3> directions, float tMin = 0, float tMax = float.PositiveInfinity)
         {
             if (origins.Length != directions.Length)
@@ -444,21 +487,44 @@ namespace SdfKit
     public partial class Voxels
     {
         /// <summary>Writes the mesh's signed distance (and blended vertex colours) into this volume's device twin.</summary>
-        public void SampleMesh (MeshSdf mesh, float maxDistance = float.PositiveInfinity)
+        public void SampleMesh (MeshSdf mesh, float maxDistance = float.PositiveInfinity, MeshSign sign = MeshSign.Parity,
+                                float beta = MeshSdf.DefaultWindingBeta)
         {
-            Native.Check (Native.sdfk_trimesh_to_volume (mesh.Handle, EnsureDevice (mesh.HasColors || deviceHasColors), maxDistance));
+            IntPtr v = EnsureDevice (mesh.HasColors || deviceHasColors);
+            if (sign == MeshSign.Parity)
+                Native.Check (Native.sdfk_trimesh_to_volume (mesh.Handle, v, maxDistance));
+            else
+                Native.Check (Native.sdfk_trimesh_to_volume_signed (mesh.Handle, v, maxDistance, (int)sign, beta));
             deviceIsNewer = true; hostMayBeNewer = false;
         }
     }
+
+    /// <summary>The sign of MeshSdf.ToVoxels: SDFK_TRIMESH_SIGN_PARITY / SDFK_TRIMESH_SIGN_WINDING.</summary>
+    public enum MeshSign { Parity = 0, Winding = 1 }
 
     public static class MeshToVoxelsExtensions
     {
         /// <summary>Mesh.ToVoxels: the mesh as a signed distance volume (MeshSdf.ToVoxels).</summary>
         public static Voxels ToVoxels (this Mesh mesh, Vector3 min, Vector3 max, int nx, int ny, int nz,
-                                       float maxDistance = float.PositiveInfinity, bool clipToBounds = false)
+                                       float maxDistance = float.PositiveInfinity, bool clipToBounds = false, MeshSign sign = MeshSign.Parity,
+                                       float beta = MeshSdf.DefaultWindingBeta)
         {
             using var m = new MeshSdf (mesh);
-            return m.ToVoxels (min, max, nx, ny, nz, maxDistance, clipToBounds);
+            return m.ToVoxels (min, max, nx, ny, nz, maxDistance, clipToBounds, sign, beta);
+        }
+
+        /// <summary>Mesh.WindingNumber: the generalized winding number of every point (MeshSdf.WindingNumber).</summary>
+        public static float[] WindingNumber (this Mesh mesh, ReadOnlySpan<Vector3> points, float beta = MeshSdf.DefaultWindingBeta)
+        {
+            using var m = new MeshSdf (mesh);
+            return m.WindingNumber (points, beta);
+        }
+
+        /// <summary>Mesh.Contains: whether each point is inside the mesh, |winding number| &gt; 1/2 (MeshSdf.Contains).</summary>
+        public static bool[] Contains (this Mesh mesh, ReadOnlySpan<Vector3> points, float beta = MeshSdf.DefaultWindingBeta)
+        {
+            using var m = new MeshSdf (mesh);
+            return m.Contains (points, beta);
         }
 
         /// <summary>Mesh.SamplePoints: n points on the mesh in proportion to area (MeshSdf.SamplePoints).</summary>

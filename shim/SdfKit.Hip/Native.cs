@@ -209,6 +209,11 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_trimesh_render_device(IntPtr trimesh, int width, int height, float* cameraPosition,
                                                                              float* viewProjectionInverse, float near, float far, IntPtr depthDev, IntPtr rgbDev,
                                                                              IntPtr triangleDev);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_winding(IntPtr trimesh, float* queries3, long n, float beta, float* winding, byte* inside);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_winding_device(IntPtr trimesh, IntPtr queries3Dev, long n, float beta, IntPtr windingDev,
+                                                                              IntPtr insideDev);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_to_volume_signed(IntPtr trimesh, IntPtr volume, float maxDistance, int signMode, float beta);
+        [DllImport(Lib)] public static extern int sdfk_trimesh_winding_stats(IntPtr trimesh, long* stats8);
         [DllImport(Lib)] public static extern void sdfk_trimesh_free(IntPtr trimesh);
         [DllImport(Lib)] public static extern int sdfk_volume_redistance(IntPtr src, IntPtr dst, float isoValue, float maxDistance, long* stats4);
         // several GPUs from ONE process (the managed host is one process): include/sdfkit_hip.h, "one process, several GPUs"
