@@ -191,6 +191,7 @@ using SdfIndexedOutputModifierFunc = std::function<Vec3(Vec3 /*index*/, Vec3 /*p
 class Mesh;
 class Voxels;
 class MeshSdf;
+class DepthFusion;
 struct FloatData;
 struct Vec3Data;
 struct Matrix4x4;
@@ -640,6 +641,7 @@ public:
 private:
     friend class MeshSdf;   // (writes distances straight into the device volume)
     friend class KdTree;    // (likewise: KdTree::SampleInto)
+    friend class DepthFusion;   // (likewise: DepthFusion::Integrate averages into the device volumes)
     Val Read(int opcode, const Vec3& p, int channel) const
     {
         Builder* b = p.X.b ? p.X.b : (p.Y.b ? p.Y.b : p.Z.b);
@@ -1786,6 +1788,138 @@ inline Vec3Data Mesh::ToImage(int width, int height, Vector3 cameraPosition, Vec
 {
     return ToImage(width, height, Matrix4x4::CreateLookAt(cameraPosition, cameraTarget, cameraUp), verticalFieldOfViewDegrees, nearPlaneDistance,
                    farPlaneDistance);
+}
+
+// ---- depth frames into volumes and points (include/sdfkit_hip.h, "Depth images: fusion and unprojection") ------------------
+// A depth frame is what RayMarcher::RenderDepth and MeshSdf::RenderDepth make: the distance along every pixel's ray, +inf where
+// nothing was seen.  DepthFusion averages frames with poses into a volume of truncated signed distances (Curless & Levoy 1996).
+// The unseen convention: a voxel no frame has observed keeps `unseen`.  With the default -truncation and carve (a pixel that saw
+// nothing within depthMax frees the space along its ray) unseen space is solid and seen-empty space is free, so a fully scanned
+// object meshes watertight; unseen = +truncation without carving is the classic open surface, with a spurious sheet one
+// truncation behind every observed surface.
+struct DepthFusionStats { int64_t Updated = 0, Surface = 0, First = 0, ValidPixels = 0; };
+
+class DepthFusion {
+public:
+    float Truncation, Unseen, MaxWeight;
+    bool Carve;
+    int Frames = 0;
+    Voxels Values, Weights;
+    // unseen NAN: -truncation
+    DepthFusion(Vector3 min, Vector3 max, int nx, int ny, int nz, float truncation, float unseen = NAN, bool carve = true, float maxWeight = INFINITY)
+        : Truncation(truncation), Unseen(unseen != unseen ? -truncation : unseen), MaxWeight(maxWeight), Carve(carve), Values(min, max, nx, ny, nz),
+          Weights(min, max, nx, ny, nz)
+    {
+        const std::vector<float> fill((size_t)nx * ny * nz, Unseen), zero((size_t)nx * ny * nz, 0.0f);
+        Values.Ensure(false);
+        Weights.Ensure(false);
+        Check(sdfk_volume_upload(Values.h_, fill.data(), nullptr));
+        Check(sdfk_volume_upload(Weights.h_, zero.data(), nullptr));
+    }
+    // One frame into the average, seen by the camera it was rendered with (RayMarcher's lens and defaults).  depthMin / depthMax:
+    // the range of depths that are observations (NAN: the near / the far plane).
+    DepthFusion& Integrate(const FloatData& depth, const Matrix4x4& viewTransform, float weight = 1.0f, float depthMin = NAN, float depthMax = NAN,
+                           DepthFusionStats* stats = nullptr, float verticalFieldOfViewDegrees = 60.0f, float nearPlaneDistance = 1.0f,
+                           float farPlaneDistance = 100.0f);
+    DepthFusion& Integrate(const FloatData& depth, Vector3 cameraPosition, Vector3 cameraTarget, Vector3 cameraUp, float weight = 1.0f,
+                           float depthMin = NAN, float depthMax = NAN, DepthFusionStats* stats = nullptr, float verticalFieldOfViewDegrees = 60.0f,
+                           float nearPlaneDistance = 1.0f, float farPlaneDistance = 100.0f)
+    {
+        return Integrate(depth, Matrix4x4::CreateLookAt(cameraPosition, cameraTarget, cameraUp), weight, depthMin, depthMax, stats,
+                         verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance);
+    }
+    // From a depth image in device memory, queued on the library stream: the camera position and the FORWARD view-projection
+    // (ViewTransform x projection, the matrix whose inverse the renders take).
+    DepthFusion& IntegrateDevice(const void* depthDev, int width, int height, const float cameraPosition[3], const Matrix4x4& viewProjection,
+                                 float depthMin, float depthMax, float weight = 1.0f, DepthFusionStats* stats = nullptr)
+    {
+        const sdfk_fusion_params prm{Truncation, depthMin, depthMax, weight, MaxWeight, Carve ? SDFK_FUSE_CARVE_BEYOND : 0};
+        int64_t st[4] = {0, 0, 0, 0};
+        Check(sdfk_volume_integrate_depth_device(Handle(Values), Handle(Weights), depthDev, width, height, cameraPosition, &viewProjection.M[0][0], &prm,
+                                                 stats ? st : nullptr));
+        Done(stats, st);
+        return *this;
+    }
+    Voxels& ToVoxels() { return Values; }
+    // The surface of the fused volume; redistance: through Voxels::Redistance first, which makes distances of the projective,
+    // clamped values.
+    inline Mesh ToMesh(float isoValue = 0.0f, bool redistance = true);
+
+private:
+    static sdfk_volume* Handle(Voxels& v)
+    {
+        sdfk_volume* h = v.Sync();   // (host edits go up first, as everywhere)
+        v.values_.clear();
+        v.version_++;
+        return h;
+    }
+    void Done(DepthFusionStats* stats, const int64_t st[4])
+    {
+        Frames++;
+        if (stats) { stats->Updated = st[0]; stats->Surface = st[1]; stats->First = st[2]; stats->ValidPixels = st[3]; }
+    }
+};
+
+struct DepthPoints {
+    std::vector<Vector3> Points, Colors;   // Colors: empty without rgb
+    std::vector<int32_t> Pixels;           // j * width + i of every point
+};
+
+inline DepthFusion& DepthFusion::Integrate(const FloatData& depth, const Matrix4x4& viewTransform, float weight, float depthMin, float depthMax,
+                                           DepthFusionStats* stats, float verticalFieldOfViewDegrees, float nearPlaneDistance, float farPlaneDistance)
+{
+    float pos[3];
+    Matrix4x4 vpi;
+    RayMarcher::CameraOf(viewTransform, depth.Width, depth.Height, verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance, pos, vpi);
+    const Matrix4x4 vp = viewTransform * Matrix4x4::CreatePerspectiveFieldOfView(verticalFieldOfViewDegrees * 3.14159274f / 180.0f,
+                                                                                  (float)depth.Width / (float)depth.Height, nearPlaneDistance,
+                                                                                  farPlaneDistance);
+    const sdfk_fusion_params prm{Truncation, depthMin != depthMin ? nearPlaneDistance : depthMin, depthMax != depthMax ? farPlaneDistance : depthMax,
+                                 weight, MaxWeight, Carve ? SDFK_FUSE_CARVE_BEYOND : 0};
+    int64_t st[4] = {0, 0, 0, 0};
+    Check(sdfk_volume_integrate_depth(Handle(Values), Handle(Weights), depth.Values.data(), depth.Width, depth.Height, pos, &vp.M[0][0], &prm,
+                                      stats ? st : nullptr));
+    Done(stats, st);
+    return *this;
+}
+inline Mesh DepthFusion::ToMesh(float isoValue, bool redistance)
+{
+    if (!redistance) return Values.ToMesh(isoValue);
+    Voxels r = Values.Redistance(isoValue);
+    return r.ToMesh(isoValue);
+}
+
+// A depth frame as points: camera + ray * depth for every pixel with depthMin <= depth <= depthMax (NAN: the near / the far
+// plane), in pixel order -- for a frame MeshSdf::RenderDepth made, that render's hit points bit for bit.  rgb: the colours to gather.
+inline DepthPoints DepthToPoints(const FloatData& depth, const Matrix4x4& viewTransform, const Vec3Data* rgb = nullptr, float depthMin = NAN,
+                                 float depthMax = NAN, float verticalFieldOfViewDegrees = 60.0f, float nearPlaneDistance = 1.0f,
+                                 float farPlaneDistance = 100.0f)
+{
+    float pos[3];
+    Matrix4x4 vpi;
+    RayMarcher::CameraOf(viewTransform, depth.Width, depth.Height, verticalFieldOfViewDegrees, nearPlaneDistance, farPlaneDistance, pos, vpi);
+    const size_t n = (size_t)(depth.Width > 0 ? depth.Width : 0) * (size_t)(depth.Height > 0 ? depth.Height : 0);
+    if (rgb && (rgb->Width != depth.Width || rgb->Height != depth.Height)) throw std::invalid_argument("SdfKit::DepthToPoints: rgb is not the depth image's size");
+    DepthPoints out;
+    out.Points.resize(n);
+    out.Pixels.resize(n);
+    if (rgb) out.Colors.resize(n);
+    int64_t k = 0;
+    EnsureInit();
+    Check(sdfk_depth_unproject(depth.Values.data(), rgb ? rgb->Values.data() : nullptr, depth.Width, depth.Height, pos, &vpi.M[0][0],
+                               depthMin != depthMin ? nearPlaneDistance : depthMin, depthMax != depthMax ? farPlaneDistance : depthMax,
+                               n ? &out.Points[0].X : nullptr, rgb && n ? &out.Colors[0].X : nullptr, out.Pixels.data(), &k));
+    out.Points.resize((size_t)k);
+    out.Pixels.resize((size_t)k);
+    if (rgb) out.Colors.resize((size_t)k);
+    return out;
+}
+inline DepthPoints DepthToPoints(const FloatData& depth, Vector3 cameraPosition, Vector3 cameraTarget, Vector3 cameraUp, const Vec3Data* rgb = nullptr,
+                                 float depthMin = NAN, float depthMax = NAN, float verticalFieldOfViewDegrees = 60.0f, float nearPlaneDistance = 1.0f,
+                                 float farPlaneDistance = 100.0f)
+{
+    return DepthToPoints(depth, Matrix4x4::CreateLookAt(cameraPosition, cameraTarget, cameraUp), rgb, depthMin, depthMax, verticalFieldOfViewDegrees,
+                         nearPlaneDistance, farPlaneDistance);
 }
 
 }  // namespace SdfKit

@@ -1409,6 +1409,66 @@ int sdfk_trimesh_winding_stats(const sdfk_trimesh* t, int64_t stats[8]);
  * included, 0 when there is no front; [1] tile-sweeps executed; [2] front voxels; [3] voxels whose T exceeds max_distance. */
 int sdfk_volume_redistance(const sdfk_volume* src, sdfk_volume* dst, float iso_value, float max_distance, int64_t stats[4]);
 
+/* ---- Depth images: fusion and unprojection (DepthFusion, DepthToPoints) ----------------------------------------------------
+ * The way from depth frames with poses to a surface (Curless & Levoy 1996): sdfk_volume_integrate_depth averages one frame into
+ * a volume of truncated signed distances, sdfk_depth_unproject gives a frame as points.  A depth image is FloatData's layout
+ * (pixel (i, j) at j * width + i) and holds the distance ALONG THE PIXEL'S RAY from camera_position: what sdfk_raymarch and
+ * sdfk_trimesh_render write.  Both functions are f32 arithmetic on the f32 inputs, every + - * / and sqrt correctly rounded in
+ * the order written here, no contraction: csrc/depth_fusion.h, restated in tests/depth_fusion_model.py, compared bit for bit.
+ *
+ * sdfk_volume_integrate_depth: `values` (D) and `weights` (W) are two volumes of one shape, box and slab (a slab uses its global
+ * z); the weights volume needs no colours.  view_projection is the FORWARD matrix ViewTransform x projection, row-major, row
+ * vectors (Vector3.Transform): the matrix whose inverse the renders take.  Per voxel, at the f32 cell centre p that sdfk_sample
+ * uses (see sdfk_trimesh_to_volume):
+ * 1. Project.  c_q = ((p0 m[q] + p1 m[4 + q]) + p2 m[8 + q]) + m[12 + q] for q = 0, 1, 3.  Skipped unless c_3 > 0.
+ * 2. Pixel.  u = (c_0 / c_3 + 1) * ((float)(width - 1) * 0.5f), v = (1 - c_1 / c_3) * ((float)(height - 1) * 0.5f): the inverse
+ *    of the renders' pixel -> NDC map (pixel 0 at NDC -1).  fu = floorf(u + 0.5f), fv likewise.  Skipped unless 0 <= fu <=
+ *    width - 1 and 0 <= fv <= height - 1, compared in float BEFORE any conversion and before the load: a NaN fails every
+ *    comparison, and no out-of-range index is ever formed.  i = (int)fu, j = (int)fv.
+ * 3. Depth.  d = depth[j * width + i]; r = sqrt((dx dx + dy dy) + dz dz), dx = p0 - cam0 and so on; s = d - r.
+ * 4. Classify.  depth_min <= d <= depth_max (false for a NaN) is a SURFACE OBSERVATION: skipped when s < -truncation, else
+ *    t = s when s <= truncation, else t = truncation.  With SDFK_FUSE_CARVE_BEYOND a pixel with d > depth_max (+inf included)
+ *    says "nothing within range": the voxel is updated with t = truncation when r <= depth_max.  Everything else is skipped.
+ * 5. Update.  When W > 0: D' = (W D + weight t) / (W + weight), W' = min(W + weight, max_weight).  Otherwise (a zero, negative
+ *    or NaN weight: unseen) D' = t and W' = min(weight, max_weight): whatever D held never enters the arithmetic.
+ * 6. Skipped voxels are not written: their bits stay.  Cached sign bits of both volumes are dropped, as for a write through
+ *    sdfk_volume_device_ptrs.  Colours are left alone.
+ * THE UNSEEN CONVENTION.  An unseen voxel keeps the value it had before its first observation, so the fill of `values` decides
+ * what a mesh of the volume shows.  Filled with -truncation and integrated with SDFK_FUSE_CARVE_BEYOND: unseen space is solid,
+ * seen-empty space is free (Curless and Levoy's hole filling) -- a fully scanned object meshes watertight, its unscanned
+ * interior negative.  Filled with +truncation without carving: the classic open surface, with a spurious sheet one truncation
+ * behind every observed surface.  Away from the zero set the values are projective distances (scaled by 1 / cos of the viewing
+ * angle, clamped): sdfk_volume_redistance makes them distances again.
+ * stats (may be NULL; reading them synchronises): [0] voxels updated; [1] of them, surface observations with s <= truncation;
+ * [2] of them, first observations; [3] pixels with depth_min <= d <= depth_max.
+ * Refused (SDFK_ERR_INVALID, nothing written): a NULL handle, image, camera, matrix or prm; values == weights; shapes, boxes or
+ * slabs that differ, or a volume without storage; width or height < 1, or 2^31 pixels or more; a truncation or weight that is
+ * not finite and > 0; max_weight NaN or below weight (+inf allowed); a NaN depth_min or depth_max, or depth_min > depth_max;
+ * unknown flag bits.  The host form is synchronous; the _device form (depth_dev a device buffer) queues on the library stream.
+ *
+ * sdfk_depth_unproject: for every pixel with depth_min <= d <= depth_max, in ascending pixel order: r = the camera ray of the
+ * renders (csrc/trimesh_ray.h, camera_ray: view_projection_inverse is the matrix they take), point = cam + r * d, a multiply
+ * then an add per component -- for a frame sdfk_trimesh_render made, that render's hit points bit for bit.  colors3 gathers the
+ * pixel's rgb (it must be NULL when rgb is NULL), pixel gets j * width + i.  The outputs are compacted (the scan of
+ * csrc/device_scan.h) and sized for width * height entries by the caller, who must not rely on what lies beyond *n_valid; any
+ * output but n_valid may be NULL.  An image of width or height 1 has non-finite camera rays (the renders leave such frames
+ * without a valid depth): a valid depth on such an image yields non-finite points, as camera_ray gives them.  Refused: a NULL
+ * depth, camera, matrix or n_valid, colors3 without rgb, and the image and range refusals above.  Reading n_valid synchronises. */
+typedef struct sdfk_fusion_params { float truncation, depth_min, depth_max, weight, max_weight; int32_t flags; } sdfk_fusion_params;
+#define SDFK_FUSE_CARVE_BEYOND 1
+int sdfk_volume_integrate_depth(sdfk_volume* values, sdfk_volume* weights, const float* depth, int32_t width, int32_t height,
+                                const float camera_position[3], const float view_projection[16], const sdfk_fusion_params* prm,
+                                int64_t stats[4]);
+int sdfk_volume_integrate_depth_device(sdfk_volume* values, sdfk_volume* weights, const void* depth_dev, int32_t width, int32_t height,
+                                       const float camera_position[3], const float view_projection[16], const sdfk_fusion_params* prm,
+                                       int64_t stats[4]);
+int sdfk_depth_unproject(const float* depth, const float* rgb, int32_t width, int32_t height, const float camera_position[3],
+                         const float view_projection_inverse[16], float depth_min, float depth_max, float* points3, float* colors3,
+                         int32_t* pixel, int64_t* n_valid);
+int sdfk_depth_unproject_device(const void* depth_dev, const void* rgb_dev, int32_t width, int32_t height, const float camera_position[3],
+                                const float view_projection_inverse[16], float depth_min, float depth_max, void* points3_dev,
+                                void* colors3_dev, void* pixel_dev, int64_t* n_valid);
+
 /* ---- pinned host arena -------------------------------------------------------
  * Host memory the GPU can write directly (hipHostMalloc), recycled through size-class free lists:
  * destinations inside such a block make sdfk_mesh_copy / sdfk_volume_download / sdfk_raymarch plain

@@ -10,6 +10,7 @@ dense mesh smaller (Mesh.Simplify).
 `api` mirrors the reference's public types over that ABI.  There is no CPU path.
 """
 from .api import (DefaultBatchSize, MarchingCubes, Mesh, Sdf, SdfExprs, SdfFunc, SdfFuncs, Sdfs, Voxels)
+from .fusion import DepthFusion, DepthToPoints
 from .expr import MathF, Mod, VMax, Vec3, Vec4
 from .meshsdf import MeshAdjacency, MeshComponents, MeshSamples, MeshSdf, MeshSelection, MeshSimplify, MeshTopology, MeshWeld
 from .points import IterativeClosestPoint, KdTree
@@ -18,4 +19,4 @@ from .raymarch import FloatData, Matrix4x4, RayMarcher, Vec3Data
 __all__ = ["DefaultBatchSize", "MarchingCubes", "Mesh", "Sdf", "SdfExprs", "SdfFunc", "SdfFuncs", "Sdfs",
            "Voxels", "MathF", "Mod", "VMax", "Vec3", "Vec4", "FloatData", "Matrix4x4", "RayMarcher", "Vec3Data",
            "KdTree", "IterativeClosestPoint", "MeshSdf", "MeshSamples", "MeshComponents", "MeshTopology",
-           "MeshSelection", "MeshAdjacency", "MeshWeld", "MeshSimplify"]
+           "MeshSelection", "MeshAdjacency", "MeshWeld", "MeshSimplify", "DepthFusion", "DepthToPoints"]

@@ -184,6 +184,10 @@ SIGNATURES = {
     "sdfk_trimesh_winding_stats": (C.c_int, [_vp, C.POINTER(_i64)]),
     "sdfk_trimesh_free": (None, [_vp]),
     "sdfk_volume_redistance": (C.c_int, [_vp, _vp, C.c_float, C.c_float, C.POINTER(_i64)]),
+    "sdfk_volume_integrate_depth": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _fp, _fp, _vp, C.POINTER(_i64)]),
+    "sdfk_volume_integrate_depth_device": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _fp, _fp, _vp, C.POINTER(_i64)]),
+    "sdfk_depth_unproject": (C.c_int, [_vp, _vp, _i32, _i32, _fp, _fp, C.c_float, C.c_float, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "sdfk_depth_unproject_device": (C.c_int, [_vp, _vp, _i32, _i32, _fp, _fp, C.c_float, C.c_float, _vp, _vp, _vp, C.POINTER(_i64)]),
     "sdfk_icp_register": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),
     "sdfk_icp_register_device": (C.c_int, [_vp, _vp, _vp, _i64, _fp, C.POINTER(_i32)]),
     "sdfk_icp_register_plane": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _fp, C.POINTER(_i32), C.POINTER(_i64)]),
@@ -191,6 +195,12 @@ SIGNATURES = {
     "sdfk_profile_count": (C.c_int, []),
     "sdfk_profile_get": (C.c_int, [_i32, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(_i64)]),
 }
+
+
+class FusionParams(C.Structure):
+    """struct sdfk_fusion_params"""
+    _fields_ = [("truncation", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float), ("weight", C.c_float),
+                ("max_weight", C.c_float), ("flags", C.c_int32)]
 
 
 class IcpParams(C.Structure):

@@ -991,3 +991,7 @@ def _fmt_single(x):
     else:
         out = digits[0] + ("." + digits[1:] if len(digits) > 1 else "") + "E" + ("+" if e >= 0 else "-") + "%02d" % abs(e)
     return ("-" if neg else "") + out
+
+
+# depth frames into volumes and point clouds (next to Voxels for callers; the module needs Voxels, so it comes last)
+from .fusion import DepthFusion, DepthToPoints  # noqa: E402,F401

@@ -1,6 +1,6 @@
 """Builds libsdfkit_hip.so (the C-ABI HIP library) in-tree with hipcc for gfx950.
 
-The library is twenty-one translation units (csrc/lib_*.hip + csrc/mc_kernels.hip) compiled in parallel -- objects under csrc/_obj/, rebuilt
+The library is twenty-two translation units (csrc/lib_*.hip + csrc/mc_kernels.hip) compiled in parallel -- objects under csrc/_obj/, rebuilt
 only when a file they include is newer -- and linked with the version script that exports exactly include/sdfkit_hip.h's symbols."""
 import os
 import re
@@ -16,12 +16,13 @@ LIB = os.path.join(HERE, "libsdfkit_hip.so")
 # mesh accessors; the sharded step; the marching-cubes kernels; KdTree / IterativeClosestPoint; triangle-mesh distance volumes;
 # redistancing of volumes; KdTree's k-nearest and radius queries; point-cloud normals and volumes; the orientation of normals;
 # the point-cloud filters; the connectivity of triangle meshes; their adjacency, smoothing and vertex normals; their welding;
-# the clustering of point clouds; the simplification of triangle meshes; rays against triangle meshes; their generalized winding number
+# the clustering of point clouds; the simplification of triangle meshes; rays against triangle meshes; their generalized winding number;
+# depth images fused into volumes and unprojected to points
 SOURCES = ["lib_context.hip", "lib_jit.hip", "lib_volume.hip", "lib_march.hip", "lib_mesh.hip", "lib_dist.hip", "mc_kernels.hip", "lib_points.hip",
            "lib_trimesh.hip", "lib_redistance.hip", "lib_points_knn.hip", "lib_pointcloud.hip", "lib_orient.hip", "lib_points_filter.hip", "lib_trimesh_topology.hip",
            "lib_trimesh_smooth.hip", "lib_trimesh_weld.hip", "lib_points_cluster.hip", "lib_trimesh_simplify.hip", "lib_trimesh_ray.hip",
-           "lib_trimesh_winding.hip"]
-HEADERS = ["lib_internal.h", "device_stage.h", "points_grid.h", "points_set.h", "points_knn.h", "points_walk.h", "points_normals.h", "points_orient.h", "points_filter.h", "points_color.h", "points_cluster.h", "device_forest.h", "icp_solve.h", "trimesh_sdf.h", "trimesh_sample.h", "trimesh_handle.h", "trimesh_topology.h", "trimesh_adjacency.h", "trimesh_weld.h", "trimesh_simplify.h", "trimesh_ray.h", "trimesh_winding.h", "device_sort.h", "redistance.h", "device_scan.h", "device_reduce.h", "mc_kernels.h", "mc_device.h", "mc_decide.h", "mc_signbytes.h", "mc_params.h", "mc_luts.h", "sample_codegen.h", "vol_pyramid.h", "mathops.h", "dist_rccl.h", "node_local.h",
+           "lib_trimesh_winding.hip", "lib_fusion.hip"]
+HEADERS = ["lib_internal.h", "device_stage.h", "points_grid.h", "points_set.h", "points_knn.h", "points_walk.h", "points_normals.h", "points_orient.h", "points_filter.h", "points_color.h", "points_cluster.h", "device_forest.h", "icp_solve.h", "trimesh_sdf.h", "trimesh_sample.h", "trimesh_handle.h", "trimesh_topology.h", "trimesh_adjacency.h", "trimesh_weld.h", "trimesh_simplify.h", "trimesh_ray.h", "trimesh_winding.h", "depth_fusion.h", "device_sort.h", "redistance.h", "device_scan.h", "device_reduce.h", "mc_kernels.h", "mc_device.h", "mc_decide.h", "mc_signbytes.h", "mc_params.h", "mc_luts.h", "sample_codegen.h", "vol_pyramid.h", "mathops.h", "dist_rccl.h", "node_local.h",
            "slab_protocol.h", os.path.join("..", "..", "include", "sdfkit_hip.h")]
 DEPS = ["exports.map"] + SOURCES + HEADERS
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fno-fast-math", "-fvisibility=hidden", "-Wall",

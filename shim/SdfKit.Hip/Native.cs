@@ -16,6 +16,14 @@ namespace SdfKit.Hip
         public float Imm;
     }
 
+    /// <summary>struct sdfk_fusion_params (include/sdfkit_hip.h)</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SdfkFusionParams
+    {
+        public float Truncation, DepthMin, DepthMax, Weight, MaxWeight;
+        public int Flags;   // SDFK_FUSE_CARVE_BEYOND = 1
+    }
+
     /// <summary>struct sdfk_icp_params (include/sdfkit_hip.h)</summary>
     [StructLayout(LayoutKind.Sequential)]
     public struct SdfkIcpParams
@@ -216,6 +224,17 @@ namespace SdfKit.Hip
         [DllImport(Lib)] public static extern int sdfk_trimesh_winding_stats(IntPtr trimesh, long* stats8);
         [DllImport(Lib)] public static extern void sdfk_trimesh_free(IntPtr trimesh);
         [DllImport(Lib)] public static extern int sdfk_volume_redistance(IntPtr src, IntPtr dst, float isoValue, float maxDistance, long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_volume_integrate_depth(IntPtr values, IntPtr weights, float* depth, int width, int height,
+                                                                              float* cameraPosition, float* viewProjection, SdfkFusionParams* prm, long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_volume_integrate_depth_device(IntPtr values, IntPtr weights, IntPtr depthDev, int width, int height,
+                                                                                     float* cameraPosition, float* viewProjection, SdfkFusionParams* prm,
+                                                                                     long* stats4);
+        [DllImport(Lib)] public static extern int sdfk_depth_unproject(float* depth, float* rgb, int width, int height, float* cameraPosition,
+                                                                       float* viewProjectionInverse, float depthMin, float depthMax, float* points3,
+                                                                       float* colors3, int* pixel, out long nValid);
+        [DllImport(Lib)] public static extern int sdfk_depth_unproject_device(IntPtr depthDev, IntPtr rgbDev, int width, int height, float* cameraPosition,
+                                                                              float* viewProjectionInverse, float depthMin, float depthMax, IntPtr points3Dev,
+                                                                              IntPtr colors3Dev, IntPtr pixelDev, out long nValid);
         // several GPUs from ONE process (the managed host is one process): include/sdfkit_hip.h, "one process, several GPUs"
         [DllImport(Lib)] public static extern int sdfk_node_open(int* devices, int nDevices, out IntPtr node);
         [DllImport(Lib)] public static extern int sdfk_node_info(IntPtr node, out int world, out int backend);

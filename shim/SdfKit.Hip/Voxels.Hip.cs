@@ -93,6 +93,9 @@ namespace SdfKit
             deviceIsNewer = true; hostMayBeNewer = false;
         }
 
+        /// <summary>The device twin after a call that wrote into it (DepthFusion.Integrate): the managed arrays are stale.</summary>
+        internal void DeviceWritten() { deviceIsNewer = true; hostMayBeNewer = false; }
+
         /// <summary>The device twin with the current truth in it (uploads the managed arrays when they may be newer).</summary>
         internal unsafe IntPtr SyncToDevice()
         {
