@@ -22,7 +22,7 @@ SOURCES = ["lib_context.hip", "lib_jit.hip", "lib_volume.hip", "lib_march.hip", 
            "lib_trimesh.hip", "lib_redistance.hip", "lib_points_knn.hip", "lib_pointcloud.hip", "lib_orient.hip", "lib_points_filter.hip", "lib_trimesh_topology.hip",
            "lib_trimesh_smooth.hip", "lib_trimesh_weld.hip", "lib_points_cluster.hip", "lib_trimesh_simplify.hip", "lib_trimesh_ray.hip",
            "lib_trimesh_winding.hip", "lib_fusion.hip"]
-HEADERS = ["lib_internal.h", "device_stage.h", "points_grid.h", "points_set.h", "points_knn.h", "points_walk.h", "points_normals.h", "points_orient.h", "points_filter.h", "points_color.h", "points_cluster.h", "device_forest.h", "icp_solve.h", "trimesh_sdf.h", "trimesh_sample.h", "trimesh_handle.h", "trimesh_topology.h", "trimesh_adjacency.h", "trimesh_weld.h", "trimesh_simplify.h", "trimesh_ray.h", "trimesh_winding.h", "depth_fusion.h", "device_sort.h", "redistance.h", "device_scan.h", "device_reduce.h", "mc_kernels.h", "mc_device.h", "mc_decide.h", "mc_signbytes.h", "mc_params.h", "mc_luts.h", "sample_codegen.h", "vol_pyramid.h", "mathops.h", "dist_rccl.h", "node_local.h",
+HEADERS = ["lib_internal.h", "device_stage.h", "device_wave.h", "points_grid.h", "points_set.h", "points_knn.h", "points_walk.h", "points_normals.h", "points_orient.h", "points_filter.h", "points_color.h", "points_cluster.h", "device_forest.h", "icp_solve.h", "trimesh_sdf.h", "trimesh_sample.h", "trimesh_handle.h", "trimesh_topology.h", "trimesh_adjacency.h", "trimesh_weld.h", "trimesh_simplify.h", "trimesh_ray.h", "trimesh_winding.h", "depth_fusion.h", "device_sort.h", "redistance.h", "device_scan.h", "device_reduce.h", "mc_kernels.h", "mc_device.h", "mc_decide.h", "mc_signbytes.h", "mc_params.h", "mc_luts.h", "sample_codegen.h", "vol_pyramid.h", "mathops.h", "dist_rccl.h", "node_local.h",
            "slab_protocol.h", os.path.join("..", "..", "include", "sdfkit_hip.h")]
 DEPS = ["exports.map"] + SOURCES + HEADERS
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fno-fast-math", "-fvisibility=hidden", "-Wall",

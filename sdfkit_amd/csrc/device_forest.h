@@ -11,6 +11,7 @@
 #pragma once
 #include "lib_internal.h"
 #include "device_stage.h"
+#include "device_wave.h"
 
 #include <algorithm>
 
@@ -27,13 +28,6 @@ struct ForestCtl {
     unsigned long long rounds, shortcuts;     // hook rounds run, shortcut launches that worked
 };
 
-// every lane of the wave calls this (the shuffle); lane 0 holds the sum
-__device__ __forceinline__ unsigned long long forest_wave_sum(unsigned long long v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
-
 // A hook kernel, launch number q: first this, by every thread ...
 __device__ __forceinline__ void forest_hook_begin(ForestCtl* ctl, int q)
 {
@@ -45,7 +39,7 @@ __device__ __forceinline__ void forest_hook_begin(ForestCtl* ctl, int q)
 // ... and at its end, by every lane of every wave, with the number of parents the lane lowered
 __device__ __forceinline__ void forest_hook_end(ForestCtl* ctl, int q, unsigned changed)
 {
-    const unsigned long long n = forest_wave_sum(changed);
+    const unsigned long long n = wave_sum(changed);
     if ((threadIdx.x & 63) == 0 && n) {
         atomicAdd(&ctl->count[q % 3], (unsigned)n);
         atomicAdd(&ctl->hook_changes, n);
@@ -70,7 +64,7 @@ __global__ __launch_bounds__(kForestBlock) void k_forest_shortcut(int32_t* paren
             changed = 1;
         }
     }
-    const unsigned long long sum = forest_wave_sum(changed);
+    const unsigned long long sum = wave_sum(changed);
     if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&ctl->count[q % 3], (unsigned)sum);
 }
 

@@ -1,7 +1,8 @@
 // device_stage.h -- what owns device memory for the length of one call on g.stream, for the point-cloud, the triangle-mesh and
 // the volume units alike: Staged, the scratch of a work function and the device copies of a host form's arrays, with the one rule of
 // when queueing stops, when the stream is waited for and which error is reported; read_back, a device value the host needs on the
-// way; copy_out, the front of a compacted device array into the caller's.  hipcc only.
+// way; copy_out, the front of a compacted device array into the caller's; ProfCount, the 64-bit device words that a launch's lanes
+// count into.  hipcc only.
 #pragma once
 #include "lib_internal.h"
 
@@ -115,5 +116,25 @@ public:
         if (r) return r;
         if (failed) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : es));
         return SDFK_OK;
+    }
+};
+
+// The N 64-bit device words one launch counts into (with wave_add of device_wave.h), as steps of the call's Staged: begin() before
+// the launch -- when `on`, scratch and its zeroing; otherwise dev stays null and the kernel counts nothing -- and end() after it,
+// which reads the words back (synchronises).  Putting them on a handle is the caller's business.
+template <int N>
+struct ProfCount {
+    unsigned long long* dev = nullptr;
+    void begin(Staged& st, bool on = g.prof_on)
+    {
+        if (!on) return;
+        dev = st.scratch<unsigned long long>(N);
+        st.run([&] { return hipMemsetAsync(dev, 0, N * sizeof(unsigned long long), g.stream); });
+    }
+    bool end(Staged& st, unsigned long long (&host)[N])   // true: host[] holds the counts
+    {
+        if (!dev) return false;
+        st.read(host, dev, sizeof host);
+        return st.ok();
     }
 };

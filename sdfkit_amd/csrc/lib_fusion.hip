@@ -13,6 +13,7 @@
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "device_stage.h"
+#include "device_wave.h"
 #include "depth_fusion.h"
 
 namespace {
@@ -41,9 +42,9 @@ __device__ __forceinline__ void set_lane(uint4& q, int e, float v)
 }
 
 // the wave's sum of `n` into the block's partial sums of count `slot`
-__device__ __forceinline__ void wave_count(int slot, unsigned n, unsigned* s_part)
+__device__ __forceinline__ void block_part(int slot, unsigned n, unsigned* s_part)
 {
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
+    n = (unsigned)wave_sum(n);   // (a block's count fits 32 bits: the low word of the sum is all that is kept)
     if ((threadIdx.x & 63) == 0) s_part[slot * 4 + (threadIdx.x >> 6)] = n;
 }
 
@@ -92,10 +93,10 @@ __global__ __launch_bounds__(kBlock) void k_fuse_depth(FuseArgs A)
     if (!A.stats) return;   // (uniform)
     const int64_t lanes = (int64_t)gridDim.x * kBlock;
     for (int64_t k = gq; k < A.npix; k += lanes) n_pix += depth_valid(A.depth[k], A.P.depth_min, A.P.depth_max);
-    wave_count(0, n_upd, s_part);
-    wave_count(1, n_surf, s_part);
-    wave_count(2, n_first, s_part);
-    wave_count(3, n_pix, s_part);
+    block_part(0, n_upd, s_part);
+    block_part(1, n_surf, s_part);
+    block_part(2, n_first, s_part);
+    block_part(3, n_pix, s_part);
     __syncthreads();
     if (threadIdx.x < 4) {
         const unsigned* s = s_part + 4 * threadIdx.x;
@@ -187,15 +188,14 @@ int integrate_launch(sdfk_volume* values, sdfk_volume* weights, const float* dep
     A.depth = depth_dev;
     Staged st;
     unsigned long long host[4] = {0, 0, 0, 0};
-    if (stats) {
-        A.stats = st.scratch<unsigned long long>(4);
-        st.run([&] { return hipMemsetAsync(A.stats, 0, sizeof host, g.stream); });
-    }
+    ProfCount<4> pc;
+    pc.begin(st, stats != nullptr);
+    A.stats = pc.dev;
     st.run([&] {
         ProfScope ps("k_fuse_depth");
         hipLaunchKernelGGL(k_fuse_depth, dim3((unsigned)((A.nquads + kBlock - 1) / kBlock)), dim3(kBlock), 0, g.stream, A);
     });
-    if (stats) st.read(host, A.stats, sizeof host);
+    pc.end(st, host);
     if (int r = st.finish(who, false)) return r;
     if (stats)
         for (int k = 0; k < 4; k++) stats[k] = (int64_t)host[k];

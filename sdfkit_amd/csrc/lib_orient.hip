@@ -24,6 +24,7 @@
 // read tells it whether the seed's growth ended and whether unoriented valid points remain for another seed.
 // Rounds that left early are not counted: stats[0] counts seeds and live rounds only, whatever the batch length.
 #include "lib_internal.h"
+#include "device_wave.h"
 #include "points_knn.h"
 #include "points_orient.h"
 #include "points_set.h"
@@ -45,8 +46,6 @@ struct Ctl {
     int level[3];                            // ring by launch number: the level launch q ran at (kLevels: growth over)
     unsigned count[3];                       // ring: the points launch q oriented
 };
-
-__device__ __forceinline__ unsigned wave_count(bool flag) { return (unsigned)__popcll(__ballot(flag)); }
 
 template <int CAP>
 __global__ __launch_bounds__(block_of<CAP>()) void k_or_rows(const float4* __restrict__ sorted, const uint32_t* __restrict__ starts, Grid G,

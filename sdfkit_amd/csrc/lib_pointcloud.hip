@@ -78,7 +78,7 @@ __global__ __launch_bounds__(block_of<CAP>()) void k_pc_normals(const float4* __
         if (A.normals) { A.normals[3 * t] = nrm[0]; A.normals[3 * t + 1] = nrm[1]; A.normals[3 * t + 2] = nrm[2]; }
         if (A.variation) A.variation[t] = var;
     }
-    add_candidates(A.candidates, ncand);
+    wave_add(A.candidates, ncand);
 }
 
 // ---- the volume ----------------------------------------------------------------------------------------------------------------
@@ -150,10 +150,10 @@ __global__ __launch_bounds__(block_of<CAP>()) void k_pc_volume(const float4* __r
         A.sgn[gidx] = s;
     }
     if (A.known) {
-        const unsigned long long c = (unsigned long long)__popcll(__ballot(known));
+        const unsigned long long c = wave_count(known);
         if ((threadIdx.x & 63) == 0 && c) atomicAdd(A.known, c);
     }
-    add_candidates(A.candidates, ncand);
+    wave_add(A.candidates, ncand);
 }
 
 // One lane per line along AXIS (2: z, 1: y, 0: x).  LAST (the pass along x): a line without a sign means a volume without one,
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(block_of<CAP>()) void k_pc_colors(const float4* __r
         }
         if (A.found) A.found[t] = nb.m;
     }
-    add_candidates(A.candidates, ncand);
+    wave_add(A.candidates, ncand);
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------------

@@ -143,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void k_pts_search(const float4* __restrict_
     unsigned long long ncand = 0;
     if (q.finite) ncand = sdfk_walk::shell_walk(sorted, starts, G, q.x, q.y, q.z, v);
     const float dist = v.bi < 0 ? FLT_MAX : (float)__builtin_sqrt((double)v.best);   // (correctly rounded sqrtf)
-    sdfk_walk::add_candidates(O.candidates, ncand);   // (every lane stays for the shuffle)
+    wave_add(O.candidates, ncand);   // (every lane stays for the shuffle)
     if (t >= nq) return;
     if (O.index) O.index[t] = v.bi;
     if (O.distance) O.distance[t] = dist;

@@ -69,9 +69,9 @@ __global__ __launch_bounds__(kBlock) void k_cl_count(const float4* __restrict__ 
         core[t] = c ? 1 : 0;
         parent[t] = (int32_t)t;
     }
-    const u64 cores = forest_wave_sum(c ? 1ull : 0ull);
+    const u64 cores = wave_sum(c ? 1ull : 0ull);
     if ((threadIdx.x & 63) == 0 && cores) atomicAdd(&totals[kTotCore], cores);
-    add_candidates(candidates, ncand);
+    wave_add(candidates, ncand);
 }
 
 // ---- hook -------------------------------------------------------------------------------------------------------------------
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(kBlock) void k_cl_hook(const float4* __restrict__ s
         changed = v.changed;
     }
     forest_hook_end(ctl, q, changed);
-    add_candidates(candidates, ncand);
+    wave_add(candidates, ncand);
 }
 
 // ---- labels -----------------------------------------------------------------------------------------------------------------
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(kBlock) void k_cl_border(const float4* __restrict__
         const int32_t from = border_source(v.best);
         if (from >= 0 && from < n) label[t] = label[from];
     }
-    add_candidates(candidates, ncand);
+    wave_add(candidates, ncand);
 }
 
 // ---- sizes ------------------------------------------------------------------------------------------------------------------
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(kBlock) void k_cl_sizes(const int32_t* __restrict__
     int32_t c = i < n ? label[i] : -1;
     const bool noise = i < n && c < 0, border = i < n && c >= 0 && !core[i];
     if (c >= C) c = -1;   // (never: a label is below C)
-    const u64 nb = forest_wave_sum(border ? 1ull : 0ull), nn = forest_wave_sum(noise ? 1ull : 0ull);
+    const u64 nb = wave_sum(border ? 1ull : 0ull), nn = wave_sum(noise ? 1ull : 0ull);
     if ((threadIdx.x & 63) == 0) {
         if (nb) atomicAdd(&totals[kTotBorder], nb);
         if (nn) atomicAdd(&totals[kTotNoise], nn);
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(kBlock) void k_cl_sizes(const int32_t* __restrict__
     const bool uniform = wave_uniform(c, &c0);
     if (c0 < 0) return;
     if (uniform) {
-        const u64 members = forest_wave_sum(c >= 0 ? 1ull : 0ull);
+        const u64 members = wave_sum(c >= 0 ? 1ull : 0ull);
         if ((threadIdx.x & 63) == 0) atomicAdd(&sizes[c0], (int32_t)members);
     } else if (c >= 0)
         atomicAdd(&sizes[c], 1);

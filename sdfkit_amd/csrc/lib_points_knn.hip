@@ -51,7 +51,7 @@ __global__ __launch_bounds__(block_of<CAP>()) void k_pts_knn(const float4* __res
         });
         if (O.found) O.found[t] = nb.m;
     }
-    add_candidates(O.candidates, ncand);
+    wave_add(O.candidates, ncand);
 }
 
 // ---- within a radius ---------------------------------------------------------------------------------------------------------
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(kBlock) void k_pts_radius_count(const float4* __res
     unsigned long long ncand = 0;
     if (q.finite) ncand = shell_walk(sorted, starts, G, q.x, q.y, q.z, v);
     if (t < nq) counts[t] = v.n;
-    add_candidates(candidates, ncand);
+    wave_add(candidates, ncand);
 }
 
 // a query's segment as heap storage.  WITH_D2: the d2 bits live in the distance array until the end.
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(kBlock) void k_pts_radius_fill(const float4* __rest
         if constexpr (WITH_D2)
             for (int i = 0; i < m; i++) v.seg.d2bits[i] = f32_bits(sqrt_rn(bits_f32(v.seg.d2bits[i])));   // d2 -> distance, in place
     }
-    add_candidates(candidates, ncand);
+    wave_add(candidates, ncand);
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 // scratch of a Staged (device_stage.h), which also makes the reads of the control block.
 #include "lib_internal.h"
 #include "device_stage.h"
+#include "device_wave.h"
 #include "redistance.h"
 
 namespace {
@@ -95,9 +96,7 @@ __global__ __launch_bounds__(kBlock) void k_rd_front(const float* __restrict__ v
     }
     const int total = __syncthreads_count(nfront > 0) ? 1 : 0;
     // (the count itself: one atomic per wave)
-    unsigned long long c = (unsigned long long)nfront;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&ctl->front, c);
+    wave_add(&ctl->front, (unsigned long long)nfront);
     if (threadIdx.x == 0) {
         flag0[tile] = (uint32_t)total;
         if (total) atomicMax(&ctl->last, 0);

@@ -21,6 +21,7 @@
 // Host side: every work function holds its scratch, and every host form its device copies, in a Staged (device_stage.h).
 #include "lib_internal.h"
 #include "device_scan.h"
+#include "device_wave.h"
 #include "points_grid.h"
 #include "trimesh_handle.h"
 #include "trimesh_sdf.h"
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void k_tm_bin_count(const TriPack* __restri
                 for (int x = c0[0]; x <= c1[0]; x++) atomicAdd(&counts[((uint32_t)z * (uint32_t)G.dim[1] + (uint32_t)y) * (uint32_t)G.dim[0] + (uint32_t)x], 1u);
         n = (unsigned long long)(c1[0] - c0[0] + 1) * (unsigned long long)(c1[1] - c0[1] + 1) * (unsigned long long)(c1[2] - c0[2] + 1);
     }
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
+    n = wave_sum(n);   // (total is never null: no test of it, unlike wave_add)
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(total, n);
 }
 
@@ -156,6 +157,7 @@ struct Best {
     unsigned long long ncand;
 };
 
+// (the corners of a TriPack the lane holds; by index from the array: PackTris, trimesh_handle.h)
 __device__ __forceinline__ void load_tri(const TriPack& P, float a[3], float b[3], float c[3])
 {
     a[0] = P.p0.x; a[1] = P.p0.y; a[2] = P.p0.z;
@@ -293,11 +295,7 @@ __global__ __launch_bounds__(kBlock) void k_tm_closest(SearchGrid S, const float
     if (active)
         for (int a = 0; a < 3; a++) q[a] = queries[3 * t + a];
     if (isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2])) tm_search(S, q, INFINITY, B);
-    if (O.candidates) {
-        unsigned long long n = B.ncand;
-        for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
-        if ((threadIdx.x & 63) == 0 && n) atomicAdd(O.candidates, n);
-    }
+    wave_add(O.candidates, B.ncand);
     if (!active) return;
     const bool found = B.bi >= 0;
     if (O.triangle) O.triangle[t] = B.bi;
@@ -389,11 +387,7 @@ __global__ __launch_bounds__(kBlock) void k_tm_volume(SearchGrid S, VolArgs A)
     B.ncand = 0;
     B.bi = -1;
     if (active) tm_search(S, q, A.stop2, B);
-    if (A.candidates) {
-        unsigned long long s = B.ncand;
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-        if ((threadIdx.x & 63) == 0 && s) atomicAdd(A.candidates, s);
-    }
+    wave_add(A.candidates, B.ncand);
     if (!active) return;
     unsigned cnt = 0;
     if (A.sign) cnt = A.sign[g0] ? 1u : 0u;   // (the caller's sign: lib_trimesh_winding.hip)
@@ -462,7 +456,7 @@ __global__ __launch_bounds__(kBlock) void k_tm_sample_weights(const double* __re
         w[t] = v;
         n = v ? 1ull : 0ull;
     }
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
+    n = wave_sum(n);   // (nonzero is never null)
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(nonzero, n);
 }
 
@@ -672,20 +666,14 @@ int trimesh_make(const void* v, int64_t nv, const void* tris, int64_t ni, const 
 int closest_launch(const sdfk_trimesh* t, const float* q, int64_t n, QueryOut O)
 {
     Staged st;
-    if (g.prof_on) {
-        O.candidates = st.scratch<unsigned long long>(1);
-        st.run([&] { return hipMemsetAsync(O.candidates, 0, sizeof(unsigned long long), g.stream); });
-    }
+    ProfCount<1> pc;
+    pc.begin(st);
+    O.candidates = pc.dev;
     st.run([&] {
         ProfScope ps("k_tm_closest");
         hipLaunchKernelGGL(k_tm_closest, dim3(grid1(n)), dim3(kBlock), 0, g.stream, search_grid(t), q, n, O);
     });
-    if (g.prof_on) {
-        unsigned long long c = 0;
-        st.read(&c, O.candidates, sizeof c);
-        const_cast<sdfk_trimesh*>(t)->last_candidates = (int64_t)c;
-        const_cast<sdfk_trimesh*>(t)->last_queries = n;
-    }
+    trimesh_keep_count(st, pc, t, n);
     return st.finish("sdfk_trimesh_closest", false);
 }
 
@@ -702,7 +690,6 @@ int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band, const uint8_t* 
     Staged st;
     uint32_t* col = nullptr;
     double* zrec = nullptr;
-    unsigned long long* cand = nullptr;
     unsigned long long n_items = 0;
     uint32_t n_cross = 0;
     auto grid_items = [](unsigned long long n) { return (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>((n + kBlock - 1) / kBlock, 1u << 20)); };
@@ -729,26 +716,19 @@ int to_volume(const sdfk_trimesh* t, sdfk_volume* v, float band, const uint8_t* 
                 hipLaunchKernelGGL(k_tm_cross<1>, dim3(grid_items(n_items)), dim3(kBlock), 0, g.stream, t->tri, nt, Q, box, items, n_items, cursor, zrec);
             });
     }
-    if (g.prof_on) {
-        cand = st.scratch<unsigned long long>(1);
-        st.run([&] { return hipMemsetAsync(cand, 0, sizeof(unsigned long long), g.stream); });
-    }
+    ProfCount<1> pc;
+    pc.begin(st);
     // every d2 whose f32 distance (float)sqrt(d2) is <= band is below next^2 (next: the f32 after band), so the search may stop
     // there: a voxel it leaves unresolved has an f32 distance > band and is clamped, as its exact distance would be
     const double next = (double)nextafterf(band, INFINITY);
     const double stop2 = next * next;
     st.run([&] {
         VolArgs A{v->values, v->colors, t->colors, t->idx, v->nx, v->ny, v->nz, v->pitch(), v->z0, m[0], m[1], m[2], d[0], d[1], d[2],
-                  band, stop2, col, zrec, sign, cand};
+                  band, stop2, col, zrec, sign, pc.dev};
         ProfScope ps("k_tm_volume");
         hipLaunchKernelGGL(k_tm_volume, dim3(grid1((int64_t)v->nx * v->ny * v->nz)), dim3(kBlock), 0, g.stream, search_grid(t), A);
     });
-    if (cand) {
-        unsigned long long c = 0;
-        st.read(&c, cand, sizeof c);
-        const_cast<sdfk_trimesh*>(t)->last_candidates = (int64_t)c;
-        const_cast<sdfk_trimesh*>(t)->last_queries = (int64_t)v->nx * v->ny * v->nz;
-    }
+    trimesh_keep_count(st, pc, t, (int64_t)v->nx * v->ny * v->nz);
     const_cast<sdfk_trimesh*>(t)->last_crossings = n_cross;
     return st.finish(who, false);   // (on success the scratch goes back to the stream-ordered pool under the queued volume pass)
 }

@@ -9,6 +9,7 @@
 // Host side: trimesh_check, a Staged for the host forms' device copies, the library stream; nothing is kept on the handle but the
 // two diagnostic counts of a profiled call.
 #include "lib_internal.h"
+#include "device_wave.h"
 #include "trimesh_handle.h"
 #include "trimesh_ray.h"
 
@@ -18,36 +19,12 @@ using namespace sdfk_trimesh_ray;
 
 constexpr int kBlock = 256;
 
-struct PackTris {
-    const TriPack* tri;
-    __device__ __forceinline__ void box(uint32_t t, float lo[3], float hi[3]) const
-    {
-        const float4 p2 = tri[t].p2, p3 = tri[t].p3;
-        lo[0] = p2.y; lo[1] = p2.z; lo[2] = p2.w;
-        hi[0] = p3.x; hi[1] = p3.y; hi[2] = p3.z;
-    }
-    __device__ __forceinline__ void corners(uint32_t t, float a[3], float b[3], float c[3]) const
-    {
-        const float4 p0 = tri[t].p0, p1 = tri[t].p1;
-        a[0] = p0.x; a[1] = p0.y; a[2] = p0.z;
-        b[0] = p0.w; b[1] = p1.x; b[2] = p1.y;
-        c[0] = p1.z; c[1] = p1.w; c[2] = tri[t].p2.x;
-    }
-};
-
 struct RayGrid {
     const TriPack* tri;
     const uint32_t* list;
     const uint32_t* starts;
     Grid G;
 };
-
-__device__ __forceinline__ void count_tests(unsigned long long* total, unsigned long long n)
-{
-    if (!total) return;
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(total, n);
-}
 
 struct RayOut {
     int32_t* triangle;
@@ -69,7 +46,7 @@ __global__ __launch_bounds__(kBlock) void k_tm_raycast(RayGrid S, const float* _
     const PackTris T{S.tri};
     Caster<PackTris, ANY> C(T, S.list, R);
     walk(S.G, S.starts, R, C);
-    count_tests(O.tests, C.tests);
+    wave_add(O.tests, C.tests);
     if (!active) return;
     if (O.triangle) O.triangle[i] = C.best.tri;
     if (ANY) return;
@@ -107,7 +84,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_tm_render(RayGrid S, RenderArgs A
     const PackTris T{S.tri};
     Caster<PackTris, false> C(T, S.list, R);
     walk(S.G, S.starts, R, C);
-    count_tests(A.tests, C.tests);
+    wave_add(A.tests, C.tests);
     if (!active) return;
     const bool hit = C.best.tri >= 0;
     float dist = INFINITY, w[3] = {NAN, NAN, NAN};
@@ -133,25 +110,6 @@ __global__ __launch_bounds__(kBlock, 4) void k_tm_render(RayGrid S, RenderArgs A
 
 RayGrid ray_grid(const sdfk_trimesh* t) { return RayGrid{t->tri, t->list, t->starts, t->G}; }
 
-// the test counter of a profiled call: made before the launch, read after it
-struct TestCount {
-    unsigned long long* dev = nullptr;
-    void begin(Staged& st)
-    {
-        if (!g.prof_on) return;
-        dev = st.scratch<unsigned long long>(1);
-        st.run([&] { return hipMemsetAsync(dev, 0, sizeof(unsigned long long), g.stream); });
-    }
-    void end(Staged& st, const sdfk_trimesh* t, int64_t rays)
-    {
-        if (!dev) return;
-        unsigned long long c = 0;
-        st.read(&c, dev, sizeof c);
-        const_cast<sdfk_trimesh*>(t)->last_candidates = (int64_t)c;
-        const_cast<sdfk_trimesh*>(t)->last_queries = rays;
-    }
-};
-
 int raycast_check(const sdfk_trimesh* t, const void* origins, const void* directions, int64_t n, float t_min, float t_max, int32_t flags,
                   const void* distance, const void* weights3, const char* who)
 {
@@ -171,9 +129,9 @@ int raycast_launch(const sdfk_trimesh* t, const float* o, const float* d, int64_
                    const char* who)
 {
     Staged st;
-    TestCount tc;
-    tc.begin(st);
-    O.tests = tc.dev;
+    ProfCount<1> pc;
+    pc.begin(st);
+    O.tests = pc.dev;
     st.run([&] {
         ProfScope ps("k_tm_raycast");
         if (flags & SDFK_RAY_ANY_HIT)
@@ -181,7 +139,7 @@ int raycast_launch(const sdfk_trimesh* t, const float* o, const float* d, int64_
         else
             hipLaunchKernelGGL(k_tm_raycast<false>, dim3(grid1(n)), dim3(kBlock), 0, g.stream, ray_grid(t), o, d, n, (double)t_min, (double)t_max, O);
     });
-    tc.end(st, t, n);
+    trimesh_keep_count(st, pc, t, n);
     return st.finish(who, false);
 }
 
@@ -210,14 +168,14 @@ int render_launch(const sdfk_trimesh* t, int32_t width, int32_t height, const fl
     A.depth = depth; A.rgb = rgb; A.triangle = triangle;
     const int64_t n = (int64_t)width * height;
     Staged st;
-    TestCount tc;
-    tc.begin(st);
-    A.tests = tc.dev;
+    ProfCount<1> pc;
+    pc.begin(st);
+    A.tests = pc.dev;
     st.run([&] {
         ProfScope ps("k_tm_render");
         hipLaunchKernelGGL(k_tm_render, dim3(grid1(n)), dim3(kBlock), 0, g.stream, ray_grid(t), A);
     });
-    tc.end(st, t, n);
+    trimesh_keep_count(st, pc, t, n);
     return st.finish(who, false);
 }
 

@@ -27,6 +27,7 @@
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "device_sort.h"
+#include "device_wave.h"
 #include "trimesh_handle.h"
 #include "trimesh_simplify.h"
 
@@ -50,10 +51,11 @@ struct SimplifyOut {
     float* colors;
 };
 
-__device__ __forceinline__ void wave_count(bool flag, unsigned long long* counter)
+// counter += the wave's lanes whose flag is set
+__device__ __forceinline__ void count_flagged(bool flag, unsigned long long* counter)
 {
-    const unsigned long long m = __ballot(flag);
-    if (m && (threadIdx.x & 63) == 0) atomicAdd(counter, (unsigned long long)__popcll(m));
+    const unsigned n = wave_count(flag);
+    if (n && (threadIdx.x & 63) == 0) atomicAdd(counter, (unsigned long long)n);
 }
 
 // ---- groups -----------------------------------------------------------------------------------------------------------------
@@ -90,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void k_ts_tri_keys(const int32_t* __restric
         degenerate = !has_vertex_set(s);
         if (rec) rec[t] = Rec{triple_key_first(s), (uint32_t)t, 0u};
     }
-    wave_count(degenerate, &ctl->degenerate);
+    count_flagged(degenerate, &ctl->degenerate);
 }
 
 __global__ __launch_bounds__(kBlock) void k_ts_tri_rekey(const int32_t* __restrict__ idx, int64_t nt, const int32_t* __restrict__ rep,
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(kBlock) void k_ts_place(int64_t groups, int64_t nv,
             }
         }
     }
-    wave_count(fallback, &ctl->fallbacks);
+    count_flagged(fallback, &ctl->fallbacks);
 }
 
 __global__ __launch_bounds__(kBlock) void k_ts_vertices(const uint32_t* __restrict__ vnew, const int32_t* __restrict__ rep, int64_t nv, SimplifyOut O)

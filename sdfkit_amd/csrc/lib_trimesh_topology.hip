@@ -30,6 +30,7 @@
 #include "lib_internal.h"
 #include "device_scan.h"
 #include "device_sort.h"
+#include "device_wave.h"
 #include "trimesh_handle.h"
 #include "trimesh_topology.h"
 
@@ -49,12 +50,6 @@ struct Ctl {
     u64 hook_changes;      // over all hook rounds
     u64 rounds, shortcuts; // hook rounds run, shortcut launches that worked
 };
-
-__device__ __forceinline__ u64 wave_sum(u64 v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;   // (lane 0 holds the sum)
-}
 
 // ---- labels -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_tt_init(int32_t* __restrict__ parent, uint8_t* __restrict__ referenced, int64_t nv)
@@ -211,8 +206,7 @@ __global__ __launch_bounds__(kBlock) void k_tt_keys(const int32_t* __restrict__ 
             rec[3 * t + k] = skip ? Rec{kSkipKey, (uint32_t)t, 0u} : Rec{edge_key(u, v), (uint32_t)t, edge_forward(u, v) ? 1u : 0u};
         }
     }
-    degenerate = wave_sum(degenerate);
-    if ((threadIdx.x & 63) == 0 && degenerate) atomicAdd(&census[kCensusDegenerate], degenerate);
+    wave_add(&census[kCensusDegenerate], degenerate);
 }
 
 __global__ __launch_bounds__(kBlock) void k_tt_heads(const Rec* __restrict__ s, int64_t n, uint32_t* __restrict__ head, uint32_t* __restrict__ fwd)

@@ -16,6 +16,7 @@
 // with their own live state, and one kernel holding both would carry the registers of both for the whole of its run.
 #include "lib_internal.h"
 #include "device_sort.h"
+#include "device_wave.h"
 #include "trimesh_handle.h"
 #include "trimesh_sdf.h"
 #include "trimesh_winding.h"
@@ -26,17 +27,6 @@ using namespace sdfk_trimesh_wn;
 using sdfk_trimesh_sdf::col_coord;
 
 constexpr int kBlock = 256;
-
-struct PackTris {
-    const TriPack* tri;
-    __device__ __forceinline__ void corners(uint32_t t, float a[3], float b[3], float c[3]) const
-    {
-        const float4 p0 = tri[t].p0, p1 = tri[t].p1;
-        a[0] = p0.x; a[1] = p0.y; a[2] = p0.z;
-        b[0] = p0.w; b[1] = p1.x; b[2] = p1.y;
-        c[0] = p1.z; c[1] = p1.w; c[2] = tri[t].p2.x;
-    }
-};
 
 // ---- build ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_wn_keys(const TriPack* __restrict__ tri, int64_t nt, Lattice A, Rec* __restrict__ rec,
@@ -144,15 +134,12 @@ struct Tree {
     double beta2;
 };
 
-__device__ __forceinline__ void count_terms(unsigned long long* total, const Counts& K)
+// (terms: the two words of a profiled call, or null)
+__device__ __forceinline__ void count_terms(unsigned long long* terms, const Counts& K)
 {
-    if (!total) return;
-    unsigned long long a = K.clusters, b = K.triangles;
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o); b += __shfl_down(b, o); }
-    if ((threadIdx.x & 63) == 0) {
-        if (a) atomicAdd(&total[0], a);
-        if (b) atomicAdd(&total[1], b);
-    }
+    if (!terms) return;
+    wave_add(&terms[0], K.clusters);
+    wave_add(&terms[1], K.triangles);
 }
 
 __global__ __launch_bounds__(kBlock) void k_wn_query(Tree S, const float* __restrict__ queries, int64_t n, float* __restrict__ winding,
@@ -248,25 +235,15 @@ int winding_build(sdfk_trimesh* t, const char* who)
 
 Tree tree_of(const sdfk_trimesh* t, float beta) { return Tree{(const Node*)t->wn_nodes, t->wn_order, t->tri, t->wn_levels, (double)beta * (double)beta}; }
 
-// the two term counters of a profiled call: made before the launch, read after it
-struct TermCount {
-    unsigned long long* dev = nullptr;
-    void begin(Staged& st)
-    {
-        if (!g.prof_on) return;
-        dev = st.scratch<unsigned long long>(2);
-        st.run([&] { return hipMemsetAsync(dev, 0, 2 * sizeof(unsigned long long), g.stream); });
-    }
-    void end(Staged& st, sdfk_trimesh* t, int64_t queries)
-    {
-        if (!dev) return;
-        unsigned long long c[2] = {0, 0};
-        st.read(c, dev, sizeof c);
-        t->last_wn_clusters = (int64_t)c[0];
-        t->last_wn_triangles = (int64_t)c[1];
-        t->last_wn_queries = queries;
-    }
-};
+// the two term counts of a profiled call, onto the handle
+void keep_terms(Staged& st, ProfCount<2>& pc, sdfk_trimesh* t, int64_t queries)
+{
+    unsigned long long c[2];
+    if (!pc.end(st, c)) return;
+    t->last_wn_clusters = (int64_t)c[0];
+    t->last_wn_triangles = (int64_t)c[1];
+    t->last_wn_queries = queries;
+}
 
 int winding_check(const sdfk_trimesh* t, const void* queries, int64_t n, float beta, const char* who)
 {
@@ -281,13 +258,13 @@ int winding_check(const sdfk_trimesh* t, const void* queries, int64_t n, float b
 int winding_launch(sdfk_trimesh* t, const float* q, int64_t n, float beta, float* winding, uint8_t* inside, const char* who)
 {
     Staged st;
-    TermCount tc;
-    tc.begin(st);
+    ProfCount<2> pc;
+    pc.begin(st);
     st.run([&] {
         ProfScope ps("k_wn_query");
-        hipLaunchKernelGGL(k_wn_query, dim3(grid1(n)), dim3(kBlock), 0, g.stream, tree_of(t, beta), q, n, winding, inside, tc.dev);
+        hipLaunchKernelGGL(k_wn_query, dim3(grid1(n)), dim3(kBlock), 0, g.stream, tree_of(t, beta), q, n, winding, inside, pc.dev);
     });
-    tc.end(st, t, n);
+    keep_terms(st, pc, t, n);
     return st.finish(who, false);
 }
 
@@ -300,14 +277,14 @@ int volume_winding(sdfk_trimesh* t, sdfk_volume* v, float band, float beta, cons
     const int64_t n = (int64_t)v->nx * v->ny * v->nz;
     Staged st;
     uint8_t* sign = st.scratch<uint8_t>((size_t)n);
-    TermCount tc;
-    tc.begin(st);
+    ProfCount<2> pc;
+    pc.begin(st);
     st.run([&] {
         const SignArgs A{v->nx, v->ny, v->nz, v->z0, m[0], m[1], m[2], d[0], d[1], d[2]};
         ProfScope ps("k_wn_volume_sign");
-        hipLaunchKernelGGL(k_wn_volume_sign, dim3(grid1(n)), dim3(kBlock), 0, g.stream, tree_of(t, beta), A, sign, tc.dev);
+        hipLaunchKernelGGL(k_wn_volume_sign, dim3(grid1(n)), dim3(kBlock), 0, g.stream, tree_of(t, beta), A, sign, pc.dev);
     });
-    tc.end(st, t, n);
+    keep_terms(st, pc, t, n);
     st.run([&] { return trimesh_to_volume(t, v, band, sign); });
     return st.finish(who, false);   // (the bytes go back to the stream-ordered pool under the queued volume pass)
 }

@@ -7,6 +7,7 @@
 // k-nearest stopping rule is points_knn.h's.  hipcc only.
 #pragma once
 #include "lib_internal.h"
+#include "device_wave.h"
 #include "points_knn.h"
 #include "points_set.h"
 
@@ -93,14 +94,6 @@ __device__ __forceinline__ unsigned long long shell_walk(const float4* __restric
         if (v.done(lb_sq(gap, base2))) break;
     }
     return ncand;
-}
-
-// every lane of the block calls this (the shuffle)
-__device__ __forceinline__ void add_candidates(unsigned long long* total, unsigned long long ncand)
-{
-    if (!total) return;
-    for (int o = 32; o > 0; o >>= 1) ncand += __shfl_down(ncand, o);
-    if ((threadIdx.x & 63) == 0) atomicAdd(total, ncand);
 }
 
 struct Query {
@@ -226,36 +219,30 @@ inline void launch_tier(int k, int64_t n, F&& launch)
 // The launch of a walk kernel (or of the tiers of one): launch(counter) queues it under the span `name`, counter being the device
 // word its lanes add their candidates to -- null unless profiling is on (and `counted`), when the call zeroes it before, and reads
 // it into sdfk_points_stats[3..4] with the nq queries after (which synchronises).  launch returns nothing, or the SDFK_ERR_* of
-// what it queued besides.  SDFK_OK or the failure as "<who>: <error string>": the launch's HIP error before the counter's, then
-// what launch returned.
+// what it queued besides.  The counter is a ProfCount of a Staged of this call (device_stage.h), which reports SDFK_OK or the
+// failure as "<who>: <error string>": the launch's HIP error before the counter's, then what launch returned.  A call that failed
+// -- a HIP error or an SDFK_ERR_* from launch alike -- waits for the stream, as every Staged does, and leaves the stats as they were.
 template <class F>
 inline int walk_launch(const sdfk_points* s, int64_t nq, const char* name, const char* who, F&& launch, bool counted = true)
 {
-    unsigned long long* dev = nullptr;
-    if (counted && g.prof_on) {
-        if (int r = dev_alloc((void**)&dev, sizeof(unsigned long long))) return r;
-        if (hipMemsetAsync(dev, 0, sizeof(unsigned long long), g.stream) != hipSuccess) {
-            dev_free(dev);
-            return fail(SDFK_ERR_HIP, "points query: memset");
-        }
-    }
+    Staged st;
+    ProfCount<1> pc;
+    pc.begin(st, counted && g.prof_on);
     int r = SDFK_OK;
-    {
+    st.run([&] {   // (a step that returns nothing: the launch's HIP error is taken first, what launch returned comes after the counter)
         ProfScope ps(name);
-        if constexpr (std::is_void<decltype(launch(dev))>::value) launch(dev);
-        else r = launch(dev);
-    }
-    hipError_t e = hipGetLastError();
-    if (dev) {
-        unsigned long long c = 0;
-        const hipError_t ec = read_back(&c, dev, sizeof c);
-        const_cast<sdfk_points*>(s)->last_candidates = (int64_t)c;
+        if constexpr (std::is_void<decltype(launch(pc.dev))>::value) launch(pc.dev);
+        else r = launch(pc.dev);
+    });
+    unsigned long long c[1];
+    const bool read = pc.end(st, c);
+    st.run([&] { return r; });
+    if (int rf = st.finish(who, false)) return rf;
+    if (read) {
+        const_cast<sdfk_points*>(s)->last_candidates = (int64_t)c[0];
         const_cast<sdfk_points*>(s)->last_queries = nq;
-        dev_free(dev);
-        if (e == hipSuccess) e = ec;
     }
-    if (e != hipSuccess) return fail(SDFK_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    return r;
+    return SDFK_OK;
 }
 
 }  // namespace sdfk_walk

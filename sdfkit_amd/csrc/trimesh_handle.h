@@ -21,6 +21,25 @@ struct TriPack {
     float4 p3;   // hix hiy hiz -
 };
 
+// the reader of the packed triangles: what the walks shared with the host tests (trimesh_ray.h, trimesh_winding.h) take as their
+// triangle source, and what a kernel unpacks a TriPack with
+struct PackTris {
+    const TriPack* tri;
+    __device__ __forceinline__ void box(uint32_t t, float lo[3], float hi[3]) const
+    {
+        const float4 p2 = tri[t].p2, p3 = tri[t].p3;
+        lo[0] = p2.y; lo[1] = p2.z; lo[2] = p2.w;
+        hi[0] = p3.x; hi[1] = p3.y; hi[2] = p3.z;
+    }
+    __device__ __forceinline__ void corners(uint32_t t, float a[3], float b[3], float c[3]) const
+    {
+        const float4 p0 = tri[t].p0, p1 = tri[t].p1;
+        a[0] = p0.x; a[1] = p0.y; a[2] = p0.z;
+        b[0] = p0.w; b[1] = p1.x; b[2] = p1.y;
+        c[0] = p1.z; c[1] = p1.w; c[2] = tri[t].p2.x;
+    }
+};
+
 struct sdfk_trimesh {
     DeviceState* owner = &cur_state();
     int64_t nv = 0, nt = 0;
@@ -52,6 +71,16 @@ struct sdfk_trimesh {
     int64_t wn_occupied = 0, wn_max_leaf = 0, wn_builds = 0;
     int64_t last_wn_clusters = 0, last_wn_triangles = 0, last_wn_queries = 0;
 };
+
+// The count of a profiled call (the candidates of a search, the triangle tests of a ray cast) and its queries onto the handle, for
+// sdfk_trimesh_stats; nothing when the call was not profiled or has failed.  Ends pc: synchronises.
+inline void trimesh_keep_count(Staged& st, ProfCount<1>& pc, const sdfk_trimesh* t, int64_t queries)
+{
+    unsigned long long c[1];
+    if (!pc.end(st, c)) return;
+    const_cast<sdfk_trimesh*>(t)->last_candidates = (int64_t)c[0];
+    const_cast<sdfk_trimesh*>(t)->last_queries = queries;
+}
 
 // The sampling weights and their scan, once per handle (lib_trimesh.hip): synchronises to read the total.  A mesh in which no
 // triangle has an area gets W = 0 everywhere and sample_no_area; refusing it is the sampler's business.
